@@ -9,12 +9,22 @@ HBM before the timed region.
 
 One timed BLOCK = a fresh solve from x0 = 0: exactly W iterations untimed, then exactly K
 iterations timed between barrier + synchronize on both sides (max_iter is raised from W to
-W + K on the live solve; the device stops on it).  A block lasts a few milliseconds, in which
-the GPU still runs at its boost clock; a long solve does not (the kernel is power-limited,
-DESIGN.md 4.1).  So the block is REPEATED - same workload, same iterations 1..W+K, back to back -
-until at least ``--min-seconds`` (default 0.6 s) of timed work has run (at most ``--max-blocks``),
-and ``value`` / ``ms_per_step`` are the MEDIAN block: the sustained rate on a warm device.  The
-first and last block are reported beside it.
+W + K on the live solve; the device stops on it).  A solve of this workload ends by itself after
+some 19 000 iterations at n = 1e8 (ZF_BACKTRACK_FAILED at the resolution limit of the acceptance
+test): a longer block goes on with a fresh solve, W untimed iterations again, until K are timed
+(config.solves_per_block).  A plain run times ONE block: K steps, and
+``ms_per_step`` is that block / K (a short block runs once untimed before: PRIME_MAX_STEPS).
+``--dump-outputs DIR`` then writes what the block's solve returns (``solve_outputs``) as
+DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output.
+
+``--full`` adds everything beyond the headline figure.  A block of K = 20 lasts a few
+milliseconds, in which the GPU still runs at its boost clock; a long solve does not (the kernel
+is power-limited).  So under --full the block is REPEATED - same workload, same
+iterations 1..W+K, back to back - until at least ``--min-seconds`` (default 0.6 s) of timed work
+has run (at most ``--max-blocks``), and ``value`` / ``ms_per_step`` are the MEDIAN block: the
+sustained rate on a warm device; the first and last block are reported beside it.  --full also
+measures the other regimes of the workload (config.iterations_per_sec_by_regime) and, on one
+GPU, the CPU baseline.
 
 One launch ("pass") of the fused kernel carries a chain of up to S = 16 iterations (temporal
 blocking), so K iterations take about K / S passes.  Rank 0 prints ONE JSON line.
@@ -70,6 +80,10 @@ ISA_PROFILE = "r02_isa_mix_trial_kernel_s{S}.json"
 PMC_R3 = {"full": ("r05_pmc_defaults_k100_w10.json", "part0"), "mid": ("r05_pmc_driver_k20_w5.json", "part3_L{len}"),
           "general": ("r05_pmc_defaults_k100_w10.json", "part2")}
 MID_MIN, MID_MAX = 9, 15   # trials of the branch-free mid chains (csrc/zf_kernels_step.h: ZF_MID_MIN .. ZF_MID_MAX), one kernel per length
+PRIME_MAX_STEPS = 4096     # a plain run with K up to this runs its block once untimed before timing it (~0.4 s at n = 1e8)
+# --dump-outputs: at most this many elements of x (32 MiB of float64) and trace rows of the timed iterations (4 MiB)
+DUMP_X_ELEMENTS = 1 << 22
+DUMP_TRACE_ROWS = 1 << 16
 
 
 def make_inputs(n, seed, device):
@@ -130,6 +144,17 @@ def valu_per_element_trial(sub_iters):
     return None if not prof else prof.get("valu_per_element_trial")
 
 
+def solve_outputs(run, rows):
+    """What a caller of the timed path receives once its last step is done: the iterate x (a fixed, seeded sample
+    of DUMP_X_ELEMENTS when n is larger: one element drawn from each of that many consecutive, nearly equal
+    slices), F(x), and the trace rows of the timed iterations (the last DUMP_TRACE_ROWS; columns zfista_amd._lib.TR_*)."""
+    x = run.solver.get_x()
+    if x.size > DUMP_X_ELEMENTS:
+        k = np.arange(DUMP_X_ELEMENTS + 1, dtype=np.int64) * x.size // DUMP_X_ELEMENTS   # slice bounds
+        x = x[k[:-1] + (np.random.default_rng(0).random(DUMP_X_ELEMENTS) * np.diff(k)).astype(np.int64)]
+    return {"x": x, "fun": np.array([run.solver.ctl.F_old]), "trace": rows[-DUMP_TRACE_ROWS:]}
+
+
 def cpu_baseline(d, c, iters=3):
     """The oracle (NumPy restatement of the reference path) on the host cores, on the FULL
     vectors of this workload (n = 1e8, 3 iterations).  Reported, never a target."""
@@ -165,9 +190,15 @@ def main():
     ap.add_argument("--total-n", type=int, default=0,
                     help="strong scaling: total length of x, split evenly over the GPUs (e.g. 800000000, "
                          "BASELINE cfg5); overrides --n")
-    ap.add_argument("--min-seconds", type=float, default=0.6,
-                    help="repeat the W + K block until this much timed work has run (sustained clocks)")
-    ap.add_argument("--max-blocks", type=int, default=400)
+    ap.add_argument("--full", action="store_true",
+                    help="beyond the headline: the block repeated for --min-seconds (median block reported), the other "
+                         "regimes of the workload and, on one GPU, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed block's solve returns as DIR/<name>.npy (float64)")
+    ap.add_argument("--min-seconds", type=float,
+                    help="with --full: repeat the W + K block until this much timed work has run (sustained clocks; "
+                         "default 0.6)")
+    ap.add_argument("--max-blocks", type=int, help="with --full: at most this many blocks (default 400)")
     ap.add_argument("--sub-iters", type=int, default=0, help="chain length S: 1 / 2 / 4 / 8 / 16 (0 = library default)")
     ap.add_argument("--libcomm", action="store_true",
                     help="N = 1 only: run the sharded step sequence over a 1-rank RCCL communicator created "
@@ -176,12 +207,12 @@ def main():
                     help="how the sufficient-decrease test is evaluated (zfista_amd.minimize_proximal_gradient's keyword): "
                          "'reference' = zfista/proximal_gradient.py:303 as written (the metric's configuration); 'resolved' = the "
                          "same inequality with f(x+) - f(y) accumulated element by element - no rounding-noise rejections")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-kernel-events", action="store_true",
                     help="do not bracket every trial kernel with HIP events (roofline becomes null); "
                          "shows what the per-kernel timing itself costs")
     ap.add_argument("--no-regimes", action="store_true",
-                    help="skip the brief second measurement of the other regime (config.iterations_per_sec_by_regime)")
+                    help="with --full: skip the brief measurements of the other regimes (config.iterations_per_sec_by_regime)")
     ap.add_argument("--thread-ranks", type=int, default=0,
                     help="DRY RUN of the N > 1 code path on ONE GPU: this many rank THREADS in this process, one stream "
                          "and one solver each, x sharded over them through the library's own communicator "
@@ -189,6 +220,13 @@ def main():
                          "sequence, same JSON line (n_gpus stays 1, config.thread_ranks says how many); use a "
                          "smaller --n (8 x 1e7 fits the time of a test).  Not a scaling measurement.")
     args = ap.parse_args()
+    if not args.full and (args.min_seconds is not None or args.max_blocks is not None):
+        ap.error("--min-seconds / --max-blocks repeat the timed block: they go with --full (a plain run times K steps)")
+    if args.full:
+        args.min_seconds = 0.6 if args.min_seconds is None else args.min_seconds
+        args.max_blocks = 400 if args.max_blocks is None else args.max_blocks
+    else:
+        args.min_seconds, args.max_blocks = 0.0, 1
 
     # Only the JSON line may reach stdout: libraries (RCCL prints "Hostname : ..." banners at
     # communicator creation) are pointed at stderr for the whole run.
@@ -318,8 +356,9 @@ def rank_body(args, rank, world, group, barrier, max_over_ranks, thread_ranks=0)
         barrier()
         torch.cuda.synchronize()
 
-    def measure(K, W, min_seconds, max_blocks, acceptance=None):
-        """Blocks of W untimed + K timed iterations (a fresh solve each) until min_seconds are timed."""
+    def measure(K, W, min_seconds, max_blocks, acceptance=None, outputs=None):
+        """Blocks of W untimed + K timed iterations (a fresh solve each) until min_seconds are timed.
+        `outputs` (a dict) receives solve_outputs of the last block."""
         o = dict(opts, max_iter=max(W, 1))
         if acceptance:
             o["acceptance"] = acceptance
@@ -328,47 +367,65 @@ def rank_body(args, rank, world, group, barrier, max_over_ranks, thread_ranks=0)
         m = dict(blocks=[], timed=0.0, full_ms=0.0, full_n=0, part_ms=0.0, part_n=0, part_fresh=0, part_lag=0, S=S,
                  tiles=None)
         while True:
-            while W > 0 and run.status == _lib.ZF_RUNNING:   # warm-up: exactly W iterations, then MAXITER
-                run.advance((W - run.nit_seen + S - 1) // S)
-            if timing:
-                run.solver.pass_stats()                      # reset the event window after warm-up
-            nit0 = run.nit_seen
-            run.set_max_iter(nit0 + K)
-            sync_all()
-            t0 = time.perf_counter()
-            trials0 = int(run.solver.ctl.total_trials) - run.nit_seen
-            while run.status == _lib.ZF_RUNNING:
-                # the passes the remaining iterations need if no chain breaks; a rejected trial (lr halves, :305)
-                # costs further passes: once this block has seen rejections, two spare passes ride along with every
-                # round (a pass enqueued behind the end of the solve exits at once) instead of a poll round trip each
-                spare = 2 if int(run.solver.ctl.total_trials) - run.nit_seen > trials0 else 0
-                run.enqueue_only((K - (run.nit_seen - nit0) + S - 1) // S + spare)
-                run.collect()
-            sync_all()
-            dt = time.perf_counter() - t0
-            assert run.status == _lib.ZF_MAXITER and run.nit_seen - nit0 == K, \
-                f"expected {K} accepted iterations, got {run.nit_seen - nit0} (status {run.status})"
-            if timing:
-                (fm, fn), (pm, pn), (pf, pl) = run.solver.pass_stats_ex()
-                m["full_ms"] += fm * fn
-                m["full_n"] += fn
-                m["part_ms"] += pm * pn
-                m["part_n"] += pn
-                m["part_fresh"] += pf
-                m["part_lag"] += pl
-            rep_ = run.solver.ahead_report()
-            m["ra_passes"] = m.get("ra_passes", 0) + rep_["runahead"]
-            m["ra_ahead"] = m.get("ra_ahead", 0) + rep_["runahead_overlapped"]
-            for key in ("timeouts", "void", "ahead", "ahead_void"):
-                m["rep_" + key] = m.get("rep_" + key, 0) + rep_[key]
-            m["ra_off"] = m.get("ra_off", False) or rep_["runahead_off"]
-            note_comm(run)
+            # A solve of this workload ends by itself after some 19 000 iterations at n = 1e8: it has long converged, and
+            # at the resolution limit of the acceptance test one iteration rejects all max_backtrack_iter trials
+            # (ZF_BACKTRACK_FAILED).  A longer block goes on with a fresh solve - W untimed iterations again - for the rest.
+            dt, done = 0.0, 0
+            trace = [] if outputs is not None else None
+            while True:
+                while W > 0 and run.status == _lib.ZF_RUNNING:   # warm-up: exactly W iterations, then MAXITER
+                    run.advance((W - run.nit_seen + S - 1) // S)
+                if timing:
+                    run.solver.pass_stats()                      # reset the event window after warm-up
+                nit0 = run.nit_seen
+                run.set_max_iter(nit0 + K - done)
+                sync_all()
+                t0 = time.perf_counter()
+                trials0 = int(run.solver.ctl.total_trials) - run.nit_seen
+                while run.status == _lib.ZF_RUNNING:
+                    # the passes the remaining iterations need if no chain breaks; a rejected trial (lr halves, :305)
+                    # costs further passes: once this block has seen rejections, two spare passes ride along with every
+                    # round (a pass enqueued behind the end of the solve exits at once) instead of a poll round trip each
+                    spare = 2 if int(run.solver.ctl.total_trials) - run.nit_seen > trials0 else 0
+                    run.enqueue_only((K - done - (run.nit_seen - nit0) + S - 1) // S + spare)
+                    rows = run.collect()
+                    if trace is not None:
+                        trace.append(rows)
+                sync_all()
+                dt += time.perf_counter() - t0
+                got = run.nit_seen - nit0
+                assert (run.status == _lib.ZF_MAXITER and done + got == K) or (run.status == _lib.ZF_BACKTRACK_FAILED and got > 0), \
+                    f"expected {K - done} accepted iterations, got {got} (status {run.status})"
+                done += got
+                if timing:
+                    (fm, fn), (pm, pn), (pf, pl) = run.solver.pass_stats_ex()
+                    m["full_ms"] += fm * fn
+                    m["full_n"] += fn
+                    m["part_ms"] += pm * pn
+                    m["part_n"] += pn
+                    m["part_fresh"] += pf
+                    m["part_lag"] += pl
+                rep_ = run.solver.ahead_report()
+                m["ra_passes"] = m.get("ra_passes", 0) + rep_["runahead"]
+                m["ra_ahead"] = m.get("ra_ahead", 0) + rep_["runahead_overlapped"]
+                for key in ("timeouts", "void", "ahead", "ahead_void"):
+                    m["rep_" + key] = m.get("rep_" + key, 0) + rep_[key]
+                m["ra_off"] = m.get("ra_off", False) or rep_["runahead_off"]
+                note_comm(run)
+                m["solves"] = m.get("solves", 0) + 1
+                if done == K:
+                    break
+                run.solver.close()
+                run = NativeRun(prob, x0, o, timing=timing)
             dt = max_over_ranks(dt)
             m["blocks"].append(dt)
             m["timed"] += dt
             m["tiles"] = getattr(run.solver, "tiles_per_wg", None)
+            last = m["timed"] >= min_seconds or len(m["blocks"]) >= max_blocks   # (dt is the max over ranks: same decision everywhere)
+            if last and outputs is not None:
+                outputs.update(solve_outputs(run, np.concatenate(trace)))
             run.solver.close()
-            if m["timed"] >= min_seconds or len(m["blocks"]) >= max_blocks:   # (dt is the max over ranks: same decision everywhere)
+            if last:
                 break
             run = NativeRun(prob, x0, o, timing=timing)   # the same workload again, on a warmer device
         return m
@@ -389,7 +446,18 @@ def rank_body(args, rank, world, group, barrier, max_over_ranks, thread_ranks=0)
             comm_seen.update({"via": "torch.distributed fallback (host-driven trial / all-gather / decide per pass)",
                               "world": sv.world, "rank": sv.rank, "rank_count_seen": sv.world, "library": None})
 
-    M = measure(K, W, args.min_seconds, args.max_blocks)
+    if not args.full and K <= PRIME_MAX_STEPS:
+        # every shape-specific kernel is loaded on its first launch (~0.5 ms each, tools/bench_configs.py): a short block
+        # timed once would count that as solve time, so the same block runs once untimed first (--full's repeated blocks
+        # report the median instead)
+        measure(K, W, 0.0, 1)
+        comm_seen.clear()
+    outputs = {} if args.dump_outputs and rank == 0 else None   # (rank 0's shard when x is sharded)
+    M = measure(K, W, args.min_seconds, args.max_blocks, outputs=outputs)
+    if outputs is not None:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in outputs.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
     S, blocks, timed, tiles = M["S"], M["blocks"], M["timed"], M["tiles"]
     full_ms, full_n, part_ms, part_n = M["full_ms"], M["full_n"], M["part_ms"], M["part_n"]
     part_fresh, part_lag = M["part_fresh"], M["part_lag"]
@@ -397,23 +465,24 @@ def rank_body(args, rank, world, group, barrier, max_over_ranks, thread_ranks=0)
     passes = full_n + part_n
     # The two regimes of this workload side by side, whatever the flags: 20 iterations from iteration 5 stay clear of
     # the resolution limit of the acceptance test (no trial is rejected); 100 iterations from iteration 10 cross it
-    # at iteration ~89 and pay for two or three rounding-noise rejections.  The other one is measured
-    # briefly after the main measurement (every rank takes part: the exchanges are collective).
+    # at iteration ~89 and pay for two or three rounding-noise rejections.  Under --full the others are
+    # measured briefly after the main measurement (every rank takes part: the exchanges are collective).
     regimes = {}
+    others = args.full and not args.no_regimes
     # (round 4: K = 24 / 28 / 30 beside K = 20 - tails of 12 + 12, 14 + 14, 15 + 15 trials: every tail length has a
     #  branch-free kernel of its own now, the line no longer has one privileged block length)
     for (k2, w2), tag in (((20, 5), "clean_regime_K20_W5"), ((24, 5), "clean_regime_K24_W5"), ((28, 5), "clean_regime_K28_W5"),
                           ((30, 5), "clean_regime_K30_W5"), ((100, 10), "across_the_noise_floor_K100_W10")):
         if (k2, w2) == (K, W):
             regimes[tag] = (world * K / dt * (n / N_PER_GPU)) if not args.total_n else K / dt
-        elif not args.no_regimes:
+        elif others:
             m2 = measure(k2, w2, 0.2, 60)
             d2 = statistics.median(m2["blocks"])
             regimes[tag] = (world * k2 / d2 * (n / N_PER_GPU)) if not args.total_n else k2 / d2
 
     # ... and the noisy regime once more with the acceptance test resolved below ulp(F) (acceptance="resolved": the same
     # inequality, f(x+) - f(y) accumulated element by element - no trial of this workload is rejected, 7 passes instead of 9)
-    if not args.no_regimes and args.acceptance == "reference":
+    if others and args.acceptance == "reference":
         m3 = measure(100, 10, 0.2, 60, acceptance="resolved")
         d3 = statistics.median(m3["blocks"])
         regimes["across_the_noise_floor_K100_W10_acceptance_resolved"] = (world * 100 / d3 * (n / N_PER_GPU)) if not args.total_n else 100 / d3
@@ -442,8 +511,10 @@ def rank_body(args, rank, world, group, barrier, max_over_ranks, thread_ranks=0)
                 "n_per_gpu": n,
                 "n_total": args.total_n if args.total_n else n * world,
                 "iters_per_sec_full_problem": K / dt,
-                "timing": f"median of {len(blocks)} back-to-back blocks of W={W} untimed + K={K} timed iterations "
-                          f"(fresh solve each), {timed:.2f} s timed in total",
+                "timing": (f"median of {len(blocks)} back-to-back blocks of W={W} untimed + K={K} timed iterations "
+                           f"(fresh solve each), {timed:.2f} s timed in total") if args.full else
+                          f"one block of W={W} untimed + K={K} timed iterations ({M['solves']} fresh solve(s), each "
+                          f"starting with the W untimed ones), {timed:.4f} s timed",
                 "blocks": len(blocks),
                 "ms_per_step_first_block": blocks[0] / K * 1e3,
                 "ms_per_step_median_block": dt / K * 1e3,
@@ -451,6 +522,7 @@ def rank_body(args, rank, world, group, barrier, max_over_ranks, thread_ranks=0)
                 "ms_per_step_min_block": min(blocks) / K * 1e3,
                 "temporal_blocking_chain": S,
                 "passes_per_block": passes / len(blocks) if timing else None,
+                "solves_per_block": M["solves"] / len(blocks),
                 "full_chain_passes": full_n if timing else None,
                 "other_passes": part_n if timing else None,
                 "tiles_per_workgroup": tiles,
@@ -574,7 +646,7 @@ def rank_body(args, rank, world, group, barrier, max_over_ranks, thread_ranks=0)
                 "equivalent_note": "40 B x n x trials per pass (SURVEY 8d's per-iteration bytes x iterations per pass) / duration: "
                                    "not a bandwidth - the chain does not move those bytes",
             }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(d, c)
     return line
 

@@ -1,3 +1,4 @@
+import glob
 import os
 import sys
 
@@ -40,16 +41,23 @@ def pytest_collection_modifyitems(session, config, items):
 
 
 class Golden:
-    """Prefix view over one committed .npz fixture."""
+    """Prefix view over one committed .npz fixture - NAME.npz, or NAME.part1.npz, NAME.part2.npz, ... when one file
+    would be larger than a committed file may be (tests/golden/make_golden.py: save)."""
 
     def __init__(self, name):
-        self.z = np.load(os.path.join(GOLDEN, name))
+        path = os.path.join(GOLDEN, name)
+        parts = [path] if os.path.exists(path) else sorted(glob.glob(path[:-len(".npz")] + ".part*.npz"))
+        assert parts, f"no golden fixture {name}"
+        self.z = [np.load(p) for p in parts]
 
     def __call__(self, key):
-        return self.z[key]
+        for z in self.z:
+            if key in z.files:
+                return z[key]
+        raise KeyError(key)
 
     def has(self, key):
-        return key in self.z.files
+        return any(key in z.files for z in self.z)
 
 
 @pytest.fixture(scope="session")

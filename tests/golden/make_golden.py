@@ -80,9 +80,20 @@ def trace_arrays(r, o, keep=None):
 
 
 def save(name, **arrays):
-    path = os.path.join(HERE, name)
-    np.savez_compressed(path, **arrays)
-    print(f"wrote {name}: {os.path.getsize(path) / 1024:.1f} KiB")
+    """NAME.npz, or - when that would be larger than a committed file may be (1 MiB) - the arrays in order over as few
+    files NAME.part1.npz, NAME.part2.npz, ... as stay below it (tests/conftest.py: Golden reads either form)."""
+    keys, k = list(arrays), 1
+    while True:
+        paths = [os.path.join(HERE, name)] if k == 1 else [os.path.join(HERE, f"{name[:-4]}.part{i + 1}.npz") for i in range(k)]
+        for i, path in enumerate(paths):
+            np.savez_compressed(path, **{key: arrays[key] for key in keys[i * len(keys) // k:(i + 1) * len(keys) // k]})
+        if all(os.path.getsize(path) <= 1 << 20 for path in paths):
+            break
+        for path in paths:
+            os.remove(path)
+        k += 1
+    for path in paths:
+        print(f"wrote {os.path.basename(path)}: {os.path.getsize(path) / 1024:.1f} KiB")
 
 
 def g1_toy():

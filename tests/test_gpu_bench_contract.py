@@ -1,10 +1,11 @@
 """GPU: bench.py keeps the driver's contract - exactly one JSON line on stdout with the agreed
-keys, exactly K timed iterations, a roofline block and (N = 1) a CPU baseline block."""
+keys, exactly K timed iterations, a roofline block and (--full, N = 1) a CPU baseline block."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from conftest import ROOT
@@ -13,7 +14,7 @@ pytestmark = pytest.mark.gpu
 
 
 def _run(*extra):
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--n", "2000000", "--steps", "21",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--n", "2000000", "--steps", "21",
                           "--warmup", "5", "--min-seconds", "0.05", *extra], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
@@ -55,11 +56,52 @@ def test_bench_json_line():
     assert abs(d["ms_per_step"] * d["steps"] / 1e3 - d["steps"] / d["value"] * (2000000 / 1e8)) < 1e-9
 
 
+def test_bench_plain_run_times_k_steps_and_dumps_its_outputs(tmp_path):
+    """A plain run times ONE block of exactly K steps and measures nothing else; --dump-outputs writes what that
+    block's solve returns, the same from run to run (seeded inputs): x sampled down to 2^22 elements, F(x), the trace."""
+    n, lines = 5000000, []
+    for tag in ("a", "b"):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--n", str(n), "--steps", "21",
+                              "--warmup", "5", "--dump-outputs", str(tmp_path / tag)], capture_output=True, text=True,
+                             timeout=600, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines.append([ln for ln in out.stdout.splitlines() if ln.strip()])
+    assert len(lines[0]) == 1, f"stdout must hold exactly one line, got {len(lines[0])}"
+    d = json.loads(lines[0][0])
+    assert (d["steps"], d["warmup"], d["unit"], d["dtype"], d["higher_is_better"]) == (21, 5, "iterations/s", "f64", True)
+    assert d["metric"] == "fista_iterations_per_sec_n1e8_per_gpu_shard" and d["value"] > 0
+    cfg = d["config"]
+    assert cfg["blocks"] == 1 and cfg["iterations_per_sec_by_regime"] == {} and "cpu_baseline" not in d
+    assert cfg["ms_per_step_first_block"] == cfg["ms_per_step_last_block"] == d["ms_per_step"]
+    assert abs(d["ms_per_step"] * 21 / 1e3 - 21 / d["value"] * (n / 1e8)) < 1e-9
+    got = {tag: {name: np.load(tmp_path / tag / f"{name}.npy") for name in ("x", "fun", "trace")} for tag in ("a", "b")}
+    a = got["a"]
+    assert sorted(os.listdir(tmp_path / "a")) == ["fun.npy", "trace.npy", "x.npy"]
+    assert all(v.dtype == np.float64 for v in a.values()) and sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert a["x"].shape == (1 << 22,) and a["fun"].shape == (1,) and a["trace"].shape == (21, 8)
+    assert np.all(np.isfinite(a["x"])) and np.any(a["x"] != 0.0)
+    assert a["fun"][0] == a["trace"][-1, 1]        # F(x) of the last accepted iteration (column TR_F)
+    for name in a:
+        assert np.array_equal(a[name], got["b"][name]), name
+
+
+def test_bench_steps_outlast_one_solve():
+    """--steps is the number of timed steps however many there are: a solve of the headline problem ends by itself
+    after 19 425 iterations (converged; at the resolution limit of the acceptance test every trial of one iteration is
+    rejected), so a block of 20 000 goes on with a second fresh solve."""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20000", "--warmup", "10"],
+                         capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    d = json.loads([ln for ln in out.stdout.splitlines() if ln.strip()][0])
+    assert d["steps"] == 20000 and d["config"]["blocks"] == 1 and d["config"]["solves_per_block"] == 2
+    assert abs(d["ms_per_step"] * 20000 / 1e3 - 20000 / d["value"]) < 1e-9
+
+
 def test_bench_line_says_when_passes_ran_ahead():
     """64 iterations from iteration 16 at n = 2e6: four full chains in a row on a one-round grid - the second to
     fourth are launched on the other stream while their predecessor is finalised, and the line says so."""
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--n", "2000000", "--steps", "64", "--warmup", "16",
-                          "--min-seconds", "0.05", "--no-cpu-baseline", "--no-regimes"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--n", "2000000", "--steps", "64",
+                          "--warmup", "16", "--min-seconds", "0.05", "--no-cpu-baseline", "--no-regimes"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads([ln for ln in out.stdout.splitlines() if ln.strip()][0])
     ra = d["config"]["runahead"]
@@ -106,7 +148,7 @@ def test_bench_two_ranks_share_the_gpu_over_gloo():
     # --standalone: the agent's own store (bound to port 0 and kept open) is the rendezvous - no picked port
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--standalone", "--local-addr", "127.0.0.1",
                           "--nnodes=1", "--nproc-per-node", "2", os.path.join(ROOT, "bench.py"),
-                          "--gpus", "2", "--elements", "2000000", "--steps", "24", "--warmup", "8",
+                          "--gpus", "2", "--full", "--elements", "2000000", "--steps", "24", "--warmup", "8",
                           "--min-seconds", "0.05"],
                          capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -125,8 +167,8 @@ def test_bench_n_gt_1_code_path_with_eight_thread_ranks():
     timing, max over ranks, ONE JSON line from rank 0 - as a dry run on this one GPU: 8 rank THREADS x n = 1e7
     (BASELINE cfg5's layout at an eighth of its size) through the in-process communicator group behind the same
     zf_comm_all_gather RCCL serves (--thread-ranks).  The JSON contract must hold; n_gpus stays 1."""
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--thread-ranks", "8", "--n", "10000000",
-                          "--steps", "20", "--warmup", "5", "--min-seconds", "0.2", "--no-regimes"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--thread-ranks", "8", "--full", "--n",
+                          "10000000", "--steps", "20", "--warmup", "5", "--min-seconds", "0.2", "--no-regimes"],
                          capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]

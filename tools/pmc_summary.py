@@ -39,7 +39,7 @@ full_w = [w for w in write if w > 0.9 * max(write)] if write else []
 fetch = [f for f in fetch if f > 0.9 * max(fetch)] if fetch else []
 model = (48 if S > 1 else 40) * n
 res = {
-    "command": f"rocprofv3 --pmc <COUNTER> --output-format csv -- python3 bench.py --sub-iters {S} --no-cpu-baseline "
+    "command": f"rocprofv3 --pmc <COUNTER> --output-format csv -- python3 bench.py --full --sub-iters {S} --no-cpu-baseline "
                "--steps 40 --warmup 8 --min-seconds 0.1  (one run per counter, no trace domains; tools/profile_bench.sh)",
     "kernel": f"zf_trial_kernel<grad inline, nesterov, nt, S={S}> (P-diag)",
     "n": n,

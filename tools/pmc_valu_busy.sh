@@ -7,7 +7,7 @@ ROOT="${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}"
 OUT="$ROOT/gpurun_out/valu_busy_s$S"
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-SHORT="--sub-iters $S --no-cpu-baseline --steps 64 --warmup 16 --min-seconds 0.1"
+SHORT="--full --sub-iters $S --no-cpu-baseline --steps 64 --warmup 16 --min-seconds 0.1"
 rocprofv3 --pmc GRBM_GUI_ACTIVE SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_BUSY_CU_CYCLES --output-format csv -d "$OUT/a" -o a -- python3 "$ROOT/bench.py" $SHORT > /dev/null 2>&1
 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY --output-format csv -d "$OUT/b" -o b -- python3 "$ROOT/bench.py" $SHORT > /dev/null 2>&1
 python3 - "$OUT" <<'PY'

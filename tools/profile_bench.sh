@@ -16,11 +16,11 @@ mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 NOCPU="--no-cpu-baseline"
 [ "$S" = "8" ] && NOCPU=""
-python3 "$ROOT/bench.py" --sub-iters "$S" $NOCPU > "$OUT/bench.json" 2> "$OUT/bench.err"
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o trace -- python3 "$ROOT/bench.py" --sub-iters "$S" --no-cpu-baseline > "$OUT/bench_traced.json" 2> /dev/null
-SHORT="--sub-iters $S --no-cpu-baseline --steps 40 --warmup 8 --min-seconds 0.1"
+python3 "$ROOT/bench.py" --full --sub-iters "$S" $NOCPU > "$OUT/bench.json" 2> "$OUT/bench.err"
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o trace -- python3 "$ROOT/bench.py" --full --sub-iters "$S" --no-cpu-baseline > "$OUT/bench_traced.json" 2> /dev/null
+SHORT="--full --sub-iters $S --no-cpu-baseline --steps 40 --warmup 8 --min-seconds 0.1"
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/fetch" -o fetch -- python3 "$ROOT/bench.py" $SHORT > /dev/null 2>&1
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/write" -o write -- python3 "$ROOT/bench.py" $SHORT > /dev/null 2>&1
-rocprofv3 --pmc GRBM_GUI_ACTIVE SQ_INSTS_VALU SQ_BUSY_CYCLES --output-format csv -d "$OUT/clock" -o clock -- python3 "$ROOT/bench.py" --sub-iters "$S" --no-cpu-baseline > /dev/null 2>&1 || echo "clock counters not collected"
+rocprofv3 --pmc GRBM_GUI_ACTIVE SQ_INSTS_VALU SQ_BUSY_CYCLES --output-format csv -d "$OUT/clock" -o clock -- python3 "$ROOT/bench.py" --full --sub-iters "$S" --no-cpu-baseline > /dev/null 2>&1 || echo "clock counters not collected"
 python3 "$ROOT/tools/pmc_summary.py" "$OUT" 100000000 "$S" > "$OUT/pmc_traffic.json"
 ls "$OUT" "$OUT/trace" | head -30

@@ -11,9 +11,9 @@ ROOT="${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}"
 OUT="$ROOT/gpurun_out/prof_$LABEL"
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-python3 "$ROOT/bench.py" "$@" > "$OUT/bench.json" 2> "$OUT/bench.err"
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o trace -- python3 "$ROOT/bench.py" "$@" --no-cpu-baseline --no-regimes > "$OUT/bench_traced.json" 2> /dev/null
-SHORT="--no-cpu-baseline --no-regimes --min-seconds 0.1"
+python3 "$ROOT/bench.py" --full "$@" > "$OUT/bench.json" 2> "$OUT/bench.err"
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o trace -- python3 "$ROOT/bench.py" --full "$@" --no-cpu-baseline --no-regimes > "$OUT/bench_traced.json" 2> /dev/null
+SHORT="--full --no-cpu-baseline --no-regimes --min-seconds 0.1"
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/fetch" -o fetch -- python3 "$ROOT/bench.py" "$@" $SHORT > /dev/null 2>&1
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/write" -o write -- python3 "$ROOT/bench.py" "$@" $SHORT > /dev/null 2>&1
 rocprofv3 --pmc GRBM_GUI_ACTIVE SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_BUSY_CU_CYCLES --output-format csv -d "$OUT/clock" -o clock -- python3 "$ROOT/bench.py" "$@" $SHORT > /dev/null 2>&1 || echo "clock counters not collected"

@@ -1,7 +1,7 @@
 #!/bin/bash
 # acceptance="resolved" beside the reference's evaluation of the test: the bench's two regimes and the long solves across the noise floor
 out=gpurun_out/r5_accept; mkdir -p $out; : > $out/ab.jsonl
-b() { tag=$1; shift; line=$(python bench.py "$@" --no-cpu-baseline --no-regimes 2>/dev/null | tail -1); echo "{\"tag\": \"$tag\", \"line\": $line}" >> $out/ab.jsonl; echo "$tag done"; }
+b() { tag=$1; shift; line=$(python bench.py --full "$@" --no-cpu-baseline --no-regimes 2>/dev/null | tail -1); echo "{\"tag\": \"$tag\", \"line\": $line}" >> $out/ab.jsonl; echo "$tag done"; }
 for rep in 1 2; do
   b k100_reference --steps 100 --warmup 10
   b k100_resolved --steps 100 --warmup 10 --acceptance resolved

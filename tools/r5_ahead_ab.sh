@@ -5,7 +5,7 @@
 out=gpurun_out/r5_ahead; mkdir -p $out; : > $out/ab.jsonl
 run() {  # tag, env, bench args
   tag=$1; envs=$2; shift 2
-  line=$(env $envs python bench.py "$@" --no-cpu-baseline --no-regimes 2>/dev/null | tail -1)
+  line=$(env $envs python bench.py --full "$@" --no-cpu-baseline --no-regimes 2>/dev/null | tail -1)
   echo "{\"tag\": \"$tag\", \"env\": \"$envs\", \"args\": \"$*\", \"line\": $line}" >> $out/ab.jsonl
   echo "$tag done"
 }

@@ -9,7 +9,7 @@ for mode in ahead perpass libcomm; do
     libcomm) e="ZF_X=1"; extra="--libcomm";;
   esac
   rm -rf /tmp/tr_$mode
-  env $e rocprofv3 --kernel-trace --output-format csv -d /tmp/tr_$mode -o t -- python3 bench.py --n 10000000 --steps 64 --warmup 16 --min-seconds 0.05 --no-cpu-baseline --no-regimes --no-kernel-events $extra > /dev/null 2>&1
+  env $e rocprofv3 --kernel-trace --output-format csv -d /tmp/tr_$mode -o t -- python3 bench.py --full --n 10000000 --steps 64 --warmup 16 --min-seconds 0.05 --no-cpu-baseline --no-regimes --no-kernel-events $extra > /dev/null 2>&1
   f=$(find /tmp/tr_$mode -name "*kernel_trace.csv" | head -1)
   python3 - "$f" $mode <<'PY'
 import csv, sys

@@ -7,7 +7,7 @@ out=$PWD/gpurun_out/r5_ab; mkdir -p $out
 for rep in 1 2 3; do
   for tree in r3 head; do
     if [ $tree = r3 ]; then dir=$PWD/_ab/r3tree; else dir=$PWD; fi
-    line=$(cd $dir && python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-regimes 2>/dev/null | tail -1)
+    line=$(cd $dir && python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-regimes 2>/dev/null | tail -1)
     echo "$tree $line" >> $out/headline.txt
     echo "$tree rep $rep done"
   done

@@ -8,7 +8,7 @@ out=gpurun_out/r5_ra_mid/ab.jsonl; : > $out
 for rep in 1 2; do
  for ra in 0 1; do
   echo "ra=$ra n=1e7 K20 W5" >> $out
-  ZF_RUNAHEAD=$ra timeout -k 10 300 python bench.py --n 10000000 --steps 20 --warmup 5 --no-cpu-baseline --no-regimes >> $out 2>/dev/null || exit 1
+  ZF_RUNAHEAD=$ra timeout -k 10 300 python bench.py --full --n 10000000 --steps 20 --warmup 5 --no-cpu-baseline --no-regimes >> $out 2>/dev/null || exit 1
   echo "ra=$ra n=1e6 K64 W16" >> $out
   ZF_RUNAHEAD=$ra timeout -k 10 300 python tools/block_probe.py --n 1000000 --steps 64 >> $out 2>/dev/null || exit 1
   echo "ra=$ra n=1e6 K20" >> $out

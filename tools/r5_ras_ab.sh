@@ -4,7 +4,7 @@
 export TMPDIR=/tmp
 mkdir -p gpurun_out/ras
 out=gpurun_out/ras/ab.jsonl; : > $out
-line() { python bench.py "$@" --no-cpu-baseline --no-regimes 2>/dev/null | tail -1; }
+line() { python bench.py --full "$@" --no-cpu-baseline --no-regimes 2>/dev/null | tail -1; }
 for rep in 1 2; do
   for n in 10000000 1000000; do
     for K in "64 16" "20 5"; do

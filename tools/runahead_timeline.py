@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Run-ahead passes in rocprofv3's kernel trace: do consecutive passes overlap, and what is the period?
 
-    rocprofv3 --kernel-trace --output-format csv -d DIR -o t -- python3 bench.py --n 10000000 --steps 64 --warmup 16 ...
+    rocprofv3 --kernel-trace --output-format csv -d DIR -o t -- python3 bench.py --full --n 10000000 --steps 64 --warmup 16 ...
     tools/runahead_timeline.py DIR
 
 Reads DIR/**/*kernel_trace.csv, takes the launches of zf_runahead_kernel in start order and prints one JSON object:

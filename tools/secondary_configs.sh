@@ -14,8 +14,8 @@ $B --cfg 4 --steps 100 --warmup 5 --dual-solver native 2>/dev/null >> "$OUT"
 $B --cfg 4 --steps 10 --warmup 2 --dual-solver scipy 2>/dev/null >> "$OUT"
 python3 "$ROOT/tools/long_run.py" 1e8 300 2>/dev/null >> "$OUT"
 python3 "$ROOT/tools/long_run.py" 1e7 400 2>/dev/null >> "$OUT"
-python3 "$ROOT/bench.py" --total-n 800000000 --no-cpu-baseline --no-regimes 2>/dev/null | python3 -c "
+python3 "$ROOT/bench.py" --full --total-n 800000000 --no-cpu-baseline --no-regimes 2>/dev/null | python3 -c "
 import sys, json
 d = json.loads(sys.stdin.read())
-print(json.dumps({'workload': 'P-diag n = 8e8 on ONE GPU (bench.py --total-n 800000000, defaults K = 100, W = 10)', 'value_it_per_s': d['value'], 'ms_per_step': d['ms_per_step']}))" >> "$OUT"
+print(json.dumps({'workload': 'P-diag n = 8e8 on ONE GPU (bench.py --full --total-n 800000000, defaults K = 100, W = 10)', 'value_it_per_s': d['value'], 'ms_per_step': d['ms_per_step']}))" >> "$OUT"
 wc -l "$OUT"
