@@ -345,6 +345,13 @@ int zf_solver_trial_kernel_ms(zf_solver* s, double* avg_ms, int64_t* launches);
  * kernels of consecutive exactly predicted full / mid chains back to back on the solver's stream, each on the head the host
  * expects, while finalisation, all-gather and decide of the pass before run on the second stream (ZF_AHEAD=0: off). */
 int zf_solver_launch_counts(zf_solver* s, int64_t* out, int64_t count /* >= 2 */);
+/* least squares: the kernels the passes of zf_solver_enqueue_steps run, fixed at zf_solver_create.  out[0] = the column
+ * sweep A^T r: 0 not least squares, 1 the small-matrix step kernel (zf_ls_small_step_kernel), 2 the MFMA sweep
+ * (zf_gemvT_partial_mfma_kernel), 3 the VALU sweep with 16-byte loads (zf_gemvT_partial_kernel<2>), 4 with scalar loads
+ * (<1>); out[1] = the row sweep A x+: 1 zf_ls_small_rows_kernel, 2 zf_gemv_rows_kernel<2>, 3 <1>; out[2] = row slices
+ * of the general column sweep, out[3] = rows per slice (the last slice may be shorter).
+ * (A host-driven trial - zf_solver_enqueue_trial - always takes the general path.) */
+int zf_solver_ls_plan(zf_solver* s, int64_t* out, int64_t count /* >= 4 */);
 /* the same window split by the shape of the pass, which the kernel logs itself: out[0], out[1] = mean
  * ms and count of full chains (sub_iters fresh trials, nothing replayed); out[2], out[3] = every other
  * pass (shorter chains, replays, materialise-only).  Resets the window. */

@@ -254,28 +254,35 @@ class DiagQuadL1Ref:
 
 
 class LeastSquaresL1Ref:
-    """f(x) = scale ||Ax - b||^2,  g(x) = lam ||x||_1   (P-lasso; scale 1/2).
+    """f(x) = scale ||Ax - b||^2,  g(x) = lam ||x||_1 (+ box)   (P-lasso; scale 1/2).
 
     The test closures of the reference are the scale = 1/6 member
-    (tests/test_proximal_gradient.py:81-97).
+    (tests/test_proximal_gradient.py:81-97).  ``bounds = (lo, hi)``: g is inf outside the box (as
+    ``ProblemRef.g``) and the prox clips the soft-thresholded point into it (as ``ProblemRef.prox_wsum_g``).
     """
 
-    def __init__(self, A, b, lam, scale=0.5):
+    def __init__(self, A, b, lam, scale=0.5, bounds=None):
         self.A = np.asarray(A, float)
         self.b = np.asarray(b, float)
         self.lam, self.scale = float(lam), float(scale)
+        self.bounds = None if bounds is None else (float(bounds[0]), float(bounds[1]))
 
     def f(self, x):
         return self.scale * np.linalg.norm(self.A @ x - self.b) ** 2
 
     def g(self, x):
+        if self.bounds is not None and ((x < self.bounds[0]).any() or (x > self.bounds[1]).any()):
+            return np.inf
         return self.lam * np.linalg.norm(x, ord=1)
 
     def jac_f(self, x):
         return (2 * self.scale) * (self.A.T @ (self.A @ x - self.b))
 
     def prox_wsum_g(self, weight, x):
-        return soft_threshold(x, self.lam * weight)
+        x = soft_threshold(x, self.lam * weight)
+        if self.bounds is not None:
+            x = clip_box(x, self.bounds[0], self.bounds[1])
+        return x
 
     def callbacks(self):
         return self.f, self.g, self.jac_f, self.prox_wsum_g
@@ -309,6 +316,43 @@ def make_pdiag(n, seed=1, lam=0.1):
     d = rng.uniform(0.5, 2.0, n)
     c = rng.standard_normal(n)
     return d, c, lam
+
+
+def ls_longdouble(A, b, x, scale, grad=True):
+    """f(x) = scale ||Ax - b||^2 and grad f(x) = 2 scale A^T (Ax - b) in np.longdouble, with the a-priori bounds of an
+    fp64 evaluation of the same sums in any order (Higham, Accuracy and Stability of Numerical Algorithms, 3.1):
+    u = 2^-53, gamma_k = k u / (1 - k u), c = |A||x| + |b|,
+
+        |g_hat - g|_j <= 2 gamma_(m+n+2) 2 scale (|A|^T c)_j     (n terms of A x, b, m terms of A^T r, the factor)
+        |f_hat - f|   <= 2 gamma_(m+2n+6) scale ||c||^2          (r_i^2 doubles the error of r_i; the sum of m squares,
+                                                                  sqrt, square and the factor)
+
+    each with a safety factor of 2.  Returns (f, grad, f_bound, grad_bound): f and grad as longdouble, the bounds as
+    float64 (grad=False: f and f_bound only, None for the others).  Raises RuntimeError when np.longdouble does not carry at least 63 mantissa bits (the reference value
+    would then be no more exact than the evaluation it checks)."""
+    if np.finfo(np.longdouble).nmant < 63:
+        raise RuntimeError(f"np.longdouble has {np.finfo(np.longdouble).nmant} mantissa bits here: "
+                           "an fp64 evaluation cannot be checked against it")
+    A = np.asarray(A, dtype=np.float64)
+    m, n = A.shape
+    Al = A.astype(np.longdouble)
+    xl = np.asarray(x, dtype=np.float64).astype(np.longdouble)
+    r = Al @ xl - np.asarray(b, dtype=np.float64).astype(np.longdouble)
+    sc = np.longdouble(scale)
+    f = sc * np.sum(r * r)
+    g = (2 * sc) * (Al.T @ r) if grad else None
+    del Al
+    absA = np.abs(A)
+    c = absA @ np.abs(np.asarray(x, dtype=np.float64)) + np.abs(np.asarray(b, dtype=np.float64))
+    u = 2.0 ** -53
+
+    def gamma(k):
+        return k * u / (1 - k * u)
+
+    # (the bounds are evaluated in fp64: their own rounding is far inside the safety factor)
+    g_bound = 2 * gamma(m + n + 2) * (2 * scale) * (absA.T @ c) if grad else None
+    f_bound = 2 * gamma(m + 2 * n + 6) * scale * float(c @ c)
+    return f, g, f_bound, g_bound
 
 
 def make_plasso(m_rows, n, seed=0, n_informative=20, noise=0.01, lam_frac=0.1):

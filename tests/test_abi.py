@@ -107,6 +107,9 @@ def test_short_output_buffers_are_refused():
     assert rc == -2 and cnt.value == 7
     rc = raw(lib.zf_solver_launch_counts, [P, P, I], C.addressof(dummy), _lib.ptr(iout), 0)
     assert rc == -2 and not iout.any()
+    # the least-squares plan query takes four values
+    rc = raw(lib.zf_solver_ls_plan, [P, P, I], C.addressof(dummy), _lib.ptr(iout), 3)
+    assert rc == -2 and b"fewer than 4" in lib.zf_last_error() and not iout.any()
     assert (np.frombuffer(dummy, dtype=np.uint8) == 0xA5).all(), "an entry point wrote through the handle before checking its arguments"
 
 

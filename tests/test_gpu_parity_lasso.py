@@ -63,28 +63,65 @@ def test_lasso_lr_sequence(golden):
     run.solver.close()
 
 
-@pytest.mark.parametrize("shape", [(3, 1), (7, 5), (64, 33), (33, 64), (129, 1000), (1000, 130),
-                                   (7, 32), (16, 128), (100, 96), (257, 2048)])
-def test_lasso_vs_oracle_shapes(shape):
-    """Odd / even n (scalar and 16-B VALU kernels), n % 32 == 0 (MFMA A^T r kernel, with
-    row counts that are / are not multiples of its 16-row step), tall and wide A."""
+def _solve_recording_plan(monkeypatch, prob, x0, kw):
+    """minimize_proximal_gradient on the native path, and the ls_plan() of the solver that ran it."""
+    from zfista_amd import minimize_proximal_gradient, proximal_gradient as pg
+
+    plans = []
+
+    class _Recorded(pg.NativeRun):
+        def __init__(self, *a, **k):
+            super().__init__(*a, **k)
+            plans.append(self.solver.ls_plan())
+
+    monkeypatch.setattr(pg, "NativeRun", _Recorded)
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        res = minimize_proximal_gradient(*prob.callbacks(), x0, **kw)
+    assert len(plans) == 1
+    return res, plans[0]
+
+
+def _lasso_vs_oracle(shape, monkeypatch, small, form):
     from oracle import cpu_ref, problems_ref as P
-    from zfista_amd import minimize_proximal_gradient
     from zfista_amd.problems import LeastSquaresL1
 
+    monkeypatch.delenv("ZF_GEMV_MFMA", raising=False)
+    if small:
+        monkeypatch.delenv("ZF_LS_SMALL", raising=False)
+    else:
+        monkeypatch.setenv("ZF_LS_SMALL", "0")
     m, n = shape
     A, b, lam = P.make_plasso(m, n, seed=4, n_informative=max(1, n // 4))
     prob, ref = LeastSquaresL1(A, b, lam, scale=0.5), P.LeastSquaresL1Ref(A, b, lam, scale=0.5)
     kw = dict(lr=1.0, nesterov=True, tol=1e-7, max_iter=60, return_all=True)
     x0 = np.zeros(n)
+    res, plan = _solve_recording_plan(monkeypatch, prob, x0, kw)
+    assert plan[0] == form, plan   # zf_solver_ls_plan: 1 small matrix, 2 MFMA, 3 VALU 16-B, 4 VALU scalar
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
-        res = minimize_proximal_gradient(*prob.callbacks(), x0, **kw)
         exp = cpu_ref.minimize_proximal_gradient(*ref.callbacks(), x0, **kw)
     assert res.nit == exp.nit
     for a, e in zip(res.allvecs, exp.allvecs):
         assert rel_err(a, e) <= TOL
     np.testing.assert_allclose(res.allfuns, exp.allfuns, rtol=TOL)
+
+
+@pytest.mark.parametrize("shape", [(3, 1), (7, 5), (64, 33), (33, 64), (129, 1000), (1000, 130),
+                                   (7, 32), (16, 128), (100, 96), (257, 2048)])
+def test_lasso_vs_oracle_shapes(shape, monkeypatch):
+    """Odd n (the scalar VALU A^T r kernel), even n (the 16-B VALU kernel) and n % 32 == 0 - which at these sizes
+    (m <= 4096, m n <= 2^22) the small-matrix kernels take, two launches per trial; tall and wide A.  The MFMA A^T r
+    kernel: test_lasso_vs_oracle_shapes_general_path."""
+    n = shape[1]
+    _lasso_vs_oracle(shape, monkeypatch, True, 1 if n % 32 == 0 else 4 if n % 2 else 3)
+
+
+@pytest.mark.parametrize("shape", [(33, 64), (7, 32), (16, 128), (100, 96), (257, 2048)])
+def test_lasso_vs_oracle_shapes_general_path(shape, monkeypatch):
+    """The n % 32 == 0 shapes above with the small-matrix form switched off (ZF_LS_SMALL=0): the MFMA A^T r kernel,
+    with row slices of 7 or 8 rows (its tail loop only) and a last slice shorter than the others."""
+    _lasso_vs_oracle(shape, monkeypatch, False, 2)
 
 
 def test_lasso_2048x8192_vs_oracle():

@@ -14,13 +14,14 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 
-@pytest.mark.parametrize("world,shape", [(2, (300, 1000)), (3, (129, 301)), (4, (64, 4096))])
+@pytest.mark.parametrize("world,shape", [(2, (300, 1000)), (3, (129, 301)), (4, (64, 4096)), (2, (1500, 256))])
 @pytest.mark.parametrize("nesterov", [False, True])
 def test_sharded_least_squares_lockstep(world, shape, nesterov):
     """Column-sharded LASSO: rank p holds A_p, x_p; per trial the ranks
     exchange the m-vector A_p x_p (C2) and the scalar pack (C1).  Two..four solver objects
     in lockstep on one GPU, collectives emulated by D2D copies; compared with the oracle on
-    the unsharded problem (tolerance 1e-10: the row sums are added in a different order)."""
+    the unsharded problem (tolerance 1e-10: the row sums are added in a different order).  (2, 1500 x 256): each rank
+    holds 1500 x 128 on the MFMA A^T r kernel, 24 rows per slice = 16 main + 8 tail, and a last slice of 12 rows."""
     import torch
 
     from conftest import rel_err
@@ -47,6 +48,8 @@ def test_sharded_least_squares_lockstep(world, shape, nesterov):
         s = DeviceSolver(fields, opts, keepalive=(Ap, bd))
         s.init_begin(x0.data_ptr())
         solvers.append(s)
+    if shape == (1500, 256):   # every rank: the MFMA sweep (form 2), 63 slices of 24 rows (zf_solver_ls_plan)
+        assert all(s.ls_plan() == (2, 2, 63, 24) for s in solvers)
 
     def exchange_svec():
         allp = torch.cat([s._s_part for s in solvers])

@@ -1720,6 +1720,20 @@ extern "C" int zf_solver_launch_counts(zf_solver* s, int64_t* out, int64_t count
     return ZF_OK;
 }
 
+// which least-squares kernels zf_solver_create chose for the passes of zf_solver_enqueue_steps (include/zfista_hip.h)
+extern "C" int zf_solver_ls_plan(zf_solver* s, int64_t* out, int64_t count) {
+    ZF_REQUIRE(s && out, "zf_solver_ls_plan: null argument");
+    ZF_REQUIRE(count >= 4, "zf_solver_ls_plan: the output holds fewer than 4 values");
+    out[0] = out[1] = out[2] = out[3] = 0;
+    if (s->desc.kind != ZF_PROBLEM_LEAST_SQUARES_L1) return ZF_OK;
+    const bool odd = s->desc.n % 2 != 0;
+    out[0] = s->ls_small ? 1 : s->gemv_mfma ? 2 : odd ? 4 : 3;
+    out[1] = s->ls_small ? 1 : odd ? 3 : 2;
+    out[2] = s->slices;
+    out[3] = s->rows_per_slice;
+    return ZF_OK;
+}
+
 extern "C" int zf_solver_sub_iters(zf_solver* s, int32_t* sub_iters) {
     ZF_REQUIRE(s && sub_iters, "zf_solver_sub_iters: null argument");
     *sub_iters = s->sub;

@@ -273,6 +273,14 @@ class DeviceSolver:
         _lib.check(self.lib.zf_solver_launch_counts(self.handle, C.c_void_p(_lib.ptr(out)), out.size))
         return int(out[0]), int(out[1])
 
+    def ls_plan(self):
+        """Least squares: (column-sweep form, row-sweep form, row slices, rows per slice) of the passes this solver
+        runs (zf_solver_ls_plan).  Column sweep: 0 not least squares, 1 small matrix, 2 MFMA, 3 VALU 16-byte loads,
+        4 VALU scalar loads; row sweep: 1 the small-matrix rows kernel, 2 zf_gemv_rows_kernel<2>, 3 <1>."""
+        out = np.zeros(4, dtype=np.int64)
+        _lib.check(self.lib.zf_solver_ls_plan(self.handle, C.c_void_p(_lib.ptr(out)), out.size))
+        return tuple(int(v) for v in out)
+
     def runahead_counts(self):
         """(run-ahead passes launched, those of them launched while their predecessor was still in flight) since the
         solver was created (zf_runahead_kernel: consecutive full chains on two streams)."""
