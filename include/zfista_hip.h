@@ -275,7 +275,10 @@ int zf_solver_flush(zf_solver* s);
 /* world > 1 with a communicator attached: the solver issues the exchanges of a sharded step itself
  * (packed all-gather of the scalar packs; for column-sharded least squares also of A_p x_p) on its
  * stream - zf_solver_enqueue_steps then works for world > 1 and a pass needs no host code.
- * zf_solver_enqueue_init_all = init + exchanges + commit in one call (world == 1 too). */
+ * zf_solver_enqueue_init_all = init + exchanges + commit in one call (world == 1 too).
+ * Call it BEFORE zf_solver_enqueue_init / _init_all / zf_solver_restore: a one-rank solver may grow its iterate ring for
+ * passes ahead here; once an initialisation is enqueued, a call that would grow it is refused with ZF_ERR_STATE (nothing
+ * attached). */
 int zf_solver_set_comm(zf_solver* s, zf_comm* comm);
 int zf_solver_enqueue_init_all(zf_solver* s, const double* x0_dev);
 /* world > 1 without one: the two halves of a step; the caller gathers pack_local -> pack_all between them */
@@ -343,7 +346,10 @@ int zf_solver_trial_kernel_ms(zf_solver* s, double* avg_ms, int64_t* launches);
  * With count >= 10: out[8] = passes launched AHEAD at kernel granularity, out[9] = those of them void: sharded solves through
  * the library's communicator (and, ZF_AHEAD_UNSHARDED=1, unsharded grids the run-ahead kernel does not take) run the trial
  * kernels of consecutive exactly predicted full / mid chains back to back on the solver's stream, each on the head the host
- * expects, while finalisation, all-gather and decide of the pass before run on the second stream (ZF_AHEAD=0: off). */
+ * expects, while finalisation, all-gather and decide of the pass before run on the second stream (ZF_AHEAD=0: off).
+ * With count >= 12, as of the last zf_solver_poll: out[11] = second passes of a run (of either scheme) whose first pass
+ * started behind a pass that broke unseen and left on a head that did not come true; they run no body (the buffers they
+ * would write hold the real x_k, x_{k-1} then). */
 int zf_solver_launch_counts(zf_solver* s, int64_t* out, int64_t count /* >= 2 */);
 /* least squares: the kernels the passes of zf_solver_enqueue_steps run, fixed at zf_solver_create.  out[0] = the column
  * sweep A^T r: 0 not least squares, 1 the small-matrix step kernel (zf_ls_small_step_kernel), 2 the MFMA sweep

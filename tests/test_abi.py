@@ -107,6 +107,13 @@ def test_short_output_buffers_are_refused():
     assert rc == -2 and cnt.value == 7
     rc = raw(lib.zf_solver_launch_counts, [P, P, I], C.addressof(dummy), _lib.ptr(iout), 0)
     assert rc == -2 and not iout.any()
+    # ... and writes exactly `count` values, at most 12 (out[11]: second passes of a run behind a void first one) - it only
+    # copies counters out of the handle, so the patterned region serves as one
+    wide = np.full(14, -7, dtype=np.int64)
+    for count, written in ((11, 11), (12, 12), (13, 12)):
+        wide[:] = -7
+        rc = raw(lib.zf_solver_launch_counts, [P, P, I], C.addressof(dummy), _lib.ptr(wide), count)
+        assert rc == 0 and (wide[:written] != -7).all() and (wide[written:] == -7).all(), (count, wide)
     # the least-squares plan query takes four values
     rc = raw(lib.zf_solver_ls_plan, [P, P, I], C.addressof(dummy), _lib.ptr(iout), 3)
     assert rc == -2 and b"fewer than 4" in lib.zf_last_error() and not iout.any()

@@ -160,6 +160,18 @@ def test_passes_ahead_on_an_unsharded_grid_of_several_rounds(monkeypatch):
             assert got["report"]["ahead"] >= 2 and got["report"]["runahead"] == 0
 
 
+# Thread ranks share one device: their sharded run-ahead passes need every rank's grid to be a few workgroups (two passes
+# of every rank resident at once).  The void-pass cases at a total n <= 10^5: a termination inside a chain, rejections
+# first, and a long run to the end of what the acceptance test resolves.  (At this size the chains of this problem do not
+# break at the noise floor - 4000 iterations on 2 and 3 ranks, every trial accepted: the iterates reach their fixed point
+# first - so the long run ends where its steps fall below tol = 1e-12, inside a chain.)
+SMALL_CASES = {
+    3: (99_991, dict(lr=0.45, nesterov=True, tol=1e-7, max_iter=5000), None),
+    4: (99_991, dict(lr=16.0, nesterov=True, tol=0.0, max_iter=150), None),
+    5: (99_991, dict(lr=0.45, nesterov=True, tol=1e-12, max_iter=4000), None),
+}
+
+
 @pytest.mark.parametrize("world", [1, 2, 3])
 @pytest.mark.parametrize("case", range(len(CASES)))
 def test_sharded_run_ahead_passes_equal_sequential_passes(case, world, monkeypatch):
@@ -167,10 +179,10 @@ def test_sharded_run_ahead_passes_equal_sequential_passes(case, world, monkeypat
     all-gather + decide of pass p on a third stream beside the workgroups of pass p + 1.  The results of one pass at a time,
     bit for bit, whatever the chunking; every rank launches the same passes.  World 1 = the 1-rank RCCL communicator; thread
     ranks (several ranks of ONE device - by default they keep to passes ahead) only with grids of a few workgroups, all
-    of which the device holds at once."""
-    n, opts, bounds = CASES[case]
-    if world > 1 and n > 100_000:
-        pytest.skip("thread ranks share one device: their run-ahead passes would wait for workgroups that have no slot")
+    of which the device holds at once: the cases of more than 10^5 unknowns - the void passes - run at small n there
+    (SMALL_CASES)."""
+    n, opts, bounds = CASES[case] if world == 1 else SMALL_CASES.get(case, CASES[case])
+    assert world == 1 or n <= 100_000, "thread ranks share one device: every rank's grid must be a few workgroups"
     x0 = np.zeros(n) if case % 2 == 0 else np.random.default_rng(case).standard_normal(n)
     monkeypatch.setenv("ZF_RUNAHEAD_SHARDED", "0")
     monkeypatch.setenv("ZF_AHEAD", "0")
@@ -299,3 +311,127 @@ def test_two_unsharded_solvers_share_one_gpu(monkeypatch):
         assert rep["runahead"] >= 1
         assert rep["runahead_off"] == (rep["timeouts"] > 0)
         r.solver.close()
+
+
+# Every scheduler that can start a run of passes in the middle of a chunk, on a head the host PREDICTS: (world - 0 for no
+# communicator, 1 for the one-rank RCCL communicator, 2 / 3 thread ranks -, environment, box)
+RUN_SCHEDULERS = {
+    "ahead_rccl": (1, {"ZF_RUNAHEAD_SHARDED": "0"}, None),   # sharded passes ahead
+    "ahead_threads2": (2, {}, None),                            # (thread ranks keep to passes ahead by default)
+    "ahead_threads3": (3, {}, None),
+    "runahead_rccl": (1, {}, None),                             # sharded run-ahead passes
+    "runahead": (0, {}, None),                                  # unsharded run-ahead passes
+    "mixed": (0, {"ZF_AHEAD_UNSHARDED": "1"}, None),            # both unsharded schemes on
+    "mixed_box": (0, {"ZF_AHEAD_UNSHARDED": "1"}, (-0.3, 0.4)),  # ... on a clipped problem
+}
+
+
+@pytest.mark.parametrize("sched", list(RUN_SCHEDULERS))
+def test_runs_that_start_behind_a_pass_that_broke_unseen(sched, monkeypatch):
+    """A run that starts in the middle of a chunk - where the step counter wraps (the streams are joined there), where the
+    unsharded schemes meet - starts on the head the host predicts.  With lr = 16 the line search cuts the step inside the
+    first chunk: its first pass breaks, every pass the host predicted behind it is void, and the wrap (j steps after
+    0x7ffffff0 - j) falls behind that break for every j >= 1.  The first pass of the new run leaves on its head; the
+    SECOND one, on the head predicted behind the first, would write the buffers that hold the real x_k, x_{k-1} (six
+    buffers, two per pass: every third alignment) unless it finds the first void.  16 k + 26 iterations: k full chains and
+    a shared tail of two mid chains, so that the pass that broke is followed by at least two exactly predicted chains.
+    Bit for bit what one pass at a time computes, for chunks 64 and 3, and the device saw the dangerous state."""
+    world, env, bounds = RUN_SCHEDULERS[sched]
+    n, seed = 300_001, 83
+
+    def solve(chunk):
+        if world == 0:
+            from zfista_amd.problems import DiagQuadL1
+
+            d, c, lam = _data(n, seed)
+            return [_solve(DiagQuadL1(d, c, lam, bounds=bounds), np.zeros(n), opts, chunk=chunk)]
+        return _sharded(world, n, seed, opts, chunk, bounds)
+
+    seen = launched = 0
+    for max_iter in (16 * 1 + 26, 16 * 4 + 26):   # (the tail right behind the first full chain; three more in between)
+        opts = dict(lr=16.0, nesterov=True, tol=0.0, max_iter=max_iter)
+        for k in ("ZF_PASS_SEQ_START", *env):
+            monkeypatch.delenv(k, raising=False)
+        monkeypatch.setenv("ZF_AHEAD", "0")
+        monkeypatch.setenv("ZF_RUNAHEAD", "0")
+        ref = solve(64)
+        assert all(r["report"]["ahead"] == 0 and r["report"]["runahead"] == 0 for r in ref)
+        assert ref[0]["trials"] > ref[0]["nit"], "the line search was expected to cut the step"
+        monkeypatch.delenv("ZF_AHEAD")
+        monkeypatch.delenv("ZF_RUNAHEAD")
+        for k, v in env.items():
+            monkeypatch.setenv(k, v)
+        for j in range(9):
+            monkeypatch.setenv("ZF_PASS_SEQ_START", str(0x7ffffff0 - j))
+            for chunk in (64, 3):
+                got = solve(chunk)
+                for r in range(len(got)):
+                    _same(got[r], ref[r])
+                    assert got[r]["report"] == got[0]["report"], "every rank launches the same passes"
+                    assert got[r]["report"]["timeouts"] == 0
+                rep = got[0]["report"]
+                launched += rep["ahead"] + rep["runahead"]
+                seen += rep["second_void"]
+    assert launched >= 2 * 9 * 2, "passes ahead of their predecessor's decision were expected"
+    # the dangerous state was reached: a run whose first pass left on its head had a second pass
+    assert seen >= 1, "no run had a second pass behind a first one that left on its head"
+
+
+def test_set_comm_after_an_enqueued_initialisation_is_refused(monkeypatch):
+    """zf_solver_set_comm grows the iterate ring of a one-rank solver from four to six buffers (passes ahead need them).
+    After zf_solver_enqueue_init that would drop the x0 already copied into the ring: refused, nothing attached - and the
+    solver goes on as if set_comm had not been called.  Attached first, the solve runs with passes ahead, bit for bit as
+    one pass at a time."""
+    import ctypes as C
+
+    import torch
+
+    from zfista_amd import _lib
+    from zfista_amd.comm import LibComm
+    from zfista_amd.engine import DeviceSolver
+    from zfista_amd.problems import DiagQuadL1
+
+    n = 300_001
+    d, c, lam = _data(n, 41)
+    opts = dict(lr=0.45, nesterov=True, tol=0.0, max_iter=16 * 3 + 26)
+    monkeypatch.setenv("ZF_RUNAHEAD", "0")   # (a one-rank solver of four buffers: nothing runs ahead without a communicator)
+    ref = _solve(DiagQuadL1(d, c, lam), np.zeros(n), opts)
+    assert ref["report"]["ahead"] == 0 and ref["report"]["runahead"] == 0
+    comm = LibComm(0, 1, LibComm.new_unique_id())
+    try:
+        refused = []
+
+        def late_comm(fields, options, problem, x0):
+            s = DeviceSolver(fields, options, keepalive=problem._descriptor()[1])
+            x0_dev = torch.from_numpy(np.ascontiguousarray(x0, dtype=np.float64)).cuda()
+            s.init_begin(x0_dev.data_ptr())
+            rc = s.lib.zf_solver_set_comm(s.handle, comm.handle)
+            refused.append((rc, s.lib.zf_last_error()))
+            s.init_commit()
+            t = C.c_int32(1)
+            _lib.check(s.lib.zf_solver_autotune(s.handle, C.byref(t)), "geometry")
+            torch.cuda.current_stream().synchronize()
+            return s
+
+        from zfista_amd.proximal_gradient import NativeRun
+
+        o = dict(BASE, **opts, sub_iters=16)
+        run = NativeRun(DiagQuadL1(d, c, lam), np.zeros(n), o, solver_factory=late_comm)
+        rows = [np.zeros((0, _lib.ZF_TRACE_COLS))]
+        while run.status == _lib.ZF_RUNNING:
+            rows.append(run.advance(64))
+        ctl = run.solver.ctl
+        late = dict(rows=np.concatenate(rows), x=run.solver.get_x(), xp=run.solver.get_x_prev(), nit=int(ctl.nit),
+                    status=int(ctl.status), lr=ctl.lr, F=ctl.F_old, trials=int(ctl.total_trials))
+        rep = run.solver.ahead_report()
+        run.solver.close()
+        (rc, msg), = refused
+        assert rc == -3 and b"zf_solver_set_comm: call before zf_solver_enqueue_init" in msg, (rc, msg)
+        _same(late, ref)   # x0 kept, one pass at a time
+        assert rep["ahead"] == 0 and rep["runahead"] == 0
+    finally:
+        comm.close()
+    # attached before the initialisation: six buffers, passes ahead through the communicator, the same bits
+    got = _sharded(1, n, 41, opts, 64)[0]
+    _same(got, ref)
+    assert got["report"]["ahead"] >= 2, got["report"]

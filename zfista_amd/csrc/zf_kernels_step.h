@@ -303,13 +303,15 @@ struct zf_step_args {
     // is still finalising - workgroup j waits for workgroup j of the predecessor only (ra_flags), runs on the control
     // block the host EXPECTS (ra_head), and its deciding wave accepts the pass only if every pass since the last
     // one that was verified against the real block turned out as expected (ra_word)
-    unsigned long long* ra_word;   // done_seq << 32 | good_seq: the last pass decided (or voided) / the last that matched its prediction
+    unsigned long long* ra_word;   // done_seq << 32 | good_seq: the last pass decided (or voided) / the last that matched its prediction;
+                                   // [1]: the step number of the last first pass of a run that left on its head (zf_first_pass_left)
     unsigned* ra_flags;            // [grid] pass_seq of the last pass whose workgroup j has stored its iterates; [grid + (pass_seq & 3)]: poison (a wait of that pass timed out)
     int ra_wait;                   // pass_seq of the predecessor in flight on the other stream (0: nothing in flight - the block is read)
     int ra_need;                   // entry: good_seq must have reached this pass_seq (the pass whose inputs this one overwrites); 0: no condition
     unsigned ra_spin;              // polls before a wait gives up (the pass is then void)
     zf_pass_head ra_head;          // the head of this pass by the host's account (beta_next: unused - taken from the momentum ring)
-    unsigned* ra_stats;            // [0] waits of run-ahead workgroups that gave up, [1] void run-ahead passes, [2] void passes AHEAD (below); polled with the control block
+    unsigned* ra_stats;            // [0] waits of run-ahead workgroups that gave up, [1] void run-ahead passes, [2] void passes AHEAD (below),
+                                   // [3] second passes of a run whose first pass left on its head (they run no body); polled with the control block
     // Passes AHEAD of their predecessor's decision at KERNEL granularity (zf_trial_kernel<..., AHEAD>; sharded solves and
     // grids of more than one round): the trial kernel takes its head from ra_head - the control block may be being
     // decided on the other stream - stores its row plainly (row-major, fin_mode 2) and retires; zf_tail_kernel on the
@@ -1308,6 +1310,25 @@ __device__ __forceinline__ void zf_pass_finish(const zf_step_args& A, const doub
     zf_pass_tail<SP>(A, v);
 }
 
+// The first pass of a run (either scheme: ra_wait == 0) left on a head that did not come true.  One thread publishes
+// done = its step number with the good word as it is - what its decide step publishes as well: the pass behind it finds it
+// void whichever of the two stores it sees - and, before that, ra_word[1] = its step number (only such a pass writes it;
+// cleared with the word where the step counter wraps).
+__device__ __forceinline__ void zf_first_pass_left(unsigned long long* ra_word, int pass_seq) {
+    __hip_atomic_store(ra_word + 1, (unsigned long long)(unsigned)pass_seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const unsigned long long W = __hip_atomic_load(ra_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(ra_word, ((unsigned long long)(unsigned)pass_seq << 32) | (unsigned)W, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// The second pass of a run found its first one (ra_wait) void in the word: counted for the poll (ra_stats[3]) when that
+// pass LEFT on its head - not when it ran and its decide step voided it, which a second pass may or may not see in time
+// (the count is the same on every rank).  One thread.
+__device__ __forceinline__ void zf_count_second_behind_left(unsigned long long* ra_word, unsigned* ra_stats, int ra_wait) {
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    if (__hip_atomic_load(ra_word + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (unsigned long long)(unsigned)ra_wait)
+        __hip_atomic_fetch_add(ra_stats + 3, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 // PART (chains only, S > 1): the bodies of a pass live in separate kernels, each of which exits at once unless the
 // pass has its shape (zf_pass_claims) -
 //   0: the full chain (nothing replayed, S fresh trials: the hot, branch-free body);
@@ -1324,7 +1345,7 @@ __device__ __forceinline__ void zf_pass_finish(const zf_step_args& A, const doub
 // head is the one the host expects (A.ra_head; nothing lagging, exactly the kernel's chain length) - the control block
 // is not read at all: the decide step of the pass before may be writing it on the other stream right now.  It leaves at
 // once when the pass two before it - whose inputs it would overwrite - did not go as expected (ra_need against the good
-// word), stores its row plainly (row-major) and retires: zf_tail_kernel on the second stream adds the rows, and the
+// word; the second pass of a run: when the first left on its head, ra_wait against the done / good word), stores its row plainly (row-major) and retires: zf_tail_kernel on the second stream adds the rows, and the
 // deciding wave there checks the block against this head before it decides (a pass on a wrong head is VOID).
 // RES: the kernels of a solver with ZF_ACCEPT_RESOLVED (zf_elem_diag<..., RES>).
 template <bool GRAD_INLINE, bool NESTEROV, bool BOX, bool NT, int S, bool HIST = false, int PART = 0, int L = 0, bool AHEAD = false,
@@ -1347,13 +1368,30 @@ __global__ __launch_bounds__(ZF_BLOCK) void zf_trial_kernel(zf_step_args A) {
             // The FIRST pass of a run: nothing is in flight (the host joined its streams), so the block may be read - and must
             // be: the host's head is a prediction, and a run that starts in the middle of a chunk (behind passes of the other
             // scheme, behind a chain that broke unseen) would otherwise write its iterates over what may be the real x_k.
-            // On a head that did not come true the pass leaves; its decide step finds the mismatch and voids it.
+            // On a head that did not come true the pass leaves; its decide step finds the mismatch and voids it.  Leaving, it
+            // publishes done = its step number with the good word as it is (what that decide step will publish too): the
+            // pass behind it on this stream reads it before that decide step may have run (below).
             const zf_control* c = A.ctl;
             constexpr int LEN0 = PART == 3 ? L : S;
             const zf_pass_head& q = A.ra_head;
             if (!(c->status == ZF_RUNNING && c->pend_status == 0 && c->lag == 0 && c->nit == q.nit && c->lr == q.lr && c->cur == q.cur &&
-                  c->prev == q.prev && zf_fresh_len(c) == LEN0))
+                  c->prev == q.prev && zf_fresh_len(c) == LEN0)) {
+                if (blockIdx.x == 0 && threadIdx.x == 0) zf_first_pass_left(A.ra_word, A.pass_seq);   // (every decide step so far is done)
                 return;
+            }
+        } else {
+            // The SECOND pass of a run (ra_wait: the first, right in front of it on this stream; no pass two before it in the
+            // run, so no ra_need).  When the first left on a head that did not come true, the real x_k, x_{k-1} are still in
+            // the buffers the pass before the run read - the ones this pass, on the head predicted behind the first, would
+            // write.  It leaves too.  Invariant: done >= ra_wait with good < ra_wait means pass ra_wait is void, whichever
+            // store this load sees - the first pass's own as it left (it precedes this kernel on the stream), or its decide
+            // step's (the same done; a void pass never raises good); the word is cleared where the step counter wraps.  A
+            // first pass that ran is void only if its decide step says so, and then this pass is void as well.
+            const unsigned long long W = __hip_atomic_load(A.ra_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if ((int)(W >> 32) >= A.ra_wait && (int)(unsigned)W < A.ra_wait) {
+                if (blockIdx.x == 0 && threadIdx.x == 0) zf_count_second_behind_left(A.ra_word, A.ra_stats, A.ra_wait);
+                return;
+            }
         }
         zf_pass_head HA = A.ra_head;
         HA.beta_next = NESTEROV ? A.beta_ring[HA.nit % ZF_RING] : 0.0;   // (zf_resolve_beta with nothing lagging)
@@ -1442,8 +1480,7 @@ __global__ __launch_bounds__(ZF_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2))
                           c->cur == HD.cur && c->prev == HD.prev && zf_fresh_len(c) == LEN;
         if (!same) {   // (every workgroup finds the same) - decided: void; a pass launched behind this one must not wait for it
             if (b == 0 && threadIdx.x == 0) {
-                const unsigned long long W = __hip_atomic_load(A.ra_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(A.ra_word, ((unsigned long long)(unsigned)A.pass_seq << 32) | (unsigned)W, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                zf_first_pass_left(A.ra_word, A.pass_seq);
                 __hip_atomic_fetch_add(A.ra_stats + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
             return;
@@ -1465,6 +1502,7 @@ __global__ __launch_bounds__(ZF_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2))
                     if ((k & 15) == 15) {
                         W = __hip_atomic_load(A.ra_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                         if ((int)(W >> 32) >= A.ra_wait && (int)(unsigned)W < A.ra_wait) {   // the predecessor is void
+                            if (A.ra_need == 0 && b == 0) zf_count_second_behind_left(A.ra_word, A.ra_stats, A.ra_wait);   // (the second pass of a run)
                             go = 2;
                             break;
                         }

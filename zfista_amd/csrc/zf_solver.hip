@@ -189,6 +189,7 @@ struct zf_solver {
     int slices = 1;
     int64_t rows_per_slice = 0;
     bool initialised = false;
+    bool init_enqueued = false;   // zf_solver_enqueue_init(_all) ran: x0 is in the ring (zf_solver_set_comm may no longer reallocate it)
     bool own_packs = true;
     bool gemv_mfma = false;       // A^T r on v_mfma_f64_16x16x4 (n % 32 == 0; ZF_GEMV_MFMA=0 disables)
     bool ls_small = false;        // cache-resident A: two fused launches per trial (zf_kernels_ls_small.h)
@@ -263,12 +264,13 @@ struct zf_solver {
     unsigned* fin_cnt2 = nullptr;
     double* pack2 = nullptr;
     int64_t ra_passes = 0, ra_ahead = 0;  // run-ahead kernels launched / of them behind a pass still in flight (zf_solver_launch_counts)
-    // What the device reports about passes that ran ahead: three counters in the slack of the control block's slot,
+    // What the device reports about passes that ran ahead: four counters in the slack of the control block's slot,
     // copied with every poll - [0] waits that gave up (a run-ahead workgroup's, or a deciding wave's), [1] void run-ahead
-    // passes, [2] void passes AHEAD (below).  After the first wait that gave up the solver launches no further run-ahead
-    // passes (ra_off): the device is being shared, and every such wait costs its whole limit.
+    // passes, [2] void passes AHEAD (below), [3] second passes of a run (either scheme) whose first pass left on a head
+    // that did not come true (they run no body).  After the first wait that gave up the solver launches no further
+    // run-ahead passes (ra_off): the device is being shared, and every such wait costs its whole limit.
     unsigned* ra_stats = nullptr;         // = ctl_trace + ZF_STATS_OFF
-    int64_t ra_timeouts = 0, ra_voids = 0, ah_voids = 0;   // as of the last poll
+    int64_t ra_timeouts = 0, ra_voids = 0, ah_voids = 0, second_voids = 0;   // as of the last poll
     bool ra_off = false;
     // Passes AHEAD at kernel granularity (zf_trial_kernel<..., AHEAD>, zf_tail_kernel, zf_decide_ahead_kernel): sharded
     // solves through the library's communicator, and (ZF_AHEAD_UNSHARDED) unsharded grids of more than one round.  The
@@ -1484,6 +1486,7 @@ extern "C" int zf_solver_set_svec_buffers(zf_solver* s, double* s_part_dev, doub
 
 extern "C" int zf_solver_enqueue_init(zf_solver* s, const double* x0_dev) {
     ZF_REQUIRE(s && x0_dev, "zf_solver_enqueue_init: null argument");
+    s->init_enqueued = true;
     s->shadow_valid = false;   // (the control block changes behind the host's back: predict again after the next poll)
     const zf_problem_desc& d = s->desc;
     const int64_t n = d.n;
@@ -1717,6 +1720,7 @@ extern "C" int zf_solver_launch_counts(zf_solver* s, int64_t* out, int64_t count
         out[9] = s->ah_voids;
     }
     if (count >= 11) out[10] = s->ra_off ? 1 : 0;   // run-ahead passes were switched off for this solver after a wait gave up
+    if (count >= 12) out[11] = s->second_voids;      // second passes of a run whose first pass left on its head, as of the last poll
     return ZF_OK;
 }
 
@@ -1778,6 +1782,13 @@ extern "C" int zf_solver_set_comm(zf_solver* s, zf_comm* comm) {
     int rc = zf_comm_info(comm, &rank, &world);
     if (rc) return rc;
     ZF_REQUIRE(rank == s->desc.rank && world == s->desc.world, "zf_solver_set_comm: rank / world differ from the problem descriptor");
+    // passes ahead of their predecessor's decision (zf_launch_ahead) need six iterate buffers: a one-rank solver created with
+    // four grows its ring here - which would lose the x0 an enqueued initialisation has already copied into it (and leave the
+    // device's control block with the old ring size).  Refused, nothing attached: the caller attaches first, then initialises.
+    if (s->ah && s->ring < 6 && (s->init_enqueued || s->initialised))
+        return zf_fail(ZF_ERR_STATE, "zf_solver_set_comm: call before zf_solver_enqueue_init / zf_solver_enqueue_init_all / "
+                                     "zf_solver_restore (attaching a communicator grows the iterate ring, which holds x0 once the "
+                                     "initialisation is enqueued)%s");
     s->comm = comm;
     {   // Thread ranks (the in-process group: several ranks of ONE device) do not hold two passes of every rank at once - sharded
         // run-ahead passes would wait for workgroups that have no slot (correct, counted, switched off at the first poll, but
@@ -2068,6 +2079,7 @@ extern "C" int zf_solver_poll(zf_solver* s, zf_control* ctl_host, int64_t ctl_by
         s->ra_timeouts = st[0];
         s->ra_voids = st[1];
         s->ah_voids = st[2];
+        s->second_voids = st[3];
         if (s->ra_timeouts > 0) s->ra_off = true;
     }
     return zf_collect_timing(s, with_log);

@@ -294,11 +294,12 @@ class DeviceSolver:
         ``timeouts`` (waits that gave up: the device did not hold two passes of this solver at once), ``void`` (run-ahead
         passes that did not count), ``runahead_off`` (the solver stopped launching them after a wait gave up),
         ``ahead`` / ``ahead_void`` (passes ahead at kernel granularity: sharded solves through the library's
-        communicator)."""
-        out = np.zeros(11, dtype=np.int64)
+        communicator), ``second_void`` (second passes of a run of either scheme that found the first one void - it left
+        on a head that did not come true - and ran no body)."""
+        out = np.zeros(12, dtype=np.int64)
         _lib.check(self.lib.zf_solver_launch_counts(self.handle, C.c_void_p(_lib.ptr(out)), out.size))
         return dict(runahead=int(out[4]), runahead_overlapped=int(out[5]), timeouts=int(out[6]), void=int(out[7]),
-                    ahead=int(out[8]), ahead_void=int(out[9]), runahead_off=bool(out[10]))
+                    ahead=int(out[8]), ahead_void=int(out[9]), runahead_off=bool(out[10]), second_void=int(out[11]))
 
     def pass_stats_ex(self):
         """pass_stats() plus (fresh trials, replayed iterations) the other passes carried in total."""
