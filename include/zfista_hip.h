@@ -356,7 +356,11 @@ int zf_solver_launch_counts(zf_solver* s, int64_t* out, int64_t count /* >= 2 */
  * (zf_gemvT_partial_mfma_kernel), 3 the VALU sweep with 16-byte loads (zf_gemvT_partial_kernel<2>), 4 with scalar loads
  * (<1>); out[1] = the row sweep A x+: 1 zf_ls_small_rows_kernel, 2 zf_gemv_rows_kernel<2>, 3 <1>; out[2] = row slices
  * of the general column sweep, out[3] = rows per slice (the last slice may be shorter).
- * (A host-driven trial - zf_solver_enqueue_trial - always takes the general path.) */
+ * (A host-driven trial - zf_solver_enqueue_trial - always takes the general path.)
+ * The operator problem (ZF_PROBLEM_BLUR_HAAR_L1) reports its plan in the same four slots: out[0] = tile height (8 or 32
+ * rows), out[1] = 1 the separable (rank-1) correlation / 0 the general one, out[2] = 1 workgroups walk their tiles /
+ * 0 one workgroup per tile, out[3] = 1 the prox step runs in the adjoint kernel's epilogue / 0 a launch of its own.
+ * Other problems: zeros. */
 int zf_solver_ls_plan(zf_solver* s, int64_t* out, int64_t count /* >= 4 */);
 /* the same window split by the shape of the pass, which the kernel logs itself: out[0], out[1] = mean
  * ms and count of full chains (sub_iters fresh trials, nothing replayed); out[2], out[3] = every other

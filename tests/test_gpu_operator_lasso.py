@@ -21,6 +21,26 @@ CASES = {
 }
 
 
+def _solve_recording_plan(monkeypatch, prob, x0, kw):
+    """minimize_proximal_gradient on the native path, and the ls_plan() of the solver that ran it: (tile height,
+    1 separable / 0 general, 1 workgroups walk their tiles / 0 one per tile, 1 fused prox step / 0 a launch of its own)."""
+    from zfista_amd import minimize_proximal_gradient, proximal_gradient as pg
+
+    plans = []
+
+    class _Recorded(pg.NativeRun):
+        def __init__(self, *a, **k):
+            super().__init__(*a, **k)
+            plans.append(self.solver.ls_plan())
+
+    monkeypatch.setattr(pg, "NativeRun", _Recorded)
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        res = minimize_proximal_gradient(*prob.callbacks(), x0, **kw)
+    assert len(plans) == 1
+    return res, plans[0]
+
+
 def _problem(size):
     from oracle import operator_ref as O
     from zfista_amd.problems import BlurHaarL1
@@ -98,7 +118,6 @@ def test_beyond_the_notebook_size_and_every_kernel_path(variant, monkeypatch):
     right and bottom edges, a kernel that is NOT separable, the separable kernel forced through the general path
     (ZF_OP_SEPARABLE=0), and the degenerate 1 x 1 kernel (zero-padded to 3 x 3)."""
     from oracle import cpu_ref, operator_ref as O
-    from zfista_amd import minimize_proximal_gradient
     from zfista_amd.problems import BlurHaarL1
 
     rng = np.random.default_rng(11)
@@ -128,9 +147,11 @@ def test_beyond_the_notebook_size_and_every_kernel_path(variant, monkeypatch):
     ref = O.BlurHaarL1Ref(kernel, observed, l1_ratio=lam)
     prob = BlurHaarL1(kernel, observed, lam)
     kw = dict(lr=1 / L, decay_rate=1, nesterov=True, tol=0.0, max_iter=iters, return_all=True)
+    res, plan = _solve_recording_plan(monkeypatch, prob, x0, kw)
+    if variant in ("separable", "general_same_kernel"):
+        assert plan[1] == (1 if variant == "separable" else 0), plan   # the path this case is about ran
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
-        res = minimize_proximal_gradient(*prob.callbacks(), x0, **kw)
         exp = cpu_ref.minimize_proximal_gradient(*ref.callbacks(), x0, **kw)
     assert res.nit == exp.nit == iters
     for k in range(1, iters + 1):
@@ -149,7 +170,6 @@ def test_prox_step_in_the_adjoint_kernel_equals_a_launch_of_its_own(case, monkey
     expression on the same values - only the order in which its four sums are added differs), same decisions, and both equal
     the oracle."""
     from oracle import cpu_ref, operator_ref as O
-    from zfista_amd import minimize_proximal_gradient
     from zfista_amd.problems import BlurHaarL1
 
     rng = np.random.default_rng(11)
@@ -171,12 +191,11 @@ def test_prox_step_in_the_adjoint_kernel_equals_a_launch_of_its_own(case, monkey
     x0 = O.dwt(observed)
     if bounds is not None:
         x0 = np.clip(x0, *bounds)
-    out = {}
+    out, plan = {}, {}
     for fuse in ("1", "0"):
         monkeypatch.setenv("ZF_OP_FUSE_PROX", fuse)
-        with warnings.catch_warnings():
-            warnings.simplefilter("ignore")
-            out[fuse] = minimize_proximal_gradient(*prob.callbacks(), x0, **kw)
+        out[fuse], plan[fuse] = _solve_recording_plan(monkeypatch, prob, x0, kw)
+    assert plan["1"] != plan["0"] and plan["1"][3] == 1 and plan["0"][3] == 0, plan   # both trials really ran
     a, b = out["1"], out["0"]
     assert a.nit == b.nit and a.status == b.status
     assert rel_err(a.x, b.x) <= 1e-13
@@ -196,7 +215,6 @@ def test_workgroups_that_walk_their_tiles_with_partial_tiles_at_the_edges(ksize,
     a workgroup walks several tiles, the apply kernel with the next tile's coefficients in flight.  ZF_OP_PERSIST=0 (a
     workgroup per tile) adds the same shares in the same order: bit-identical; both equal the oracle."""
     from oracle import cpu_ref, operator_ref as O
-    from zfista_amd import minimize_proximal_gradient
     from zfista_amd.problems import BlurHaarL1
 
     rng = np.random.default_rng(23)
@@ -208,12 +226,11 @@ def test_workgroups_that_walk_their_tiles_with_partial_tiles_at_the_edges(ksize,
     prob = BlurHaarL1(kernel, observed, 0.02)
     x0 = O.dwt(observed)
     kw = dict(lr=0.5, nesterov=True, tol=0.0, max_iter=5)
-    out = {}
+    out, plan = {}, {}
     for mode in ("1", "0"):
         monkeypatch.setenv("ZF_OP_PERSIST", mode)
-        with warnings.catch_warnings():
-            warnings.simplefilter("ignore")
-            out[mode] = minimize_proximal_gradient(*prob.callbacks(), x0, **kw)
+        out[mode], plan[mode] = _solve_recording_plan(monkeypatch, prob, x0, kw)
+    assert plan["1"] != plan["0"] and plan["1"][2] == 1 and plan["0"][2] == 0, plan   # both launch geometries really ran
     assert np.array_equal(out["1"].x, out["0"].x) and np.array_equal(np.asarray(out["1"].fun), np.asarray(out["0"].fun))
     ref = O.BlurHaarL1Ref(kernel, observed, l1_ratio=0.02)
     with warnings.catch_warnings():

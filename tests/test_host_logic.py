@@ -6,8 +6,10 @@
   result assembly, warnings, error results) driven by tests/fake_engine.FakeSolver,
   compared with the oracle and the golden vectors of the reference."""
 import ctypes as C
+import glob
 import json
 import os
+import re
 import warnings
 
 import numpy as np
@@ -390,3 +392,87 @@ def test_chained_passes_do_not_change_results(case):
         # a rejection costs at most the pass it was found in, never a second one: the accepted
         # prefix of a broken chain counts (zf_control.lag), + 1 materialise-only pass at the end
         assert r["passes"] <= -(-ref["nit"] // sub) + (ref["trials"] - ref["nit"]) + 2, (sub, r["passes"])
+
+
+# ---- the environment switches: one reader, one list ------------------------------------------------------------------
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+_C_SUFFIXES = (".hip", ".h", ".hpp", ".cpp", ".cc", ".c")
+_C_ENV = re.compile(r'getenv\(\s*"(ZF_\w+)"')
+_PY_ENV = re.compile(r"""(?:os\.environ(?:\.get|\.setdefault)?\s*[\[(]\s*|os\.getenv\(\s*)["'](ZF_\w+)["']"""
+                     r"""|["'](ZF_\w+)["']\s+(?:not\s+)?in\s+os\.environ""")
+_READER = re.compile(r"\bzf_env\s+zf_env_read\s*\(\s*\)\s*\{")
+
+
+def _env_sources():
+    """{path: text} of the product sources that may read the environment (build products left out)."""
+    csrc = [f for f in glob.glob(os.path.join(ROOT, "zfista_amd", "csrc", "*")) if f.endswith(_C_SUFFIXES)]
+    py = glob.glob(os.path.join(ROOT, "zfista_amd", "*.py")) + [os.path.join(ROOT, "bench.py")]
+    out = {}
+    for f in sorted(csrc + py):
+        with open(f, encoding="utf-8") as fh:
+            out[os.path.relpath(f, ROOT)] = fh.read()
+    return out
+
+
+def _statement(text, i):
+    """The C++ declaration that starts at text[i]: up to its ';', or to the '}' that closes its first braces."""
+    depth = 0
+    for j in range(i, len(text)):
+        ch = text[j]
+        if ch in "({[":
+            depth += 1
+        elif ch in ")}]":
+            depth -= 1
+            if ch == "}" and depth == 0:
+                return text[i:j + 1]
+        elif ch == ";" and depth == 0:
+            return text[i:j + 1]
+    return text[i:]
+
+
+def _switch_problems(sources, switches):
+    """Everything wrong with how `sources` ({path: text}) read the environment, against the list `switches`."""
+    problems, names = [], set()
+    for path, text in sources.items():
+        if path.endswith(".py"):
+            names |= {a or b for a, b in _PY_ENV.findall(text)}
+            continue
+        names |= set(_C_ENV.findall(text))
+        m = _READER.search(text)
+        lo, hi = (m.start(), m.start() + len(_statement(text, m.start()))) if m else (0, 0)
+        for g in re.finditer(r"\bgetenv\s*\(", text):
+            line = text[text.rfind("\n", 0, g.start()) + 1:text.find("\n", g.start())].strip()
+            if not lo <= g.start() < hi and '"ZF_RCCL_LIB"' not in line:
+                problems.append(f"{path}: getenv outside zf_env_read: {line}")
+        code = re.sub(r"//[^\n]*|/\*.*?\*/", "", text, flags=re.S)
+        for st in re.finditer(r"\bstatic\b", code):
+            decl = _statement(code, st.start())
+            head = decl.split("{")[0]
+            while re.search(r"\([^()]*\)", head):   # (a function's parameters may have defaults: '=' counts outside them)
+                head = re.sub(r"\([^()]*\)", "", head)
+            function = "{" in decl and "=" not in head and decl.split("{")[0].rstrip().endswith(")")
+            if "getenv" in decl and not function:
+                problems.append(f"{path}: a static initialised from getenv: {' '.join(decl.split())[:120]}")
+    if names != set(switches):
+        problems.append(f"read but not listed: {sorted(names - set(switches))}; listed but not read: {sorted(set(switches) - names)}")
+    return problems
+
+
+def test_every_environment_switch_is_listed_and_read_once_per_solver():
+    """_lib.ENV_SWITCHES is exactly the set of ZF_* names the library, the package and bench.py read; in the library
+    every getenv is inside zf_env_read (called when a solver is created) but ZF_RCCL_LIB's, and no static holds one."""
+    src = _env_sources()
+    assert any(_READER.search(t) for t in src.values()), "zf_env_read not found"
+    assert _switch_problems(src, _lib.ENV_SWITCHES) == []
+
+
+def test_the_switch_check_finds_what_it_is_for():
+    """The check above fails on each of: a static getenv cache, a stray getenv, a name missing from ENV_SWITCHES."""
+    src = _env_sources()
+    where = os.path.join("zfista_amd", "csrc", "zf_op_apply.hip")
+    cache = src[where] + 'bool f() {\n    static const bool on = [] { const char* e = getenv("ZF_OP_PERSIST"); return e; }();\n    return on;\n}\n'
+    assert any("a static initialised from getenv" in p for p in _switch_problems({**src, where: cache}, _lib.ENV_SWITCHES))
+    stray = src[where] + 'int g() { return getenv("ZF_SPECULATE") != nullptr; }\n'
+    assert any("getenv outside zf_env_read" in p for p in _switch_problems({**src, where: stray}, _lib.ENV_SWITCHES))
+    assert any("read but not listed: ['ZF_OP_PERSIST']" in p
+               for p in _switch_problems(src, tuple(k for k in _lib.ENV_SWITCHES if k != "ZF_OP_PERSIST")))

@@ -261,14 +261,15 @@ def require_gpu():
     return lib
 
 
-# Every ZF_* environment variable product code reads.  Each changes which kernels run, their launch geometry or a
-# numerics path - results that were produced under one say so (``OptimizeResult.overrides``, bench.py's
-# ``config.overrides``): numerics never change silently with the environment.
-ENV_SWITCHES = ("ZF_FIN_KERNEL", "ZF_SPECULATE", "ZF_NT", "ZF_LS_SMALL", "ZF_GEMV_MFMA", "ZF_TILES_PER_WG", "ZF_SUB_ITERS",
+# Every ZF_* environment variable product code reads (tests/test_host_logic.py checks the list against the sources).  The
+# library reads its own once per solver, when the solver is created (zf_env_read).  Each changes which kernels run, their
+# launch geometry or a numerics path - results that were produced under one say so (``OptimizeResult.overrides``,
+# bench.py's ``config.overrides``): numerics never change silently with the environment.
+ENV_SWITCHES = ("ZF_SPECULATE", "ZF_LS_SMALL", "ZF_GEMV_MFMA", "ZF_TILES_PER_WG", "ZF_SUB_ITERS",
                 "ZF_COMM", "ZF_MO_COMM", "ZF_MO_LAUNCH_AHEAD", "ZF_MO_SPIN_LIMIT", "ZF_RCCL_LIB", "ZF_DUAL_SOLVER",
-                "ZF_FORCE_SPLIT", "ZF_LIB_PATH", "ZF_MID_CHAINS", "ZF_BENCH_BACKEND",
-                "ZF_RUNAHEAD", "ZF_RUNAHEAD_SPIN_LIMIT", "ZF_SHORT_VIA_GENERAL", "ZF_PASS_SEQ_START", "ZF_AHEAD",
-                "ZF_AHEAD_UNSHARDED", "ZF_ACCEPT", "ZF_OP_SEPARABLE", "ZF_OP_TY", "ZF_OP_XCD_BANDS", "ZF_OP_FUSE_PROX", "ZF_OP_PERSIST", "ZF_RUNAHEAD_SHARDED", "ZF_RAS_LAST_INLINE")
+                "ZF_FORCE_SPLIT", "ZF_LIB_PATH", "ZF_BENCH_BACKEND",
+                "ZF_RUNAHEAD", "ZF_RUNAHEAD_SPIN_LIMIT", "ZF_PASS_SEQ_START", "ZF_AHEAD",
+                "ZF_AHEAD_UNSHARDED", "ZF_ACCEPT", "ZF_OP_SEPARABLE", "ZF_OP_FUSE_PROX", "ZF_OP_PERSIST", "ZF_RUNAHEAD_SHARDED")
 
 
 def env_overrides() -> dict:

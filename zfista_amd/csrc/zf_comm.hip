@@ -45,7 +45,8 @@ char g_rccl_err[256] = "";
 
 // (once per process, whatever thread gets here first: rank threads of a local group may race to it)
 void rccl_load_once() {
-    // ZF_RCCL_LIB names the one library to use (a pinned RCCL build; tests: a path that does not exist)
+    // ZF_RCCL_LIB names the one library to use (a pinned RCCL build; tests: a path that does not exist).  The only getenv
+    // outside zf_env_read (zf_solver.hip): the library is loaded once per process, not per solver.
     const char* pinned = getenv("ZF_RCCL_LIB");
     const char* names[] = {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"};
     void* h = nullptr;

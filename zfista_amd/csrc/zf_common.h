@@ -23,6 +23,28 @@ static inline int zf_fail(int code, const char* fmt, const char* a = "", const c
         if (!(cond)) return zf_fail(ZF_ERR_ARG, "%s%s", msg);  \
     } while (0)
 
+// ---- environment switches ------------------------------------------------
+// Every ZF_* switch the library honours (zfista_amd._lib.ENV_SWITCHES; ZF_RCCL_LIB aside: zf_comm.hip), read by
+// zf_env_read (zf_solver.hip) - the one reader of the environment - when a solver is created: a solver keeps what it saw.
+struct zf_env {
+    bool speculate;           // ZF_SPECULATE=0: always launch every shape
+    int pass_seq_start;       // ZF_PASS_SEQ_START (tests: the step counter wraps at 0x7ffffff0); 0 when unset
+    int sub_iters;            // ZF_SUB_ITERS: chain length when the options leave it to the library (<= 0: unset)
+    bool runahead;            // ZF_RUNAHEAD=0: no run-ahead passes
+    int tiles_per_wg;         // ZF_TILES_PER_WG: tiles per workgroup (0: unset - zf_tiles_for decides)
+    unsigned runahead_spin;   // ZF_RUNAHEAD_SPIN_LIMIT: polls before a run-ahead wait gives up
+    int runahead_sharded;     // ZF_RUNAHEAD_SHARDED: -1 unset, 0, 1
+    bool ahead;               // ZF_AHEAD=0: no passes ahead at kernel granularity
+    bool ahead_unsharded;     // ZF_AHEAD_UNSHARDED: passes ahead for unsharded grids as well
+    bool gemv_mfma;           // ZF_GEMV_MFMA=0: no MFMA for A^T r
+    bool ls_small;            // ZF_LS_SMALL=0: no two-launch path for cache-resident A
+    bool op_separable;        // ZF_OP_SEPARABLE=0: rank-1 blur kernels take the general path
+    bool op_fuse_prox;        // ZF_OP_FUSE_PROX=0: the operator problem's prox step is a launch of its own
+    bool op_persist;          // ZF_OP_PERSIST=0: the correlation kernels launch one workgroup per tile
+    long long mo_spin_limit;  // ZF_MO_SPIN_LIMIT: polls of a grid-wide wait of the multi-objective search (<= 0: unset)
+};
+zf_env zf_env_read();
+
 // ---- launch geometry -----------------------------------------------------
 // Streaming kernels: 256-thread blocks (4 waves, one per SIMD), at most 2048
 // blocks (256 CUs x 8) and grid-stride beyond that (guide: Guideline 11).

@@ -33,6 +33,7 @@
 
 constexpr int ZF_OP_TX = 64;                    // output tile width of a workgroup (lanes run along x)
 constexpr int ZF_OP_MAXK = 15;                  // largest supported kernel size (odd)
+constexpr int ZF_OP_WALK_MAXK = 9;              // largest kernel size whose workgroups walk several tiles (zf_op_geo::WALK)
 
 struct zf_op_args {
     const zf_control* ctl;   // NULL: no early exit, slot ignored (evaluation outside the solver loop)
@@ -40,14 +41,14 @@ struct zf_op_args {
     const double* taps;      // K x K, row-major
     const double* sep;       // NULL: general kernel; else u[ZF_OP_MAXK + 1] (rows) then v[ZF_OP_MAXK + 1] (columns): taps[i][j] = u[i] v[j]
     int tiles;               // tiles of the image (0: one per workgroup of the launch)
-    int xcd_bands;           // != 0: workgroups that share an XCD (blockIdx % 8: the dispatcher deals workgroups round-robin) take a
-                             // contiguous band of tiles, so that the halo a tile shares with its neighbours is found in THAT L2
 };
 
-// tile of workgroup `b` of `nwg` (row-major tile order).  Banded: the bijective XCD remap of the programming guide (5.5 T1) -
-// a speed choice only: any bijection is correct, and nothing relies on which XCD a workgroup really runs on.
-__device__ __forceinline__ int zf_op_tile(int b, int nwg, int banded) {
-    if (!banded || nwg < 16) return b;
+// tile of workgroup `b` of `nwg` (row-major tile order).  Workgroups that share an XCD (blockIdx % 8: the dispatcher deals
+// workgroups round-robin) take a contiguous band of tiles, so that the halo a tile shares with its neighbours is found in
+// THAT L2: the bijective XCD remap of the programming guide (5.5 T1) - a speed choice only: any bijection is correct, and
+// nothing relies on which XCD a workgroup really runs on.
+__device__ __forceinline__ int zf_op_tile(int b, int nwg) {
+    if (nwg < 16) return b;
     const int q = nwg / 8, r = nwg % 8, x = b % 8;
     return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + b / 8;
 }
@@ -117,7 +118,7 @@ struct zf_op_geo {
     // SIMD and lose up to half their rate (K = 15, general path, 4096 x 4096: 810 against 1 484 it/s).
     // WALK: a workgroup walks several tiles (the host launches what the device holds at once).  Blur sizes above 9 x 9 keep a
     // workgroup per tile: the loop costs their kernels a wave per SIMD (K = 13, general path, 4096 x 4096: 1 403 against 1 684 it/s).
-    static constexpr bool WALK = K <= 9;
+    static constexpr bool WALK = K <= ZF_OP_WALK_MAXK;
     static constexpr bool PREFETCH = WALK;
 #ifndef ZF_OP_ADJ_PREFETCH
 #define ZF_OP_ADJ_PREFETCH 0
@@ -235,7 +236,7 @@ __global__ __launch_bounds__(ZF_BLOCK) void zf_op_apply_kernel(zf_op_args P, con
     // one 2 x 2 block of W^-1 x per thread and round (tile origin and halo are even: blocks are whole); the four coefficient
     // loads of ALL rounds of a thread are issued before the first is used
     auto fetch = [&](int v) {
-        const int tile_id = zf_op_tile(v, NT, P.xcd_bands);
+        const int tile_id = zf_op_tile(v, NT);
         const int oy0 = (tile_id / tiles_x) * TY, ox0 = (tile_id % tiles_x) * ZF_OP_TX;
 #pragma unroll
         for (int rd = 0; rd < ROUNDS; ++rd) {
@@ -280,7 +281,7 @@ __global__ __launch_bounds__(ZF_BLOCK) void zf_op_apply_kernel(zf_op_args P, con
     int v = (int)blockIdx.x;
     if (G::PREFETCH && v < NT) fetch(v);
     for (; v < NT; v += (int)gridDim.x) {
-        const int tile_id = zf_op_tile(v, NT, P.xcd_bands);
+        const int tile_id = zf_op_tile(v, NT);
         const int oy0 = (tile_id / tiles_x) * TY, ox0 = (tile_id % tiles_x) * ZF_OP_TX;
         if (!G::PREFETCH) fetch(v);
         stage();
@@ -466,7 +467,7 @@ __global__ __launch_bounds__(ZF_BLOCK) void zf_op_adjoint_kernel(zf_op_args P, c
     constexpr int OFF = G::HP - G::HALF, CW = ZF_OP_TX + 2 * G::HALF, TOTAL = G::TROWS * CW, NB = (TOTAL + ZF_BLOCK - 1) / ZF_BLOCK;
     double a0[G::PREFETCH_ADJ ? NB : 1], a1[G::PREFETCH_ADJ ? NB : 1], a2[G::PREFETCH_ADJ ? NB : 1];
     auto fetch = [&](int v) {
-        const int tile_id = zf_op_tile(v, NT, P.xcd_bands);
+        const int tile_id = zf_op_tile(v, NT);
         const int oy0 = (tile_id / tiles_x) * TY, ox0 = (tile_id % tiles_x) * ZF_OP_TX;
 #pragma unroll
         for (int u = 0; u < NB; ++u) {
@@ -501,7 +502,7 @@ __global__ __launch_bounds__(ZF_BLOCK) void zf_op_adjoint_kernel(zf_op_args P, c
     if constexpr (G::PREFETCH_ADJ)
         if (v < NT) fetch(v);
     for (; v < NT; v += (int)gridDim.x) {
-        const int tile_id = zf_op_tile(v, NT, P.xcd_bands);
+        const int tile_id = zf_op_tile(v, NT);
         const int oy0 = (tile_id / tiles_x) * TY, ox0 = (tile_id % tiles_x) * ZF_OP_TX;
         double kv[PR][4], ov[PR][4];
         if (prox) {
@@ -639,14 +640,15 @@ struct zf_op_plan {
     int K;          // 3 .. 15, odd
     int ty;         // 32 or 8
     bool sep;
+    bool persist;   // workgroups walk their tiles (what the device holds at once; K <= ZF_OP_WALK_MAXK); false: a workgroup per tile
+    bool fuse_prox; // the solver's trial runs its prox step in the adjoint kernel's epilogue (zf_op_fuse.prox)
     int grid;
 };
-zf_op_plan zf_op_make_plan(int64_t h, int64_t w, int k, bool separable);
+zf_op_plan zf_op_make_plan(int64_t h, int64_t w, int k, bool separable, bool persist);
 void zf_launch_op_apply(const zf_op_plan& pl, hipStream_t st, const zf_op_args& P, const double* x0, const double* x1, const double* x2,
                         double* s0, double* s1, double* s2, int slot, const zf_op_fuse& F);
 void zf_launch_op_adjoint(const zf_op_plan& pl, hipStream_t st, const zf_op_args& P, const double* r, double* grad, double two_scale,
                           const zf_op_fuse& F);
-bool zf_op_persist();
 int zf_op_resident(const void* kernel, int* cache);
 // rank-1 test of a K x K kernel (host arrays): on success u[K], v[K] with |k[i][j] - u[i] v[j]| <= 1e-14 max |k|
 bool zf_op_factor_rank1(const double* taps, int k, double* u, double* v);

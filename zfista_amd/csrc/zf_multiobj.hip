@@ -1336,6 +1336,8 @@ extern "C" int zf_mo_create(zf_mo** out, int32_t kind, int32_t m, int64_t n, con
     s->n = n;
     s->n_global = n;
     s->stream = (hipStream_t)stream;
+    const long long spin = zf_env_read().mo_spin_limit;
+    if (spin > 0) s->spin_limit = spin > 0x7fffffffLL ? 0x7fffffffu : (unsigned)spin;
     memset(&s->G, 0, sizeof(s->G));
     s->G.m = m;
     s->G.has_l1 = l1_ratios != nullptr;
@@ -2052,10 +2054,6 @@ int mo_trial_launch(zf_mo* s, double lr, const double* f_y, const double* F_old,
         if (g > cus) g = cus;      // one workgroup per CU: the whole grid is resident (grid-wide waits)
         if (g < 1) g = 1;
         s->solve_grid = (int)g;
-        if (const char* sl = getenv("ZF_MO_SPIN_LIMIT")) {
-            const long long v = atoll(sl);
-            if (v > 0) s->spin_limit = v > 0x7fffffffLL ? 0x7fffffffu : (unsigned)v;
-        }
         // the hand-over records in UNCACHED device memory: every access is an agent-scope atomic that has to
         // reach memory anyway (the 8 XCDs' L2s are not coherent with each other); without the L2 in the way a
         // hand-over is ~0.5 us shorter (cfg4 9 700 -> 10 150-10 300 it/s, same box, A/B)

@@ -2,11 +2,11 @@
 #include "zf_kernels_op.h"
 
 template <int K, int TY, bool SEP>
-static int adjoint_wgs(int tiles) {   // (zf_op_apply.hip: the tiles, or what the device holds of this kernel at once)
+static int adjoint_wgs(const zf_op_plan& pl) {   // (zf_op_apply.hip: the tiles, or what the device holds of this kernel at once)
     static int cache = -1;
-    if (!zf_op_geo<K, TY>::WALK || !zf_op_persist()) return tiles;
+    if (!zf_op_geo<K, TY>::WALK || !pl.persist) return pl.grid;
     const int r = zf_op_resident(reinterpret_cast<const void*>(zf_op_adjoint_kernel<K, TY, SEP>), &cache);
-    return (r > 0 && tiles > r) ? r : tiles;
+    return (r > 0 && pl.grid > r) ? r : pl.grid;
 }
 
 template <int K>
@@ -14,11 +14,9 @@ static void launch_adjoint_k(const zf_op_plan& pl, hipStream_t st, const zf_op_a
                              const zf_op_fuse& F) {
     zf_op_args P = P0;
     P.tiles = pl.grid;
-#define GO(TY, SEP) hipLaunchKernelGGL((zf_op_adjoint_kernel<K, TY, SEP>), dim3(adjoint_wgs<K, TY, SEP>(pl.grid)), dim3(ZF_BLOCK), 0, st, P, r, grad, two_scale, F)
+#define GO(TY, SEP) hipLaunchKernelGGL((zf_op_adjoint_kernel<K, TY, SEP>), dim3(adjoint_wgs<K, TY, SEP>(pl)), dim3(ZF_BLOCK), 0, st, P, r, grad, two_scale, F)
     if (pl.ty == 32 && pl.sep) GO(32, true);
     else if (pl.ty == 32) GO(32, false);
-    else if (pl.ty == 16 && pl.sep) GO(16, true);
-    else if (pl.ty == 16) GO(16, false);
     else if (pl.sep) GO(8, true);
     else GO(8, false);
 #undef GO

@@ -1,20 +1,17 @@
 // zf_op_apply.hip - instantiations of zf_op_apply_kernel (B W^-1 x) and the plan of an operator problem
 #include <math.h>
-#include <stdlib.h>
 
 #include "zf_kernels_op.h"
 
-zf_op_plan zf_op_make_plan(int64_t h, int64_t w, int k, bool separable) {
+zf_op_plan zf_op_make_plan(int64_t h, int64_t w, int k, bool separable, bool persist) {
     zf_op_plan pl;
     pl.K = k < 3 ? 3 : k;
     const int64_t tx = (w + ZF_OP_TX - 1) / ZF_OP_TX;
     const int64_t tall = tx * ((h + 31) / 32);
     pl.ty = tall >= 256 ? 32 : 8;   // (measured, round 5: 1024 x 1024 = 512 tall tiles runs 20.6 k it/s on 64 x 32 tiles, 15.5 k on 64 x 8; 256 x 256 the other way round)
-    if (const char* e = getenv("ZF_OP_TY")) {   // (experiments: 8 / 16 / 32 rows per tile)
-        const int v = atoi(e);
-        if (v == 8 || v == 16 || v == 32) pl.ty = v;
-    }
     pl.sep = separable;
+    pl.persist = persist && pl.K <= ZF_OP_WALK_MAXK;
+    pl.fuse_prox = false;
     pl.grid = (int)(tx * ((h + pl.ty - 1) / pl.ty));
     return pl;
 }
@@ -40,14 +37,7 @@ bool zf_op_factor_rank1(const double* taps, int k, double* u, double* v) {
 }
 
 // workgroups of a launch: the tiles of the image, or - more tiles than the device holds workgroups of this kernel at once - that
-// many (a multiple of 8: a workgroup's tiles stay on its XCD); the kernels walk their tiles (ZF_OP_PERSIST=0: a workgroup per tile)
-bool zf_op_persist() {
-    static const bool on = [] {
-        const char* e = getenv("ZF_OP_PERSIST");
-        return e ? atoi(e) != 0 : true;
-    }();
-    return on;
-}
+// many (a multiple of 8: a workgroup's tiles stay on its XCD); the kernels walk their tiles (pl.persist false: a workgroup per tile)
 int zf_op_resident(const void* kernel, int* cache) {
     if (*cache >= 0) return *cache;
     int per_cu = 0, dev = 0;
@@ -58,11 +48,11 @@ int zf_op_resident(const void* kernel, int* cache) {
     return *cache;
 }
 template <int K, int TY, bool SEP>
-static int apply_wgs(int tiles) {
+static int apply_wgs(const zf_op_plan& pl) {
     static int cache = -1;
-    if (!zf_op_geo<K, TY>::WALK || !zf_op_persist()) return tiles;
+    if (!zf_op_geo<K, TY>::WALK || !pl.persist) return pl.grid;
     const int r = zf_op_resident(reinterpret_cast<const void*>(zf_op_apply_kernel<K, TY, SEP>), &cache);
-    return (r > 0 && tiles > r) ? r : tiles;
+    return (r > 0 && pl.grid > r) ? r : pl.grid;
 }
 
 template <int K>
@@ -70,11 +60,9 @@ static void launch_apply_k(const zf_op_plan& pl, hipStream_t st, const zf_op_arg
                            double* s0, double* s1, double* s2, int slot, const zf_op_fuse& F) {
     zf_op_args P = P0;
     P.tiles = pl.grid;
-#define GO(TY, SEP) hipLaunchKernelGGL((zf_op_apply_kernel<K, TY, SEP>), dim3(apply_wgs<K, TY, SEP>(pl.grid)), dim3(ZF_BLOCK), 0, st, P, x0, x1, x2, s0, s1, s2, slot, F)
+#define GO(TY, SEP) hipLaunchKernelGGL((zf_op_apply_kernel<K, TY, SEP>), dim3(apply_wgs<K, TY, SEP>(pl)), dim3(ZF_BLOCK), 0, st, P, x0, x1, x2, s0, s1, s2, slot, F)
     if (pl.ty == 32 && pl.sep) GO(32, true);
     else if (pl.ty == 32) GO(32, false);
-    else if (pl.ty == 16 && pl.sep) GO(16, true);
-    else if (pl.ty == 16) GO(16, false);
     else if (pl.sep) GO(8, true);
     else GO(8, false);
 #undef GO

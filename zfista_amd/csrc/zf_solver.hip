@@ -168,7 +168,7 @@ struct zf_solver {
     double* slice_part = nullptr; // ZF_NPART x ZF_FIN_WGS
     unsigned* fin_cnt = nullptr;  // arrival counters: of the finalize workgroups / of the in-kernel finalisation (zf_pass_tail)
     double* grp_part = nullptr;   // ZF_NPART x S x ZF_FIN_GROUPS group rows of the in-kernel finalisation
-    bool nt = true;               // nontemporal policy for once-touched streams
+    zf_env env;                   // the environment switches as zf_solver_create read them
     char* ctl_trace = nullptr;    // one allocation: the control block (ZF_CTL_SLOT bytes) and the trace ring behind it
     char* mail = nullptr;         // pinned host mirror of ctl_trace: what a poll copies into
     zf_control* ctl = nullptr;    // = ctl_trace
@@ -227,9 +227,6 @@ struct zf_solver {
     int part_mask = 7;                    // ZF_K_* bits (ZF_K_ALL until a prediction says otherwise)
     int mid_len = 0;                      // ZF_K_MID: trials of the mid chain
     int fb_part = -1, fb_len = 0;         // ZF_K_FALLBACK: the general body runs what this kernel does not (-1: everything)
-    bool mid_chains = true;               // ZF_MID_CHAINS=0 at creation: tails of 9 .. 15 trials through the general body (A/B)
-    bool short_general = false;           // ZF_SHORT_VIA_GENERAL=1 at creation: the shapes of PART 1 through the general body (A/B)
-    bool speculate = true;                // ZF_SPECULATE=0 at creation: always launch every shape
     int64_t steps_issued = 0, kernels_issued = 0;   // trial steps and the shape kernels launched for them (zf_solver_launch_counts)
     int pass_seq = 0;                     // step counter (zf_step_args.pass_seq)
     zf_control shadow;                    // the control block as the host expects it after the passes enqueued so far
@@ -242,7 +239,6 @@ struct zf_solver {
     bool ra = false;                      // eligible (separable f, chains of 16, one rank, a one-round grid) and not switched off (ZF_RUNAHEAD=0)
     int ra_cap = -1;                      // co-resident workgroups of the run-ahead full chain (-1: not asked yet)
     int ra_cap_mid[ZF_MAX_SUB_ITERS] = {};   // ... of the run-ahead mid chain of that length (0: no such kernel; asked at the first use: -1)
-    unsigned ra_spin = 1u << 13;          // polls before a wait gives up (ZF_RUNAHEAD_SPIN_LIMIT): ~15 ms, some tens of passes' worth; 0: every pass behind a pass in flight gives up at once (tests)
     hipStream_t stream2 = nullptr;
     hipStream_t stream3 = nullptr;        // sharded run-ahead passes: all-gather + decide of the pass before, beside the two trial streams
     hipEvent_t ra_join3 = nullptr;        // stream3 -> stream at the end of such a run
@@ -296,9 +292,31 @@ constexpr size_t ZF_TRACE_BYTES = sizeof(double) * ZF_RING * ZF_TRACE_COLS;
 constexpr size_t ZF_MAIL_BYTES = ZF_CTL_SLOT + ZF_TRACE_BYTES + sizeof(int) * ZF_PASS_LOG;
 
 static int zf_tiles_for(int64_t ntiles);
-static bool zf_fin_kernel_mode();
 // passes ahead at kernel granularity for UNSHARDED grids of more than one round (ZF_AHEAD_UNSHARDED overrides)
 constexpr bool ZF_AHEAD_UNSHARDED_DEFAULT = false;
+
+// The one reader of the environment (zf_common.h); "ZF_X=0" switches a default off, any other value on.
+zf_env zf_env_read() {
+    zf_env v;
+    const char* e;
+    v.speculate = !((e = getenv("ZF_SPECULATE")) && atoi(e) == 0);
+    v.pass_seq_start = (e = getenv("ZF_PASS_SEQ_START")) ? (int)std::min<long long>(std::max<long long>(atoll(e), 0), 0x7ffffff0LL) : 0;
+    v.sub_iters = (e = getenv("ZF_SUB_ITERS")) ? atoi(e) : 0;
+    v.runahead = !((e = getenv("ZF_RUNAHEAD")) && atoi(e) == 0);
+    v.tiles_per_wg = (e = getenv("ZF_TILES_PER_WG")) ? std::max(1, atoi(e)) : 0;
+    // ~15 ms, some tens of passes' worth; 0: every pass behind a pass in flight gives up at once (tests)
+    v.runahead_spin = (e = getenv("ZF_RUNAHEAD_SPIN_LIMIT")) ? (unsigned)strtoul(e, nullptr, 10) : 1u << 13;
+    v.runahead_sharded = (e = getenv("ZF_RUNAHEAD_SHARDED")) ? (atoi(e) != 0 ? 1 : 0) : -1;
+    v.ahead = !((e = getenv("ZF_AHEAD")) && atoi(e) == 0);
+    v.ahead_unsharded = (e = getenv("ZF_AHEAD_UNSHARDED")) ? atoi(e) != 0 : ZF_AHEAD_UNSHARDED_DEFAULT;
+    v.gemv_mfma = !((e = getenv("ZF_GEMV_MFMA")) && atoi(e) == 0);
+    v.ls_small = !((e = getenv("ZF_LS_SMALL")) && atoi(e) == 0);
+    v.op_separable = !((e = getenv("ZF_OP_SEPARABLE")) && atoi(e) == 0);
+    v.op_fuse_prox = !((e = getenv("ZF_OP_FUSE_PROX")) && atoi(e) == 0);
+    v.op_persist = !((e = getenv("ZF_OP_PERSIST")) && atoi(e) == 0);
+    v.mo_spin_limit = (e = getenv("ZF_MO_SPIN_LIMIT")) ? atoll(e) : 0;
+    return v;
+}
 
 static int zf_solver_free_all(zf_solver* s) {
     if (s->stream2) (void)hipStreamDestroy(s->stream2);
@@ -329,6 +347,9 @@ static int zf_solver_free_all(zf_solver* s) {
     return ZF_OK;
 }
 
+// the trial kernels' variant of this solver (zf_trial_launch.h)
+static zf_trial_sel zf_sel_of(const zf_solver* s) { return zf_trial_sel{s->opt.nesterov != 0, s->box, s->res}; }
+
 static bool zf_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 // least squares with an explicit matrix, or with the blur o inverse-Haar operator (zf_kernels_op.h): everything
@@ -342,8 +363,6 @@ static zf_op_args zf_op_of(const zf_problem_desc& d, const zf_control* ctl, cons
     P.K = pl.K;
     P.taps = taps;
     P.sep = pl.sep ? sep : nullptr;
-    static const int bands = [] { const char* e = getenv("ZF_OP_XCD_BANDS"); return e ? atoi(e) : 1; }();
-    P.xcd_bands = bands;
     P.tiles = pl.grid;
     return P;
 }
@@ -353,11 +372,12 @@ static zf_op_fuse zf_op_no_fuse() {
     memset(&F, 0, sizeof(F));
     return F;
 }
+constexpr int64_t ZF_OP_FUSE_MAX_PIXELS = int64_t(5) << 20;   // operator problem: the prox step rides in the adjoint kernel up to this size
 // The taps as the kernels take them: K x K with K the launched size (1 x 1 is zero-padded to 3 x 3), and - when the
-// kernel has rank 1 and ZF_OP_SEPARABLE is not 0 - its factors u, v behind them.  *buf: one device allocation
-// (caller frees); `st`: the stream the upload is ordered on.
-static int zf_op_prepare(const double* taps_dev, int k, int64_t h, int64_t w, hipStream_t st, zf_op_plan* pl, double** buf,
-                         const double** taps_out, const double** sep_out) {
+// kernel has rank 1 and ZF_OP_SEPARABLE is not 0 - its factors u, v behind them; the plan as `env` shapes it.  *buf: one
+// device allocation (caller frees); `st`: the stream the upload is ordered on.
+static int zf_op_prepare(const zf_env& env, const double* taps_dev, int k, int64_t h, int64_t w, hipStream_t st, zf_op_plan* pl,
+                         double** buf, const double** taps_out, const double** sep_out) {
     double host[ZF_OP_MAXK * ZF_OP_MAXK];
     ZF_HIP(hipMemcpyAsync(host, taps_dev, sizeof(double) * k * k, hipMemcpyDeviceToHost, st));
     ZF_HIP(hipStreamSynchronize(st));
@@ -369,9 +389,9 @@ static int zf_op_prepare(const double* taps_dev, int k, int64_t h, int64_t w, hi
         for (int j = 0; j < k; ++j) up[(i + pad) * K + j + pad] = host[i * k + j];
     double* u = up + ZF_OP_MAXK * ZF_OP_MAXK;
     double* v = u + ZF_OP_MAXK + 1;
-    const char* e = getenv("ZF_OP_SEPARABLE");
-    const bool sep = !(e && atoi(e) == 0) && zf_op_factor_rank1(up, K, u, v);
-    *pl = zf_op_make_plan(h, w, k, sep);
+    const bool sep = env.op_separable && zf_op_factor_rank1(up, K, u, v);
+    *pl = zf_op_make_plan(h, w, k, sep, env.op_persist);
+    pl->fuse_prox = env.op_fuse_prox && h * w <= ZF_OP_FUSE_MAX_PIXELS;
     ZF_HIP(hipMalloc(buf, sizeof(up)));
     ZF_HIP(hipMemcpyAsync(*buf, up, sizeof(up), hipMemcpyHostToDevice, st));
     ZF_HIP(hipStreamSynchronize(st));   // `up` is a stack object
@@ -379,7 +399,6 @@ static int zf_op_prepare(const double* taps_dev, int k, int64_t h, int64_t w, hi
     *sep_out = *buf + ZF_OP_MAXK * ZF_OP_MAXK;
     return ZF_OK;
 }
-static int zf_op_grid(const zf_problem_desc& d) { return zf_op_make_plan(d.op_h, d.op_w, d.op_k, false).grid; }
 
 // s[(cur + slot) % 3] = A x[(cur + slot) % 3] inside the loop (ctl given), or sout.p[0] = A xr.p[0] outside it (ctl NULL)
 static void zf_launch_apply_A(zf_solver* s, const zf_control* ctl, zf_ring3 xr, zf_ring3 sout, int slot) {
@@ -469,11 +488,8 @@ extern "C" int zf_solver_create(zf_solver** out, const zf_problem_desc* desc, co
     if (!s) return zf_fail(ZF_ERR_ARG, "zf_solver_create: out of host memory");
     s->desc = *desc;
     s->opt = *opt;
-    if (const char* e = getenv("ZF_SPECULATE")) s->speculate = atoi(e) != 0;
-    if (const char* e = getenv("ZF_MID_CHAINS")) s->mid_chains = atoi(e) != 0;
-    if (const char* e = getenv("ZF_SHORT_VIA_GENERAL")) s->short_general = atoi(e) != 0;
-    if (const char* e = getenv("ZF_PASS_SEQ_START"))   // (tests: the step counter wraps at 0x7ffffff0)
-        s->pass_seq = (int)std::min<long long>(std::max<long long>(atoll(e), 0), 0x7ffffff0LL);
+    s->env = zf_env_read();
+    s->pass_seq = s->env.pass_seq_start;
     s->stream = reinterpret_cast<hipStream_t>(stream);
     s->box = !(desc->box_lo == -INFINITY && desc->box_hi == INFINITY);
     if (opt->accept_mode != ZF_ACCEPT_REFERENCE) {
@@ -498,8 +514,6 @@ extern "C" int zf_solver_create(zf_solver** out, const zf_problem_desc* desc, co
         s->grid = (int)ntiles;            // tiles_per_wg = 1: the largest grid; buffers are sized for it
         s->max_grid = s->grid;
     }
-    const char* nt_env = getenv("ZF_NT");
-    if (nt_env) s->nt = atoi(nt_env) != 0;
 #define ZF_TRY(expr)                                                                    \
     do {                                                                                \
         hipError_t _e = (expr);                                                         \
@@ -513,14 +527,12 @@ extern "C" int zf_solver_create(zf_solver** out, const zf_problem_desc* desc, co
         // every term of the recursion is elementwise for this f, so one pass may run `sub`
         // consecutive iterations in registers (zf_kernels_step.h); 0 = library default
         int sub = opt->sub_iters;
-        const char* se = getenv("ZF_SUB_ITERS");
-        if (sub <= 0 && se) sub = atoi(se);
+        if (sub <= 0) sub = s->env.sub_iters;
         if (sub <= 0) sub = ZF_DEFAULT_SUB_ITERS;
         if (sub > ZF_MAX_SUB) sub = ZF_MAX_SUB;
         s->sub = sub >= 16 ? 16 : sub >= 8 ? 8 : sub >= 4 ? 4 : sub >= 2 ? 2 : 1;
         // (the kernels of ZF_ACCEPT_RESOLVED exist for chains of 16 and single trials, nontemporal policy)
         if (s->res && s->sub != 16) s->sub = 1;
-        if (s->res) s->nt = true;
     }
     s->ring = s->sub > 1 ? 4 : 3;   // x_k, x_{k-1} + the one or two iterates a pass stores
     {   // passes that run ahead of their predecessor's decision (chains of 16 of the separable problem), two ways:
@@ -529,26 +541,19 @@ extern "C" int zf_solver_create(zf_solver** out, const zf_problem_desc* desc, co
         //   every variant, mid chains where the per-pass mid chains exist (no box);
         // * passes AHEAD at KERNEL granularity: every grid, boxes too; for sharded solves through the library's
         //   communicator (zf_solver_set_comm) and - ZF_AHEAD_UNSHARDED - unsharded grids the other scheme does not take.
-        const char* e = getenv("ZF_RUNAHEAD");
-        const bool on = e ? atoi(e) != 0 : true;
-        const char* te = getenv("ZF_TILES_PER_WG");
-        const int t = te ? std::max(1, atoi(te)) : zf_tiles_for(s->ntiles);
+        const int t = s->env.tiles_per_wg > 0 ? s->env.tiles_per_wg : zf_tiles_for(s->ntiles);
         const int64_t grid = (s->ntiles + t - 1) / t;
-        if (const char* l = getenv("ZF_RUNAHEAD_SPIN_LIMIT")) s->ra_spin = (unsigned)strtoul(l, nullptr, 10);
-        const bool chains16 = desc->kind == ZF_PROBLEM_DIAG_QUAD_L1 && s->sub >= 16 && !zf_fin_kernel_mode();
+        const bool chains16 = desc->kind == ZF_PROBLEM_DIAG_QUAD_L1 && s->sub >= 16;
         // (world > 1, or one rank behind a communicator: the SHARDED run-ahead passes - same kernels, packs instead of a decision)
-        s->ra = on && chains16;
-        if (const char* se = getenv("ZF_RUNAHEAD_SHARDED")) s->ra_sharded = atoi(se) != 0;
+        s->ra = s->env.runahead && chains16;
+        if (s->env.runahead_sharded >= 0) s->ra_sharded = s->env.runahead_sharded != 0;
         if (s->ra) {
-            const zf_trial_sel v = {s->opt.nesterov != 0, s->box, s->nt, s->res};
-            s->ra_cap = zf_runahead_capacity(v, s->sub);
+            s->ra_cap = zf_runahead_capacity(zf_sel_of(s), s->sub);
             s->ra = grid <= s->ra_cap;
             for (int l = 0; l < ZF_MAX_SUB_ITERS; ++l) s->ra_cap_mid[l] = -1;
         }
-        const char* ae = getenv("ZF_AHEAD");
-        s->ah = (ae ? atoi(ae) != 0 : true) && chains16 && s->nt;
-        const char* ue = getenv("ZF_AHEAD_UNSHARDED");
-        s->ah_unsharded = s->ah && desc->world == 1 && (ue ? atoi(ue) != 0 : ZF_AHEAD_UNSHARDED_DEFAULT);
+        s->ah = s->env.ahead && chains16;
+        s->ah_unsharded = s->ah && desc->world == 1 && s->env.ahead_unsharded;
     }
     if (s->ra || (s->ah && (desc->world > 1 || s->ah_unsharded))) {
         s->ring = 6;   // a pass never writes what its predecessor reads (zf_free_bufs)
@@ -595,7 +600,7 @@ extern "C" int zf_solver_create(zf_solver** out, const zf_problem_desc* desc, co
         for (int k = 0; k < 3; ++k) s->sring.p[k] = s->sbuf + k * m_pad;
         ZF_TRY(hipMalloc(&s->resid, sizeof(double) * m_pad));
         ZF_TRY(hipMalloc(&s->ls_scal, sizeof(double) * 8));
-        if (zf_op_prepare(desc->op_taps, (int)desc->op_k, desc->op_h, desc->op_w, s->stream, &s->op_plan, &s->op_buf, &s->op_taps, &s->op_sep) != ZF_OK) {
+        if (zf_op_prepare(s->env, desc->op_taps, (int)desc->op_k, desc->op_h, desc->op_w, s->stream, &s->op_plan, &s->op_buf, &s->op_taps, &s->op_sep) != ZF_OK) {
             zf_solver_free_all(s);
             delete s;
             return ZF_ERR_HIP;   // (message set by zf_op_prepare)
@@ -617,8 +622,7 @@ extern "C" int zf_solver_create(zf_solver** out, const zf_problem_desc* desc, co
         if (slices > 64) slices = 64;
         s->rows_per_slice = (m + slices - 1) / slices;
         s->slices = (int)((m + s->rows_per_slice - 1) / s->rows_per_slice);
-        const char* mf = getenv("ZF_GEMV_MFMA");
-        s->gemv_mfma = (n % 32 == 0) && !(mf && atoi(mf) == 0);
+        s->gemv_mfma = (n % 32 == 0) && s->env.gemv_mfma;
         ZF_TRY(hipMalloc(&s->grad, sizeof(double) * n_pad));
         ZF_TRY(hipMalloc(&s->sbuf, sizeof(double) * 3 * m_pad));
         for (int k = 0; k < 3; ++k) s->sring.p[k] = s->sbuf + k * m_pad;
@@ -631,9 +635,8 @@ extern "C" int zf_solver_create(zf_solver** out, const zf_problem_desc* desc, co
             ZF_TRY(hipMalloc(&s->s_all, sizeof(double) * len * desc->world));
         }
         // launch-bound sizes (BASELINE cfg1): two fused launches per trial; ZF_LS_SMALL=0 keeps the general path
-        const char* sm = getenv("ZF_LS_SMALL");
         s->ls_small = desc->world == 1 && n % LS_SMALL_COLS == 0 && m <= LS_SMALL_MAX_M &&
-                      m * n <= LS_SMALL_MAX_ELEMS && zf_aligned16(desc->A) && !(sm && atoi(sm) == 0);
+                      m * n <= LS_SMALL_MAX_ELEMS && zf_aligned16(desc->A) && s->env.ls_small;
         if (s->ls_small) {
             ZF_TRY(hipMalloc(&s->row_part, sizeof(double) * ((m + ZF_WAVES - 1) / ZF_WAVES)));
             ZF_TRY(hipMalloc(&s->ls_cnt, 64));
@@ -666,7 +669,7 @@ enum {
 };
 
 static void zf_launch_trial_kernels(zf_solver* s, const zf_step_args& a, bool grad_inline) {
-    const zf_trial_sel v = {s->opt.nesterov != 0, s->box, s->nt, s->res};
+    const zf_trial_sel v = zf_sel_of(s);
     const int mask = s->part_mask;
     const int grid = s->grid;
     hipStream_t st = s->stream;
@@ -778,14 +781,8 @@ static void zf_fin_groups(int grid, int* gsz, int* ng) {
     *ng = (grid + *gsz - 1) / *gsz;
 }
 
-static bool zf_fin_kernel_mode() {
-    static const bool on = [] { const char* e = getenv("ZF_FIN_KERNEL"); return e && atoi(e) != 0; }();
-    return on;
-}
-
 // grids of at most this many workgroups are latency-bound: a second (idle) launch per pass costs more than a slower body
 constexpr int ZF_SMALL_GRID = 64;
-constexpr int64_t ZF_OP_FUSE_MAX_PIXELS = int64_t(5) << 20;   // operator problem: the prox step rides in the adjoint kernel up to this size
 // tiles per workgroup (a function of n: zf_tiles_for) between which a run of run-ahead passes may START with a mid chain
 constexpr int ZF_RA_MID_START_MIN_TILES = 4;    // n >= ~4e6
 constexpr int ZF_RA_MID_START_MAX_TILES = 12;   // n <= ~1.2e7
@@ -820,11 +817,10 @@ static void zf_shadow_advance(zf_control& c) {
 // A wrong prediction costs passes that do nothing (no kernel finds its shape, the control block stays as it is) until
 // the next poll - never a wrong result.
 static int zf_predict_parts(zf_solver* s) {
-    const bool off = !s->speculate;   // (ZF_SPECULATE=0 when the solver was created)
     // (x sharded: only with the library's communicator, whose decide step checks that every rank's packs are those
     //  of this step - all ranks predict from identical control blocks; a host-driven exchange launches everything)
-    if (off || s->sub <= 1 || !s->shadow_valid || (s->desc.world != 1 && !s->comm) ||
-        s->desc.kind != ZF_PROBLEM_DIAG_QUAD_L1 || zf_fin_kernel_mode())
+    if (!s->env.speculate || s->sub <= 1 || !s->shadow_valid || (s->desc.world != 1 && !s->comm) ||
+        s->desc.kind != ZF_PROBLEM_DIAG_QUAD_L1)
         return ZF_K_ALL;
     zf_control& c = s->shadow;
     const int S = s->sub;
@@ -847,14 +843,10 @@ static int zf_predict_parts(zf_solver* s) {
     const int lag = c.lag;
     const int nf = zf_fresh_len(&c);
     int part = zf_pass_part(S, lag, nf);
-    const zf_trial_sel v = {s->opt.nesterov != 0, s->box, s->nt, s->res};
-    if (part == 3 && (!s->mid_chains || !zf_have_s16_mid(v, nf))) part = 2;
+    const zf_trial_sel v = zf_sel_of(s);
+    if (part == 3 && !zf_have_s16_mid(v, nf)) part = 2;
     int mask = part == 3 ? ZF_K_MID : (1 << part);
     s->mid_len = nf;
-    if (part == 1 && s16 && s->short_general) {
-        s->fb_part = -1;
-        mask = ZF_K_FALLBACK;
-    }
     if (s->careful && s->steps_since_poll > 0) {
         // Chains have been breaking: behind the first step the shape is no longer known.  A pass behind a broken chain
         // replays and has at most S / 2 fresh trials, or only materialises (PART 1); a pass with nothing lagging far
@@ -914,7 +906,7 @@ static int zf_gather_packs(zf_solver* s, int64_t packs, hipStream_t st, const do
 // publishes the done / good word the kernels read.  What a sharded one-round grid gets out of it is what the unsharded one
 // gets: the finalisation, the exchange and the decision of a pass no longer lie between two passes.
 static int zf_launch_runahead(zf_solver* s, zf_step_args a, const zf_control& before, int nf, hipEvent_t e0, hipEvent_t e1) {
-    const zf_trial_sel v = {s->opt.nesterov != 0, s->box, s->nt, s->res};
+    const zf_trial_sel v = zf_sel_of(s);
     const bool sharded = s->comm != nullptr;
     const int mode = sharded ? 3 : 1;
     zf_pass_head h;
@@ -955,7 +947,7 @@ static int zf_launch_runahead(zf_solver* s, zf_step_args a, const zf_control& be
     a.ra_stats = s->ra_stats;
     a.ra_wait = chain ? s->ra_last : 0;
     a.ra_need = chain ? s->ra_last2 : 0;
-    a.ra_spin = s->ra_spin;
+    a.ra_spin = s->env.runahead_spin;
     a.ra_head = h;
     if (idx == 1) {
         a.blk_part = s->blk_part2;
@@ -979,9 +971,8 @@ static int zf_launch_runahead(zf_solver* s, zf_step_args a, const zf_control& be
         // exchange and decide step: on the third stream behind an event - but for the LAST pass of a chunk, which nothing
         // runs beside: on the pass's own stream (one hop between queues, ~20 us, less in front of the poll; the decide steps stay
         // in order through the event of the one before, long signalled by then)
-        static const bool last_inline = [] { const char* e = getenv("ZF_RAS_LAST_INLINE"); return e ? atoi(e) != 0 : true; }();
         hipStream_t ds = s->stream3;
-        if (s->chunk_last && last_inline) {
+        if (s->chunk_last) {
             ds = st;
             if (k >= 1) ZF_HIP(hipStreamWaitEvent(ds, s->ah_evD[(k - 1) & 3], 0));
         } else if (e1) {
@@ -1025,7 +1016,7 @@ static int zf_launch_runahead(zf_solver* s, zf_step_args a, const zf_control& be
 // come true is VOID (zf_decide_ahead).  Nothing waits inside a kernel: every grid size, every sharing of the device.
 // `before`: the shadow control block in front of this pass; nf: its fresh trials; part: 0 full chain, 3 mid chain.
 static int zf_launch_ahead(zf_solver* s, zf_step_args a, const zf_control& before, int part, int nf, hipEvent_t e0, hipEvent_t e1) {
-    const zf_trial_sel v = {s->opt.nesterov != 0, s->box, s->nt, s->res};
+    const zf_trial_sel v = zf_sel_of(s);
     zf_pass_head h;
     h.cur = before.cur;
     h.prev = before.prev;
@@ -1122,10 +1113,7 @@ static int zf_launch_trial(zf_solver* s, bool decide_in_launch, bool dry = false
     if (d.kind == ZF_PROBLEM_DIAG_QUAD_L1) {
         a.p0 = d.d;
         a.p1 = d.c;
-        // (ZF_FIN_KERNEL=1: the round-2 sequence - plain rows, a separate zf_finalize_kernel launch - for A/B
-        //  measurements on one box; its sums are added in another order, so knife-edge decisions may differ)
-        const bool fin_kernel = zf_fin_kernel_mode();
-        if (!dry && !fin_kernel) {
+        if (!dry) {
             // the pass finalises itself (zf_pass_tail): packs, and - unsharded - the decide pass, in the same launch
             a.fin_mode = 1;
             zf_fin_groups(s->grid, &a.fin_gsz, &a.fin_ng);
@@ -1143,7 +1131,7 @@ static int zf_launch_trial(zf_solver* s, bool decide_in_launch, bool dry = false
         zf_control before;
         // passes that run ahead of their predecessor's decision: at workgroup granularity (unsharded one-round grids), or
         // at kernel granularity (through the library's communicator; ZF_AHEAD_UNSHARDED: other unsharded grids)
-        const bool two_streams = s->stream2 != nullptr && !dry && !fin_kernel && !s->hist && s->shadow_valid;
+        const bool two_streams = s->stream2 != nullptr && !dry && !s->hist && s->shadow_valid;
         // (behind a communicator only from zf_solver_enqueue_steps, which hands over done_ahead: a caller that drives trial /
         //  exchange / decide itself - zf_solver_enqueue_trial - gets one pass at a time, whatever is attached)
         const bool ra_can = two_streams && s->ra && !s->ra_off &&
@@ -1170,7 +1158,7 @@ static int zf_launch_trial(zf_solver* s, bool decide_in_launch, bool dry = false
         if (ra_can && exact && !ra_ok && s->part_mask == ZF_K_MID && nf_before == s->mid_len && nf_before < ZF_MAX_SUB_ITERS &&
             (mid_run || (s->tiles >= ZF_RA_MID_START_MIN_TILES && s->tiles <= ZF_RA_MID_START_MAX_TILES))) {
             int& cap = s->ra_cap_mid[nf_before];
-            if (cap < 0) cap = zf_runahead_capacity(zf_trial_sel{s->opt.nesterov != 0, s->box, s->nt, s->res}, nf_before);
+            if (cap < 0) cap = zf_runahead_capacity(zf_sel_of(s), nf_before);
             ra_ok = cap > 0 && s->grid <= cap;
         }
         const bool ah_ok = ah_can && !ra_ok && exact && ((s->part_mask == ZF_K_FULL && nf_before == s->sub) ||
@@ -1208,7 +1196,6 @@ static int zf_launch_trial(zf_solver* s, bool decide_in_launch, bool dry = false
             if (e1) ZF_HIP(hipEventRecord(e1, s->stream));
         }
         s->part_mask = ZF_K_ALL;
-        if (!dry && fin_kernel) zf_launch_finalize(s, d.world == 1 && decide_in_launch);
     } else if (s->ls_small && !dry && decide_in_launch) {
         // cache-resident A: the whole trial in two launches (zf_kernels_ls_small.h)
         zf_ls_small_args P;
@@ -1279,15 +1266,11 @@ static int zf_launch_trial(zf_solver* s, bool decide_in_launch, bool dry = false
             F.ctl_rw = s->ctl;
             F.trace = s->trace;
             F.beta_ring = s->beta_ring;
-            static const bool fuse_env = [] {
-                const char* e = getenv("ZF_OP_FUSE_PROX");
-                return e ? atoi(e) != 0 : true;
-            }();
             // (images whose six arrays - x_k, x_{k-1}, x+, the two cached B W^-1 x, b - no longer fit the 256 MB of memory-side
             //  cache gain nothing: 3072^2 and 4096^2 -0.3 ... -0.7 %, the epilogue's 256-byte pieces of four coefficient
             //  quadrants go to HBM at 0.56 of peak where the separate step streams at 0.74; up to 2048^2: +6 ... +16 %,
             //  profiles/r05_operator_fuse_prox_ab.txt)
-            const bool fuse_prox = fuse_env && decide_in_launch && !s->hist && d.n <= ZF_OP_FUSE_MAX_PIXELS;
+            const bool fuse_prox = s->op_plan.fuse_prox && decide_in_launch && !s->hist;
             if (fuse_prox) {
                 F.prox = 1;
                 F.box = s->box ? 1 : 0;
@@ -1674,7 +1657,7 @@ extern "C" int zf_solver_enqueue_trial(zf_solver* s) {
 extern "C" int zf_solver_enqueue_decide(zf_solver* s) {
     ZF_REQUIRE(s && s->initialised, "zf_solver_enqueue_decide: solver not initialised");
     // (separable problems finalise in the trial launch and stamp their packs: zf_pack_stamp)
-    const int stamped = (s->desc.kind == ZF_PROBLEM_DIAG_QUAD_L1 && !zf_fin_kernel_mode()) ? 1 : 0;
+    const int stamped = s->desc.kind == ZF_PROBLEM_DIAG_QUAD_L1 ? 1 : 0;
     hipLaunchKernelGGL(zf_decide_kernel, dim3(1), dim3(64), 0, s->stream, s->ctl, s->pack_all, s->trace,
                        s->beta_ring, s->sub, stamped);
     ZF_HIP(hipGetLastError());
@@ -1729,6 +1712,14 @@ extern "C" int zf_solver_ls_plan(zf_solver* s, int64_t* out, int64_t count) {
     ZF_REQUIRE(s && out, "zf_solver_ls_plan: null argument");
     ZF_REQUIRE(count >= 4, "zf_solver_ls_plan: the output holds fewer than 4 values");
     out[0] = out[1] = out[2] = out[3] = 0;
+    if (s->desc.kind == ZF_PROBLEM_BLUR_HAAR_L1) {   // the operator plan (zf_op_plan; fused: as zf_launch_trial decides it)
+        const zf_op_plan& pl = s->op_plan;
+        out[0] = pl.ty;
+        out[1] = pl.sep ? 1 : 0;
+        out[2] = pl.persist ? 1 : 0;
+        out[3] = (pl.fuse_prox && !s->hist) ? 1 : 0;
+        return ZF_OK;
+    }
     if (s->desc.kind != ZF_PROBLEM_LEAST_SQUARES_L1) return ZF_OK;
     const bool odd = s->desc.n % 2 != 0;
     out[0] = s->ls_small ? 1 : s->gemv_mfma ? 2 : odd ? 4 : 3;
@@ -1794,7 +1785,7 @@ extern "C" int zf_solver_set_comm(zf_solver* s, zf_comm* comm) {
         // run-ahead passes would wait for workgroups that have no slot (correct, counted, switched off at the first poll, but
         // 15 ms per wait): those groups keep to passes ahead, which never wait inside a kernel.  ZF_RUNAHEAD_SHARDED=1 insists.
         zf_comm_desc cd;
-        if (world > 1 && !getenv("ZF_RUNAHEAD_SHARDED") && zf_comm_describe(comm, &cd, (int64_t)sizeof(cd)) == ZF_OK && cd.kind == 1)
+        if (world > 1 && s->env.runahead_sharded < 0 && zf_comm_describe(comm, &cd, (int64_t)sizeof(cd)) == ZF_OK && cd.kind == 1)
             s->ra_sharded = false;
     }
     // passes ahead of their predecessor's decision (zf_launch_ahead) need six iterate buffers and the second stream: a
@@ -1941,8 +1932,7 @@ static int zf_tiles_for(int64_t ntiles) {
 
 extern "C" int zf_solver_autotune(zf_solver* s, int32_t* chosen_tiles) {
     ZF_REQUIRE(s && s->initialised, "zf_solver_autotune: solver not initialised");
-    const char* env = getenv("ZF_TILES_PER_WG");
-    if (env) zf_set_tiles(s, atoi(env));
+    if (s->env.tiles_per_wg > 0) zf_set_tiles(s, s->env.tiles_per_wg);
     else if (s->desc.kind == ZF_PROBLEM_DIAG_QUAD_L1) zf_set_tiles(s, zf_tiles_for(s->ntiles));
     else zf_set_tiles(s, 1);
     if (chosen_tiles) *chosen_tiles = s->tiles;
@@ -2305,7 +2295,7 @@ extern "C" int zf_op_eval(const double* taps_dev, int32_t k, const double* b_dev
     double *x = nullptr, *sv = nullptr, *grad = nullptr, *fdev = nullptr, *opbuf = nullptr;
     zf_op_plan pl;
     const double *taps = nullptr, *sep = nullptr;
-    int rc = zf_op_prepare(taps_dev, (int)k, h, w, nullptr, &pl, &opbuf, &taps, &sep);
+    int rc = zf_op_prepare(zf_env_read(), taps_dev, (int)k, h, w, nullptr, &pl, &opbuf, &taps, &sep);
     if (rc) return rc;
 #define ZF_OP(expr)                                                               \
     do {                                                                          \

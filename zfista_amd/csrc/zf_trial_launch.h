@@ -7,7 +7,7 @@
 #include "zf_kernels_step.h"
 
 struct zf_trial_sel {
-    bool nest, box, nt;
+    bool nest, box;
     bool res = false;   // ZF_ACCEPT_RESOLVED: the kernels that accumulate f(x+) - f(y) (zf_elem_diag<..., RES>; nontemporal
                         // policy, chains of 16 and single trials only - zf_solver_create holds such a solver to that)
 };
@@ -59,17 +59,13 @@ void zf_launch_hist(const zf_trial_sel& v, bool grad_inline, int S, int part, in
 // gradient vector read from HBM (least squares), S = 1
 void zf_launch_vec(const zf_trial_sel& v, int grid, hipStream_t st, const zf_step_args& a);
 
-// CALL(NEST, BOX, NT) for the variant `v`
-#define ZF_SEL_NBT(v, CALL)                                  \
-    do {                                                     \
-        if ((v).nest && (v).box && (v).nt) { CALL(true, true, true); }          \
-        else if ((v).nest && (v).box) { CALL(true, true, false); }              \
-        else if ((v).nest && (v).nt) { CALL(true, false, true); }               \
-        else if ((v).nest) { CALL(true, false, false); }                        \
-        else if ((v).box && (v).nt) { CALL(false, true, true); }                \
-        else if ((v).box) { CALL(false, true, false); }                         \
-        else if ((v).nt) { CALL(false, false, true); }                          \
-        else { CALL(false, false, false); }                                     \
+// CALL(NEST, BOX, NT) for the variant `v`, NT = true: the solver runs the nontemporal store policy only
+#define ZF_SEL_NBT(v, CALL)                                   \
+    do {                                                      \
+        if ((v).nest && (v).box) { CALL(true, true, true); }  \
+        else if ((v).nest) { CALL(true, false, true); }       \
+        else if ((v).box) { CALL(false, true, true); }        \
+        else { CALL(false, false, true); }                    \
     } while (0)
 #define ZF_LAUNCH_TRIAL(GI, N, B, T, S, HIST, PART, L) \
     hipLaunchKernelGGL((zf_trial_kernel<GI, N, B, T, S, HIST, PART, L>), dim3(grid), dim3(ZF_BLOCK), 0, st, a)

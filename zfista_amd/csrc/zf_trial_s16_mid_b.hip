@@ -4,7 +4,7 @@
 bool zf_launch_s16_mid_a(bool nest, int len, int grid, hipStream_t st, const zf_step_args& a);
 
 bool zf_have_s16_mid(const zf_trial_sel& v, int len) {
-    return !v.box && v.nt && len >= ZF_MID_MIN && len <= ZF_MID_MAX;
+    return !v.box && len >= ZF_MID_MIN && len <= ZF_MID_MAX;
 }
 
 bool zf_launch_s16_mid(const zf_trial_sel& v, int len, int grid, hipStream_t st, const zf_step_args& a) {

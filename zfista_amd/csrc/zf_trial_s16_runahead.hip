@@ -10,7 +10,7 @@ static int zf_ra_op(const zf_trial_sel& v, int len, int grid, hipStream_t st, co
         ZF_SEL_NBT(v, FULL);
 #undef FULL
     }
-    if (v.box || !v.nt || len < ZF_MID_MIN || len > ZF_MID_MAX) return -1;
+    if (v.box || len < ZF_MID_MIN || len > ZF_MID_MAX) return -1;
     return len <= 12 ? zf_ra_op_mid_a(v, len, grid, st, a) : zf_ra_op_mid_b(v, len, grid, st, a);
 }
 

@@ -276,7 +276,10 @@ class DeviceSolver:
     def ls_plan(self):
         """Least squares: (column-sweep form, row-sweep form, row slices, rows per slice) of the passes this solver
         runs (zf_solver_ls_plan).  Column sweep: 0 not least squares, 1 small matrix, 2 MFMA, 3 VALU 16-byte loads,
-        4 VALU scalar loads; row sweep: 1 the small-matrix rows kernel, 2 zf_gemv_rows_kernel<2>, 3 <1>."""
+        4 VALU scalar loads; row sweep: 1 the small-matrix rows kernel, 2 zf_gemv_rows_kernel<2>, 3 <1>.
+        The operator problem (BlurHaarL1): (tile height - 8 or 32 rows, 1 separable correlation / 0 general,
+        1 workgroups walk their tiles / 0 one workgroup per tile, 1 prox step fused into the adjoint kernel / 0 a
+        launch of its own).  Other problems: zeros."""
         out = np.zeros(4, dtype=np.int64)
         _lib.check(self.lib.zf_solver_ls_plan(self.handle, C.c_void_p(_lib.ptr(out)), out.size))
         return tuple(int(v) for v in out)
