@@ -116,7 +116,11 @@ def test_beyond_the_notebook_size_and_every_kernel_path(variant, monkeypatch):
     rank-1 kernels, 64 x 8 tiles for images of few tiles).  Every path against the oracle on the same callbacks at
     sizes where the 64 x 32 tiles run (1024 x 1024: the verdict's "parity test at 1024^2"), with partial tiles at the
     right and bottom edges, a kernel that is NOT separable, the separable kernel forced through the general path
-    (ZF_OP_SEPARABLE=0), and the degenerate 1 x 1 kernel (zero-padded to 3 x 3)."""
+    (ZF_OP_SEPARABLE=0), and the degenerate 1 x 1 kernel (zero-padded to 3 x 3).
+
+    "Every path" is the correlation paths of the three-launch trial: return_all=True gives the solver a history ring,
+    and a history ring switches the fused prox step off (zf_solver.hip: fuse_prox = ... && !s->hist).  The fused trial of
+    every instantiation, and all 28 of them element by element, are in tests/test_gpu_operator_kernels.py."""
     from oracle import cpu_ref, operator_ref as O
     from zfista_amd.problems import BlurHaarL1
 

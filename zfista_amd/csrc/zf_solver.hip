@@ -569,7 +569,12 @@ extern "C" int zf_solver_create(zf_solver** out, const zf_problem_desc* desc, co
     for (int k = 0; k < s->ring; ++k) s->xb[k] = s->xbuf + k * n_pad;
     ZF_TRY(hipMalloc(&s->partials, sizeof(double) * ZF_NPART * ZF_MAX_GRID));
     {   // (the small least-squares step kernel has n / 32 workgroups: more than tiles)
-        const int64_t parts = std::max<int64_t>(s->max_grid, n / LS_SMALL_COLS + 1);
+        int64_t parts = std::max<int64_t>(s->max_grid, n / LS_SMALL_COLS + 1);
+        // (operator problem: the fused prox step writes a row per workgroup of the adjoint kernel - one per image tile, and a
+        //  narrow image has more tiles than n / 32: 1000 x 2 is 125 tiles of 64 x 8 on 2000 coefficients.  The tile count
+        //  depends on the image and the kernel size only, not on the path zf_op_prepare picks below.)
+        if (desc->kind == ZF_PROBLEM_BLUR_HAAR_L1)
+            parts = std::max<int64_t>(parts, zf_op_make_plan(desc->op_h, desc->op_w, (int)desc->op_k, false, false).grid);
         ZF_TRY(hipMalloc(&s->blk_part, sizeof(double) * ZF_NPART * s->sub * parts));
     }
     ZF_TRY(hipMalloc(&s->slice_part, sizeof(double) * ZF_NPART * s->sub * ZF_FIN_WGS));
