@@ -52,6 +52,8 @@ extern "C" {
 #define ZF_PROBLEM_BLUR_HAAR_L1 3     /* (ABI 5) f = scale |B W^-1 x - b|^2 with B an op_k x op_k correlation with symmetric
                                          boundary and W one orthonormal Haar level: the operator-form LASSO of the
                                          reference's examples/cameraman.ipynb:219-272; g = lam |x|_1 (+box)        */
+#define ZF_PROBLEM_SPARSE_LS_L1 4     /* f = scale |Ax-b|^2 with A a CSR matrix behind a zf_spmat handle
+                                         (zf_solver_create_sparse);     g = lam |x|_1 (+box)                       */
 
 #define ZF_PACK_LEN 8    /* doubles in one per-trial scalar pack */
 #define ZF_MAX_SUB_ITERS 16 /* packs per pass: a rank's pack buffer holds sub_iters x ZF_PACK_LEN doubles */
@@ -326,7 +328,11 @@ int zf_solver_get_x_prev(zf_solver* s, double* x_host, int64_t count /* >= n */)
 int zf_solver_restore(zf_solver* s, const double* xk_dev, const double* xprev_dev, const zf_control* saved,
                       int64_t saved_bytes /* == zf_sizeof_control(): a block of another layout is refused */);
 /* average duration (ms) of the trial kernel over the launches since the last
- * call, measured with HIP events on the solver's stream; resets the window */
+ * call, measured with HIP events on the solver's stream; resets the window.
+ * What the event pair brackets depends on the kind: the fused trial kernel (the prox step) for ZF_PROBLEM_DIAG_QUAD_L1,
+ * ZF_PROBLEM_LEAST_SQUARES_L1 and ZF_PROBLEM_BLUR_HAAR_L1 - the sweeps over A are NOT in it - but the WHOLE trial
+ * (residual at y, both sweeps, prox step, f(x+), finalize) for ZF_PROBLEM_SPARSE_LS_L1.  The same holds for
+ * zf_solver_pass_stats(_ex) and zf_solver_pass_records. */
 int zf_solver_trial_kernel_ms(zf_solver* s, double* avg_ms, int64_t* launches);
 /* since creation: out[0] = trial steps issued, out[1] = trial kernels launched for them; with count >= 4 also
  * out[2] = out[3] = 0 (ABI 5: the counts of a multi-pass kernel that round 5 withdrew).  A chained pass has
@@ -360,6 +366,10 @@ int zf_solver_launch_counts(zf_solver* s, int64_t* out, int64_t count /* >= 2 */
  * The operator problem (ZF_PROBLEM_BLUR_HAAR_L1) reports its plan in the same four slots: out[0] = tile height (8 or 32
  * rows), out[1] = 1 the separable (rank-1) correlation / 0 the general one, out[2] = 1 workgroups walk their tiles /
  * 0 one workgroup per tile, out[3] = 1 the prox step runs in the adjoint kernel's epilogue / 0 a launch of its own.
+ * Sparse least squares (ZF_PROBLEM_SPARSE_LS_L1): out[0] = 5, out[1] = lanes per row of the sweep over A, out[2] = lanes
+ * per row of the sweep over A^T, out[3] = split rows of A plus split rows of A^T.  (Beyond 32768 rows this kind forms
+ * r = A y - b, f(y) and f(x+) with up to 1024 workgroups and adds their chunk sums in chunk order; up to there with the one
+ * workgroup of the dense kind: the order of those two sums is a function of m alone, and changes at that size.)
  * Other problems: zeros. */
 int zf_solver_ls_plan(zf_solver* s, int64_t* out, int64_t count /* >= 4 */);
 /* the same window split by the shape of the pass, which the kernel logs itself: out[0], out[1] = mean
@@ -424,6 +434,47 @@ int zf_host_diag_grad(double* out_host, const double* x_host, const double* d_de
  * (tests/test_proximal_gradient.py:49-57) */
 int zf_ls_eval(const double* A_dev, const double* b_dev, int64_t m_rows, int64_t n, double scale,
                const double* x_host, double* f_out, double* grad_out_host);
+
+/* ---- sparse least squares (ZF_PROBLEM_SPARSE_LS_L1) -------------------------
+ * A (m x n) comes as TWO canonical CSR matrices in HBM - A itself and A^T, each with sorted, duplicate-free column
+ * indices: int64 row pointers (rows + 1), int32 column indices, float64 values; 24 B per stored element for the pair.
+ * Both sweeps of a trial are row sums against a gathered vector (csrc/zf_kernels_spmv.h): s+ = A x+ on the first,
+ * grad f(y) = 2 scale A^T r on the second - no atomics, every sum in an order fixed by the matrix and its plan.
+ * The device arrays stay the caller's and must outlive the handle; m, n < 2^31; nnz = 0 is legal (indices / values
+ * may then be NULL).
+ * The plan of one matrix is built by the caller on the host from its row pointers (zfista_amd.sparse.plan_rows):
+ * `lanes` lanes walk a row (a power of two, 4 .. 64, from the mean row length); rows LONGER than `threshold` elements
+ * are cut into segments of `threshold` elements (the last one shorter) summed by a wave each, and added per row in
+ * segment order.  split_row (nsplit, increasing), split_first (nsplit + 1: the first segment of each split row, ending
+ * with nseg) and seg_start (nseg: the first element of each segment) are HOST arrays.  zf_spmat_create copies the row
+ * pointers to the host once and checks the plan against them - split_row must list exactly the rows longer than
+ * `threshold`, the segments of a row must start with the row, lie `threshold` apart and cover it - returns ZF_ERR_ARG for
+ * a plan that does not fit, and keeps device copies.  plan_bytes = sizeof(zf_spmv_plan).
+ * The handle is immutable once created: any number of solvers and zf_spmat_eval calls may use it at the same time, on any
+ * streams (the segment sums of split rows belong to each solver / each call). */
+typedef struct zf_spmv_plan {
+    int32_t lanes;
+    int32_t reserved;
+    int64_t threshold;
+    int64_t nsplit;
+    int64_t nseg;
+    const int64_t* split_row;
+    const int64_t* split_first;
+    const int64_t* seg_start;
+} zf_spmv_plan;
+typedef struct zf_spmat zf_spmat; /* opaque */
+int zf_spmat_create(zf_spmat** out, int64_t m, int64_t n, int64_t nnz, const int64_t* indptr_dev, const int32_t* indices_dev,
+                    const double* values_dev, const zf_spmv_plan* plan, const int64_t* t_indptr_dev, const int32_t* t_indices_dev,
+                    const double* t_values_dev, const zf_spmv_plan* t_plan, int64_t plan_bytes);
+int zf_spmat_destroy(zf_spmat* h);
+/* f = scale |A x - b|^2 and (grad_out_host != NULL) grad = 2 scale A^T (A x - b) for a host vector x (n doubles; b_dev: m):
+ * the callback bodies of zfista_amd.problems.SparseLeastSquaresL1, on the kernels the solver runs */
+int zf_spmat_eval(const zf_spmat* h, const double* b_dev, double scale, const double* x_host, double* f_out,
+                  double* grad_out_host);
+/* zf_solver_create for ZF_PROBLEM_SPARSE_LS_L1: desc->kind = 4, A = NULL, b (dev, m), m_rows = m and n as the handle's,
+ * scale, lam and the box as for the dense kind, world = 1.  The handle must outlive the solver.  Everything else - init,
+ * steps, poll, restore, history - is the solver's as for every kind. */
+int zf_solver_create_sparse(zf_solver** out, const zf_problem_desc* desc, const zf_spmat* h, const zf_options* opt, void* stream);
 
 /* ---- multi-objective trial (m >= 2), device side ---------------------------
  * The dual of the scalarised subproblem is minimised on the host by SciPy exactly

@@ -20,6 +20,7 @@ LIB_PATH = os.environ.get("ZF_LIB_PATH") or os.path.join(CSRC, "libzfista_hip.so
 ZF_OK = 0
 ZF_RUNNING, ZF_CONVERGED, ZF_MAXITER, ZF_BACKTRACK_FAILED = 0, 1, 2, 3
 ZF_PROBLEM_DIAG_QUAD_L1, ZF_PROBLEM_LEAST_SQUARES_L1, ZF_PROBLEM_BLUR_HAAR_L1 = 1, 2, 3
+ZF_PROBLEM_SPARSE_LS_L1 = 4
 ZF_MO_GENERIC, ZF_MO_JOS1, ZF_MO_FDS = 0, 1, 2
 ZF_PACK_LEN, ZF_TRACE_COLS, ZF_RING = 8, 8, 1024
 ZF_MAX_SUB_ITERS = 16
@@ -83,6 +84,15 @@ class CommDesc(C.Structure):
         ("rank", C.c_int32), ("world", C.c_int32), ("kind", C.c_int32), ("nccl_count", C.c_int32),
         ("nccl_user_rank", C.c_int32), ("nccl_device", C.c_int32), ("rccl_version", C.c_int32), ("reserved", C.c_int32),
         ("all_gathers", C.c_int64), ("library", C.c_char * 256),
+    ]
+
+
+class SpmvPlan(C.Structure):
+    """Mirror of ``zf_spmv_plan``: the row plan of one CSR matrix (zfista_amd.sparse.plan_rows), host arrays."""
+
+    _fields_ = [
+        ("lanes", C.c_int32), ("reserved", C.c_int32), ("threshold", C.c_int64), ("nsplit", C.c_int64), ("nseg", C.c_int64),
+        ("split_row", C.c_void_p), ("split_first", C.c_void_p), ("seg_start", C.c_void_p),
     ]
 
 
@@ -197,6 +207,11 @@ SIGNATURES = {
     "zf_mo_post_terms": (C.c_int, [_P, C.c_double, _P, _P, _P]),
     "zf_op_eval": (C.c_int, [_P, C.c_int32, _P, C.c_int64, C.c_int64, C.c_double, _P, C.POINTER(C.c_double), _P]),
     "zf_ls_eval": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_double, _P, C.POINTER(C.c_double), _P]),
+    "zf_spmat_create": (C.c_int, [C.POINTER(_P), C.c_int64, C.c_int64, C.c_int64, _P, _P, _P, C.POINTER(SpmvPlan),
+                                  _P, _P, _P, C.POINTER(SpmvPlan), C.c_int64]),
+    "zf_spmat_destroy": (C.c_int, [_P]),
+    "zf_spmat_eval": (C.c_int, [_P, _P, C.c_double, _P, C.POINTER(C.c_double), _P]),
+    "zf_solver_create_sparse": (C.c_int, [C.POINTER(_P), C.POINTER(ProblemDesc), _P, C.POINTER(Options), _P]),
 }
 
 _lib = None

@@ -19,6 +19,7 @@
 #include "zf_kernels_gemv.h"
 #include "zf_kernels_ls_small.h"
 #include "zf_kernels_op.h"
+#include "zf_spmv.h"
 #include "zf_kernels_step.h"
 #include "zf_trial_launch.h"
 
@@ -193,10 +194,12 @@ struct zf_solver {
     bool own_packs = true;
     bool gemv_mfma = false;       // A^T r on v_mfma_f64_16x16x4 (n % 32 == 0; ZF_GEMV_MFMA=0 disables)
     bool ls_small = false;        // cache-resident A: two fused launches per trial (zf_kernels_ls_small.h)
+    const zf_spmat* spmat = nullptr;   // sparse least squares: A and A^T with their plans (the caller's handle: zf_solver_create_sparse; never written through)
+    double* sp_part_A = nullptr, *sp_part_At = nullptr;   // ... this solver's segment sums of the split rows of A / of A^T
     zf_op_plan op_plan = {};      // operator problem: which instantiation of the correlation kernels runs it (zf_op_make_plan)
     double* op_buf = nullptr;     // its taps as launched (zero-padded to K x K) and, behind them, the rank-1 factors u, v when the kernel is separable
     const double* op_taps = nullptr, *op_sep = nullptr;
-    double* row_part = nullptr;   // ls_small: workgroup sums of the row kernel
+    double* row_part = nullptr;   // ls_small: workgroup sums of the row kernel; sparse: chunk sums of the two residuals
     unsigned* ls_cnt = nullptr;
     int64_t ntiles = 1;           // 16 KiB tiles of the trial kernel
     int tiles = 1;                // interleaved tiles per workgroup (zf_solver_autotune picks it)
@@ -328,7 +331,7 @@ static int zf_solver_free_all(zf_solver* s) {
     }
     if (s->ra_join) (void)hipEventDestroy(s->ra_join);
     if (s->ra_fork) (void)hipEventDestroy(s->ra_fork);
-    void* ptrs[] = {s->op_buf, s->row_part, s->ls_cnt, s->blk_part, s->slice_part, s->fin_cnt, s->grp_part, s->xbuf, s->partials, s->ctl_trace, s->beta_ring,
+    void* ptrs[] = {s->sp_part_A, s->sp_part_At, s->op_buf, s->row_part, s->ls_cnt, s->blk_part, s->slice_part, s->fin_cnt, s->grp_part, s->xbuf, s->partials, s->ctl_trace, s->beta_ring,
                     s->ra_word, s->ra_flags, s->blk_part2, s->grp_part2, s->fin_cnt2, s->pack2,
                     s->own_packs ? s->pack_local : nullptr, s->own_packs ? s->pack_all : nullptr,
                     s->grad, s->sbuf, s->resid, s->slab, s->ls_scal,
@@ -352,9 +355,11 @@ static zf_trial_sel zf_sel_of(const zf_solver* s) { return zf_trial_sel{s->opt.n
 
 static bool zf_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
-// least squares with an explicit matrix, or with the blur o inverse-Haar operator (zf_kernels_op.h): everything
-// around the two applications of A / its adjoint is shared
-static bool zf_is_ls(int kind) { return kind == ZF_PROBLEM_LEAST_SQUARES_L1 || kind == ZF_PROBLEM_BLUR_HAAR_L1; }
+// least squares with an explicit matrix - dense, or CSR (zf_kernels_spmv.h) - or with the blur o inverse-Haar operator
+// (zf_kernels_op.h): everything around the two applications of A / its adjoint is shared
+static bool zf_is_ls(int kind) {
+    return kind == ZF_PROBLEM_LEAST_SQUARES_L1 || kind == ZF_PROBLEM_BLUR_HAAR_L1 || kind == ZF_PROBLEM_SPARSE_LS_L1;
+}
 static zf_op_args zf_op_of(const zf_problem_desc& d, const zf_control* ctl, const zf_op_plan& pl, const double* taps, const double* sep) {
     zf_op_args P;
     P.ctl = ctl;
@@ -409,6 +414,11 @@ static void zf_launch_apply_A(zf_solver* s, const zf_control* ctl, zf_ring3 xr, 
                            zf_op_no_fuse());
         return;
     }
+    if (d.kind == ZF_PROBLEM_SPARSE_LS_L1) {
+        const zf_spmv_io io = {{xr.p[0], xr.p[1], xr.p[2]}, {sout.p[0], sout.p[1], sout.p[2]}};
+        zf_launch_spmv(s->spmat->A, s->stream, ctl, false, io, slot, 1.0, s->sp_part_A);
+        return;
+    }
     const int V = (n % 2 == 0) ? 2 : 1;
     int gr = (int)((m + GEMV_ROWS - 1) / GEMV_ROWS);
     if (gr > 8 * ZF_MAX_GRID) gr = 8 * ZF_MAX_GRID;
@@ -454,8 +464,8 @@ static hipError_t zf_second_stream(zf_solver* s) {
     return hipSuccess;
 }
 
-extern "C" int zf_solver_create(zf_solver** out, const zf_problem_desc* desc, const zf_options* opt,
-                                void* stream) {
+// sp: the matrix handle of ZF_PROBLEM_SPARSE_LS_L1 (zf_solver_create_sparse), NULL for every other kind
+static int zf_solver_create_impl(zf_solver** out, const zf_problem_desc* desc, const zf_options* opt, void* stream, const zf_spmat* sp) {
     ZF_REQUIRE(out && desc && opt, "zf_solver_create: null argument");
     ZF_REQUIRE(desc->n >= 1, "zf_solver_create: n must be >= 1");
     ZF_REQUIRE(desc->world >= 1 && desc->rank >= 0 && desc->rank < desc->world,
@@ -481,6 +491,11 @@ extern "C" int zf_solver_create(zf_solver** out, const zf_problem_desc* desc, co
                        desc->op_k / 2 < desc->op_w,
                    "zf_solver_create: op_k must be odd, at most 15 and smaller than twice the image");
         ZF_REQUIRE(desc->world == 1, "zf_solver_create: the operator problem is not sharded");
+    } else if (desc->kind == ZF_PROBLEM_SPARSE_LS_L1) {
+        ZF_REQUIRE(sp, "zf_solver_create: ZF_PROBLEM_SPARSE_LS_L1 takes its matrix through zf_solver_create_sparse");
+        ZF_REQUIRE(desc->b && !desc->A, "zf_solver_create_sparse: b is required and A must be NULL (the matrix is the handle's)");
+        ZF_REQUIRE(desc->m_rows == sp->m && desc->n == sp->n, "zf_solver_create_sparse: m_rows and n differ from the matrix handle's");
+        ZF_REQUIRE(desc->world == 1, "zf_solver_create_sparse: sparse least squares is not sharded");
     } else {
         return zf_fail(ZF_ERR_ARG, "zf_solver_create: unknown problem kind");
     }
@@ -488,6 +503,7 @@ extern "C" int zf_solver_create(zf_solver** out, const zf_problem_desc* desc, co
     if (!s) return zf_fail(ZF_ERR_ARG, "zf_solver_create: out of host memory");
     s->desc = *desc;
     s->opt = *opt;
+    s->spmat = sp;
     s->env = zf_env_read();
     s->pass_seq = s->env.pass_seq_start;
     s->stream = reinterpret_cast<hipStream_t>(stream);
@@ -615,6 +631,18 @@ extern "C" int zf_solver_create(zf_solver** out, const zf_problem_desc* desc, co
         ZF_TRY(hipMalloc(&s->ls_cnt, 64));
         ZF_TRY(hipMemsetAsync(s->ls_cnt, 0, 64, s->stream));
     }
+    if (desc->kind == ZF_PROBLEM_SPARSE_LS_L1) {   // what the dense kind takes, minus the slab, plus the segment sums of split rows
+        // (per solver: solves that share a matrix handle may run at the same time on other streams)
+        if (sp->A.nseg > 0) ZF_TRY(hipMalloc(&s->sp_part_A, sizeof(double) * sp->A.nseg));
+        if (sp->At.nseg > 0) ZF_TRY(hipMalloc(&s->sp_part_At, sizeof(double) * sp->At.nseg));
+        const int64_t m_pad = (desc->m_rows + 63) & ~int64_t(63);
+        ZF_TRY(hipMalloc(&s->grad, sizeof(double) * n_pad));
+        ZF_TRY(hipMalloc(&s->sbuf, sizeof(double) * 3 * m_pad));
+        for (int k = 0; k < 3; ++k) s->sring.p[k] = s->sbuf + k * m_pad;
+        ZF_TRY(hipMalloc(&s->resid, sizeof(double) * m_pad));
+        ZF_TRY(hipMalloc(&s->ls_scal, sizeof(double) * 8));
+        ZF_TRY(hipMalloc(&s->row_part, sizeof(double) * 2 * ZF_SPMV_RESID_MAX_CHUNKS));   // chunk sums of |r(y)|^2 and of |s+ - b|^2
+    }
     if (desc->kind == ZF_PROBLEM_LEAST_SQUARES_L1) {
         const int64_t m = desc->m_rows;
         const int64_t m_pad = (m + 63) & ~int64_t(63);
@@ -651,6 +679,16 @@ extern "C" int zf_solver_create(zf_solver** out, const zf_problem_desc* desc, co
 #undef ZF_TRY
     *out = s;
     return ZF_OK;
+}
+
+extern "C" int zf_solver_create(zf_solver** out, const zf_problem_desc* desc, const zf_options* opt, void* stream) {
+    return zf_solver_create_impl(out, desc, opt, stream, nullptr);
+}
+
+extern "C" int zf_solver_create_sparse(zf_solver** out, const zf_problem_desc* desc, const zf_spmat* h, const zf_options* opt, void* stream) {
+    ZF_REQUIRE(out && desc && h && opt, "zf_solver_create_sparse: null argument");
+    ZF_REQUIRE(desc->kind == ZF_PROBLEM_SPARSE_LS_L1, "zf_solver_create_sparse: desc->kind must be ZF_PROBLEM_SPARSE_LS_L1");
+    return zf_solver_create_impl(out, desc, opt, stream, h);
 }
 
 extern "C" int zf_solver_destroy(zf_solver* s) {
@@ -1241,8 +1279,16 @@ static int zf_launch_trial(zf_solver* s, bool decide_in_launch, bool dry = false
     } else {
         const int64_t n = d.n, m = d.m_rows;
         const int V = (n % 2 == 0) ? 2 : 1;
+        // (the sparse kind times the whole trial - the event pair brackets every launch of it, not the prox step alone)
+        const bool time_whole = d.kind == ZF_PROBLEM_SPARSE_LS_L1;
+        if (time_whole && e0) ZF_HIP(hipEventRecord(e0, s->stream));
         // (1) r = A y - b by linearity, f(y); grad = 2 scale A^T r   [only when y changed]
-        if (d.kind != ZF_PROBLEM_BLUR_HAAR_L1)   // (the operator problem forms r inside its adjoint kernel)
+        // (sparse matrices have 1e5 .. 1e7 rows: beyond what one workgroup should walk, the residuals take many - zf_kernels_spmv.h)
+        const bool wide_resid = d.kind == ZF_PROBLEM_SPARSE_LS_L1 && m > ZF_SPMV_WIDE_RESID_MIN_ROWS;
+        if (wide_resid)
+            zf_launch_spmv_resid_y(s->stream, s->ctl, s->sring.p[0], s->sring.p[1], s->sring.p[2], d.b, s->resid, d.scale, m,
+                                   (int)s->opt.nesterov, s->row_part, s->ls_scal + 0);
+        else if (d.kind != ZF_PROBLEM_BLUR_HAAR_L1)   // (the operator problem forms r inside its adjoint kernel)
             hipLaunchKernelGGL(zf_resid_y_kernel, dim3(1), dim3(RESID_BLOCK), 0, s->stream, s->ctl,
                                s->beta_ring, s->sring, d.b, s->resid, d.scale, m, s->ls_scal + 0,
                                (int)s->opt.nesterov);
@@ -1308,6 +1354,27 @@ static int zf_launch_trial(zf_solver* s, bool decide_in_launch, bool dry = false
                                    d.scale, m, s->ls_scal + 1);
                 zf_launch_finalize(s, false);
             }
+            ZF_HIP(hipGetLastError());
+            return ZF_OK;
+        }
+        if (d.kind == ZF_PROBLEM_SPARSE_LS_L1) {
+            // the trial of a dense matrix with its two sweeps swapped for the CSR row sums: grad = 2 scale A^T r over the
+            // stored A^T (only when y changed), the prox step, s+ = A x+, f(x+), finalize
+            const zf_spmv_io gio = {{s->resid, s->resid, s->resid}, {s->grad, s->grad, s->grad}};
+            zf_launch_spmv(s->spmat->At, s->stream, s->ctl, true, gio, -1, 2 * d.scale, s->sp_part_At);
+            a.p0 = s->grad;
+            a.p1 = nullptr;
+            zf_launch_trial_kernels(s, a, false);
+            zf_ring3 xr3 = {{s->xb[0], s->xb[1], s->xb[2]}};
+            zf_launch_apply_A(s, s->ctl, xr3, s->sring, 1);
+            if (wide_resid)
+                zf_launch_spmv_resid_x(s->stream, s->ctl, s->sring.p[0], s->sring.p[1], s->sring.p[2], 1, d.b, d.scale, m,
+                                       s->row_part + ZF_SPMV_RESID_MAX_CHUNKS, s->ls_scal + 1);
+            else
+                hipLaunchKernelGGL(zf_resid_x_kernel, dim3(1), dim3(RESID_BLOCK), 0, s->stream, s->ctl, s->sring, 1, d.b, d.scale, m,
+                                   s->ls_scal + 1);
+            zf_launch_finalize(s, decide_in_launch);
+            if (e1) ZF_HIP(hipEventRecord(e1, s->stream));
             ZF_HIP(hipGetLastError());
             return ZF_OK;
         }
@@ -1723,6 +1790,13 @@ extern "C" int zf_solver_ls_plan(zf_solver* s, int64_t* out, int64_t count) {
         out[1] = pl.sep ? 1 : 0;
         out[2] = pl.persist ? 1 : 0;
         out[3] = (pl.fuse_prox && !s->hist) ? 1 : 0;
+        return ZF_OK;
+    }
+    if (s->desc.kind == ZF_PROBLEM_SPARSE_LS_L1) {
+        out[0] = 5;
+        out[1] = s->spmat->A.lanes;
+        out[2] = s->spmat->At.lanes;
+        out[3] = s->spmat->A.nsplit + s->spmat->At.nsplit;
         return ZF_OK;
     }
     if (s->desc.kind != ZF_PROBLEM_LEAST_SQUARES_L1) return ZF_OK;
@@ -2278,6 +2352,48 @@ extern "C" int zf_ls_eval(const double* A_dev, const double* b_dev, int64_t m_ro
     }
 #undef ZF_LS
     for (void* p : {(void*)x, (void*)s, (void*)slab, (void*)grad, (void*)fdev})
+        if (p) (void)hipFree(p);
+    return rc;
+}
+
+// the same for a CSR matrix behind a handle (zf_spmat_create), on the two sweeps the solver runs
+extern "C" int zf_spmat_eval(const zf_spmat* h, const double* b_dev, double scale, const double* x_host, double* f_out,
+                             double* grad_out_host) {
+    ZF_REQUIRE(h && b_dev && x_host && f_out, "zf_spmat_eval: null argument");
+    const int64_t m = h->m, n = h->n;
+    double *x = nullptr, *sv = nullptr, *grad = nullptr, *fdev = nullptr, *part_A = nullptr, *part_At = nullptr;
+    int rc = ZF_OK;
+#define ZF_SP(expr)                                                               \
+    do {                                                                          \
+        hipError_t _e = (expr);                                                   \
+        if (_e != hipSuccess && rc == ZF_OK)                                      \
+            rc = zf_fail(ZF_ERR_HIP, "%s: %s", #expr, hipGetErrorString(_e));     \
+    } while (0)
+    ZF_SP(hipMalloc(&x, sizeof(double) * n));
+    ZF_SP(hipMalloc(&sv, sizeof(double) * m));
+    ZF_SP(hipMalloc(&fdev, sizeof(double) * 2));
+    if (grad_out_host) ZF_SP(hipMalloc(&grad, sizeof(double) * n));
+    // (the segment sums of split rows are this call's own: the handle is shared with solvers running on other streams)
+    if (h->A.nseg > 0) ZF_SP(hipMalloc(&part_A, sizeof(double) * h->A.nseg));
+    if (grad_out_host && h->At.nseg > 0) ZF_SP(hipMalloc(&part_At, sizeof(double) * h->At.nseg));
+    if (rc == ZF_OK) {
+        ZF_SP(hipMemcpyAsync(x, x_host, sizeof(double) * n, hipMemcpyHostToDevice, nullptr));
+        zf_ring3 sr = {{sv, sv, sv}};
+        const zf_spmv_io aio = {{x, x, x}, {sv, sv, sv}};
+        zf_launch_spmv(h->A, nullptr, nullptr, false, aio, -1, 1.0, part_A);
+        hipLaunchKernelGGL(zf_resid_x_kernel, dim3(1), dim3(RESID_BLOCK), 0, nullptr, nullptr, sr, -1, b_dev, scale, m, fdev);
+        if (grad_out_host) {
+            hipLaunchKernelGGL(zf_axmb_kernel, dim3(zf_grid_for(m)), dim3(ZF_BLOCK), 0, nullptr, sv, b_dev, m);
+            const zf_spmv_io gio = {{sv, sv, sv}, {grad, grad, grad}};
+            zf_launch_spmv(h->At, nullptr, nullptr, false, gio, -1, 2 * scale, part_At);
+            ZF_SP(hipMemcpyAsync(grad_out_host, grad, sizeof(double) * n, hipMemcpyDeviceToHost, nullptr));
+        }
+        ZF_SP(hipGetLastError());
+        ZF_SP(hipMemcpyAsync(f_out, fdev, sizeof(double), hipMemcpyDeviceToHost, nullptr));
+        ZF_SP(hipStreamSynchronize(nullptr));
+    }
+#undef ZF_SP
+    for (void* p : {(void*)x, (void*)sv, (void*)grad, (void*)fdev, (void*)part_A, (void*)part_At})
         if (p) (void)hipFree(p);
     return rc;
 }

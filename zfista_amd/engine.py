@@ -78,15 +78,21 @@ class DeviceSolver:
             stream = torch.cuda.current_stream().cuda_stream
         self.stream = stream
         d = _lib.ProblemDesc()
+        spmat = desc_fields.get("spmat")   # a zf_spmat handle: the matrix of a sparse problem is no descriptor field
         for k, v in desc_fields.items():
-            setattr(d, k, v)
+            if k != "spmat":
+                setattr(d, k, v)
         o = _lib.Options()
         for k, v in options.items():
             setattr(o, k, v)
         self.nesterov = bool(options.get("nesterov", 0))
         h = C.c_void_p()
-        _lib.check(self.lib.zf_solver_create(C.byref(h), C.byref(d), C.byref(o), C.c_void_p(stream)),
-                   "zf_solver_create")
+        if spmat is not None:
+            _lib.check(self.lib.zf_solver_create_sparse(C.byref(h), C.byref(d), C.c_void_p(spmat), C.byref(o), C.c_void_p(stream)),
+                       "zf_solver_create_sparse")
+        else:
+            _lib.check(self.lib.zf_solver_create(C.byref(h), C.byref(d), C.byref(o), C.c_void_p(stream)),
+                       "zf_solver_create")
         self.handle = h
         sub = C.c_int32(1)
         _lib.check(self.lib.zf_solver_sub_iters(h, C.byref(sub)), "zf_solver_sub_iters")
@@ -279,7 +285,8 @@ class DeviceSolver:
         4 VALU scalar loads; row sweep: 1 the small-matrix rows kernel, 2 zf_gemv_rows_kernel<2>, 3 <1>.
         The operator problem (BlurHaarL1): (tile height - 8 or 32 rows, 1 separable correlation / 0 general,
         1 workgroups walk their tiles / 0 one workgroup per tile, 1 prox step fused into the adjoint kernel / 0 a
-        launch of its own).  Other problems: zeros."""
+        launch of its own).  Sparse least squares (SparseLeastSquaresL1): (5, lanes per row of the sweep over A, lanes per
+        row of the sweep over A^T, split rows of both).  Other problems: zeros."""
         out = np.zeros(4, dtype=np.int64)
         _lib.check(self.lib.zf_solver_ls_plan(self.handle, C.c_void_p(_lib.ptr(out)), out.size))
         return tuple(int(v) for v in out)

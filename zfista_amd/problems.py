@@ -200,6 +200,97 @@ class LeastSquaresL1(NativeProblem):
         return fields, (self.A, self.b)
 
 
+class _SpmatHandle:
+    """Owner of a ``zf_spmat`` handle and of the device arrays behind it."""
+
+    def __init__(self, prep):
+        import torch
+
+        lib = _lib.require_gpu()
+        self.lib = lib
+        names = ("indptr", "indices", "data", "t_indptr", "t_indices", "t_data")
+        self.dev = {k: torch.from_numpy(prep[k]).cuda() for k in names}
+        self.plans = []   # (the host arrays a zf_spmv_plan points to, for the duration of the call)
+        for key in ("plan", "t_plan"):
+            p = prep[key]
+            c = _lib.SpmvPlan(lanes=p["lanes"], threshold=p["threshold"], nsplit=p["split_row"].size, nseg=p["seg_start"].size,
+                              split_row=_lib.ptr(p["split_row"]) if p["split_row"].size else None,
+                              split_first=_lib.ptr(p["split_first"]) if p["split_row"].size else None,
+                              seg_start=_lib.ptr(p["seg_start"]) if p["seg_start"].size else None)
+            self.plans.append((c, p))
+        dp = lambda k: C.c_void_p(self.dev[k].data_ptr() if self.dev[k].numel() else None)
+        h = C.c_void_p()
+        _lib.check(lib.zf_spmat_create(C.byref(h), prep["m"], prep["n"], prep["nnz"], dp("indptr"), dp("indices"), dp("data"),
+                                       C.byref(self.plans[0][0]), dp("t_indptr"), dp("t_indices"), dp("t_data"),
+                                       C.byref(self.plans[1][0]), C.sizeof(_lib.SpmvPlan)), "zf_spmat_create")
+        self.value = h
+
+    def __del__(self):
+        try:
+            if getattr(self, "value", None):
+                self.lib.zf_spmat_destroy(self.value)
+                self.value = None
+        except Exception:
+            pass
+
+
+class SparseLeastSquaresL1(NativeProblem):
+    r"""f(x) = scale \|Ax - b\|^2,  g(x) = lam \|x\|_1 (+ optional box) with a SPARSE A: the problem of
+    ``LeastSquaresL1`` - same keywords, same result fields - for matrices that have no dense form in HBM.
+
+    ``A``: a scipy.sparse matrix / array of any format and real dtype (m x n; m, n < 2**31).  It is made canonical CSR on
+    the host (duplicates summed, indices sorted; float64 values, int32 column indices, int64 row pointers), and so is
+    ``A.T``: both sweeps of a trial - A x+ and A^T r - are row sums of a stored matrix against a gathered vector
+    (csrc/zf_kernels_spmv.h), with no atomics and in an order fixed by the matrix alone.  Both copies go to HBM: 24 B per
+    stored element in total.  A matrix with no stored element is legal.  Single GPU."""
+
+    kind = _lib.ZF_PROBLEM_SPARSE_LS_L1
+
+    def __init__(self, A, b, lam, scale=0.5, bounds=None):
+        import torch
+
+        from . import sparse
+
+        b_host = b.detach().cpu().numpy() if isinstance(b, torch.Tensor) else b
+        prep = sparse.prepare(A, b_host)   # (every ValueError comes from here, before anything touches the device)
+        self.b = _to_device(b, "b")
+        self.lam, self.scale = float(lam), float(scale)
+        self.box = (-np.inf, np.inf) if bounds is None else (float(bounds[0]), float(bounds[1]))
+        self.m_rows, self.n_features, self.nnz = prep["m"], prep["n"], prep["nnz"]
+        self.plan = (prep["plan"], prep["t_plan"])
+        self.group = None
+        self._spmat = _SpmatHandle(prep)
+
+    def _ls(self, x, want_grad):
+        x = _as_host(x)
+        if x.size != self.n_features:
+            raise ValueError(f"len(x) should be equal to n_features, got {x}.")
+        lib = _lib.require_gpu()
+        fval = C.c_double(0.0)
+        grad = np.empty_like(x) if want_grad else None
+        _lib.check(lib.zf_spmat_eval(self._spmat.value, C.c_void_p(self.b.data_ptr()), self.scale, C.c_void_p(_lib.ptr(x)),
+                                     C.byref(fval), C.c_void_p(_lib.ptr(grad)) if want_grad else None), "zf_spmat_eval")
+        return np.float64(fval.value), grad
+
+    def f(self, x):
+        return self._ls(x, False)[0]
+
+    def jac_f(self, x):
+        return self._ls(x, True)[1]
+
+    def _eval_fg(self, x):
+        lib = _lib.require_gpu()
+        s = C.c_double(0.0)
+        _lib.check(lib.zf_host_asum(C.c_void_p(_lib.ptr(x)), x.size, C.byref(s)), "zf_host_asum")
+        return None, np.float64(self.lam * s.value)
+
+    def _descriptor(self):
+        fields = dict(kind=self.kind, world=1, rank=0, n=self.n_features, m_rows=self.m_rows, row_sharded=0,
+                      d=None, c=None, A=None, b=self.b.data_ptr(), scale=self.scale, lam=self.lam,
+                      box_lo=self.box[0], box_hi=self.box[1], spmat=self._spmat.value.value)
+        return fields, (self._spmat, self.b)
+
+
 class BlurHaarL1(NativeProblem):
     r"""Operator-form LASSO: f(x) = scale \|B W^{-1} x - b\|^2,  g(x) = lam \|x\|_1 (+ optional box), with B the
     correlation with ``kernel`` (odd size <= 15, symmetric boundary - ``scipy.signal.correlate2d(..., mode="same",
