@@ -54,6 +54,9 @@ extern "C" {
                                          reference's examples/cameraman.ipynb:219-272; g = lam |x|_1 (+box)        */
 #define ZF_PROBLEM_SPARSE_LS_L1 4     /* f = scale |Ax-b|^2 with A a CSR matrix behind a zf_spmat handle
                                          (zf_solver_create_sparse);     g = lam |x|_1 (+box)                       */
+#define ZF_PROBLEM_LOGISTIC_L1 5      /* f = scale sum_i softplus(-b_i (Ax)_i), b_i in {-1, +1} (the labels; the caller checks
+                                         them), A dense row-major as for kind 2; g = lam |x|_1 (+box); world = 1        */
+#define ZF_PROBLEM_SPARSE_LOGISTIC_L1 6 /* the same f with A a CSR matrix behind a zf_spmat handle (zf_solver_create_sparse) */
 
 #define ZF_PACK_LEN 8    /* doubles in one per-trial scalar pack */
 #define ZF_MAX_SUB_ITERS 16 /* packs per pass: a rank's pack buffer holds sub_iters x ZF_PACK_LEN doubles */
@@ -331,7 +334,8 @@ int zf_solver_restore(zf_solver* s, const double* xk_dev, const double* xprev_de
  * call, measured with HIP events on the solver's stream; resets the window.
  * What the event pair brackets depends on the kind: the fused trial kernel (the prox step) for ZF_PROBLEM_DIAG_QUAD_L1,
  * ZF_PROBLEM_LEAST_SQUARES_L1 and ZF_PROBLEM_BLUR_HAAR_L1 - the sweeps over A are NOT in it - but the WHOLE trial
- * (residual at y, both sweeps, prox step, f(x+), finalize) for ZF_PROBLEM_SPARSE_LS_L1.  The same holds for
+ * (residual at y, both sweeps, prox step, f(x+), finalize) for ZF_PROBLEM_SPARSE_LS_L1.  The logistic kinds follow their
+ * siblings: ZF_PROBLEM_LOGISTIC_L1 as kind 2, ZF_PROBLEM_SPARSE_LOGISTIC_L1 as kind 4.  The same holds for
  * zf_solver_pass_stats(_ex) and zf_solver_pass_records. */
 int zf_solver_trial_kernel_ms(zf_solver* s, double* avg_ms, int64_t* launches);
 /* since creation: out[0] = trial steps issued, out[1] = trial kernels launched for them; with count >= 4 also
@@ -370,6 +374,10 @@ int zf_solver_launch_counts(zf_solver* s, int64_t* out, int64_t count /* >= 2 */
  * per row of the sweep over A^T, out[3] = split rows of A plus split rows of A^T.  (Beyond 32768 rows this kind forms
  * r = A y - b, f(y) and f(x+) with up to 1024 workgroups and adds their chunk sums in chunk order; up to there with the one
  * workgroup of the dense kind: the order of those two sums is a function of m alone, and changes at that size.)
+ * The logistic kinds report the plan of their storage form in the same slots: ZF_PROBLEM_LOGISTIC_L1 out[0] = 2, 3 or 4 and
+ * out[1] = 2 or 3 as ZF_PROBLEM_LEAST_SQUARES_L1 (never 1: the small-matrix kernels hold the squared loss), out[2], out[3]
+ * the slices; ZF_PROBLEM_SPARSE_LOGISTIC_L1 out[0] = 5 and the lanes / split rows as ZF_PROBLEM_SPARSE_LS_L1.  (Both form
+ * rho(y), f(y) and f(x+) with one workgroup up to 32768 rows and with up to 1024 beyond, chunk sums added in chunk order.)
  * Other problems: zeros. */
 int zf_solver_ls_plan(zf_solver* s, int64_t* out, int64_t count /* >= 4 */);
 /* the same window split by the shape of the pass, which the kernel logs itself: out[0], out[1] = mean
@@ -434,6 +442,11 @@ int zf_host_diag_grad(double* out_host, const double* x_host, const double* d_de
  * (tests/test_proximal_gradient.py:49-57) */
 int zf_ls_eval(const double* A_dev, const double* b_dev, int64_t m_rows, int64_t n, double scale,
                const double* x_host, double* f_out, double* grad_out_host);
+/* the same for ZF_PROBLEM_LOGISTIC_L1: f = scale sum_i softplus(-b_i (A x)_i) and (grad_out_host != NULL) grad = scale A^T rho,
+ * rho_i = -b_i sigma(-b_i (A x)_i); b_dev: the labels, +-1 (m_rows doubles).  Finite for every finite margin: one
+ * exp(-|t|) per row feeds softplus(t) = max(t, 0) + log1p(e) and sigma(t) = t >= 0 ? 1 / (1 + e) : e / (1 + e) */
+int zf_logistic_eval(const double* A_dev, const double* b_dev, int64_t m_rows, int64_t n, double scale,
+                     const double* x_host, double* f_out, double* grad_out_host);
 
 /* ---- sparse least squares (ZF_PROBLEM_SPARSE_LS_L1) -------------------------
  * A (m x n) comes as TWO canonical CSR matrices in HBM - A itself and A^T, each with sorted, duplicate-free column
@@ -471,7 +484,10 @@ int zf_spmat_destroy(zf_spmat* h);
  * the callback bodies of zfista_amd.problems.SparseLeastSquaresL1, on the kernels the solver runs */
 int zf_spmat_eval(const zf_spmat* h, const double* b_dev, double scale, const double* x_host, double* f_out,
                   double* grad_out_host);
-/* zf_solver_create for ZF_PROBLEM_SPARSE_LS_L1: desc->kind = 4, A = NULL, b (dev, m), m_rows = m and n as the handle's,
+/* zf_logistic_eval over the handle: f and grad of ZF_PROBLEM_SPARSE_LOGISTIC_L1 (b_dev: the labels, +-1) */
+int zf_spmat_logistic_eval(const zf_spmat* h, const double* b_dev, double scale, const double* x_host, double* f_out,
+                           double* grad_out_host);
+/* zf_solver_create for ZF_PROBLEM_SPARSE_LS_L1 and ZF_PROBLEM_SPARSE_LOGISTIC_L1: desc->kind = 4 or 6, A = NULL, b (dev, m), m_rows = m and n as the handle's,
  * scale, lam and the box as for the dense kind, world = 1.  The handle must outlive the solver.  Everything else - init,
  * steps, poll, restore, history - is the solver's as for every kind. */
 int zf_solver_create_sparse(zf_solver** out, const zf_problem_desc* desc, const zf_spmat* h, const zf_options* opt, void* stream);

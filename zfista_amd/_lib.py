@@ -21,6 +21,7 @@ ZF_OK = 0
 ZF_RUNNING, ZF_CONVERGED, ZF_MAXITER, ZF_BACKTRACK_FAILED = 0, 1, 2, 3
 ZF_PROBLEM_DIAG_QUAD_L1, ZF_PROBLEM_LEAST_SQUARES_L1, ZF_PROBLEM_BLUR_HAAR_L1 = 1, 2, 3
 ZF_PROBLEM_SPARSE_LS_L1 = 4
+ZF_PROBLEM_LOGISTIC_L1, ZF_PROBLEM_SPARSE_LOGISTIC_L1 = 5, 6
 ZF_MO_GENERIC, ZF_MO_JOS1, ZF_MO_FDS = 0, 1, 2
 ZF_PACK_LEN, ZF_TRACE_COLS, ZF_RING = 8, 8, 1024
 ZF_MAX_SUB_ITERS = 16
@@ -207,6 +208,8 @@ SIGNATURES = {
     "zf_mo_post_terms": (C.c_int, [_P, C.c_double, _P, _P, _P]),
     "zf_op_eval": (C.c_int, [_P, C.c_int32, _P, C.c_int64, C.c_int64, C.c_double, _P, C.POINTER(C.c_double), _P]),
     "zf_ls_eval": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_double, _P, C.POINTER(C.c_double), _P]),
+    "zf_logistic_eval": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_double, _P, C.POINTER(C.c_double), _P]),
+    "zf_spmat_logistic_eval": (C.c_int, [_P, _P, C.c_double, _P, C.POINTER(C.c_double), _P]),
     "zf_spmat_create": (C.c_int, [C.POINTER(_P), C.c_int64, C.c_int64, C.c_int64, _P, _P, _P, C.POINTER(SpmvPlan),
                                   _P, _P, _P, C.POINTER(SpmvPlan), C.c_int64]),
     "zf_spmat_destroy": (C.c_int, [_P]),

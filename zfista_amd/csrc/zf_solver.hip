@@ -20,6 +20,7 @@
 #include "zf_kernels_ls_small.h"
 #include "zf_kernels_op.h"
 #include "zf_spmv.h"
+#include "zf_kernels_loss.h"
 #include "zf_kernels_step.h"
 #include "zf_trial_launch.h"
 
@@ -199,7 +200,7 @@ struct zf_solver {
     zf_op_plan op_plan = {};      // operator problem: which instantiation of the correlation kernels runs it (zf_op_make_plan)
     double* op_buf = nullptr;     // its taps as launched (zero-padded to K x K) and, behind them, the rank-1 factors u, v when the kernel is separable
     const double* op_taps = nullptr, *op_sep = nullptr;
-    double* row_part = nullptr;   // ls_small: workgroup sums of the row kernel; sparse: chunk sums of the two residuals
+    double* row_part = nullptr;   // ls_small: workgroup sums of the row kernel; sparse and logistic: chunk sums of the two residuals / losses
     unsigned* ls_cnt = nullptr;
     int64_t ntiles = 1;           // 16 KiB tiles of the trial kernel
     int tiles = 1;                // interleaved tiles per workgroup (zf_solver_autotune picks it)
@@ -360,6 +361,13 @@ static bool zf_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p)
 static bool zf_is_ls(int kind) {
     return kind == ZF_PROBLEM_LEAST_SQUARES_L1 || kind == ZF_PROBLEM_BLUR_HAAR_L1 || kind == ZF_PROBLEM_SPARSE_LS_L1;
 }
+// the logistic loss of the margins A x (zf_kernels_loss.h) on the same two storage forms of A: the trial of the squared
+// loss with the residual kernels swapped for the loss kernels and the sweeps called with scale for 2 scale
+static bool zf_is_logistic(int kind) { return kind == ZF_PROBLEM_LOGISTIC_L1 || kind == ZF_PROBLEM_SPARSE_LOGISTIC_L1; }
+static bool zf_is_dense_mat(int kind) { return kind == ZF_PROBLEM_LEAST_SQUARES_L1 || kind == ZF_PROBLEM_LOGISTIC_L1; }
+static bool zf_is_sparse_mat(int kind) { return kind == ZF_PROBLEM_SPARSE_LS_L1 || kind == ZF_PROBLEM_SPARSE_LOGISTIC_L1; }
+// f is a loss of A x: the margins of x_k, x_{k-1} are kept in a ring and A y follows by linearity
+static bool zf_has_margins(int kind) { return zf_is_ls(kind) || zf_is_logistic(kind); }
 static zf_op_args zf_op_of(const zf_problem_desc& d, const zf_control* ctl, const zf_op_plan& pl, const double* taps, const double* sep) {
     zf_op_args P;
     P.ctl = ctl;
@@ -414,7 +422,7 @@ static void zf_launch_apply_A(zf_solver* s, const zf_control* ctl, zf_ring3 xr, 
                            zf_op_no_fuse());
         return;
     }
-    if (d.kind == ZF_PROBLEM_SPARSE_LS_L1) {
+    if (zf_is_sparse_mat(d.kind)) {
         const zf_spmv_io io = {{xr.p[0], xr.p[1], xr.p[2]}, {sout.p[0], sout.p[1], sout.p[2]}};
         zf_launch_spmv(s->spmat->A, s->stream, ctl, false, io, slot, 1.0, s->sp_part_A);
         return;
@@ -479,9 +487,10 @@ static int zf_solver_create_impl(zf_solver** out, const zf_problem_desc* desc, c
         ZF_REQUIRE(desc->d && desc->c, "zf_solver_create: d and c are required");
         ZF_REQUIRE(zf_aligned16(desc->d) && zf_aligned16(desc->c),
                    "zf_solver_create: d and c must be 16-byte aligned");
-    } else if (desc->kind == ZF_PROBLEM_LEAST_SQUARES_L1) {
+    } else if (zf_is_dense_mat(desc->kind)) {
         ZF_REQUIRE(desc->A && desc->b && desc->m_rows >= 1, "zf_solver_create: A, b, m_rows required");
         ZF_REQUIRE(zf_aligned16(desc->A), "zf_solver_create: A must be 16-byte aligned");
+        ZF_REQUIRE(desc->kind == ZF_PROBLEM_LEAST_SQUARES_L1 || desc->world == 1, "zf_solver_create: logistic regression is not sharded");
     } else if (desc->kind == ZF_PROBLEM_BLUR_HAAR_L1) {
         ZF_REQUIRE(desc->b && desc->op_taps, "zf_solver_create: b (the observed image) and op_taps are required");
         ZF_REQUIRE(desc->op_h >= 2 && desc->op_w >= 2 && desc->op_h % 2 == 0 && desc->op_w % 2 == 0 &&
@@ -491,11 +500,11 @@ static int zf_solver_create_impl(zf_solver** out, const zf_problem_desc* desc, c
                        desc->op_k / 2 < desc->op_w,
                    "zf_solver_create: op_k must be odd, at most 15 and smaller than twice the image");
         ZF_REQUIRE(desc->world == 1, "zf_solver_create: the operator problem is not sharded");
-    } else if (desc->kind == ZF_PROBLEM_SPARSE_LS_L1) {
-        ZF_REQUIRE(sp, "zf_solver_create: ZF_PROBLEM_SPARSE_LS_L1 takes its matrix through zf_solver_create_sparse");
+    } else if (zf_is_sparse_mat(desc->kind)) {
+        ZF_REQUIRE(sp, "zf_solver_create: ZF_PROBLEM_SPARSE_LS_L1 and ZF_PROBLEM_SPARSE_LOGISTIC_L1 take their matrix through zf_solver_create_sparse");
         ZF_REQUIRE(desc->b && !desc->A, "zf_solver_create_sparse: b is required and A must be NULL (the matrix is the handle's)");
         ZF_REQUIRE(desc->m_rows == sp->m && desc->n == sp->n, "zf_solver_create_sparse: m_rows and n differ from the matrix handle's");
-        ZF_REQUIRE(desc->world == 1, "zf_solver_create_sparse: sparse least squares is not sharded");
+        ZF_REQUIRE(desc->world == 1, "zf_solver_create_sparse: sparse problems are not sharded");
     } else {
         return zf_fail(ZF_ERR_ARG, "zf_solver_create: unknown problem kind");
     }
@@ -631,7 +640,7 @@ static int zf_solver_create_impl(zf_solver** out, const zf_problem_desc* desc, c
         ZF_TRY(hipMalloc(&s->ls_cnt, 64));
         ZF_TRY(hipMemsetAsync(s->ls_cnt, 0, 64, s->stream));
     }
-    if (desc->kind == ZF_PROBLEM_SPARSE_LS_L1) {   // what the dense kind takes, minus the slab, plus the segment sums of split rows
+    if (zf_is_sparse_mat(desc->kind)) {   // what the dense kind takes, minus the slab, plus the segment sums of split rows
         // (per solver: solves that share a matrix handle may run at the same time on other streams)
         if (sp->A.nseg > 0) ZF_TRY(hipMalloc(&s->sp_part_A, sizeof(double) * sp->A.nseg));
         if (sp->At.nseg > 0) ZF_TRY(hipMalloc(&s->sp_part_At, sizeof(double) * sp->At.nseg));
@@ -641,9 +650,9 @@ static int zf_solver_create_impl(zf_solver** out, const zf_problem_desc* desc, c
         for (int k = 0; k < 3; ++k) s->sring.p[k] = s->sbuf + k * m_pad;
         ZF_TRY(hipMalloc(&s->resid, sizeof(double) * m_pad));
         ZF_TRY(hipMalloc(&s->ls_scal, sizeof(double) * 8));
-        ZF_TRY(hipMalloc(&s->row_part, sizeof(double) * 2 * ZF_SPMV_RESID_MAX_CHUNKS));   // chunk sums of |r(y)|^2 and of |s+ - b|^2
+        ZF_TRY(hipMalloc(&s->row_part, sizeof(double) * 2 * ZF_SPMV_RESID_MAX_CHUNKS));   // chunk sums of |r(y)|^2 and of |s+ - b|^2 (logistic: of the two losses)
     }
-    if (desc->kind == ZF_PROBLEM_LEAST_SQUARES_L1) {
+    if (zf_is_dense_mat(desc->kind)) {
         const int64_t m = desc->m_rows;
         const int64_t m_pad = (m + 63) & ~int64_t(63);
         // enough row slices that panels x slices fills the chip (>= ~2048 workgroups)
@@ -668,13 +677,16 @@ static int zf_solver_create_impl(zf_solver** out, const zf_problem_desc* desc, c
             ZF_TRY(hipMalloc(&s->s_all, sizeof(double) * len * desc->world));
         }
         // launch-bound sizes (BASELINE cfg1): two fused launches per trial; ZF_LS_SMALL=0 keeps the general path
-        s->ls_small = desc->world == 1 && n % LS_SMALL_COLS == 0 && m <= LS_SMALL_MAX_M &&
+        // (the squared loss is written into those two kernels: the logistic kind always takes the general path)
+        s->ls_small = desc->kind == ZF_PROBLEM_LEAST_SQUARES_L1 && desc->world == 1 && n % LS_SMALL_COLS == 0 && m <= LS_SMALL_MAX_M &&
                       m * n <= LS_SMALL_MAX_ELEMS && zf_aligned16(desc->A) && s->env.ls_small;
         if (s->ls_small) {
             ZF_TRY(hipMalloc(&s->row_part, sizeof(double) * ((m + ZF_WAVES - 1) / ZF_WAVES)));
             ZF_TRY(hipMalloc(&s->ls_cnt, 64));
             ZF_TRY(hipMemsetAsync(s->ls_cnt, 0, 64, s->stream));
         }
+        if (desc->kind == ZF_PROBLEM_LOGISTIC_L1)   // chunk sums of the loss at y and at x+ (read beyond ZF_SPMV_WIDE_RESID_MIN_ROWS rows)
+            ZF_TRY(hipMalloc(&s->row_part, sizeof(double) * 2 * ZF_SPMV_RESID_MAX_CHUNKS));
     }
 #undef ZF_TRY
     *out = s;
@@ -687,7 +699,7 @@ extern "C" int zf_solver_create(zf_solver** out, const zf_problem_desc* desc, co
 
 extern "C" int zf_solver_create_sparse(zf_solver** out, const zf_problem_desc* desc, const zf_spmat* h, const zf_options* opt, void* stream) {
     ZF_REQUIRE(out && desc && h && opt, "zf_solver_create_sparse: null argument");
-    ZF_REQUIRE(desc->kind == ZF_PROBLEM_SPARSE_LS_L1, "zf_solver_create_sparse: desc->kind must be ZF_PROBLEM_SPARSE_LS_L1");
+    ZF_REQUIRE(zf_is_sparse_mat(desc->kind), "zf_solver_create_sparse: desc->kind must be ZF_PROBLEM_SPARSE_LS_L1 or ZF_PROBLEM_SPARSE_LOGISTIC_L1");
     return zf_solver_create_impl(out, desc, opt, stream, h);
 }
 
@@ -1280,12 +1292,18 @@ static int zf_launch_trial(zf_solver* s, bool decide_in_launch, bool dry = false
         const int64_t n = d.n, m = d.m_rows;
         const int V = (n % 2 == 0) ? 2 : 1;
         // (the sparse kind times the whole trial - the event pair brackets every launch of it, not the prox step alone)
-        const bool time_whole = d.kind == ZF_PROBLEM_SPARSE_LS_L1;
+        const bool time_whole = zf_is_sparse_mat(d.kind);
+        // the logistic kinds: rho(y), f(y) and f(x+) from zf_kernels_loss.h, and grad = scale A^T rho
+        const bool logistic = zf_is_logistic(d.kind);
+        const double gfac = logistic ? d.scale : 2 * d.scale;
         if (time_whole && e0) ZF_HIP(hipEventRecord(e0, s->stream));
         // (1) r = A y - b by linearity, f(y); grad = 2 scale A^T r   [only when y changed]
         // (sparse matrices have 1e5 .. 1e7 rows: beyond what one workgroup should walk, the residuals take many - zf_kernels_spmv.h)
         const bool wide_resid = d.kind == ZF_PROBLEM_SPARSE_LS_L1 && m > ZF_SPMV_WIDE_RESID_MIN_ROWS;
-        if (wide_resid)
+        if (logistic)
+            zf_launch_logit_y(s->stream, s->ctl, s->sring.p[0], s->sring.p[1], s->sring.p[2], d.b, s->resid, d.scale, m, (int)s->opt.nesterov,
+                              s->row_part, s->ls_scal + 0);
+        else if (wide_resid)
             zf_launch_spmv_resid_y(s->stream, s->ctl, s->sring.p[0], s->sring.p[1], s->sring.p[2], d.b, s->resid, d.scale, m,
                                    (int)s->opt.nesterov, s->row_part, s->ls_scal + 0);
         else if (d.kind != ZF_PROBLEM_BLUR_HAAR_L1)   // (the operator problem forms r inside its adjoint kernel)
@@ -1357,17 +1375,20 @@ static int zf_launch_trial(zf_solver* s, bool decide_in_launch, bool dry = false
             ZF_HIP(hipGetLastError());
             return ZF_OK;
         }
-        if (d.kind == ZF_PROBLEM_SPARSE_LS_L1) {
+        if (zf_is_sparse_mat(d.kind)) {
             // the trial of a dense matrix with its two sweeps swapped for the CSR row sums: grad = 2 scale A^T r over the
             // stored A^T (only when y changed), the prox step, s+ = A x+, f(x+), finalize
             const zf_spmv_io gio = {{s->resid, s->resid, s->resid}, {s->grad, s->grad, s->grad}};
-            zf_launch_spmv(s->spmat->At, s->stream, s->ctl, true, gio, -1, 2 * d.scale, s->sp_part_At);
+            zf_launch_spmv(s->spmat->At, s->stream, s->ctl, true, gio, -1, gfac, s->sp_part_At);
             a.p0 = s->grad;
             a.p1 = nullptr;
             zf_launch_trial_kernels(s, a, false);
             zf_ring3 xr3 = {{s->xb[0], s->xb[1], s->xb[2]}};
             zf_launch_apply_A(s, s->ctl, xr3, s->sring, 1);
-            if (wide_resid)
+            if (logistic)
+                zf_launch_logit_x(s->stream, s->ctl, s->sring.p[0], s->sring.p[1], s->sring.p[2], 1, d.b, d.scale, m,
+                                  s->row_part + ZF_SPMV_RESID_MAX_CHUNKS, s->ls_scal + 1);
+            else if (wide_resid)
                 zf_launch_spmv_resid_x(s->stream, s->ctl, s->sring.p[0], s->sring.p[1], s->sring.p[2], 1, d.b, d.scale, m,
                                        s->row_part + ZF_SPMV_RESID_MAX_CHUNKS, s->ls_scal + 1);
             else
@@ -1394,7 +1415,7 @@ static int zf_launch_trial(zf_solver* s, bool decide_in_launch, bool dry = false
         // (row blocks: this rank's part 2 scale A_p^T r_p goes to s_part; the caller gathers the parts
         //  and zf_solver_enqueue_trial_finish() adds them and runs the rest of the trial)
         hipLaunchKernelGGL(zf_gemvT_combine_kernel, dim3(zf_grid_for(n)), dim3(ZF_BLOCK), 0, s->stream,
-                           rows ? nullptr : s->ctl, s->slab, rows ? s->s_part : s->grad, 2 * d.scale, n, s->slices);
+                           rows ? nullptr : s->ctl, s->slab, rows ? s->s_part : s->grad, gfac, n, s->slices);
         if (rows) {
             // (the prox step of a row-sharded trial runs in zf_solver_enqueue_trial_finish, after the exchange: the
             //  event pair and the log slot taken above belong to a launch that does not happen here - give them back,
@@ -1426,8 +1447,12 @@ static int zf_launch_trial(zf_solver* s, bool decide_in_launch, bool dry = false
             hipLaunchKernelGGL(zf_gemv_rows_kernel<1>, dim3(gr), dim3(ZF_BLOCK), 0, s->stream, s->ctl, d.A,
                                xr, sout, 1, m, n);
         if (d.world == 1) {
-            hipLaunchKernelGGL(zf_resid_x_kernel, dim3(1), dim3(RESID_BLOCK), 0, s->stream, s->ctl, s->sring, 1,
-                               d.b, d.scale, m, s->ls_scal + 1);
+            if (logistic)
+                zf_launch_logit_x(s->stream, s->ctl, s->sring.p[0], s->sring.p[1], s->sring.p[2], 1, d.b, d.scale, m,
+                                  s->row_part + ZF_SPMV_RESID_MAX_CHUNKS, s->ls_scal + 1);
+            else
+                hipLaunchKernelGGL(zf_resid_x_kernel, dim3(1), dim3(RESID_BLOCK), 0, s->stream, s->ctl, s->sring, 1,
+                                   d.b, d.scale, m, s->ls_scal + 1);
             zf_launch_finalize(s, decide_in_launch);
         }
     }
@@ -1486,7 +1511,9 @@ static int zf_init_ls_tail(zf_solver* s) {
     const int64_t n = d.n, m = d.m_rows;
     zf_ring3 s0 = {{s->sring.p[0], s->sring.p[0], s->sring.p[0]}};
     ZF_HIP(hipMemcpyAsync(s->sring.p[2], s->sring.p[0], sizeof(double) * m, hipMemcpyDeviceToDevice, s->stream));
-    if (m > (int64_t)1 << 18) {   // long residuals (the operator problem at image sizes beyond 512 x 512): two launches, many workgroups
+    if (zf_is_logistic(d.kind)) {   // the same loss, in the order the loop sums f(x+) (zf_kernels_loss.h)
+        zf_launch_logit_x(s->stream, nullptr, s0.p[0], s0.p[0], s0.p[0], -1, d.b, d.scale, m, s->row_part, s->ls_scal + 1);
+    } else if (m > (int64_t)1 << 18) {   // long residuals (the operator problem at image sizes beyond 512 x 512): two launches, many workgroups
         const int wgs = zf_grid_for(m / 8);
         hipLaunchKernelGGL(zf_resid_x_wide_kernel, dim3(wgs), dim3(ZF_BLOCK), 0, s->stream, s0.p[0], d.b, m, s->partials);
         hipLaunchKernelGGL(zf_resid_x_finish_kernel, dim3(1), dim3(RESID_BLOCK), 0, s->stream, s->partials, wgs, d.scale, s->ls_scal + 1);
@@ -1653,7 +1680,7 @@ extern "C" int zf_solver_restore(zf_solver* s, const double* xk_dev, const doubl
         ZF_HIP(hipMemsetAsync(s->pack_all, 0, sizeof(double) * ZF_PACK_LEN * s->sub * d.world, s->stream));
     ZF_HIP(hipMemcpyAsync(s->ctl, &c, sizeof(c), hipMemcpyHostToDevice, s->stream));
     ZF_HIP(hipStreamSynchronize(s->stream));   // `c` is a stack object
-    if (zf_is_ls(d.kind)) {
+    if (zf_has_margins(d.kind)) {
         const int at[2] = {0, 2};   // A x_k -> sring[cur], A x_{k-1} -> sring[(cur + 2) % 3]
         for (int k = 0; k < 2; ++k) {
             double* xsrc = s->xb[at[k]];
@@ -1792,14 +1819,14 @@ extern "C" int zf_solver_ls_plan(zf_solver* s, int64_t* out, int64_t count) {
         out[3] = (pl.fuse_prox && !s->hist) ? 1 : 0;
         return ZF_OK;
     }
-    if (s->desc.kind == ZF_PROBLEM_SPARSE_LS_L1) {
+    if (zf_is_sparse_mat(s->desc.kind)) {
         out[0] = 5;
         out[1] = s->spmat->A.lanes;
         out[2] = s->spmat->At.lanes;
         out[3] = s->spmat->A.nsplit + s->spmat->At.nsplit;
         return ZF_OK;
     }
-    if (s->desc.kind != ZF_PROBLEM_LEAST_SQUARES_L1) return ZF_OK;
+    if (!zf_is_dense_mat(s->desc.kind)) return ZF_OK;
     const bool odd = s->desc.n % 2 != 0;
     out[0] = s->ls_small ? 1 : s->gemv_mfma ? 2 : odd ? 4 : 3;
     out[1] = s->ls_small ? 1 : odd ? 3 : 2;
@@ -2290,10 +2317,10 @@ extern "C" int zf_decide_host(zf_control* ctl, int64_t ctl_bytes, const double* 
 // ---------------------------------------------------------------------------
 // least-squares operator at a host point (callback contract, not the hot loop)
 // ---------------------------------------------------------------------------
-extern "C" int zf_ls_eval(const double* A_dev, const double* b_dev, int64_t m_rows, int64_t n, double scale,
-                          const double* x_host, double* f_out, double* grad_out_host) {
-    ZF_REQUIRE(A_dev && b_dev && x_host && f_out && m_rows >= 1 && n >= 1, "zf_ls_eval: bad argument");
-    ZF_REQUIRE(zf_aligned16(A_dev), "zf_ls_eval: A must be 16-byte aligned");
+// logistic: the loss of zf_kernels_loss.h on the same sweeps (zf_logistic_eval) - rho = -b sigma(-b s) takes the place of
+// r = s - b, scale that of 2 scale
+static int zf_dense_eval(const double* A_dev, const double* b_dev, int64_t m_rows, int64_t n, double scale,
+                         const double* x_host, double* f_out, double* grad_out_host, bool logistic) {
     const int V = (n % 2 == 0) ? 2 : 1;
     const int64_t nv = n / V;
     const int64_t panels = (nv + ZF_BLOCK - 1) / ZF_BLOCK;
@@ -2303,7 +2330,7 @@ extern "C" int zf_ls_eval(const double* A_dev, const double* b_dev, int64_t m_ro
     if (slices > 64) slices = 64;
     const int64_t rps = (m_rows + slices - 1) / slices;
     slices = (m_rows + rps - 1) / rps;
-    double *x = nullptr, *s = nullptr, *slab = nullptr, *grad = nullptr, *fdev = nullptr;
+    double *x = nullptr, *s = nullptr, *slab = nullptr, *grad = nullptr, *fdev = nullptr, *rho = nullptr, *part = nullptr;
     int rc = ZF_OK;
 #define ZF_LS(expr)                                                               \
     do {                                                                          \
@@ -2314,6 +2341,10 @@ extern "C" int zf_ls_eval(const double* A_dev, const double* b_dev, int64_t m_ro
     ZF_LS(hipMalloc(&x, sizeof(double) * (n + 2)));
     ZF_LS(hipMalloc(&s, sizeof(double) * (m_rows + 2)));
     ZF_LS(hipMalloc(&fdev, sizeof(double) * 2));
+    if (logistic) {
+        ZF_LS(hipMalloc(&part, sizeof(double) * ZF_SPMV_RESID_MAX_CHUNKS));
+        if (grad_out_host) ZF_LS(hipMalloc(&rho, sizeof(double) * m_rows));
+    }
     if (grad_out_host) {
         ZF_LS(hipMalloc(&slab, sizeof(double) * slices * n));
         ZF_LS(hipMalloc(&grad, sizeof(double) * n));
@@ -2329,21 +2360,28 @@ extern "C" int zf_ls_eval(const double* A_dev, const double* b_dev, int64_t m_ro
         else
             hipLaunchKernelGGL(zf_gemv_rows_kernel<1>, dim3(gr), dim3(ZF_BLOCK), 0, nullptr, nullptr, A_dev, xr, sr,
                                -1, m_rows, n);
-        hipLaunchKernelGGL(zf_resid_x_kernel, dim3(1), dim3(RESID_BLOCK), 0, nullptr, nullptr, sr, -1, b_dev, scale,
-                           m_rows, fdev);
+        if (!logistic)
+            hipLaunchKernelGGL(zf_resid_x_kernel, dim3(1), dim3(RESID_BLOCK), 0, nullptr, nullptr, sr, -1, b_dev, scale,
+                               m_rows, fdev);
+        else if (grad_out_host)
+            zf_launch_logit_y(nullptr, nullptr, s, s, s, b_dev, rho, scale, m_rows, 0, part, fdev);
+        else
+            zf_launch_logit_x(nullptr, nullptr, s, s, s, -1, b_dev, scale, m_rows, part, fdev);
         if (grad_out_host) {
             // r = s - b in place, then column sums
-            hipLaunchKernelGGL(zf_axmb_kernel, dim3(zf_grid_for(m_rows)), dim3(ZF_BLOCK), 0, nullptr, s, b_dev,
-                               m_rows);
+            if (!logistic)
+                hipLaunchKernelGGL(zf_axmb_kernel, dim3(zf_grid_for(m_rows)), dim3(ZF_BLOCK), 0, nullptr, s, b_dev,
+                                   m_rows);
+            const double* rv = logistic ? rho : s;
             dim3 gT((unsigned)panels, (unsigned)slices);
             if (V == 2)
-                hipLaunchKernelGGL(zf_gemvT_partial_kernel<2>, gT, dim3(ZF_BLOCK), 0, nullptr, nullptr, A_dev, s,
+                hipLaunchKernelGGL(zf_gemvT_partial_kernel<2>, gT, dim3(ZF_BLOCK), 0, nullptr, nullptr, A_dev, rv,
                                    slab, m_rows, n, rps);
             else
-                hipLaunchKernelGGL(zf_gemvT_partial_kernel<1>, gT, dim3(ZF_BLOCK), 0, nullptr, nullptr, A_dev, s,
+                hipLaunchKernelGGL(zf_gemvT_partial_kernel<1>, gT, dim3(ZF_BLOCK), 0, nullptr, nullptr, A_dev, rv,
                                    slab, m_rows, n, rps);
             hipLaunchKernelGGL(zf_gemvT_combine_kernel, dim3(zf_grid_for(n)), dim3(ZF_BLOCK), 0, nullptr, nullptr,
-                               slab, grad, 2 * scale, n, (int)slices);
+                               slab, grad, logistic ? scale : 2 * scale, n, (int)slices);
             ZF_LS(hipMemcpyAsync(grad_out_host, grad, sizeof(double) * n, hipMemcpyDeviceToHost, nullptr));
         }
         ZF_LS(hipGetLastError());
@@ -2351,17 +2389,32 @@ extern "C" int zf_ls_eval(const double* A_dev, const double* b_dev, int64_t m_ro
         ZF_LS(hipStreamSynchronize(nullptr));
     }
 #undef ZF_LS
-    for (void* p : {(void*)x, (void*)s, (void*)slab, (void*)grad, (void*)fdev})
+    for (void* p : {(void*)x, (void*)s, (void*)slab, (void*)grad, (void*)fdev, (void*)rho, (void*)part})
         if (p) (void)hipFree(p);
     return rc;
 }
 
+extern "C" int zf_ls_eval(const double* A_dev, const double* b_dev, int64_t m_rows, int64_t n, double scale,
+                          const double* x_host, double* f_out, double* grad_out_host) {
+    ZF_REQUIRE(A_dev && b_dev && x_host && f_out && m_rows >= 1 && n >= 1, "zf_ls_eval: bad argument");
+    ZF_REQUIRE(zf_aligned16(A_dev), "zf_ls_eval: A must be 16-byte aligned");
+    return zf_dense_eval(A_dev, b_dev, m_rows, n, scale, x_host, f_out, grad_out_host, false);
+}
+
+// f = scale sum softplus(-b (A x)) and (grad_out_host != NULL) grad = scale A^T rho of ZF_PROBLEM_LOGISTIC_L1 for a host
+// vector: the callback bodies of zfista_amd.problems.LogisticL1, on the loss kernels the solver runs
+extern "C" int zf_logistic_eval(const double* A_dev, const double* b_dev, int64_t m_rows, int64_t n, double scale,
+                                const double* x_host, double* f_out, double* grad_out_host) {
+    ZF_REQUIRE(A_dev && b_dev && x_host && f_out && m_rows >= 1 && n >= 1, "zf_logistic_eval: bad argument");
+    ZF_REQUIRE(zf_aligned16(A_dev), "zf_logistic_eval: A must be 16-byte aligned");
+    return zf_dense_eval(A_dev, b_dev, m_rows, n, scale, x_host, f_out, grad_out_host, true);
+}
+
 // the same for a CSR matrix behind a handle (zf_spmat_create), on the two sweeps the solver runs
-extern "C" int zf_spmat_eval(const zf_spmat* h, const double* b_dev, double scale, const double* x_host, double* f_out,
-                             double* grad_out_host) {
-    ZF_REQUIRE(h && b_dev && x_host && f_out, "zf_spmat_eval: null argument");
+static int zf_sparse_eval(const zf_spmat* h, const double* b_dev, double scale, const double* x_host, double* f_out,
+                          double* grad_out_host, bool logistic) {
     const int64_t m = h->m, n = h->n;
-    double *x = nullptr, *sv = nullptr, *grad = nullptr, *fdev = nullptr, *part_A = nullptr, *part_At = nullptr;
+    double *x = nullptr, *sv = nullptr, *grad = nullptr, *fdev = nullptr, *part_A = nullptr, *part_At = nullptr, *rho = nullptr, *part = nullptr;
     int rc = ZF_OK;
 #define ZF_SP(expr)                                                               \
     do {                                                                          \
@@ -2373,6 +2426,10 @@ extern "C" int zf_spmat_eval(const zf_spmat* h, const double* b_dev, double scal
     ZF_SP(hipMalloc(&sv, sizeof(double) * m));
     ZF_SP(hipMalloc(&fdev, sizeof(double) * 2));
     if (grad_out_host) ZF_SP(hipMalloc(&grad, sizeof(double) * n));
+    if (logistic) {
+        ZF_SP(hipMalloc(&part, sizeof(double) * ZF_SPMV_RESID_MAX_CHUNKS));
+        if (grad_out_host) ZF_SP(hipMalloc(&rho, sizeof(double) * m));
+    }
     // (the segment sums of split rows are this call's own: the handle is shared with solvers running on other streams)
     if (h->A.nseg > 0) ZF_SP(hipMalloc(&part_A, sizeof(double) * h->A.nseg));
     if (grad_out_host && h->At.nseg > 0) ZF_SP(hipMalloc(&part_At, sizeof(double) * h->At.nseg));
@@ -2381,11 +2438,17 @@ extern "C" int zf_spmat_eval(const zf_spmat* h, const double* b_dev, double scal
         zf_ring3 sr = {{sv, sv, sv}};
         const zf_spmv_io aio = {{x, x, x}, {sv, sv, sv}};
         zf_launch_spmv(h->A, nullptr, nullptr, false, aio, -1, 1.0, part_A);
-        hipLaunchKernelGGL(zf_resid_x_kernel, dim3(1), dim3(RESID_BLOCK), 0, nullptr, nullptr, sr, -1, b_dev, scale, m, fdev);
+        if (!logistic)
+            hipLaunchKernelGGL(zf_resid_x_kernel, dim3(1), dim3(RESID_BLOCK), 0, nullptr, nullptr, sr, -1, b_dev, scale, m, fdev);
+        else if (grad_out_host)
+            zf_launch_logit_y(nullptr, nullptr, sv, sv, sv, b_dev, rho, scale, m, 0, part, fdev);
+        else
+            zf_launch_logit_x(nullptr, nullptr, sv, sv, sv, -1, b_dev, scale, m, part, fdev);
         if (grad_out_host) {
-            hipLaunchKernelGGL(zf_axmb_kernel, dim3(zf_grid_for(m)), dim3(ZF_BLOCK), 0, nullptr, sv, b_dev, m);
-            const zf_spmv_io gio = {{sv, sv, sv}, {grad, grad, grad}};
-            zf_launch_spmv(h->At, nullptr, nullptr, false, gio, -1, 2 * scale, part_At);
+            if (!logistic) hipLaunchKernelGGL(zf_axmb_kernel, dim3(zf_grid_for(m)), dim3(ZF_BLOCK), 0, nullptr, sv, b_dev, m);
+            const double* rv = logistic ? rho : sv;
+            const zf_spmv_io gio = {{rv, rv, rv}, {grad, grad, grad}};
+            zf_launch_spmv(h->At, nullptr, nullptr, false, gio, -1, logistic ? scale : 2 * scale, part_At);
             ZF_SP(hipMemcpyAsync(grad_out_host, grad, sizeof(double) * n, hipMemcpyDeviceToHost, nullptr));
         }
         ZF_SP(hipGetLastError());
@@ -2393,9 +2456,22 @@ extern "C" int zf_spmat_eval(const zf_spmat* h, const double* b_dev, double scal
         ZF_SP(hipStreamSynchronize(nullptr));
     }
 #undef ZF_SP
-    for (void* p : {(void*)x, (void*)sv, (void*)grad, (void*)fdev, (void*)part_A, (void*)part_At})
+    for (void* p : {(void*)x, (void*)sv, (void*)grad, (void*)fdev, (void*)part_A, (void*)part_At, (void*)rho, (void*)part})
         if (p) (void)hipFree(p);
     return rc;
+}
+
+extern "C" int zf_spmat_eval(const zf_spmat* h, const double* b_dev, double scale, const double* x_host, double* f_out,
+                             double* grad_out_host) {
+    ZF_REQUIRE(h && b_dev && x_host && f_out, "zf_spmat_eval: null argument");
+    return zf_sparse_eval(h, b_dev, scale, x_host, f_out, grad_out_host, false);
+}
+
+// the logistic loss (ZF_PROBLEM_SPARSE_LOGISTIC_L1) over the same handle: zf_logistic_eval for a CSR matrix
+extern "C" int zf_spmat_logistic_eval(const zf_spmat* h, const double* b_dev, double scale, const double* x_host, double* f_out,
+                                      double* grad_out_host) {
+    ZF_REQUIRE(h && b_dev && x_host && f_out, "zf_spmat_logistic_eval: null argument");
+    return zf_sparse_eval(h, b_dev, scale, x_host, f_out, grad_out_host, true);
 }
 
 // f(x) = scale |B W^-1 x - b|^2 and (optionally) jac_f(x) = 2 scale W B (B W^-1 x - b) of the operator problem

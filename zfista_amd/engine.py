@@ -286,7 +286,8 @@ class DeviceSolver:
         The operator problem (BlurHaarL1): (tile height - 8 or 32 rows, 1 separable correlation / 0 general,
         1 workgroups walk their tiles / 0 one workgroup per tile, 1 prox step fused into the adjoint kernel / 0 a
         launch of its own).  Sparse least squares (SparseLeastSquaresL1): (5, lanes per row of the sweep over A, lanes per
-        row of the sweep over A^T, split rows of both).  Other problems: zeros."""
+        row of the sweep over A^T, split rows of both).  LogisticL1 / SparseLogisticL1: the slots of their storage form (the dense
+        kind never reports 1: the small-matrix kernels hold the squared loss).  Other problems: zeros."""
         out = np.zeros(4, dtype=np.int64)
         _lib.check(self.lib.zf_solver_ls_plan(self.handle, C.c_void_p(_lib.ptr(out)), out.size))
         return tuple(int(v) for v in out)

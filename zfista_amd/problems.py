@@ -135,26 +135,15 @@ class DiagQuadL1(NativeProblem):
         return fields, (self.d, self.c)
 
 
-class LeastSquaresL1(NativeProblem):
-    r"""f(x) = scale \|Ax - b\|^2,  g(x) = lam \|x\|_1 (+ optional box); A dense row-major.
+class _DenseMarginsL1(NativeProblem):
+    """What the dense single-GPU problems f(x) = scale * sum_i loss_i((Ax)_i), g = lam |x|_1 (+ box) share: A (m x n, dense
+    row-major) and the m-vector b in HBM, f / jac_f at a host vector through the entry point the subclass names, the
+    descriptor of one GPU.  The loss is the subclass's: its ``kind``, its ``_eval_name``, what b means."""
 
-    The LASSO closures of tests/test_proximal_gradient.py:49-61,81-97 are the
-    ``scale = 1/6`` member; BASELINE cfg1 / cfg3 use ``scale = 1/2``.
-    """
+    kind = None
+    _eval_name = None   # f and jac_f at a host vector
 
-    kind = _lib.ZF_PROBLEM_LEAST_SQUARES_L1
-
-    def __init__(self, A, b, lam, scale=0.5, bounds=None, group=None, shard="columns"):
-        """With ``group`` set and ``shard="columns"`` (default), ``A`` is this rank's column block A_p
-        (m x n_p, row-major) of a matrix whose columns - and the decision vector - are partitioned
-        over the ranks of that process group; ``b`` is replicated; the solve exchanges the m-vector
-        A_p x_p once per trial.  ``shard="rows"``: ``A`` (m_p x n) and ``b`` (m_p) are this rank's ROW
-        block, x is replicated on every rank (pass the whole x0) and the n-vector A_p^T r_p is
-        exchanged instead - the layout for tall matrices.  ``f`` / ``jac_f`` as plain callables
-        refer to the local block only."""
-        if shard not in ("columns", "rows"):
-            raise ValueError("shard must be 'columns' or 'rows'")
-        self.shard = shard
+    def _set(self, A, b, lam, scale, bounds):
         self.A = _to_device(A, "A")
         self.b = _to_device(b, "b")
         if self.A.ndim != 2 or self.b.ndim != 1 or self.A.shape[0] != self.b.shape[0]:
@@ -162,7 +151,7 @@ class LeastSquaresL1(NativeProblem):
         self.lam, self.scale = float(lam), float(scale)
         self.box = (-np.inf, np.inf) if bounds is None else (float(bounds[0]), float(bounds[1]))
         self.m_rows, self.n_features = int(self.A.shape[0]), int(self.A.shape[1])
-        self.group = group
+        self.group = None
 
     def _ls(self, x, want_grad):
         x = _as_host(x)
@@ -171,10 +160,10 @@ class LeastSquaresL1(NativeProblem):
         lib = _lib.require_gpu()
         fval = C.c_double(0.0)
         grad = np.empty_like(x) if want_grad else None
-        _lib.check(lib.zf_ls_eval(C.c_void_p(self.A.data_ptr()), C.c_void_p(self.b.data_ptr()),
-                                  self.m_rows, self.n_features, self.scale, C.c_void_p(_lib.ptr(x)),
-                                  C.byref(fval), C.c_void_p(_lib.ptr(grad)) if want_grad else None),
-                   "zf_ls_eval")
+        _lib.check(getattr(lib, self._eval_name)(C.c_void_p(self.A.data_ptr()), C.c_void_p(self.b.data_ptr()),
+                                                 self.m_rows, self.n_features, self.scale, C.c_void_p(_lib.ptr(x)),
+                                                 C.byref(fval), C.c_void_p(_lib.ptr(grad)) if want_grad else None),
+                   self._eval_name)
         return np.float64(fval.value), grad
 
     def f(self, x):
@@ -189,15 +178,42 @@ class LeastSquaresL1(NativeProblem):
         _lib.check(lib.zf_host_asum(C.c_void_p(_lib.ptr(x)), x.size, C.byref(s)), "zf_host_asum")
         return None, np.float64(self.lam * s.value)
 
+    def _descriptor(self, rank=0, world=1, row_sharded=0):
+        fields = dict(kind=self.kind, world=world, rank=rank, n=self.n_features, m_rows=self.m_rows, row_sharded=row_sharded,
+                      d=None, c=None, A=self.A.data_ptr(), b=self.b.data_ptr(),
+                      scale=self.scale, lam=self.lam, box_lo=self.box[0], box_hi=self.box[1])
+        return fields, (self.A, self.b)
+
+
+class LeastSquaresL1(_DenseMarginsL1):
+    r"""f(x) = scale \|Ax - b\|^2,  g(x) = lam \|x\|_1 (+ optional box); A dense row-major.
+
+    The LASSO closures of tests/test_proximal_gradient.py:49-61,81-97 are the
+    ``scale = 1/6`` member; BASELINE cfg1 / cfg3 use ``scale = 1/2``.
+    """
+
+    kind = _lib.ZF_PROBLEM_LEAST_SQUARES_L1
+    _eval_name = "zf_ls_eval"
+
+    def __init__(self, A, b, lam, scale=0.5, bounds=None, group=None, shard="columns"):
+        """With ``group`` set and ``shard="columns"`` (default), ``A`` is this rank's column block A_p
+        (m x n_p, row-major) of a matrix whose columns - and the decision vector - are partitioned
+        over the ranks of that process group; ``b`` is replicated; the solve exchanges the m-vector
+        A_p x_p once per trial.  ``shard="rows"``: ``A`` (m_p x n) and ``b`` (m_p) are this rank's ROW
+        block, x is replicated on every rank (pass the whole x0) and the n-vector A_p^T r_p is
+        exchanged instead - the layout for tall matrices.  ``f`` / ``jac_f`` as plain callables
+        refer to the local block only."""
+        if shard not in ("columns", "rows"):
+            raise ValueError("shard must be 'columns' or 'rows'")
+        self.shard = shard
+        self._set(A, b, lam, scale, bounds)
+        self.group = group
+
     def _descriptor(self):
         from .comm import rank_world
 
         rank, world = rank_world(self.group)
-        fields = dict(kind=self.kind, world=world, rank=rank, n=self.n_features, m_rows=self.m_rows,
-                      row_sharded=int(self.shard == "rows" and world > 1),
-                      d=None, c=None, A=self.A.data_ptr(), b=self.b.data_ptr(),
-                      scale=self.scale, lam=self.lam, box_lo=self.box[0], box_hi=self.box[1])
-        return fields, (self.A, self.b)
+        return super()._descriptor(rank, world, int(self.shard == "rows" and world > 1))
 
 
 class _SpmatHandle:
@@ -234,19 +250,15 @@ class _SpmatHandle:
             pass
 
 
-class SparseLeastSquaresL1(NativeProblem):
-    r"""f(x) = scale \|Ax - b\|^2,  g(x) = lam \|x\|_1 (+ optional box) with a SPARSE A: the problem of
-    ``LeastSquaresL1`` - same keywords, same result fields - for matrices that have no dense form in HBM.
+class _SparseMarginsL1(NativeProblem):
+    """What the sparse single-GPU problems f(x) = scale * sum_i loss_i((Ax)_i), g = lam |x|_1 (+ box) share: the canonical
+    CSR of A and of A^T behind one immutable handle, b in HBM, f / jac_f at a host vector through the entry point the
+    subclass names, the descriptor.  The loss is the subclass's: its ``kind``, its ``_eval_name``, what b means."""
 
-    ``A``: a scipy.sparse matrix / array of any format and real dtype (m x n; m, n < 2**31).  It is made canonical CSR on
-    the host (duplicates summed, indices sorted; float64 values, int32 column indices, int64 row pointers), and so is
-    ``A.T``: both sweeps of a trial - A x+ and A^T r - are row sums of a stored matrix against a gathered vector
-    (csrc/zf_kernels_spmv.h), with no atomics and in an order fixed by the matrix alone.  Both copies go to HBM: 24 B per
-    stored element in total.  A matrix with no stored element is legal.  Single GPU."""
+    kind = None
+    _eval_name = None
 
-    kind = _lib.ZF_PROBLEM_SPARSE_LS_L1
-
-    def __init__(self, A, b, lam, scale=0.5, bounds=None):
+    def _set(self, A, b, lam, scale, bounds):
         import torch
 
         from . import sparse
@@ -268,8 +280,8 @@ class SparseLeastSquaresL1(NativeProblem):
         lib = _lib.require_gpu()
         fval = C.c_double(0.0)
         grad = np.empty_like(x) if want_grad else None
-        _lib.check(lib.zf_spmat_eval(self._spmat.value, C.c_void_p(self.b.data_ptr()), self.scale, C.c_void_p(_lib.ptr(x)),
-                                     C.byref(fval), C.c_void_p(_lib.ptr(grad)) if want_grad else None), "zf_spmat_eval")
+        _lib.check(getattr(lib, self._eval_name)(self._spmat.value, C.c_void_p(self.b.data_ptr()), self.scale, C.c_void_p(_lib.ptr(x)),
+                                                 C.byref(fval), C.c_void_p(_lib.ptr(grad)) if want_grad else None), self._eval_name)
         return np.float64(fval.value), grad
 
     def f(self, x):
@@ -289,6 +301,65 @@ class SparseLeastSquaresL1(NativeProblem):
                       d=None, c=None, A=None, b=self.b.data_ptr(), scale=self.scale, lam=self.lam,
                       box_lo=self.box[0], box_hi=self.box[1], spmat=self._spmat.value.value)
         return fields, (self._spmat, self.b)
+
+
+class SparseLeastSquaresL1(_SparseMarginsL1):
+    r"""f(x) = scale \|Ax - b\|^2,  g(x) = lam \|x\|_1 (+ optional box) with a SPARSE A: the problem of
+    ``LeastSquaresL1`` - same keywords, same result fields - for matrices that have no dense form in HBM.
+
+    ``A``: a scipy.sparse matrix / array of any format and real dtype (m x n; m, n < 2**31).  It is made canonical CSR on
+    the host (duplicates summed, indices sorted; float64 values, int32 column indices, int64 row pointers), and so is
+    ``A.T``: both sweeps of a trial - A x+ and A^T r - are row sums of a stored matrix against a gathered vector
+    (csrc/zf_kernels_spmv.h), with no atomics and in an order fixed by the matrix alone.  Both copies go to HBM: 24 B per
+    stored element in total.  A matrix with no stored element is legal.  Single GPU."""
+
+    kind = _lib.ZF_PROBLEM_SPARSE_LS_L1
+    _eval_name = "zf_spmat_eval"
+
+    def __init__(self, A, b, lam, scale=0.5, bounds=None):
+        self._set(A, b, lam, scale, bounds)
+
+
+def _check_labels(b, m=None):
+    """The labels of a logistic problem as a host vector: exactly -1 or +1, one per row.  ValueError otherwise - on the
+    host, before anything touches the device (a torch tensor is copied to the host for the check)."""
+    host = b.detach().cpu().numpy() if hasattr(b, "detach") else np.asarray(b)
+    if host.ndim != 1 or (m is not None and host.shape[0] != m):
+        raise ValueError(f"b must be a vector of {'m' if m is None else m} labels (the rows of A), got shape {host.shape}")
+    if np.dtype(host.dtype).kind not in "biuf" or not np.all((host == 1) | (host == -1)):
+        raise ValueError("the labels b must be exactly -1 or +1")
+    return host
+
+
+class LogisticL1(_DenseMarginsL1):
+    r"""f(x) = scale \sum_i softplus(-b_i (Ax)_i) with labels b_i in {-1, +1},  g(x) = lam \|x\|_1 (+ optional box); A dense
+    row-major: L1-regularised logistic regression on the device-resident trial of ``LeastSquaresL1`` - same keywords,
+    same result fields.  grad f = scale A^T rho, rho_i = -b_i sigma(-b_i (Ax)_i) (csrc/zf_kernels_loss.h: one
+    exp(-|t|) per row feeds both, finite for every finite margin).  Labels other than exactly -1 / +1 raise ValueError.
+    Single GPU."""
+
+    kind = _lib.ZF_PROBLEM_LOGISTIC_L1
+    _eval_name = "zf_logistic_eval"
+
+    def __init__(self, A, b, lam, scale=1.0, bounds=None):
+        shape = tuple(getattr(A, "shape", np.shape(A)))
+        if len(shape) != 2:
+            raise ValueError("A must be (m, n) and b (m,)")
+        _check_labels(b, shape[0])
+        self._set(A, b, lam, scale, bounds)
+
+
+class SparseLogisticL1(_SparseMarginsL1):
+    r"""``LogisticL1`` with a SPARSE A (any scipy.sparse matrix): the matrix is prepared, stored and swept exactly as for
+    ``SparseLeastSquaresL1`` (canonical CSR of A and of A^T behind one immutable handle); the loss kernels are the dense
+    class's.  Single GPU."""
+
+    kind = _lib.ZF_PROBLEM_SPARSE_LOGISTIC_L1
+    _eval_name = "zf_spmat_logistic_eval"
+
+    def __init__(self, A, b, lam, scale=1.0, bounds=None):
+        _check_labels(b)
+        self._set(A, b, lam, scale, bounds)
 
 
 class BlurHaarL1(NativeProblem):
