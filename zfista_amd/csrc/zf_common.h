@@ -168,17 +168,24 @@ __device__ __forceinline__ double zf_soft_threshold(double u, double tau) {
     a = (a < 0.0) ? 0.0 : a;
     return copysign(a, u);
 }
-// The same for tau >= 0 in four instructions: u - clamp(u, -tau, tau), sign of u copied onto the
-// result.  |u| > tau: u -/+ tau is the one rounding of sign(u) * (|u| - tau); |u| <= tau: u - u = 0,
-// signed like u, as sign(u) * 0 is; NaN and infinities propagate the same way (max/min drop a
-// NaN operand, u - t restores it).  The solver checks tau >= 0 (lam >= 0, lr > 0, decay_rate > 0)
-// at creation; hosts route other inputs through the general form above.
+// The same for tau >= 0 in three instructions: t = min(|u|, tau), m = |u| - t (the absolute value and
+// the negation are source modifiers), sign of u copied onto m.  |u| > tau: m is the one rounding of
+// |u| - tau; |u| <= tau: |u| - |u| = +0 under round-to-nearest - so m is never -0 before the sign goes
+// on: for every u the 64 bits of the general form above, signed zeros included.  NaN and infinities
+// propagate as they did: v_min_f64 drops a NaN operand (t = tau), the subtraction restores it, and
+// u = +-inf with tau = inf gives inf - inf = NaN, as u - clamp(u, -tau, tau) did - the four-instruction
+// form of rounds 2 to 5 (max, min, sub, bfi), which this one replaces bit for bit.  (|u| - tau,
+// max(., 0), bfi is three instructions too, but v_max_f64 turns a NaN u into +-0.)
+// Written as asm: the compiler canonicalises an fmin operand (one more v_max per call) and does not
+// fold |u| into both uses.  The solver checks tau >= 0 (lam >= 0, lr > 0, decay_rate > 0) at creation;
+// hosts route other inputs through the general form above.
 __device__ __forceinline__ double zf_soft_threshold_nn(double u, double tau) {
-    const double t = fmin(fmax(u, -tau), tau);
-    // copysign(u - t, u) as ONE v_bfi on the high word, in place.  (The library lowering - and the same
+    double t, m;
+    asm("v_min_f64 %0, |%1|, %2" : "=v"(t) : "v"(u), "v"(tau));
+    asm("v_add_f64 %0, |%1|, -%2" : "=v"(m) : "v"(u), "v"(t));
+    // copysign(m, u) as ONE v_bfi on the high word, in place.  (The library lowering - and the same
     // bit operations written in C - built the result in a fresh register pair, because the compiler
     // keeps m alive for the |x+| sum that follows: one v_bfi + one v_mov per element and trial.)
-    const double m = u - t;
     int mhi = __double2hiint(m);
     asm("v_bfi_b32 %0, %2, %0, %1" : "+v"(mhi) : "v"(__double2hiint(u)), "s"(0x7fffffff));
     return __hiloint2double(mhi, __double2loint(m));

@@ -421,8 +421,11 @@ __global__ __launch_bounds__(ZF_BLOCK) void zf_op_apply_kernel(zf_op_args P, con
 // the tile load from the ring of B W^-1 x (zf_op_fuse), `r` is not read.  Tiles: as in the apply kernel - a workgroup walks
 // tiles v = blockIdx.x, + gridDim.x, ...; the three arrays of the NEXT tile are fetched into registers before the correlation of
 // this one.
+// (second bound: waves per SIMD the register allocation must leave room for.  The separable 3 x 3 kernel on 64 x 32 tiles holds
+//  four workgroups per CU by its LDS and sat at 119 VGPRs; with the three-instruction soft-threshold of round 6 the scheduler
+//  gave that occupancy up - 133 VGPRs, three waves - although nothing in the kernel got larger: it is told to keep it.)
 template <int K, int TY, bool SEP>
-__global__ __launch_bounds__(ZF_BLOCK) void zf_op_adjoint_kernel(zf_op_args P, const double* __restrict__ r,
+__global__ __launch_bounds__(ZF_BLOCK, (K == 3 && TY == 32 && SEP) ? 4 : 1) void zf_op_adjoint_kernel(zf_op_args P, const double* __restrict__ r,
                                                                  double* __restrict__ grad, double two_scale, zf_op_fuse F) {
     using G = zf_op_geo<K, TY>;
     __shared__ double tile[G::TILE_DOUBLES > TY * ZF_OP_TX ? G::TILE_DOUBLES : TY * ZF_OP_TX];   // later: the blurred tile

@@ -35,7 +35,8 @@ struct zf_elem_acc {
 //   f(y)  = 1/2 sum (d r) r   with grad = d r already at hand      (NumPy: d * (r * r))
 //   f(x+) = 1/2 sum (d rn) rn  - the same formula, so f(y_{k+1}) == f(x_{k+1}) bit for bit
 //           whenever y_{k+1} == x_{k+1} (no momentum), as with one f callback
-// 20 fp64 operations per element and trial (25 unfused).
+// 19 VALU operations per element and trial: 18 fp64 + the sign copy of the soft-threshold (round 6: the threshold in
+// three instructions instead of four, zf_common.h; 20 before, 25 unfused).
 // RES (ZF_ACCEPT_RESOLVED, include/zfista_hip.h): the fifth sum is not f(x+) but the DIFFERENCE f(x+) - f(y), element by
 // element as a difference of squares - 1/2 d (rn^2 - r^2) = 1/2 (d dx)(rn + r) with dx = x+ - y = rn - r - so that the
 // acceptance test (:303) is evaluated on numbers of the size of the step, not on the difference of two sums of the size
@@ -64,7 +65,7 @@ __device__ __forceinline__ double zf_elem_diag(double xk, double xo, double d, d
 }
 
 // the same iterate arithmetic without the reductions: an iteration whose decision is already
-// known is recomputed ("replayed") in registers - 11 fp64 operations
+// known is recomputed ("replayed") in registers - 10 operations (9 fp64 + the sign copy; 11 until round 6)
 template <bool NESTEROV, bool BOX>
 __device__ __forceinline__ double zf_elem_diag_replay(double xk, double xo, double d, double c, double beta,
                                                       double lr, double tau, double lo, double hi) {
