@@ -126,9 +126,18 @@ typedef struct zf_control {
  * accumulated element by element (pack slot 7), so the test resolves ~1e-16 of the step, not of F; f(x+) is then reported
  * as f(y) + [f(x+) - f(y)].  Iterates of accepted trials are the same arithmetic either way.  One difference by design:
  * with F(x_k) = inf (x_k outside the box) the reference's expression accepts every trial (-inf <= -inf); the resolved form
- * still tests the smooth part. */
+ * still tests the smooth part.
+ * ZF_ACCEPT_REMAINDER (opt-in; ZF_PROBLEM_LEAST_SQUARES_L1 and ZF_PROBLEM_SPARSE_LS_L1) moves the dot product to the left as
+ * well: the Taylor remainder R = f(x+) - f(y) - <grad f(y), x+ - y> of a loss of the margins s = A x can be formed without
+ * cancelling anything - for least squares it is exactly scale |A (x+ - y)|^2 = scale sum_i (s+_i - s_y,i)^2 with
+ * s_y = s_k + beta (s_k - s_{k-1}), both margin vectors being in HBM already - and the test reads
+ *     R - |x+ - y|^2 / 2 / lr <= tol_internal          (:301, deprecated: R <= g(x+) + |x+ - y|^2 / 2 / lr + tol_internal),
+ * every term non-negative and of the size of the step (pack slot 7 carries R).  f(x+) is computed and reported exactly as
+ * under ZF_ACCEPT_REFERENCE: where both modes decide alike, iterates and traces are bit-identical.  With F(x_k) = inf this
+ * mode, too, still tests the smooth part. */
 #define ZF_ACCEPT_REFERENCE 0
 #define ZF_ACCEPT_RESOLVED 1
+#define ZF_ACCEPT_REMAINDER 2
 
 typedef struct zf_problem_desc {
     int32_t kind;      /* ZF_PROBLEM_*                                                */
@@ -170,7 +179,8 @@ typedef struct zf_options {  /* keyword arguments of proximal_gradient.py:317-33
                             problems (temporal blocking): 0 = library default (ZF_SUB_ITERS in the
                             environment, else ZF_DEFAULT_SUB_ITERS), 1 / 2 / 4 / 8 / 16 explicit.  Results do not depend on it;
                             lam >= 0, lr > 0, decay_rate > 0 are required by the fused kernels.     */
-    int32_t accept_mode; /* (ABI 6; was reserved = 0) ZF_ACCEPT_REFERENCE or ZF_ACCEPT_RESOLVED (ZF_PROBLEM_DIAG_QUAD_L1 only) */
+    int32_t accept_mode; /* (ABI 6; was reserved = 0) ZF_ACCEPT_REFERENCE, ZF_ACCEPT_RESOLVED (ZF_PROBLEM_DIAG_QUAD_L1 only) or
+                            ZF_ACCEPT_REMAINDER (ZF_PROBLEM_LEAST_SQUARES_L1, ZF_PROBLEM_SPARSE_LS_L1 only) */
 } zf_options;
 
 typedef struct zf_solver zf_solver; /* opaque; owns x ring, partials, control, rings */
@@ -447,6 +457,12 @@ int zf_ls_eval(const double* A_dev, const double* b_dev, int64_t m_rows, int64_t
  * exp(-|t|) per row feeds softplus(t) = max(t, 0) + log1p(e) and sigma(t) = t >= 0 ? 1 / (1 + e) : e / (1 + e) */
 int zf_logistic_eval(const double* A_dev, const double* b_dev, int64_t m_rows, int64_t n, double scale,
                      const double* x_host, double* f_out, double* grad_out_host);
+/* The Taylor remainder of the squared loss as a ZF_ACCEPT_REMAINDER solver forms it, for caller-supplied margins (host
+ * arrays of m doubles): R = scale sum_i (s+_i - s_y,i)^2, s_y = s_k + beta (s_k - s_{k-1}) (nesterov != 0) or s_k.
+ * wide = 0: the one-workgroup kernel (dense problems; sparse ones up to 32768 rows); wide = 1: the chunked pair of kernels
+ * (sparse problems beyond).  For element-wise tests of those kernels, outside any solve. */
+int zf_ls_remainder_eval(const double* s_plus_host, const double* s_k_host, const double* s_km1_host, int64_t m, double beta,
+                         int32_t nesterov, double scale, int32_t wide, double* r_out);
 
 /* ---- sparse least squares (ZF_PROBLEM_SPARSE_LS_L1) -------------------------
  * A (m x n) comes as TWO canonical CSR matrices in HBM - A itself and A^T, each with sorted, duplicate-free column

@@ -98,14 +98,14 @@ def logistic_closures(A, b, lam):
     return f, (lambda x: lam * np.linalg.norm(x, ord=1)), jac, (lambda w, x: np.sign(x) * np.maximum(np.abs(x) - lam * w, 0))
 
 
-def timed_run(prob, n, warmup, steps):
+def timed_run(prob, n, warmup, steps, acceptance="reference"):
     import torch
 
     from zfista_amd.proximal_gradient import NativeRun
 
     opts = dict(lr=1, tol=0.0, tol_internal=1e-12, max_iter=10 ** 9, max_iter_internal=100000, max_backtrack_iter=100,
                 warm_start=False, decay_rate=0.5, nesterov=True, nesterov_ratio=(0, 0.25), return_all=False, verbose=False,
-                deprecated=False)
+                deprecated=False, acceptance=acceptance)
     run = NativeRun(prob, np.zeros(n), opts, timing=True)
     plan = list(run.solver.ls_plan())
     warm = run.advance(warmup)
@@ -135,6 +135,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=16)
     ap.add_argument("--steps", type=int, default=64)
     ap.add_argument("--label", default="")
+    ap.add_argument("--acceptance", choices=("reference", "remainder"), default="reference",
+                    help="acceptance test of the LEAST-SQUARES sibling (the logistic classes have the reference's only; DESIGN 4.4)")
     args = ap.parse_args()
 
     from zfista_amd import minimize_proximal_gradient
@@ -143,7 +145,7 @@ def main():
     t0 = time.time()
     A, b_ls, lam_ls, labels, lam_lg = build_dense(args) if args.backend == "dense" else build_sparse(args)
     m, n = int(A.shape[0]), int(A.shape[1])
-    out = dict(tool="bench_logistic", label=args.label, backend=args.backend, loss=args.loss, m=m, n=n, seed=args.seed,
+    out = dict(tool="bench_logistic", label=args.label, backend=args.backend, loss=args.loss, ls_acceptance=args.acceptance, m=m, n=n, seed=args.seed,
                warmup=args.warmup, steps=args.steps, repeats=args.repeats, build_s=round(time.time() - t0, 2))
     if args.backend != "dense":
         out.update(nnz=int(A.nnz), row_len_A=lengths(A.indptr), row_len_At=lengths(A.T.tocsr().indptr))
@@ -168,7 +170,7 @@ def main():
     runs = {k: [] for k in probs}
     for _ in range(args.repeats):
         for k, prob in probs.items():   # alternated: ls, logistic, ls, logistic, ...
-            runs[k].append(timed_run(prob, n, args.warmup, args.steps))
+            runs[k].append(timed_run(prob, n, args.warmup, args.steps, args.acceptance if k == "ls" else "reference"))
     for k, rs in runs.items():
         wall = [r["ms_per_trial_wall"] for r in rs]
         out[k] = dict(plan=rs[0]["plan"], ms_per_trial_wall=wall, ms_per_trial_wall_median=float(np.median(wall)),

@@ -82,6 +82,9 @@ def main():
     ap.add_argument("--warmup", type=int, default=16)
     ap.add_argument("--steps", type=int, default=64)
     ap.add_argument("--label", default="")
+    ap.add_argument("--acceptance", choices=("reference", "remainder"), default="reference",
+                    help="how the sufficient-decrease test is evaluated (native backends; DESIGN 4.4)")
+    ap.add_argument("--repeats", type=int, default=1, help="timed solves of the same problem (native backends)")
     args = ap.parse_args()
 
     import torch
@@ -94,7 +97,7 @@ def main():
     A, b, lam = build(args)
     m, n = A.shape
     print(f"built {m} x {n}, nnz {A.nnz} in {time.time() - t0:.1f} s", file=sys.stderr, flush=True)
-    out = dict(tool="bench_sparse", label=args.label, backend=args.backend, m=m, n=n, nnz=int(A.nnz), skew=bool(args.skew),
+    out = dict(tool="bench_sparse", label=args.label, backend=args.backend, acceptance=args.acceptance, m=m, n=n, nnz=int(A.nnz), skew=bool(args.skew),
                seed=args.seed, row_len_A=lengths(A.indptr), row_len_At=lengths(A.T.tocsr().indptr),
                warmup=args.warmup, steps=args.steps, build_s=round(time.time() - t0, 2))
     if args.backend == "generic":
@@ -113,18 +116,25 @@ def main():
     prob = SparseLeastSquaresL1(A, b, lam) if args.backend == "sparse" else LeastSquaresL1(A.toarray(), b, lam)
     opts = dict(lr=1, tol=0.0, tol_internal=1e-12, max_iter=10 ** 9, max_iter_internal=100000, max_backtrack_iter=100,
                 warm_start=False, decay_rate=0.5, nesterov=True, nesterov_ratio=(0, 0.25), return_all=False, verbose=False,
-                deprecated=False)
-    run = NativeRun(prob, np.zeros(n), opts, timing=True)
-    out["plan"] = list(run.solver.ls_plan())
-    warm = run.advance(args.warmup)
-    run.solver.trial_kernel_ms()   # (resets the event window)
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    rows = run.advance(args.steps)
-    torch.cuda.synchronize()
-    dt = time.perf_counter() - t1
-    ms, count = run.solver.trial_kernel_ms()
-    accepted = len(rows)
+                deprecated=False, acceptance=args.acceptance)
+    walls = []
+    for rep_no in range(max(1, args.repeats)):   # (the figures reported below are the last repeat's; every repeat's wall time is kept)
+        if rep_no:
+            run.solver.close()
+        run = NativeRun(prob, np.zeros(n), opts, timing=True)
+        out["plan"] = list(run.solver.ls_plan())
+        warm = run.advance(args.warmup)
+        run.solver.trial_kernel_ms()   # (resets the event window)
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        rows = run.advance(args.steps)
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t1
+        ms, count = run.solver.trial_kernel_ms()
+        accepted = len(rows)
+        walls.append(dict(ms_per_trial_wall=1e3 * dt / args.steps, accepted=accepted))
+    if args.repeats > 1:
+        out["repeats"] = walls
     out.update(warmup_accepted=len(warm), accepted=accepted, trials=args.steps, seconds=dt, it_per_s=accepted / dt,
                ms_per_trial_wall=1e3 * dt / args.steps, ms_per_trial_events=ms, timed_launches=int(count),
                lr=float(rows[-1][2]) if accepted else None)

@@ -442,7 +442,7 @@ template <bool NT, int S> void run_lib_loop(const Bufs& B, int T) {
     A.p0 = B.d; A.p1 = B.c;
     A.lam = 0.1; A.lo = 0; A.hi = 0; A.n = B.n; A.tiles_per_wg = T;
     F.blk_part = A.blk_part; F.nblocks = grid; F.sub_iters = S; for (int k = 0; k < ZF_NPART; ++k) F.scale[k] = 1.0;
-    F.f_y_ext = F.f_x_ext = nullptr; F.contribute_f = 1; F.pack = pack; F.ctl = ctl; F.decide = 1; F.trace = trace; F.beta_ring = beta;
+    F.f_y_ext = F.f_x_ext = F.r_ext = nullptr; F.contribute_f = 1; F.pack = pack; F.ctl = ctl; F.decide = 1; F.trace = trace; F.beta_ring = beta;
     int wgs = (grid + ZF_FIN_THREADS - 1) / ZF_FIN_THREADS; if (wgs > ZF_FIN_WGS) wgs = ZF_FIN_WGS; if (wgs < 1) wgs = 1;
     const int K = 20;
     double ms = time_ms([&] { for (int k = 0; k < K; ++k) {

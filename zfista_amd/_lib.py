@@ -29,8 +29,9 @@ ZF_MAX_LAG = 2 * ZF_MAX_SUB_ITERS - 2
 ZF_PEND_FLUSH = -1
 TR_ERR, TR_F, TR_LR, TR_FUN, TR_TRIALS, TR_FX, TR_GX, TR_FY = range(8)
 PK_FY, PK_DOT, PK_SS, PK_GX, PK_FX, PK_ERR = range(6)
-PK_DF = 7   # ZF_ACCEPT_RESOLVED: f(x+) - f(y), accumulated element by element
-ZF_ACCEPT_REFERENCE, ZF_ACCEPT_RESOLVED = 0, 1
+PK_DF = 7   # ZF_ACCEPT_RESOLVED: f(x+) - f(y), accumulated element by element; ZF_ACCEPT_REMAINDER: the Taylor remainder R
+ZF_ACCEPT_REFERENCE, ZF_ACCEPT_RESOLVED, ZF_ACCEPT_REMAINDER = 0, 1, 2
+ACCEPT_MODES = {"reference": ZF_ACCEPT_REFERENCE, "resolved": ZF_ACCEPT_RESOLVED, "remainder": ZF_ACCEPT_REMAINDER}
 
 
 class HipUnavailable(RuntimeError):
@@ -209,6 +210,7 @@ SIGNATURES = {
     "zf_op_eval": (C.c_int, [_P, C.c_int32, _P, C.c_int64, C.c_int64, C.c_double, _P, C.POINTER(C.c_double), _P]),
     "zf_ls_eval": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_double, _P, C.POINTER(C.c_double), _P]),
     "zf_logistic_eval": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_double, _P, C.POINTER(C.c_double), _P]),
+    "zf_ls_remainder_eval": (C.c_int, [_P, _P, _P, C.c_int64, C.c_double, C.c_int32, C.c_double, C.c_int32, C.POINTER(C.c_double)]),
     "zf_spmat_logistic_eval": (C.c_int, [_P, _P, C.c_double, _P, C.POINTER(C.c_double), _P]),
     "zf_spmat_create": (C.c_int, [C.POINTER(_P), C.c_int64, C.c_int64, C.c_int64, _P, _P, _P, C.POINTER(SpmvPlan),
                                   _P, _P, _P, C.POINTER(SpmvPlan), C.c_int64]),

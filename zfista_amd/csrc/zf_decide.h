@@ -42,7 +42,8 @@
 // pack layout (per rank): sums are added over ranks in rank order, the max is
 // maxed.  [0] f(y)  [1] <grad f(y), x+ - y>  [2] |x+ - y|^2  [3] g(x+)
 //         [4] f(x+) [5] max|x+ - y|          [6] stamp of the block the pass read (sharded solves; zf_pack_stamp)
-//         [7] f(x+) - f(y), accumulated element by element (ZF_ACCEPT_RESOLVED only, else 0)
+//         [7] f(x+) - f(y), accumulated element by element (ZF_ACCEPT_RESOLVED); the Taylor remainder
+//             R = f(x+) - f(y) - <grad f(y), x+ - y>, formed directly (ZF_ACCEPT_REMAINDER); else 0
 enum { ZF_PK_FY = 0, ZF_PK_DOT = 1, ZF_PK_SS = 2, ZF_PK_GX = 3, ZF_PK_FX = 4, ZF_PK_ERR = 5, ZF_PK_DF = 7 };
 // trace row: [0] err [1] F(x+) [2] lr [3] model value [4] trials [5] f(x+) [6] g(x+) [7] f(y)
 enum { ZF_TR_ERR = 0, ZF_TR_F = 1, ZF_TR_LR = 2, ZF_TR_FUN = 3, ZF_TR_TRIALS = 4,
@@ -141,6 +142,15 @@ ZF_HD inline void zf_eval_trial(const zf_control* c, double F_old, double lr, co
         const double df = pk[ZF_PK_DF];
         if (c->deprecated) accept = (df <= fun + c->tol_internal);
         else accept = ((df - dot) - nrm * nrm / 2 / lr <= c->tol_internal);
+    }
+    else if (c->accept_mode == ZF_ACCEPT_REMAINDER) {
+        // The same inequalities with the Taylor remainder R = f(x+) - f(y) - <grad f(y), x+ - y> taken from pack slot 7, where
+        // the loss kernels left it without cancelling anything (least squares: scale |A (x+ - y)|^2).  :303, F_old and g(x+)
+        // cancelled:  R - |x+ - y|^2 / 2 / lr <= tol_internal;  :301 (deprecated) keeps g(x+):
+        // R <= g(x+) + |x+ - y|^2 / 2 / lr + tol_internal.  Every term is non-negative and of the size of the step.
+        const double R = pk[ZF_PK_DF];
+        if (c->deprecated) accept = (R <= (g_x + nrm * nrm / 2 / lr) + c->tol_internal);
+        else accept = (R - nrm * nrm / 2 / lr <= c->tol_internal);
     }
     else if (c->deprecated) accept = (f_x - f_y <= fun + c->tol_internal);    // :301
     else accept = (F_x - F_old <= fun + c->tol_internal);                     // :303

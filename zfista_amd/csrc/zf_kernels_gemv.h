@@ -161,6 +161,51 @@ __global__ __launch_bounds__(RESID_BLOCK) void zf_resid_x_kernel(const zf_contro
     }
 }
 
+// ZF_ACCEPT_REMAINDER: zf_resid_x_kernel's f(x+) - the same loop, the same sum, the same bits - and beside it the Taylor
+// remainder of the squared loss, formed directly:
+//   R = f(x+) - f(y) - <grad f(y), x+ - y> = scale |A (x+ - y)|^2 = scale sum_i (s+_i - s_y,i)^2,
+// s_y = s_k + beta (s_k - s_{k-1}) by zf_resid_y_kernel's expression (a rejected trial leaves `cur` and beta_next in place:
+// they are this trial's).  Second sum in the order of the first; no atomics.
+// slot >= 0: s+ = sr.p[(cur + slot) % 3], s_k = sr.p[cur], s_{k-1} = sr.p[(cur + 2) % 3], beta = ctl->beta_next;
+// slot < 0 (plain call, ctl unused): s+ = sr.p[0], s_k = sr.p[1], s_{k-1} = sr.p[2], beta = beta_plain.
+__global__ __launch_bounds__(RESID_BLOCK) void zf_resid_x_rem_kernel(const zf_control* ctl, zf_ring3 sr, int slot,
+                                                                     const double* __restrict__ b, double scale,
+                                                                     int64_t m_rows, double* f_out, int nesterov,
+                                                                     double beta_plain, double* r_out) {
+    __shared__ double lds[RESID_BLOCK / 64];
+    __shared__ double lds_r[RESID_BLOCK / 64];
+    int ip = 0, ik = 1, io = 2;
+    double beta = nesterov ? beta_plain : 0.0;
+    if (slot >= 0) {
+        if (ctl->status != ZF_RUNNING) return;
+        const int cur = ctl->cur;
+        ip = (cur + slot) % 3;
+        ik = cur;
+        io = (cur + 2) % 3;
+        beta = nesterov ? ctl->beta_next : 0.0;
+    }
+    const double* __restrict__ s = sr.p[ip];
+    const double* __restrict__ sk = sr.p[ik];
+    const double* __restrict__ so = sr.p[io];
+    double acc = 0.0, acc_r = 0.0;
+    for (int64_t i = threadIdx.x; i < m_rows; i += RESID_BLOCK) {
+        const double sp = s[i];
+        const double rv = sp - b[i];
+        acc += rv * rv;
+        double ay = sk[i];
+        if (nesterov) ay = ay + beta * (ay - so[i]);
+        const double dv = sp - ay;
+        acc_r += dv * dv;
+    }
+    const double t = zf_block_sum_1024(acc, lds);
+    const double tr = zf_block_sum_1024(acc_r, lds_r);
+    if (threadIdx.x == 0) {
+        const double nrm = sqrt(t);
+        *f_out = scale * (nrm * nrm);
+        *r_out = scale * tr;
+    }
+}
+
 // The same for LONG residuals (the operator problem: m = n pixels) in two launches: every workgroup the share of its
 // contiguous chunk -> partials[blockIdx.x]; then one workgroup adds the shares in order.  (One workgroup alone took 8 ms
 // for 1.7e7 pixels at the initialisation of a 4096 x 4096 deblurring solve.)

@@ -38,6 +38,7 @@ struct zf_ls_small_args {
     double* blk_part;      // ZF_NPART x grid_step partials of the step kernel
     int grid_step;
     double* row_part;      // workgroup sums of (s+ - b)^2, one per workgroup of the rows kernel
+    double* row_part_r;    // ZF_ACCEPT_REMAINDER: workgroup sums of (s+ - s_y)^2, likewise (else unused)
     unsigned* cnt;         // arrival counter of the rows kernel (zero between launches)
     double* pack;
     double* trace;
@@ -140,8 +141,13 @@ __global__ __launch_bounds__(ZF_BLOCK) void zf_ls_small_step_kernel(zf_ls_small_
     }
 }
 
+// REM (ZF_ACCEPT_REMAINDER): beside (s+ - b)^2 every row also leaves (s+ - s_y)^2, s_y = s_k + beta (s_k - s_{k-1}) by the
+// step kernel's expression; the last arriver adds those workgroup sums in the same order -> R = scale |A (x+ - y)|^2, the
+// Taylor remainder of f, into ls_scal[2] and pack slot 7.  f(x+) is the same sum, the same bits, in both instantiations.
+template <bool REM = false>
 __global__ __launch_bounds__(ZF_BLOCK) void zf_ls_small_rows_kernel(zf_ls_small_args P) {
     __shared__ double s_w[ZF_WAVES];
+    __shared__ double s_wr[REM ? ZF_WAVES : 1];
     __shared__ zf_trial_eval s_pre[ZF_MAX_SUB_ITERS];
     __shared__ double s_pack[ZF_PACK_LEN];
     __shared__ int s_last;
@@ -155,7 +161,7 @@ __global__ __launch_bounds__(ZF_BLOCK) void zf_ls_small_rows_kernel(zf_ls_small_
     double* __restrict__ s_out = P.sring.p[(cur + 1) % 3];  // A x+ (slot 1 of the s ring, as zf_gemv_rows_kernel)
     const int64_t m = P.m, n = P.n;
     const int64_t row = (int64_t)blockIdx.x * ZF_WAVES + wave;
-    double sq = 0.0;
+    double sq = 0.0, sq_r = 0.0;
     if (row < m) {
         const zf_row2* __restrict__ Ar = reinterpret_cast<const zf_row2*>(P.A + row * n);
         const zf_row2* __restrict__ xv = reinterpret_cast<const zf_row2*>(x);
@@ -180,14 +186,28 @@ __global__ __launch_bounds__(ZF_BLOCK) void zf_ls_small_rows_kernel(zf_ls_small_
             s_out[row] = acc;
             const double rv = acc - P.b[row];
             sq = rv * rv;
+            if constexpr (REM) {
+                double ay = P.sring.p[cur][row];
+                if (ctl->nesterov) ay = ay + ctl->beta_next * (ay - P.sring.p[(cur + 2) % 3][row]);
+                const double dv = acc - ay;
+                sq_r = dv * dv;
+            }
         }
     }
     if (lane == 0) s_w[wave] = sq;
+    if constexpr (REM) {
+        if (lane == 0) s_wr[wave] = sq_r;
+    }
     __syncthreads();
     if (tid == 0) {
         double t = s_w[0];
         for (int w = 1; w < ZF_WAVES; ++w) t += s_w[w];
         zf_publish(P.row_part + blockIdx.x, t);
+        if constexpr (REM) {
+            double tr = s_wr[0];
+            for (int w = 1; w < ZF_WAVES; ++w) tr += s_wr[w];
+            zf_publish(P.row_part_r + blockIdx.x, tr);
+        }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         const unsigned tk = __hip_atomic_fetch_add(P.cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         const int last = (tk == (unsigned)(gridDim.x - 1));
@@ -208,6 +228,15 @@ __global__ __launch_bounds__(ZF_BLOCK) void zf_ls_small_rows_kernel(zf_ls_small_
     }
     const double nrm = sqrt(fx);
     const double f_x = P.scale * (nrm * nrm);
+    double rem = 0.0;
+    if constexpr (REM) {
+        for (int g0 = 0; g0 < (int)gridDim.x; g0 += 64) {
+            const int g = g0 + lane;
+            const double v = g < (int)gridDim.x ? zf_consume(P.row_part_r + g) : 0.0;
+            rem += zf_wave_sum(v);
+        }
+        rem = P.scale * rem;
+    }
     double dot = 0.0, ss = 0.0, l1 = 0.0, mx = 0.0;
     const int64_t G = P.grid_step;
     for (int64_t g0 = 0; g0 < G; g0 += 64) {
@@ -226,9 +255,10 @@ __global__ __launch_bounds__(ZF_BLOCK) void zf_ls_small_rows_kernel(zf_ls_small_
     pk[ZF_PK_FX] = __shfl(f_x, 0, 64);
     pk[ZF_PK_ERR] = __shfl(mx, 0, 64);
     pk[6] = 0.0;
-    pk[7] = 0.0;
+    pk[7] = REM ? __shfl(rem, 0, 64) : 0.0;
     if (lane == 0) {
         P.ls_scal[1] = pk[ZF_PK_FX];
+        if constexpr (REM) P.ls_scal[2] = pk[ZF_PK_DF];
 #pragma unroll
         for (int k = 0; k < ZF_PACK_LEN; ++k) {
             P.pack[k] = pk[k];

@@ -336,6 +336,7 @@ struct zf_finalize_args {
     double scale[ZF_NPART];   // pack[k] = scale[k] * total[k]
     const double* f_y_ext;    // least squares: f(y), f(x+) come from the GEMV side (else NULL)
     const double* f_x_ext;
+    const double* r_ext;      // ZF_ACCEPT_REMAINDER: the Taylor remainder R of the trial, from the GEMV side as f(x+) is -> pack slot 7 (else NULL)
     int contribute_f;         // column-sharded least squares: only rank 0 contributes the replicated f values
     int contribute_x;         // row-sharded least squares: x is replicated - only rank 0 contributes its sums
     double* pack;             // local packs out (S x ZF_PACK_LEN)
@@ -459,7 +460,7 @@ __global__ __launch_bounds__(ZF_FIN_THREADS) void zf_finalize_kernel(zf_finalize
     pk[ZF_PK_FX] = F.f_x_ext ? (F.contribute_f ? *F.f_x_ext : 0.0) : F.scale[4] * sums[4];
     pk[ZF_PK_ERR] = maxs[0];
     pk[6] = 0.0;
-    pk[7] = 0.0;
+    pk[7] = F.r_ext ? (F.contribute_f ? *F.r_ext : 0.0) : 0.0;
     if (lane % LSTR == 0) {
 #pragma unroll
         for (int k = 0; k < ZF_PACK_LEN; ++k) {

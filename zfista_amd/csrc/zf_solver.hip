@@ -159,7 +159,9 @@ struct zf_solver {
     hipStream_t stream;
     int grid;                 // trial kernel grid
     bool box;
-    bool res = false;         // ZF_ACCEPT_RESOLVED: the kernels accumulate f(x+) - f(y) element by element (zf_elem_diag<..., RES>)
+    int accept_mode = ZF_ACCEPT_REFERENCE;   // ZF_ACCEPT_*: what the control block, snapshots and the resume code carry
+    bool res = false;         // ... == ZF_ACCEPT_RESOLVED: the kernels accumulate f(x+) - f(y) element by element (zf_elem_diag<..., RES>)
+    bool rem = false;         // ... == ZF_ACCEPT_REMAINDER: the residual kernels at x+ also leave R = scale |A (x+ - y)|^2 in ls_scal[2]
     // device memory owned by the solver
     double* xbuf = nullptr;   // ring * n_pad
     double* xb[ZF_MAX_RING] = {};
@@ -184,7 +186,7 @@ struct zf_solver {
     zf_ring3 sring = {{nullptr, nullptr, nullptr}};
     double* resid = nullptr;      // m_rows
     double* slab = nullptr;       // slices * n
-    double* ls_scal = nullptr;    // [0] f(y) [1] f(x+)
+    double* ls_scal = nullptr;    // [0] f(y) [1] f(x+) [2] the Taylor remainder R of the trial (ZF_ACCEPT_REMAINDER)
     double* s_part = nullptr;     // sharded: this rank's A_p x_p (m)
     double* s_all = nullptr;      // sharded: gathered parts (world x m, rank-major)
     bool own_svec = true;
@@ -518,13 +520,19 @@ static int zf_solver_create_impl(zf_solver** out, const zf_problem_desc* desc, c
     s->stream = reinterpret_cast<hipStream_t>(stream);
     s->box = !(desc->box_lo == -INFINITY && desc->box_hi == INFINITY);
     if (opt->accept_mode != ZF_ACCEPT_REFERENCE) {
-        const bool ok = opt->accept_mode == ZF_ACCEPT_RESOLVED && desc->kind == ZF_PROBLEM_DIAG_QUAD_L1;
-        if (!ok) {
+        const bool res_ok = opt->accept_mode == ZF_ACCEPT_RESOLVED && desc->kind == ZF_PROBLEM_DIAG_QUAD_L1;
+        const bool rem_ok = opt->accept_mode == ZF_ACCEPT_REMAINDER &&
+                            (desc->kind == ZF_PROBLEM_LEAST_SQUARES_L1 || desc->kind == ZF_PROBLEM_SPARSE_LS_L1);
+        if (!res_ok && !rem_ok) {
             delete s;
-            return zf_fail(ZF_ERR_ARG, "zf_solver_create: accept_mode must be ZF_ACCEPT_REFERENCE, or ZF_ACCEPT_RESOLVED for "
-                                       "ZF_PROBLEM_DIAG_QUAD_L1 (the element-wise difference f(x+) - f(y) exists for the separable problem only)%s");
+            return zf_fail(ZF_ERR_ARG, "zf_solver_create: accept_mode must be ZF_ACCEPT_REFERENCE, ZF_ACCEPT_RESOLVED for "
+                                       "ZF_PROBLEM_DIAG_QUAD_L1 (the element-wise difference f(x+) - f(y) exists for the separable problem only), or "
+                                       "ZF_ACCEPT_REMAINDER for ZF_PROBLEM_LEAST_SQUARES_L1 and ZF_PROBLEM_SPARSE_LS_L1 (the Taylor remainder "
+                                       "scale |A (x+ - y)|^2 is formed by the least-squares residual kernels only)%s");
         }
-        s->res = true;
+        s->accept_mode = opt->accept_mode;
+        s->res = res_ok;
+        s->rem = rem_ok;
     }
     const int64_t n = desc->n;
     const int64_t n_pad = (n + 63) & ~int64_t(63);   // keep every ring buffer 512-B aligned
@@ -650,7 +658,8 @@ static int zf_solver_create_impl(zf_solver** out, const zf_problem_desc* desc, c
         for (int k = 0; k < 3; ++k) s->sring.p[k] = s->sbuf + k * m_pad;
         ZF_TRY(hipMalloc(&s->resid, sizeof(double) * m_pad));
         ZF_TRY(hipMalloc(&s->ls_scal, sizeof(double) * 8));
-        ZF_TRY(hipMalloc(&s->row_part, sizeof(double) * 2 * ZF_SPMV_RESID_MAX_CHUNKS));   // chunk sums of |r(y)|^2 and of |s+ - b|^2 (logistic: of the two losses)
+        // chunk sums of |r(y)|^2 and of |s+ - b|^2 (logistic: of the two losses); ZF_ACCEPT_REMAINDER: and of |s+ - s_y|^2
+        ZF_TRY(hipMalloc(&s->row_part, sizeof(double) * 3 * ZF_SPMV_RESID_MAX_CHUNKS));
     }
     if (zf_is_dense_mat(desc->kind)) {
         const int64_t m = desc->m_rows;
@@ -681,7 +690,8 @@ static int zf_solver_create_impl(zf_solver** out, const zf_problem_desc* desc, c
         s->ls_small = desc->kind == ZF_PROBLEM_LEAST_SQUARES_L1 && desc->world == 1 && n % LS_SMALL_COLS == 0 && m <= LS_SMALL_MAX_M &&
                       m * n <= LS_SMALL_MAX_ELEMS && zf_aligned16(desc->A) && s->env.ls_small;
         if (s->ls_small) {
-            ZF_TRY(hipMalloc(&s->row_part, sizeof(double) * ((m + ZF_WAVES - 1) / ZF_WAVES)));
+            // (twice the workgroups of the rows kernel: their sums of (s+ - b)^2 and - ZF_ACCEPT_REMAINDER - of (s+ - s_y)^2)
+            ZF_TRY(hipMalloc(&s->row_part, sizeof(double) * 2 * ((m + ZF_WAVES - 1) / ZF_WAVES)));
             ZF_TRY(hipMalloc(&s->ls_cnt, 64));
             ZF_TRY(hipMemsetAsync(s->ls_cnt, 0, 64, s->stream));
         }
@@ -757,6 +767,18 @@ static void zf_launch_trial_kernels(zf_solver* s, const zf_step_args& a, bool gr
     if (s->sub > 1 && (mask & ZF_K_SHORT)) zf_launch_chain(v, s->sub, 1, grid, st, a);
 }
 
+// f(x+) of the trial from s+ = sring[(cur + 1) % 3] (one workgroup); ZF_ACCEPT_REMAINDER: the instantiation that also leaves
+// the Taylor remainder R in ls_scal[2]
+static void zf_launch_resid_x(zf_solver* s) {
+    const zf_problem_desc& d = s->desc;
+    if (s->rem)
+        hipLaunchKernelGGL(zf_resid_x_rem_kernel, dim3(1), dim3(RESID_BLOCK), 0, s->stream, s->ctl, s->sring, 1, d.b, d.scale,
+                           d.m_rows, s->ls_scal + 1, (int)s->opt.nesterov, 0.0, s->ls_scal + 2);
+    else
+        hipLaunchKernelGGL(zf_resid_x_kernel, dim3(1), dim3(RESID_BLOCK), 0, s->stream, s->ctl, s->sring, 1, d.b, d.scale,
+                           d.m_rows, s->ls_scal + 1);
+}
+
 // second launch of a step: partials -> pack (+ decide when x is unsharded)
 static void zf_launch_finalize(zf_solver* s, bool decide) {
     const zf_problem_desc& d = s->desc;
@@ -770,6 +792,7 @@ static void zf_launch_finalize(zf_solver* s, bool decide) {
     F.scale[3] = d.lam;               // g = lam * sum|x|
     F.f_y_ext = nullptr;
     F.f_x_ext = nullptr;
+    F.r_ext = nullptr;
     F.contribute_f = 1;
     F.contribute_x = 1;
     if (d.kind == ZF_PROBLEM_DIAG_QUAD_L1) {
@@ -778,6 +801,7 @@ static void zf_launch_finalize(zf_solver* s, bool decide) {
     } else {
         F.f_y_ext = s->ls_scal + 0;   // f(y), f(x+) come from the GEMV side and are replicated
         F.f_x_ext = s->ls_scal + 1;
+        if (s->rem) F.r_ext = s->ls_scal + 2;   // (contributed as f(x+) is)
         // column blocks: f is replicated, the x sums are partial; row blocks: the other way round
         F.contribute_f = (d.world == 1 || d.rank == 0 || d.row_sharded) ? 1 : 0;
         F.contribute_x = (d.world == 1 || d.rank == 0 || !d.row_sharded) ? 1 : 0;
@@ -1270,6 +1294,7 @@ static int zf_launch_trial(zf_solver* s, bool decide_in_launch, bool dry = false
         P.blk_part = s->blk_part;
         P.grid_step = (int)(d.n / LS_SMALL_COLS);
         P.row_part = s->row_part;
+        P.row_part_r = s->row_part + (d.m_rows + ZF_WAVES - 1) / ZF_WAVES;
         P.cnt = s->ls_cnt;
         P.pack = s->pack_local;
         P.trace = s->trace;
@@ -1287,7 +1312,8 @@ static int zf_launch_trial(zf_solver* s, bool decide_in_launch, bool dry = false
         else if (s->box) hipLaunchKernelGGL((zf_ls_small_step_kernel<false, true>), gs, b, 0, s->stream, P);
         else hipLaunchKernelGGL((zf_ls_small_step_kernel<false, false>), gs, b, 0, s->stream, P);
         if (e1) ZF_HIP(hipEventRecord(e1, s->stream));
-        hipLaunchKernelGGL(zf_ls_small_rows_kernel, gr, b, 0, s->stream, P);
+        if (s->rem) hipLaunchKernelGGL(zf_ls_small_rows_kernel<true>, gr, b, 0, s->stream, P);
+        else hipLaunchKernelGGL(zf_ls_small_rows_kernel<false>, gr, b, 0, s->stream, P);
     } else {
         const int64_t n = d.n, m = d.m_rows;
         const int V = (n % 2 == 0) ? 2 : 1;
@@ -1388,12 +1414,15 @@ static int zf_launch_trial(zf_solver* s, bool decide_in_launch, bool dry = false
             if (logistic)
                 zf_launch_logit_x(s->stream, s->ctl, s->sring.p[0], s->sring.p[1], s->sring.p[2], 1, d.b, d.scale, m,
                                   s->row_part + ZF_SPMV_RESID_MAX_CHUNKS, s->ls_scal + 1);
+            else if (wide_resid && s->rem)
+                zf_launch_spmv_resid_x_rem(s->stream, s->ctl, s->sring.p[0], s->sring.p[1], s->sring.p[2], 1, d.b, d.scale, m,
+                                           (int)s->opt.nesterov, 0.0, s->row_part + ZF_SPMV_RESID_MAX_CHUNKS,
+                                           s->row_part + 2 * ZF_SPMV_RESID_MAX_CHUNKS, s->ls_scal + 1, s->ls_scal + 2);
             else if (wide_resid)
                 zf_launch_spmv_resid_x(s->stream, s->ctl, s->sring.p[0], s->sring.p[1], s->sring.p[2], 1, d.b, d.scale, m,
                                        s->row_part + ZF_SPMV_RESID_MAX_CHUNKS, s->ls_scal + 1);
             else
-                hipLaunchKernelGGL(zf_resid_x_kernel, dim3(1), dim3(RESID_BLOCK), 0, s->stream, s->ctl, s->sring, 1, d.b, d.scale, m,
-                                   s->ls_scal + 1);
+                zf_launch_resid_x(s);
             zf_launch_finalize(s, decide_in_launch);
             if (e1) ZF_HIP(hipEventRecord(e1, s->stream));
             ZF_HIP(hipGetLastError());
@@ -1451,8 +1480,7 @@ static int zf_launch_trial(zf_solver* s, bool decide_in_launch, bool dry = false
                 zf_launch_logit_x(s->stream, s->ctl, s->sring.p[0], s->sring.p[1], s->sring.p[2], 1, d.b, d.scale, m,
                                   s->row_part + ZF_SPMV_RESID_MAX_CHUNKS, s->ls_scal + 1);
             else
-                hipLaunchKernelGGL(zf_resid_x_kernel, dim3(1), dim3(RESID_BLOCK), 0, s->stream, s->ctl, s->sring, 1,
-                                   d.b, d.scale, m, s->ls_scal + 1);
+                zf_launch_resid_x(s);
             zf_launch_finalize(s, decide_in_launch);
         }
     }
@@ -1490,16 +1518,14 @@ extern "C" int zf_solver_enqueue_trial_finish(zf_solver* s) {
         else
             hipLaunchKernelGGL(zf_gemv_rows_kernel<1>, dim3(gr), dim3(ZF_BLOCK), 0, s->stream, s->ctl, d.A, xr, s->sring,
                                1, m, n);
-        hipLaunchKernelGGL(zf_resid_x_kernel, dim3(1), dim3(RESID_BLOCK), 0, s->stream, s->ctl, s->sring, 1, d.b,
-                           d.scale, m, s->ls_scal + 1);
+        zf_launch_resid_x(s);
         zf_launch_finalize(s, false);
         ZF_HIP(hipGetLastError());
         return ZF_OK;
     }
     hipLaunchKernelGGL(zf_sum_parts_kernel, dim3(zf_grid_for(m)), dim3(ZF_BLOCK), 0, s->stream, s->ctl, s->s_all,
                        (int)d.world, m, s->sring, 1);
-    hipLaunchKernelGGL(zf_resid_x_kernel, dim3(1), dim3(RESID_BLOCK), 0, s->stream, s->ctl, s->sring, 1, d.b,
-                       d.scale, m, s->ls_scal + 1);
+    zf_launch_resid_x(s);
     zf_launch_finalize(s, false);
     ZF_HIP(hipGetLastError());
     return ZF_OK;
@@ -1587,7 +1613,7 @@ extern "C" int zf_solver_enqueue_init(zf_solver* s, const double* x0_dev) {
     c.cur = 0;
     c.nesterov = s->opt.nesterov;
     c.deprecated = s->opt.deprecated;
-    c.accept_mode = s->res ? ZF_ACCEPT_RESOLVED : ZF_ACCEPT_REFERENCE;
+    c.accept_mode = s->accept_mode;
     c.need_grad = 1;
     c.world = d.world;
     c.ring_size = s->ring;
@@ -1661,7 +1687,7 @@ extern "C" int zf_solver_restore(zf_solver* s, const double* xk_dev, const doubl
     c.max_backtrack = s->opt.max_backtrack_iter;
     c.nesterov = s->opt.nesterov;
     c.deprecated = s->opt.deprecated;
-    c.accept_mode = s->res ? ZF_ACCEPT_RESOLVED : ZF_ACCEPT_REFERENCE;   // (this solver's: the test a resumed solve runs is the resuming caller's choice)
+    c.accept_mode = s->accept_mode;   // (this solver's: the test a resumed solve runs is the resuming caller's choice)
     c.cur = 0;
     c.prev = s->ring - 1;
     c.ring_size = s->ring;
@@ -2312,6 +2338,45 @@ extern "C" int zf_decide_host(zf_control* ctl, int64_t ctl_bytes, const double* 
     ZF_REQUIRE(ctl_bytes == (int64_t)sizeof(zf_control), "zf_decide_host: ctl_bytes differs from zf_sizeof_control()");
     zf_decide_pass(ctl, packs, trace);
     return ZF_OK;
+}
+
+// R = scale sum (s+ - s_y)^2 by the kernels of a ZF_ACCEPT_REMAINDER solver, for margins given in host memory (element-wise tests)
+extern "C" int zf_ls_remainder_eval(const double* s_plus_host, const double* s_k_host, const double* s_km1_host, int64_t m, double beta,
+                                    int32_t nesterov, double scale, int32_t wide, double* r_out) {
+    ZF_REQUIRE(s_plus_host && s_k_host && s_km1_host && r_out && m >= 1, "zf_ls_remainder_eval: bad argument");
+    ZF_REQUIRE(wide == 0 || wide == 1, "zf_ls_remainder_eval: wide must be 0 (one workgroup) or 1 (chunked)");
+    double *sv = nullptr, *b = nullptr, *part = nullptr, *out = nullptr;
+    const int64_t m_pad = (m + 63) & ~int64_t(63);
+    int rc = ZF_OK;
+#define ZF_RM(expr)                                                               \
+    do {                                                                          \
+        hipError_t _e = (expr);                                                   \
+        if (_e != hipSuccess && rc == ZF_OK)                                      \
+            rc = zf_fail(ZF_ERR_HIP, "%s: %s", #expr, hipGetErrorString(_e));     \
+    } while (0)
+    ZF_RM(hipMalloc(&sv, sizeof(double) * 3 * m_pad));
+    ZF_RM(hipMalloc(&b, sizeof(double) * m_pad));
+    ZF_RM(hipMalloc(&part, sizeof(double) * 2 * ZF_SPMV_RESID_MAX_CHUNKS));
+    ZF_RM(hipMalloc(&out, sizeof(double) * 2));
+    if (rc == ZF_OK) {
+        const double* src[3] = {s_plus_host, s_k_host, s_km1_host};
+        for (int k = 0; k < 3; ++k) ZF_RM(hipMemcpyAsync(sv + k * m_pad, src[k], sizeof(double) * m, hipMemcpyHostToDevice, nullptr));
+        ZF_RM(hipMemsetAsync(b, 0, sizeof(double) * m_pad, nullptr));   // (f(x+) of the same kernels is not asked for here)
+        const zf_ring3 sr = {{sv, sv + m_pad, sv + 2 * m_pad}};
+        if (wide)
+            zf_launch_spmv_resid_x_rem(nullptr, nullptr, sr.p[0], sr.p[1], sr.p[2], -1, b, scale, m, nesterov ? 1 : 0, beta, part,
+                                       part + ZF_SPMV_RESID_MAX_CHUNKS, out + 0, out + 1);
+        else
+            hipLaunchKernelGGL(zf_resid_x_rem_kernel, dim3(1), dim3(RESID_BLOCK), 0, nullptr, nullptr, sr, -1, b, scale, m, out + 0,
+                               nesterov ? 1 : 0, beta, out + 1);
+        ZF_RM(hipGetLastError());
+        ZF_RM(hipMemcpyAsync(r_out, out + 1, sizeof(double), hipMemcpyDeviceToHost, nullptr));
+        ZF_RM(hipStreamSynchronize(nullptr));
+    }
+#undef ZF_RM
+    for (void* p : {(void*)sv, (void*)b, (void*)part, (void*)out})
+        if (p) (void)hipFree(p);
+    return rc;
 }
 
 // ---------------------------------------------------------------------------

@@ -59,3 +59,10 @@ void zf_launch_spmv_resid_y(hipStream_t st, const zf_control* ctl, const double*
                             double* r, double scale, int64_t m, int nesterov, double* part, double* f_out);
 void zf_launch_spmv_resid_x(hipStream_t st, const zf_control* ctl, const double* s0, const double* s1, const double* s2, int slot,
                             const double* b, double scale, int64_t m, double* part, double* f_out);
+// ZF_ACCEPT_REMAINDER: f(x+) exactly as zf_launch_spmv_resid_x leaves it, and beside it R = scale sum (s+ - s_y)^2 with
+// s_y = s_k + beta (s_k - s_{k-1}) (zf_resid_x_rem_kernel, zf_kernels_gemv.h), chunk by chunk in the same order; still two
+// launches.  part, part_r: zf_spmv_resid_chunks(m) doubles each.  slot < 0: a plain call outside the loop (ctl unused) on
+// s+ = s0, s_k = s1, s_{k-1} = s2 with beta = beta_plain.
+void zf_launch_spmv_resid_x_rem(hipStream_t st, const zf_control* ctl, const double* s0, const double* s1, const double* s2, int slot,
+                                const double* b, double scale, int64_t m, int nesterov, double beta_plain, double* part, double* part_r,
+                                double* f_out, double* r_out);

@@ -107,6 +107,77 @@ void zf_launch_spmv_resid_x(hipStream_t st, const zf_control* ctl, const double*
     hipLaunchKernelGGL(zf_spmv_resid_finish_kernel, dim3(1), dim3(ZF_BLOCK), 0, st, ctl, 0, part, chunks, scale, f_out);
 }
 
+// ZF_ACCEPT_REMAINDER (zf_spmv.h): zf_spmv_resid_kernel<1>'s chunk sums of (s+ - b)^2 and, beside them, those of (s+ - s_y)^2
+__global__ __launch_bounds__(ZF_BLOCK) void zf_spmv_resid_rem_kernel(const zf_control* ctl, const double* s0, const double* s1, const double* s2,
+                                                                     int slot, const double* __restrict__ b, int64_t m, int nesterov,
+                                                                     double beta_plain, double* __restrict__ part, double* __restrict__ part_r) {
+    __shared__ double lds[ZF_WAVES];
+    __shared__ double lds_r[ZF_WAVES];
+    const double* sr[3] = {s0, s1, s2};
+    int ip = 0, ik = 1, io = 2;
+    double beta = nesterov ? beta_plain : 0.0;
+    if (slot >= 0) {
+        if (ctl->status != ZF_RUNNING) return;
+        const int cur = ctl->cur;
+        ip = (cur + slot) % 3;
+        ik = cur;
+        io = (cur + 2) % 3;
+        beta = nesterov ? ctl->beta_next : 0.0;
+    }
+    const double* __restrict__ sv = ip == 0 ? sr[0] : ip == 1 ? sr[1] : sr[2];
+    const double* __restrict__ sk = ik == 0 ? sr[0] : ik == 1 ? sr[1] : sr[2];
+    const double* __restrict__ so = io == 0 ? sr[0] : io == 1 ? sr[1] : sr[2];
+    const int64_t per = (m + gridDim.x - 1) / gridDim.x;
+    const int64_t lo = (int64_t)blockIdx.x * per, hi = lo + per < m ? lo + per : m;
+    double acc = 0.0, acc_r = 0.0;
+    for (int64_t i = lo + threadIdx.x; i < hi; i += ZF_BLOCK) {
+        const double sp = sv[i];
+        const double rv = sp - b[i];
+        acc += rv * rv;
+        double ay = sk[i];
+        if (nesterov) ay = ay + beta * (ay - so[i]);
+        const double dv = sp - ay;
+        acc_r += dv * dv;
+    }
+    const double t = zf_spmv_block_sum(acc, lds);
+    const double tr = zf_spmv_block_sum(acc_r, lds_r);
+    if (threadIdx.x == 0) {
+        part[blockIdx.x] = t;
+        part_r[blockIdx.x] = tr;
+    }
+}
+
+// both chunk sums in zf_spmv_resid_finish_kernel's order: f = scale * sqrt(sum part)^2, R = scale * sum part_r
+__global__ __launch_bounds__(ZF_BLOCK) void zf_spmv_resid_rem_finish_kernel(const zf_control* ctl, const double* __restrict__ part,
+                                                                            const double* __restrict__ part_r, int count, double scale,
+                                                                            double* f_out, double* r_out) {
+    __shared__ double lds[ZF_WAVES];
+    __shared__ double lds_r[ZF_WAVES];
+    if (ctl && ctl->status != ZF_RUNNING) return;
+    double acc = 0.0, acc_r = 0.0;
+    for (int i = threadIdx.x; i < count; i += ZF_BLOCK) {
+        acc += part[i];
+        acc_r += part_r[i];
+    }
+    const double t = zf_spmv_block_sum(acc, lds);
+    const double tr = zf_spmv_block_sum(acc_r, lds_r);
+    if (threadIdx.x == 0) {
+        const double nrm = sqrt(t);
+        *f_out = scale * (nrm * nrm);
+        *r_out = scale * tr;
+    }
+}
+
+void zf_launch_spmv_resid_x_rem(hipStream_t st, const zf_control* ctl, const double* s0, const double* s1, const double* s2, int slot,
+                                const double* b, double scale, int64_t m, int nesterov, double beta_plain, double* part, double* part_r,
+                                double* f_out, double* r_out) {
+    const int chunks = zf_spmv_resid_chunks(m);
+    hipLaunchKernelGGL(zf_spmv_resid_rem_kernel, dim3(chunks), dim3(ZF_BLOCK), 0, st, ctl, s0, s1, s2, slot, b, m, nesterov, beta_plain, part,
+                       part_r);
+    hipLaunchKernelGGL(zf_spmv_resid_rem_finish_kernel, dim3(1), dim3(ZF_BLOCK), 0, st, slot >= 0 ? ctl : nullptr, part, part_r, chunks, scale,
+                       f_out, r_out);
+}
+
 // ---- the matrix handle ---------------------------------------------------------------------------------------------
 static int zf_spmat_free(zf_spmat* h) {
     for (int k = 0; k < h->n_owned; ++k)

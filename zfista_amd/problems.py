@@ -194,6 +194,7 @@ class LeastSquaresL1(_DenseMarginsL1):
 
     kind = _lib.ZF_PROBLEM_LEAST_SQUARES_L1
     _eval_name = "zf_ls_eval"
+    taylor_remainder = True   # acceptance="remainder": R = scale |A (x+ - y)|^2 from the residual kernels at x+
 
     def __init__(self, A, b, lam, scale=0.5, bounds=None, group=None, shard="columns"):
         """With ``group`` set and ``shard="columns"`` (default), ``A`` is this rank's column block A_p
@@ -315,6 +316,7 @@ class SparseLeastSquaresL1(_SparseMarginsL1):
 
     kind = _lib.ZF_PROBLEM_SPARSE_LS_L1
     _eval_name = "zf_spmat_eval"
+    taylor_remainder = True   # acceptance="remainder": R = scale |A (x+ - y)|^2 from the residual kernels at x+
 
     def __init__(self, A, b, lam, scale=0.5, bounds=None):
         self._set(A, b, lam, scale, bounds)

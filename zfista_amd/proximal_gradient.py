@@ -113,7 +113,7 @@ def minimize_proximal_gradient(
     sub_iters : {1, 2, 4, 8, 16}, separable single-objective problems only: iterations chained per
         pass over the data (temporal blocking).  Results do not depend on it.  Default 16 (8 with
         ``return_all``).
-    acceptance : {"reference", "resolved"}.  "reference" (default) evaluates the sufficient-decrease test as
+    acceptance : {"reference", "resolved", "remainder"}.  "reference" (default) evaluates the sufficient-decrease test as
         zfista/proximal_gradient.py:303 writes it, ``F(x+) - F(x_k) <= fun + tol_internal`` - two differences of
         O(|F|) numbers, below double-precision resolution once ``|x+ - y|^2 << ulp(F)``: at n = 1e8 trials are then
         rejected by rounding noise (and a long solve ends in "Backtracking failed") exactly as the reference's would.
@@ -121,8 +121,17 @@ def minimize_proximal_gradient(
         inequality with F(x_k) and g(x+) cancelled and ``f(x+) - f(y)`` accumulated element by element:
         ``[f(x+) - f(y)] - <grad f(y), x+ - y> - |x+ - y|^2 / 2 / lr <= tol_internal``.  Where the reference's
         evaluation resolves the test both take the same decisions; iterates of accepted trials are the same
-        arithmetic.  The result says which one ran (field ``acceptance``).  Only when the keyword is not given,
-        ZF_ACCEPT in the environment may override the default.
+        arithmetic.
+        "remainder" (``LeastSquaresL1`` and ``SparseLeastSquaresL1``; other problems raise) moves the dot product to the
+        left as well.  The Taylor remainder ``R = f(x+) - f(y) - <grad f(y), x+ - y>`` of the squared loss is exactly
+        ``scale |A (x+ - y)|^2``, a sum of squares over the margins already in HBM, so nothing cancels:
+        ``R - |x+ - y|^2 / 2 / lr <= tol_internal`` (``deprecated=True``: ``R <= g(x+) + |x+ - y|^2 / 2 / lr +
+        tol_internal``), every term non-negative and of the size of the step.  f(x+) is computed and reported as under
+        "reference": where both modes decide alike, iterates and traces are bit-identical; where the reference's test has
+        drowned in rounding (``tol <= 1e-8`` on problems with F ~ 1e7 and beyond: "Backtracking failed", or a success
+        flag after a collapse of the step size), this one keeps deciding.
+        The result says which one ran (field ``acceptance``).  Only when the keyword is not given, ZF_ACCEPT in the
+        environment may override the default (and falls back to "reference" where the problem has no such mode).
     """
     if deprecated:
         warn(_MSG_DEPRECATED, stacklevel=2)
@@ -142,8 +151,8 @@ def minimize_proximal_gradient(
         acceptance = os.environ.get("ZF_ACCEPT")
         accept_from_env = acceptance is not None
         acceptance = acceptance or "reference"
-    if acceptance not in ("reference", "resolved"):
-        raise ValueError(f"acceptance must be 'reference' or 'resolved', got {acceptance!r}")
+    if acceptance not in ("reference", "resolved", "remainder"):
+        raise ValueError(f"acceptance must be 'reference' or 'resolved' (or 'remainder', for the least-squares classes), got {acceptance!r}")
     opts = dict(
         dual_solver=dual_solver, sub_iters=int(sub_iters or 0), acceptance=acceptance,
         lr=lr, tol=tol, tol_internal=tol_internal, max_iter=max_iter,
@@ -162,6 +171,13 @@ def minimize_proximal_gradient(
         else:
             raise ValueError("acceptance='resolved' needs a separable native problem (zfista_amd.problems.DiagQuadL1): the "
                              "element-wise difference f(x+) - f(y) is formed inside its fused kernels")
+    if acceptance == "remainder" and not (native is not None and getattr(native, "taylor_remainder", False)):
+        if accept_from_env:
+            opts["acceptance"] = acceptance = "reference"   # (as above: the reference's test runs)
+        else:
+            raise ValueError("acceptance='remainder' needs a native least-squares problem (zfista_amd.problems.LeastSquaresL1 or "
+                             "zfista_amd.problems.SparseLeastSquaresL1): the Taylor remainder scale |A (x+ - y)|^2 is formed by "
+                             "their residual kernels")
     if native is not None:
         res, status = _solve_native(native, x0, opts)
     elif _is_device_tensor(x0) and native_multi is None:
@@ -202,7 +218,7 @@ class NativeRun:
             decay_rate=float(opts["decay_rate"]), max_iter=int(opts["max_iter"]),
             max_backtrack_iter=int(opts["max_backtrack_iter"]),
             nesterov=int(bool(opts["nesterov"])), deprecated=int(bool(opts["deprecated"])),
-            accept_mode=(_lib.ZF_ACCEPT_RESOLVED if opts.get("acceptance") == "resolved" else _lib.ZF_ACCEPT_REFERENCE),
+            accept_mode=_lib.ACCEPT_MODES[opts.get("acceptance") or "reference"],
             # return_all records every iterate into a ring in HBM as the trial computes it
             # (zf_solver_set_history): recording kernels exist for chains of 8 and of 1
             sub_iters=(int(opts.get("sub_iters", 0) or 0) if not opts.get("return_all")
@@ -313,12 +329,22 @@ class NativeRun:
     def from_snapshot(cls, problem, state, opts, timing=False):
         """Continue a solve from ``snapshot()`` (possibly in another process, with another
         max_iter or chain length).  The continuation is bit-identical to the uninterrupted solve.
+        The acceptance test a resumed solve runs is the resuming caller's (``opts["acceptance"]``), not the snapshot's:
+        resuming under another one is allowed - that is how a solve the reference's test has stalled is continued under
+        "remainder" - and warned about, since the continuation then is not the uninterrupted solve's.
         ``return_all`` is refused: the iterates before the snapshot are not part of it, and a history
         whose first ``nit`` entries are uninitialised memory is worse than none."""
         if opts.get("return_all"):
             raise ValueError("return_all is not available for a solve resumed from a snapshot (the iterates before "
                              "the snapshot are not part of the saved state)")
         run = cls(problem, np.asarray(state["x"]), opts, timing=timing, _snapshot=state)
+        saved_ctl = _lib.Control.from_buffer_copy(np.asarray(state["control"], dtype=np.uint8).tobytes())
+        mode_now = _lib.ACCEPT_MODES[opts.get("acceptance") or "reference"]
+        if int(saved_ctl.accept_mode) != mode_now:
+            names = {v: k for k, v in _lib.ACCEPT_MODES.items()}
+            warn(f"the snapshot was taken under acceptance={names.get(int(saved_ctl.accept_mode), saved_ctl.accept_mode)!r}, this "
+                 f"solve resumes under acceptance={names[mode_now]!r}: the same iterates as long as both tests decide alike, "
+                 "another line search from the first trial on which they differ", stacklevel=2)
         saved = int(np.asarray(state["tiles_per_wg"])) if "tiles_per_wg" in state else 0
         now = int(getattr(run.solver, "tiles_per_wg", 0) or 0)
         if saved and now and saved != now:
