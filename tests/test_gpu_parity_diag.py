@@ -96,6 +96,7 @@ def test_diag_vs_oracle_ragged_sizes(n, nesterov):
 
 
 def test_diag_box_and_deprecated():
+    from diag_tile_cases import BoxRef
     from oracle import cpu_ref, problems_ref as P
     from zfista_amd import minimize_proximal_gradient
     from zfista_amd.problems import DiagQuadL1
@@ -103,17 +104,7 @@ def test_diag_box_and_deprecated():
     n = 5001
     d, c, lam = P.make_pdiag(n, seed=3)
     lo, hi = -0.25, 0.4
-
-    class BoxRef(P.DiagQuadL1Ref):
-        def g(self, x):
-            if (x < lo).any() or (x > hi).any():
-                return np.inf
-            return super().g(x)
-
-        def prox_wsum_g(self, w, x):
-            return P.clip_box(super().prox_wsum_g(w, x), lo, hi)
-
-    ref = BoxRef(d, c, lam)
+    ref = BoxRef(d, c, lam, lo, hi)
     prob = DiagQuadL1(d, c, lam, bounds=(lo, hi))
     x0 = np.zeros(n)
     for kw in (dict(nesterov=True), dict(nesterov=True, deprecated=True), dict(decay_rate=1, lr=0.3)):
