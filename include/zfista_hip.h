@@ -508,6 +508,32 @@ int zf_spmat_logistic_eval(const zf_spmat* h, const double* b_dev, double scale,
  * steps, poll, restore, history - is the solver's as for every kind. */
 int zf_solver_create_sparse(zf_solver** out, const zf_problem_desc* desc, const zf_spmat* h, const zf_options* opt, void* stream);
 
+/* ---- duality gap of the margins kinds (csrc/zf_kernels_gap.h) -----------------------------------------------------------
+ * P(x) = sum_i phi_i((A x)_i) + lam |x|_1 with phi_i(z) = scale (z - b_i)^2 (logistic = 0) or scale softplus(-b_i z)
+ * (logistic != 0; b_i = +-1).  Dual point nu = alpha grad phi(A x), alpha = min(1, lam / |g|_inf) (1 when g = 0), g = grad f(x)
+ * = A^T grad phi(A x): |A^T nu|_inf <= lam, D = -sum_i phi_i^*(nu_i) <= min P.  The reference has no such certificate; its
+ * stopping test |x+ - y|_inf < tol measures the step.
+ * out (count >= 8 doubles) = [P, D, gap, alpha, |g|_inf, f(x), lam |x|_1, rows gap].  `gap` is NOT P - D (a difference of two
+ * numbers of the size of F) but the sum of the two Fenchel-Young gaps, every term >= 0:
+ *   rows     least squares scale (1 - alpha)^2 |A x - b|^2;  logistic scale sum_i KL(alpha q_i || q_i), q_i = sigma(-b_i (A x)_i)
+ *   columns  sum_j (lam |x_j| + alpha g_j x_j), term by term
+ * with 1 - alpha = max(0, (|g|_inf - lam) / |g|_inf).  Finite for every finite margin; alpha = 1 gives a rows gap of exactly 0;
+ * a NaN or +-inf in x or g gives a NaN gap.  No atomics, every sum in an order fixed by m or n alone.  scale > 0, lam >= 0.
+ * zf_gap_eval: dense row-major A (dev, 16-byte aligned) at a host vector x, on the sweeps a solver of that shape runs;
+ * zf_spmat_gap_eval: the same over a matrix handle. */
+int zf_gap_eval(const double* A_dev, const double* b_dev, int64_t m_rows, int64_t n, double scale, double lam, int32_t logistic,
+                const double* x_host, double* out, int64_t count /* >= 8 */);
+int zf_spmat_gap_eval(const zf_spmat* h, const double* b_dev, double scale, double lam, int32_t logistic, const double* x_host,
+                      double* out, int64_t count /* >= 8 */);
+/* The same eight values at the current x_k of a live solver of kind 2, 4, 5 or 6, on the solver's stream (synchronises it).
+ * The margins A x_k are the solver's own (its margin ring: no sweep over A); one sweep over A^T forms g.  The workspace (one
+ * m-vector, one n-vector, chunk results) is allocated by the first call: a solve that never asks launches and allocates
+ * nothing more than before.  r, the gradient, the trial's scalars and the control block are not touched - the call may come
+ * at any point between two zf_solver_enqueue_steps, also between a rejected trial and its retry, and the solve continues bit
+ * for bit.  ZF_ERR_ARG: count < 8, another problem kind, world > 1, a finite box (the dual of the boxed problem is another
+ * one).  ZF_ERR_STATE: not initialised. */
+int zf_solver_duality_gap(zf_solver* s, double* out, int64_t count /* >= 8 */);
+
 /* ---- multi-objective trial (m >= 2), device side ---------------------------
  * The dual of the scalarised subproblem is minimised on the host by SciPy exactly
  * as the reference does (proximal_gradient.py:179-205); every O(n) expression runs

@@ -216,6 +216,9 @@ SIGNATURES = {
                                   _P, _P, _P, C.POINTER(SpmvPlan), C.c_int64]),
     "zf_spmat_destroy": (C.c_int, [_P]),
     "zf_spmat_eval": (C.c_int, [_P, _P, C.c_double, _P, C.POINTER(C.c_double), _P]),
+    "zf_gap_eval": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_int32, _P, _P, C.c_int64]),
+    "zf_spmat_gap_eval": (C.c_int, [_P, _P, C.c_double, C.c_double, C.c_int32, _P, _P, C.c_int64]),
+    "zf_solver_duality_gap": (C.c_int, [_P, _P, C.c_int64]),
     "zf_solver_create_sparse": (C.c_int, [C.POINTER(_P), C.POINTER(ProblemDesc), _P, C.POINTER(Options), _P]),
 }
 

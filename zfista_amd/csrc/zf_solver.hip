@@ -21,6 +21,7 @@
 #include "zf_kernels_op.h"
 #include "zf_spmv.h"
 #include "zf_kernels_loss.h"
+#include "zf_kernels_gap.h"
 #include "zf_kernels_step.h"
 #include "zf_trial_launch.h"
 
@@ -289,6 +290,9 @@ struct zf_solver {
     // streaming return_all: caller-owned ring of iterates in HBM (zf_solver_set_history)
     double* hist = nullptr;
     int64_t hist_cap = 0, hist_stride = 0;
+    // zf_solver_duality_gap: its workspace (one m-vector, one n-vector, chunk results, scalars), allocated by the first call -
+    // a solve that never asks for the gap allocates and launches nothing for it
+    zf_gap_ws gap = {nullptr, nullptr, nullptr, nullptr};
 };
 constexpr int ZF_PASS_LOG = 4096;
 constexpr size_t ZF_CTL_SLOT = (sizeof(zf_control) + 255) / 256 * 256;   // bytes in front of the trace ring (zf_solver::ctl_trace)
@@ -337,7 +341,7 @@ static int zf_solver_free_all(zf_solver* s) {
     void* ptrs[] = {s->sp_part_A, s->sp_part_At, s->op_buf, s->row_part, s->ls_cnt, s->blk_part, s->slice_part, s->fin_cnt, s->grp_part, s->xbuf, s->partials, s->ctl_trace, s->beta_ring,
                     s->ra_word, s->ra_flags, s->blk_part2, s->grp_part2, s->fin_cnt2, s->pack2,
                     s->own_packs ? s->pack_local : nullptr, s->own_packs ? s->pack_all : nullptr,
-                    s->grad, s->sbuf, s->resid, s->slab, s->ls_scal,
+                    s->grad, s->sbuf, s->resid, s->slab, s->ls_scal, s->gap.rvec, s->gap.g, s->gap.part, s->gap.scal,
                     s->own_svec ? s->s_part : nullptr, s->own_svec ? s->s_all : nullptr};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
@@ -2588,3 +2592,163 @@ extern "C" int zf_op_eval(const double* taps_dev, int32_t k, const double* b_dev
         if (p) (void)hipFree(p);
     return rc;
 }
+
+// ---------------------------------------------------------------------------
+// duality gap (zf_kernels_gap.h): standalone at a host point, and at x_k of a live solver
+// ---------------------------------------------------------------------------
+// g = factor * A^T rvec for a dense row-major A: the column sweep a solver of this shape runs (MFMA when n % 32 == 0 and
+// ZF_GEMV_MFMA is not 0, else the VALU sweep) and the slice combine, outside the loop (ctl = NULL)
+static void zf_gap_dense_sweep(hipStream_t st, const double* A, const double* rvec, double* slab, double* g, int64_t m, int64_t n,
+                               int slices, int64_t rows_per_slice, bool mfma, double factor) {
+    const int V = (n % 2 == 0) ? 2 : 1;
+    const int64_t nv = n / V;
+    if (mfma) {
+        dim3 gM((unsigned)((n + GEMVT_MFMA_COLS - 1) / GEMVT_MFMA_COLS), (unsigned)slices);
+        hipLaunchKernelGGL(zf_gemvT_partial_mfma_kernel, gM, dim3(ZF_BLOCK), 0, st, nullptr, A, rvec, slab, m, n, rows_per_slice);
+    } else {
+        dim3 gT((unsigned)((nv + ZF_BLOCK - 1) / ZF_BLOCK), (unsigned)slices);
+        if (V == 2) hipLaunchKernelGGL(zf_gemvT_partial_kernel<2>, gT, dim3(ZF_BLOCK), 0, st, nullptr, A, rvec, slab, m, n, rows_per_slice);
+        else hipLaunchKernelGGL(zf_gemvT_partial_kernel<1>, gT, dim3(ZF_BLOCK), 0, st, nullptr, A, rvec, slab, m, n, rows_per_slice);
+    }
+    hipLaunchKernelGGL(zf_gemvT_combine_kernel, dim3(zf_grid_for(n)), dim3(ZF_BLOCK), 0, st, nullptr, slab, g, factor, n, slices);
+}
+
+#define ZF_GAP_TRY(expr)                                                          \
+    do {                                                                          \
+        hipError_t _e = (expr);                                                   \
+        if (_e != hipSuccess && rc == ZF_OK)                                      \
+            rc = zf_fail(ZF_ERR_HIP, "%s: %s", #expr, hipGetErrorString(_e));     \
+    } while (0)
+
+static int zf_gap_ws_alloc(zf_gap_ws* ws, int64_t m, int64_t n) {
+    int rc = ZF_OK;
+    ZF_GAP_TRY(hipMalloc(&ws->rvec, sizeof(double) * m));
+    ZF_GAP_TRY(hipMalloc(&ws->g, sizeof(double) * n));
+    ZF_GAP_TRY(hipMalloc(&ws->part, sizeof(double) * ZF_GAP_PART));
+    ZF_GAP_TRY(hipMalloc(&ws->scal, sizeof(double) * ZF_GAP_SCAL));
+    return rc;
+}
+static void zf_gap_ws_free(zf_gap_ws* ws) {
+    for (void* p : {(void*)ws->rvec, (void*)ws->g, (void*)ws->part, (void*)ws->scal})
+        if (p) (void)hipFree(p);
+    *ws = zf_gap_ws{nullptr, nullptr, nullptr, nullptr};
+}
+
+// dense (h == NULL) or CSR matrix; x from the host
+static int zf_gap_eval_impl(const double* A_dev, const zf_spmat* h, const double* b_dev, int64_t m, int64_t n, double scale, double lam,
+                            bool logistic, const double* x_host, double* out) {
+    zf_gap_ws ws = {nullptr, nullptr, nullptr, nullptr};
+    double *x = nullptr, *z = nullptr, *slab = nullptr, *part_A = nullptr, *part_At = nullptr;
+    int64_t slices = 1, rps = m;
+    int rc = zf_gap_ws_alloc(&ws, m, n);
+    ZF_GAP_TRY(hipMalloc(&x, sizeof(double) * (n + 2)));
+    ZF_GAP_TRY(hipMalloc(&z, sizeof(double) * (m + 2)));
+    if (h) {
+        if (h->A.nseg > 0) ZF_GAP_TRY(hipMalloc(&part_A, sizeof(double) * h->A.nseg));
+        if (h->At.nseg > 0) ZF_GAP_TRY(hipMalloc(&part_At, sizeof(double) * h->At.nseg));
+    } else {   // the slices of zf_solver_create
+        const int V = (n % 2 == 0) ? 2 : 1;
+        const int64_t panels = (n / V + ZF_BLOCK - 1) / ZF_BLOCK;
+        slices = (ZF_MAX_GRID + panels - 1) / panels;
+        if (slices > (m + 7) / 8) slices = (m + 7) / 8;
+        if (slices < 1) slices = 1;
+        if (slices > 64) slices = 64;
+        rps = (m + slices - 1) / slices;
+        slices = (m + rps - 1) / rps;
+        ZF_GAP_TRY(hipMalloc(&slab, sizeof(double) * slices * n));
+    }
+    if (rc == ZF_OK) {
+        const double gfac = logistic ? scale : 2 * scale;
+        ZF_GAP_TRY(hipMemcpyAsync(x, x_host, sizeof(double) * n, hipMemcpyHostToDevice, nullptr));
+        if (h) {
+            const zf_spmv_io aio = {{x, x, x}, {z, z, z}};
+            zf_launch_spmv(h->A, nullptr, nullptr, false, aio, -1, 1.0, part_A);
+        } else {
+            zf_ring3 xr = {{x, x, x}}, sr = {{z, z, z}};
+            int gr = (int)((m + GEMV_ROWS - 1) / GEMV_ROWS);
+            if (gr > 8 * ZF_MAX_GRID) gr = 8 * ZF_MAX_GRID;
+            if (n % 2 == 0) hipLaunchKernelGGL(zf_gemv_rows_kernel<2>, dim3(gr), dim3(ZF_BLOCK), 0, nullptr, nullptr, A_dev, xr, sr, -1, m, n);
+            else hipLaunchKernelGGL(zf_gemv_rows_kernel<1>, dim3(gr), dim3(ZF_BLOCK), 0, nullptr, nullptr, A_dev, xr, sr, -1, m, n);
+        }
+        zf_launch_gap_rows(nullptr, logistic, z, b_dev, m, scale, ws);
+        if (h) {
+            const zf_spmv_io gio = {{ws.rvec, ws.rvec, ws.rvec}, {ws.g, ws.g, ws.g}};
+            zf_launch_spmv(h->At, nullptr, nullptr, false, gio, -1, gfac, part_At);
+        } else {
+            zf_gap_dense_sweep(nullptr, A_dev, ws.rvec, slab, ws.g, m, n, (int)slices, rps, n % 32 == 0 && zf_env_read().gemv_mfma, gfac);
+        }
+        zf_launch_gap_tail(nullptr, logistic, z, b_dev, x, m, n, scale, lam, ws);
+        ZF_GAP_TRY(hipGetLastError());
+        ZF_GAP_TRY(hipMemcpyAsync(out, ws.scal + ZF_GS_OUT, sizeof(double) * 8, hipMemcpyDeviceToHost, nullptr));
+        ZF_GAP_TRY(hipStreamSynchronize(nullptr));
+    }
+    zf_gap_ws_free(&ws);
+    for (void* p : {(void*)x, (void*)z, (void*)slab, (void*)part_A, (void*)part_At})
+        if (p) (void)hipFree(p);
+    return rc;
+}
+
+extern "C" int zf_gap_eval(const double* A_dev, const double* b_dev, int64_t m_rows, int64_t n, double scale, double lam,
+                           int32_t logistic, const double* x_host, double* out, int64_t count) {
+    ZF_REQUIRE(A_dev && b_dev && x_host && out && m_rows >= 1 && n >= 1, "zf_gap_eval: bad argument");
+    ZF_REQUIRE(count >= 8, "zf_gap_eval: the output buffer holds fewer than 8 doubles");
+    ZF_REQUIRE(scale > 0.0 && lam >= 0.0, "zf_gap_eval: needs scale > 0 and lam >= 0");
+    ZF_REQUIRE(zf_aligned16(A_dev), "zf_gap_eval: A must be 16-byte aligned");
+    return zf_gap_eval_impl(A_dev, nullptr, b_dev, m_rows, n, scale, lam, logistic != 0, x_host, out);
+}
+
+extern "C" int zf_spmat_gap_eval(const zf_spmat* h, const double* b_dev, double scale, double lam, int32_t logistic,
+                                 const double* x_host, double* out, int64_t count) {
+    ZF_REQUIRE(h && b_dev && x_host && out, "zf_spmat_gap_eval: null argument");
+    ZF_REQUIRE(count >= 8, "zf_spmat_gap_eval: the output buffer holds fewer than 8 doubles");
+    ZF_REQUIRE(scale > 0.0 && lam >= 0.0, "zf_spmat_gap_eval: needs scale > 0 and lam >= 0");
+    return zf_gap_eval_impl(nullptr, h, b_dev, h->m, h->n, scale, lam, logistic != 0, x_host, out);
+}
+
+// The gap at x_k of a live solver, on its stream: the margins A x_k are the ring's (no sweep over A), the dual candidate goes
+// to the call's own m-vector, g = grad f(x_k) through the solver's column sweep to its own n-vector.  Reads the iterate and
+// margin rings, A, b; writes only its workspace (and the scratch of a sweep - the slab, the segment sums of split rows -
+// which holds nothing between two launches of a sweep): r, the gradient, ls_scal and the control block stay as they are,
+// so a solve interrupted here - also between a rejected trial and its retry - continues bit for bit.
+extern "C" int zf_solver_duality_gap(zf_solver* s, double* out, int64_t count) {
+    ZF_REQUIRE(s && out, "zf_solver_duality_gap: null argument");
+    ZF_REQUIRE(count >= 8, "zf_solver_duality_gap: the output buffer holds fewer than 8 doubles");
+    const zf_problem_desc& d = s->desc;
+    ZF_REQUIRE(zf_is_dense_mat(d.kind) || zf_is_sparse_mat(d.kind),
+               "zf_solver_duality_gap: only for ZF_PROBLEM_LEAST_SQUARES_L1, ZF_PROBLEM_SPARSE_LS_L1, ZF_PROBLEM_LOGISTIC_L1 and "
+               "ZF_PROBLEM_SPARSE_LOGISTIC_L1 (the dual of the other kinds is not built)");
+    ZF_REQUIRE(d.world == 1, "zf_solver_duality_gap: not for a sharded solve (world > 1): the dual point needs the whole A^T grad phi");
+    ZF_REQUIRE(!s->box, "zf_solver_duality_gap: not with a finite box (the dual of the boxed problem is another one)");
+    ZF_REQUIRE(d.scale > 0.0, "zf_solver_duality_gap: needs scale > 0");
+    if (!s->initialised) return zf_fail(ZF_ERR_STATE, "zf_solver_duality_gap: solver not initialised%s%s");
+    const int64_t m = d.m_rows, n = d.n;
+    if (!s->gap.scal) {
+        int rc = zf_gap_ws_alloc(&s->gap, m, n);
+        if (rc) {
+            zf_gap_ws_free(&s->gap);
+            return rc;
+        }
+    }
+    zf_control c;
+    ZF_HIP(hipMemcpyAsync(&c, s->ctl, sizeof(c), hipMemcpyDeviceToHost, s->stream));
+    ZF_HIP(hipStreamSynchronize(s->stream));
+    if (c.lag != 0 || c.cur < 0 || c.cur > 2) return zf_fail(ZF_ERR_STATE, "zf_solver_duality_gap: the iterate ring does not hold x_k%s%s");
+    const bool logistic = zf_is_logistic(d.kind);
+    const double gfac = logistic ? d.scale : 2 * d.scale;
+    const double* x = s->xb[c.cur];
+    const double* z = s->sring.p[c.cur];   // A x_k: every path of these kinds keeps it there (the fused small-matrix path too)
+    const zf_gap_ws& ws = s->gap;
+    zf_launch_gap_rows(s->stream, logistic, z, d.b, m, d.scale, ws);
+    if (zf_is_sparse_mat(d.kind)) {
+        const zf_spmv_io gio = {{ws.rvec, ws.rvec, ws.rvec}, {ws.g, ws.g, ws.g}};
+        zf_launch_spmv(s->spmat->At, s->stream, nullptr, false, gio, -1, gfac, s->sp_part_At);
+    } else {
+        zf_gap_dense_sweep(s->stream, d.A, ws.rvec, s->slab, ws.g, m, n, s->slices, s->rows_per_slice, s->gemv_mfma, gfac);
+    }
+    zf_launch_gap_tail(s->stream, logistic, z, d.b, x, m, n, d.scale, d.lam, ws);
+    ZF_HIP(hipGetLastError());
+    ZF_HIP(hipMemcpyAsync(out, ws.scal + ZF_GS_OUT, sizeof(double) * 8, hipMemcpyDeviceToHost, s->stream));
+    ZF_HIP(hipStreamSynchronize(s->stream));
+    return ZF_OK;
+}
+#undef ZF_GAP_TRY

@@ -257,6 +257,13 @@ class DeviceSolver:
         _lib.check(self.lib.zf_solver_get_x(self.handle, C.c_void_p(_lib.ptr(out)), out.size), "get_x")
         return out
 
+    def duality_gap(self) -> np.ndarray:
+        """[P, D, gap, alpha, |grad f|_inf, f, lam |x|_1, rows gap] at the current x_k (zf_solver_duality_gap: synchronises
+        the stream; the solve is not altered)."""
+        out = np.zeros(8)
+        _lib.check(self.lib.zf_solver_duality_gap(self.handle, C.c_void_p(_lib.ptr(out)), out.size), "zf_solver_duality_gap")
+        return out
+
     def x_dev_ptr(self) -> int:
         p = C.c_void_p()
         _lib.check(self.lib.zf_solver_x_dev(self.handle, C.byref(p)))

@@ -1,0 +1,32 @@
+"""Regularisation paths of the l1 problems: one device-resident matrix, a sequence of l1 weights.
+
+A new ``lam`` used to mean a new problem object and a new upload of A.  ``problem.with_lam(lam)`` is a sibling that shares
+the device matrix, b and (sparse classes) the matrix handle; ``l1_path`` solves such siblings in order, each warm-started
+from the solution before it and stopped on its duality gap - the usual way of solving a LASSO / sparse logistic regression
+for a grid of weights from ``problem.lam_max()`` downward (at ``lam_max`` and above the solution is x = 0).
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from .proximal_gradient import minimize_proximal_gradient
+
+
+def l1_path(problem, lams, x0=None, gap_tol=1e-6, **solver_kwargs):
+    """Solve ``problem.with_lam(l)`` for each ``l`` of ``lams`` in the order given, each from the solution of the one
+    before (the first from ``x0``; default zeros), with ``minimize_proximal_gradient(..., gap_tol=gap_tol, **solver_kwargs)``.
+
+    ``problem``: a ``LeastSquaresL1``, ``SparseLeastSquaresL1``, ``LogisticL1`` or ``SparseLogisticL1`` without bounds or a
+    process group; ``gap_tol``: the absolute duality gap every point is solved to (None: the solver's own ``tol`` only).
+    Returns the list of results, one per ``l``, each with an extra field ``lam``."""
+    if not getattr(problem, "has_duality_gap", False):
+        raise ValueError("l1_path needs a LeastSquaresL1, SparseLeastSquaresL1, LogisticL1 or SparseLogisticL1")
+    x = np.zeros(problem.n_features) if x0 is None else x0
+    out = []
+    for lam in lams:
+        sib = problem.with_lam(lam)
+        res = minimize_proximal_gradient(*sib.callbacks(), x, gap_tol=gap_tol, **solver_kwargs)
+        res["lam"] = float(lam)
+        out.append(res)
+        x = res.x
+    return out

@@ -135,7 +135,67 @@ class DiagQuadL1(NativeProblem):
         return fields, (self.d, self.c)
 
 
-class _DenseMarginsL1(NativeProblem):
+class DualityGap:
+    """What ``problem.duality_gap(x)`` / ``NativeRun.duality_gap()`` return: ``primal`` = P(x) = f(x) + lam |x|_1, ``dual`` =
+    D(nu) at the dual point nu = alpha grad phi(A x), ``gap`` >= 0 - the sum of the two Fenchel-Young gaps, formed term by
+    term (csrc/zf_kernels_gap.h), not ``primal - dual`` - ``alpha`` = min(1, lam / |grad f(x)|_inf) and ``grad_inf`` =
+    |grad f(x)|_inf; also ``f``, ``g_l1`` = lam |x|_1 and ``rows_gap`` (the loss part of the gap; ``gap - rows_gap`` is the
+    l1 part).  ``P(x) - min P <= gap``."""
+
+    __slots__ = ("primal", "dual", "gap", "alpha", "grad_inf", "f", "g_l1", "rows_gap")
+
+    def __init__(self, out):
+        for k, v in zip(self.__slots__, out):
+            setattr(self, k, np.float64(v))
+
+    def __repr__(self):
+        return "DualityGap(" + ", ".join(f"{k}={getattr(self, k)!r}" for k in self.__slots__) + ")"
+
+
+class _GapMixin:
+    """Duality-gap certificate, lam_max and same-matrix siblings of the four margins classes (LeastSquaresL1,
+    SparseLeastSquaresL1, LogisticL1, SparseLogisticL1)."""
+
+    has_duality_gap = True
+    _gap_logistic = 0
+
+    def _gap_refusal(self):
+        """Why this problem has no duality gap (None: it has one)."""
+        if self._has_box():
+            return "bounds are set: the dual of the boxed problem is a different one"
+        if getattr(self, "group", None) is not None:
+            return "the problem is sharded over a process group (group=): the dual point needs the whole A^T grad phi"
+        return None
+
+    def duality_gap(self, x):
+        """``DualityGap`` at ``x`` (a NumPy array or a float64 CUDA tensor), evaluated on the GPU."""
+        why = self._gap_refusal()
+        if why:
+            raise ValueError(f"duality_gap is not available: {why}")
+        if type(x).__module__.split(".")[0] == "torch":
+            x = x.detach().cpu().numpy()
+        x = _as_host(x)
+        if x.size != self.n_features:
+            raise ValueError(f"len(x) should be equal to n_features, got {x}.")
+        out = np.zeros(8)
+        self._gap_call(_lib.require_gpu(), x, out)
+        return DualityGap(out)
+
+    def lam_max(self):
+        """|grad f(0)|_inf: the smallest lam for which x = 0 is optimal."""
+        return np.float64(np.max(np.abs(self.jac_f(np.zeros(self.n_features)))))
+
+    def with_lam(self, lam):
+        """A sibling problem with another l1 weight that SHARES the device matrix, b and (sparse classes) the matrix
+        handle: nothing is uploaded."""
+        import copy
+
+        sib = copy.copy(self)
+        sib.lam = float(lam)
+        return sib
+
+
+class _DenseMarginsL1(_GapMixin, NativeProblem):
     """What the dense single-GPU problems f(x) = scale * sum_i loss_i((Ax)_i), g = lam |x|_1 (+ box) share: A (m x n, dense
     row-major) and the m-vector b in HBM, f / jac_f at a host vector through the entry point the subclass names, the
     descriptor of one GPU.  The loss is the subclass's: its ``kind``, its ``_eval_name``, what b means."""
@@ -165,6 +225,11 @@ class _DenseMarginsL1(NativeProblem):
                                                  C.byref(fval), C.c_void_p(_lib.ptr(grad)) if want_grad else None),
                    self._eval_name)
         return np.float64(fval.value), grad
+
+    def _gap_call(self, lib, x, out):
+        _lib.check(lib.zf_gap_eval(C.c_void_p(self.A.data_ptr()), C.c_void_p(self.b.data_ptr()), self.m_rows, self.n_features,
+                                   self.scale, self.lam, self._gap_logistic, C.c_void_p(_lib.ptr(x)), C.c_void_p(_lib.ptr(out)),
+                                   out.size), "zf_gap_eval")
 
     def f(self, x):
         return self._ls(x, False)[0]
@@ -251,7 +316,7 @@ class _SpmatHandle:
             pass
 
 
-class _SparseMarginsL1(NativeProblem):
+class _SparseMarginsL1(_GapMixin, NativeProblem):
     """What the sparse single-GPU problems f(x) = scale * sum_i loss_i((Ax)_i), g = lam |x|_1 (+ box) share: the canonical
     CSR of A and of A^T behind one immutable handle, b in HBM, f / jac_f at a host vector through the entry point the
     subclass names, the descriptor.  The loss is the subclass's: its ``kind``, its ``_eval_name``, what b means."""
@@ -284,6 +349,10 @@ class _SparseMarginsL1(NativeProblem):
         _lib.check(getattr(lib, self._eval_name)(self._spmat.value, C.c_void_p(self.b.data_ptr()), self.scale, C.c_void_p(_lib.ptr(x)),
                                                  C.byref(fval), C.c_void_p(_lib.ptr(grad)) if want_grad else None), self._eval_name)
         return np.float64(fval.value), grad
+
+    def _gap_call(self, lib, x, out):
+        _lib.check(lib.zf_spmat_gap_eval(self._spmat.value, C.c_void_p(self.b.data_ptr()), self.scale, self.lam, self._gap_logistic,
+                                         C.c_void_p(_lib.ptr(x)), C.c_void_p(_lib.ptr(out)), out.size), "zf_spmat_gap_eval")
 
     def f(self, x):
         return self._ls(x, False)[0]
@@ -342,6 +411,7 @@ class LogisticL1(_DenseMarginsL1):
 
     kind = _lib.ZF_PROBLEM_LOGISTIC_L1
     _eval_name = "zf_logistic_eval"
+    _gap_logistic = 1
 
     def __init__(self, A, b, lam, scale=1.0, bounds=None):
         shape = tuple(getattr(A, "shape", np.shape(A)))
@@ -358,6 +428,7 @@ class SparseLogisticL1(_SparseMarginsL1):
 
     kind = _lib.ZF_PROBLEM_SPARSE_LOGISTIC_L1
     _eval_name = "zf_spmat_logistic_eval"
+    _gap_logistic = 1
 
     def __init__(self, A, b, lam, scale=1.0, bounds=None):
         _check_labels(b)

@@ -34,6 +34,7 @@ from .problems import match_native, match_native_multi
 _MSG_OK = "Optimization terminated successfully"   # proximal_gradient.py:527
 _MSG_MAXITER = "Maximum number of iterations reached"   # :541
 _MSG_BACKTRACK = "Backtracking failed to find a suitable stepsize."   # :307
+_MSG_GAP = "Duality gap reached gap_tol"   # (no counterpart in the reference: gap_tol is an extension)
 _MSG_DEPRECATED = (
     "Using the deprecated option is not mathematically proven to converge. "
     "Please consider using the recommended condition instead."
@@ -93,7 +94,7 @@ def minimize_proximal_gradient(
     lr=1, tol=1e-5, tol_internal=1e-12, max_iter=1000000, max_iter_internal=100000,
     max_backtrack_iter=100, warm_start=False, decay_rate=0.5, nesterov=False,
     nesterov_ratio=(0, 0.25), return_all=False, verbose=False, deprecated=False,
-    *, dual_solver=None, sub_iters=None, acceptance=None,
+    *, dual_solver=None, sub_iters=None, acceptance=None, gap_tol=None, gap_every=16,
 ):
     """Minimise F = f + g by the (accelerated) proximal gradient method on MI355X.
 
@@ -132,6 +133,16 @@ def minimize_proximal_gradient(
         flag after a collapse of the step size), this one keeps deciding.
         The result says which one ran (field ``acceptance``).  Only when the keyword is not given, ZF_ACCEPT in the
         environment may override the default (and falls back to "reference" where the problem has no such mode).
+    gap_tol : float >= 0 or None (default).  ``LeastSquaresL1``, ``SparseLeastSquaresL1``, ``LogisticL1`` and ``SparseLogisticL1``
+        without bounds or a process group; anything else raises ValueError.  The reference's only stopping test,
+        ``max|x+ - y| < tol``, measures the step, not the distance to the optimum.  With ``gap_tol`` set the solve is advanced
+        ``gap_every`` passes at a time and the duality gap at x_k (``problem.duality_gap``: an upper bound of
+        ``F(x_k) - min F``, formed on the device without cancellation) is evaluated after each such chunk; the solve stops at
+        the first check with ``gap <= gap_tol`` - ``success=True``, message "Duality gap reached gap_tol", ``nit`` as of that
+        check.  The result carries ``dual_gap`` (a solve ended by ``tol`` / ``max_iter`` / a failed line search first: the gap
+        at its final x) and ``dual_gap_checks``.  Checking does not alter the iterates: ``x`` is, bit for bit, that of a
+        ``max_iter=res.nit`` solve without the keyword.
+    gap_every : int >= 1, passes between two checks (default 16: one check costs about one trial).
     """
     if deprecated:
         warn(_MSG_DEPRECATED, stacklevel=2)
@@ -153,6 +164,10 @@ def minimize_proximal_gradient(
         acceptance = acceptance or "reference"
     if acceptance not in ("reference", "resolved", "remainder"):
         raise ValueError(f"acceptance must be 'reference' or 'resolved' (or 'remainder', for the least-squares classes), got {acceptance!r}")
+    if int(gap_every) != gap_every or gap_every < 1:
+        raise ValueError(f"gap_every must be an integer >= 1, got {gap_every!r}")
+    if gap_tol is not None and not gap_tol >= 0:
+        raise ValueError(f"gap_tol must be >= 0 (or None), got {gap_tol!r}")
     opts = dict(
         dual_solver=dual_solver, sub_iters=int(sub_iters or 0), acceptance=acceptance,
         lr=lr, tol=tol, tol_internal=tol_internal, max_iter=max_iter,
@@ -178,6 +193,13 @@ def minimize_proximal_gradient(
             raise ValueError("acceptance='remainder' needs a native least-squares problem (zfista_amd.problems.LeastSquaresL1 or "
                              "zfista_amd.problems.SparseLeastSquaresL1): the Taylor remainder scale |A (x+ - y)|^2 is formed by "
                              "their residual kernels")
+    if gap_tol is not None:
+        why = ("the callbacks are not the four bound methods of one LeastSquaresL1, SparseLeastSquaresL1, LogisticL1 or "
+               "SparseLogisticL1 (with lam >= 0, lr > 0, decay_rate > 0): no dual of f + g is known"
+               if native is None or not getattr(native, "has_duality_gap", False) else native._gap_refusal())
+        if why:
+            raise ValueError(f"gap_tol is not available: {why}")
+        opts.update(gap_tol=float(gap_tol), gap_every=int(gap_every))
     if native is not None:
         res, status = _solve_native(native, x0, opts)
     elif _is_device_tensor(x0) and native_multi is None:
@@ -402,6 +424,13 @@ class NativeRun:
         self.status = int(ctl.status)
         self._fill_beta(self.nit_seen + 1)   # momentum factors for the extended range, as far as the ring allows
 
+    def duality_gap(self):
+        """``problems.DualityGap`` at the current x_k of the live solve (the four margins classes, unboxed, one GPU).  The
+        margins A x_k are the solver's own; the solve is not altered and may be advanced, snapshotted or polled afterwards."""
+        from .problems import DualityGap
+
+        return DualityGap(self.solver.duality_gap())
+
     def collect(self):
         ctl, trace = self.solver.poll()
         idx = np.arange(self.nit_seen, ctl.nit) % _lib.ZF_RING
@@ -430,6 +459,10 @@ def _solve_native(problem, x0, opts, solver_factory=None):
         allvecs = [x0]
     chunk = 1
     last_lr = float(opts["lr"])
+    # gap_tol: chunks of gap_every passes, the duality gap at x_k after each (zf_solver_duality_gap)
+    gap_tol, gap_checks, gap_last, gap_stop = opts.get("gap_tol"), 0, None, False
+    if gap_tol is not None and (streaming or not return_all):
+        chunk = int(opts["gap_every"])
     while run.status == _lib.ZF_RUNNING:
         before = run.nit_seen
         rows = run.advance(chunk)
@@ -442,8 +475,17 @@ def _solve_native(problem, x0, opts, solver_factory=None):
             last_lr = row[_lib.TR_LR]
         if return_all and not streaming and len(rows):
             allvecs.append(run.solver.get_x())   # chunk == 1: exactly this iterate
-        if streaming or not return_all:
+        if gap_tol is not None:
+            if run.status == _lib.ZF_RUNNING:
+                gap_last = run.duality_gap()
+                gap_checks += 1
+                if gap_last.gap <= gap_tol:
+                    gap_stop = True
+                    break
+        elif streaming or not return_all:
             chunk = min(chunk * 2, 256)
+    if gap_tol is not None and not gap_stop:
+        gap_last = run.duality_gap()   # the solver stopped for another reason: the gap at its final x
     if streaming:
         allvecs = run.history()
     ctl = run.solver.ctl
@@ -461,14 +503,22 @@ def _solve_native(problem, x0, opts, solver_factory=None):
         err = OptimizeResult()
         err.update(success=False, message=f"Error: {_MSG_BACKTRACK}", x=x, fun=F, nit=int(ctl.nit),
                    time=time.time() - t0, allvecs=allvecs, allfuns=allfuns, allerrs=allerrs)
+        if gap_tol is not None:
+            err.update(dual_gap=gap_last.gap, dual_gap_checks=gap_checks)
         run.solver.close()
         return err, run.status
-    if run.status == _lib.ZF_CONVERGED:
+    status = run.status
+    if gap_stop:
+        status = _lib.ZF_CONVERGED
+        res.status, res.message, res.success = 1, _MSG_GAP, True
+    elif run.status == _lib.ZF_CONVERGED:
         res.status, res.message, res.success = 1, _MSG_OK, True
     else:
         res.status, res.message, res.success = 0, _MSG_MAXITER, False
     res.update(x=x, fun=F, nit=int(ctl.nit), allvecs=allvecs, allfuns=allfuns, allerrs=allerrs,
                time=time.time() - t0)
+    if gap_tol is not None:
+        res.update(dual_gap=gap_last.gap, dual_gap_checks=gap_checks)
     report = getattr(run.solver, "ahead_report", None)
     if report is not None:
         rep = report()
@@ -478,7 +528,7 @@ def _solve_native(problem, x0, opts, solver_factory=None):
             res["runahead"] = (f"switched off after {rep['timeouts']} wait(s) of run-ahead passes gave up "
                                f"({rep['void']} void passes)")
     run.solver.close()
-    return res, run.status
+    return res, status
 
 
 # ---------------------------------------------------------------------------
