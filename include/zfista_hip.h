@@ -534,6 +534,45 @@ int zf_spmat_gap_eval(const zf_spmat* h, const double* b_dev, double scale, doub
  * one).  ZF_ERR_STATE: not initialised. */
 int zf_solver_duality_gap(zf_solver* s, double* out, int64_t count /* >= 8 */);
 
+/* ---- gap-safe screening and column restriction (csrc/zf_kernels_screen.h) ------------------------------------------------
+ * phi_i' is L-Lipschitz (least squares L = 2 scale, logistic L = scale / 4), so the dual optimum lies within r = sqrt(2 L gap)
+ * of the dual point of a gap evaluation, and column j is zero at every optimum when alpha |g_j| + r |a_j|_2 < lam.  In fp64
+ * the radius is widened to r_eff = r + E, E |a_j| a bound of the rounding of the left side (derived in zf_kernels_screen.h).
+ * All kernels: fp64, no atomics, every sum and every output order fixed by the matrix and the mask alone.
+ * Column norms: norms_dev (n doubles) = |a_j|_2, stats_dev (2 doubles) = [sum_j |a_j|^2, max_j |a_j|]; sparse: row sums of squares
+ * over the stored A^T with its plan; dense: row-major A (m_rows x n).  An empty column has norm 0 exactly. */
+int zf_spmat_col_norms(const zf_spmat* h, double* norms_dev, double* stats_dev);
+int zf_dense_col_norms(const double* A_dev, int64_t m_rows, int64_t n, double* norms_dev, double* stats_dev);
+/* zf_gap_eval / zf_spmat_gap_eval - the same kernels in the same order, out[0 .. 8) the same bits - followed by the screen of
+ * the call's g: keep_dev (n bytes) = !(alpha |g_j| + r_eff |a_j| < lam), index_dev (n int32) = the exclusive scan of keep (the
+ * new column number of a kept column), out[8 .. 12) = [r, E, r_eff, kept count].  A non-finite gap, alpha or g_j keeps
+ * everything.  count >= 12; norms_dev / stats_dev as the norms calls left them; max_row / max_col: the stored elements of the
+ * longest row / column of A (dense: n and m_rows, taken from the sizes). */
+int zf_gap_screen_eval(const double* A_dev, const double* b_dev, int64_t m_rows, int64_t n, double scale, double lam, int32_t logistic,
+                       const double* x_host, double* out, int64_t count /* >= 12 */, const double* norms_dev, const double* stats_dev,
+                       uint8_t* keep_dev, int32_t* index_dev);
+int zf_spmat_gap_screen_eval(const zf_spmat* h, const double* b_dev, double scale, double lam, int32_t logistic, const double* x_host,
+                             double* out, int64_t count /* >= 12 */, const double* norms_dev, const double* stats_dev, int64_t max_row,
+                             int64_t max_col, uint8_t* keep_dev, int32_t* index_dev);
+/* index_dev (n int32) = the exclusive scan of a caller's mask keep_dev (n bytes, non-zero = kept), *count_out = the kept count:
+ * one workgroup up to 4096 elements, contiguous chunks combined in chunk order beyond. */
+int zf_screen_scan(const uint8_t* keep_dev, int64_t n, int32_t* index_dev, int64_t* count_out);
+/* The restriction of a matrix handle to its kept columns, in two calls around the caller's scans of the lengths.
+ * zf_spmat_restrict_count: index_dev (n) = the scan of keep_dev, *count_out = k; len_dev (m int64) = the kept elements of every row
+ * of A; t_len_dev[c] (c < k; room for n) = the length of the c-th kept row of A^T; seg_off_dev (int32, one per segment of A's plan;
+ * may be NULL without split rows) = where the kept elements of a segment start inside their row.
+ * zf_spmat_restrict_fill: with indptr_dev (m + 1) and t_indptr_dev (k + 1) the exclusive scans of those lengths, both ending at
+ * nnz_new (checked), writes the canonical CSR of A[:, keep] - every row's kept elements in stored order, columns renumbered -
+ * and of its transpose (the kept rows of A^T, whole).  keep, index and seg_off must be those of the count call. */
+int zf_spmat_restrict_count(const zf_spmat* h, const uint8_t* keep_dev, int32_t* index_dev, int64_t* len_dev, int64_t* t_len_dev,
+                            int32_t* seg_off_dev, int64_t* count_out);
+int zf_spmat_restrict_fill(const zf_spmat* h, const uint8_t* keep_dev, const int32_t* index_dev, const int32_t* seg_off_dev, int64_t k,
+                           int64_t nnz_new, const int64_t* indptr_dev, int32_t* indices_dev, double* values_dev,
+                           const int64_t* t_indptr_dev, int32_t* t_indices_dev, double* t_values_dev);
+/* out_dev (m_rows x k, row-major) = A[:, keep]; index_dev (n): scratch for the scan of keep_dev; k must be the kept count (>= 1). */
+int zf_dense_restrict(const double* A_dev, int64_t m_rows, int64_t n, const uint8_t* keep_dev, int32_t* index_dev, int64_t k,
+                      double* out_dev);
+
 /* ---- multi-objective trial (m >= 2), device side ---------------------------
  * The dual of the scalarised subproblem is minimised on the host by SciPy exactly
  * as the reference does (proximal_gradient.py:179-205); every O(n) expression runs

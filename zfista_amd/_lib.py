@@ -220,6 +220,15 @@ SIGNATURES = {
     "zf_spmat_gap_eval": (C.c_int, [_P, _P, C.c_double, C.c_double, C.c_int32, _P, _P, C.c_int64]),
     "zf_solver_duality_gap": (C.c_int, [_P, _P, C.c_int64]),
     "zf_solver_create_sparse": (C.c_int, [C.POINTER(_P), C.POINTER(ProblemDesc), _P, C.POINTER(Options), _P]),
+    "zf_spmat_col_norms": (C.c_int, [_P, _P, _P]),
+    "zf_dense_col_norms": (C.c_int, [_P, C.c_int64, C.c_int64, _P, _P]),
+    "zf_gap_screen_eval": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_int32, _P, _P, C.c_int64, _P, _P, _P, _P]),
+    "zf_spmat_gap_screen_eval": (C.c_int, [_P, _P, C.c_double, C.c_double, C.c_int32, _P, _P, C.c_int64, _P, _P, C.c_int64, C.c_int64,
+                                           _P, _P]),
+    "zf_screen_scan": (C.c_int, [_P, C.c_int64, _P, C.POINTER(C.c_int64)]),
+    "zf_spmat_restrict_count": (C.c_int, [_P, _P, _P, _P, _P, _P, C.POINTER(C.c_int64)]),
+    "zf_spmat_restrict_fill": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int64, _P, _P, _P, _P, _P, _P]),
+    "zf_dense_restrict": (C.c_int, [_P, C.c_int64, C.c_int64, _P, _P, C.c_int64, _P]),
 }
 
 _lib = None

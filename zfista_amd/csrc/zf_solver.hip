@@ -20,6 +20,7 @@
 #include "zf_kernels_ls_small.h"
 #include "zf_kernels_op.h"
 #include "zf_spmv.h"
+#include "zf_screen.h"
 #include "zf_kernels_loss.h"
 #include "zf_kernels_gap.h"
 #include "zf_kernels_step.h"
@@ -2635,12 +2636,19 @@ static void zf_gap_ws_free(zf_gap_ws* ws) {
 }
 
 // dense (h == NULL) or CSR matrix; x from the host
+// scr != NULL (zf_gap_screen_eval / zf_spmat_gap_screen_eval): the screen of zf_kernels_screen.h over the call's g behind the
+// same sequence - its four scalars follow the eight outputs; scr->cnt and scr->scal are allocated here
 static int zf_gap_eval_impl(const double* A_dev, const zf_spmat* h, const double* b_dev, int64_t m, int64_t n, double scale, double lam,
-                            bool logistic, const double* x_host, double* out) {
+                            bool logistic, const double* x_host, double* out, const zf_screen_req* scr = nullptr) {
     zf_gap_ws ws = {nullptr, nullptr, nullptr, nullptr};
-    double *x = nullptr, *z = nullptr, *slab = nullptr, *part_A = nullptr, *part_At = nullptr;
+    double *x = nullptr, *z = nullptr, *slab = nullptr, *part_A = nullptr, *part_At = nullptr, *scr_scal = nullptr;
+    int32_t* scr_cnt = nullptr;
     int64_t slices = 1, rps = m;
     int rc = zf_gap_ws_alloc(&ws, m, n);
+    if (scr) {
+        ZF_GAP_TRY(hipMalloc(&scr_scal, sizeof(double) * ZF_SCREEN_SCAL));
+        ZF_GAP_TRY(hipMalloc(&scr_cnt, sizeof(int32_t) * (ZF_SCREEN_MAX_CHUNKS + 1)));
+    }
     ZF_GAP_TRY(hipMalloc(&x, sizeof(double) * (n + 2)));
     ZF_GAP_TRY(hipMalloc(&z, sizeof(double) * (m + 2)));
     if (h) {
@@ -2678,12 +2686,19 @@ static int zf_gap_eval_impl(const double* A_dev, const zf_spmat* h, const double
             zf_gap_dense_sweep(nullptr, A_dev, ws.rvec, slab, ws.g, m, n, (int)slices, rps, n % 32 == 0 && zf_env_read().gemv_mfma, gfac);
         }
         zf_launch_gap_tail(nullptr, logistic, z, b_dev, x, m, n, scale, lam, ws);
+        if (scr) {
+            zf_screen_req rq = *scr;
+            rq.cnt = scr_cnt;
+            rq.scal = scr_scal;
+            zf_launch_screen(nullptr, rq, ws.g, ws.scal + ZF_GS_OUT, ws.scal + ZF_GS_ASUM, ws.scal + ZF_GS_RR, m, n, scale, lam, logistic);
+        }
         ZF_GAP_TRY(hipGetLastError());
         ZF_GAP_TRY(hipMemcpyAsync(out, ws.scal + ZF_GS_OUT, sizeof(double) * 8, hipMemcpyDeviceToHost, nullptr));
+        if (scr) ZF_GAP_TRY(hipMemcpyAsync(out + 8, scr_scal, sizeof(double) * ZF_SCREEN_SCAL, hipMemcpyDeviceToHost, nullptr));
         ZF_GAP_TRY(hipStreamSynchronize(nullptr));
     }
     zf_gap_ws_free(&ws);
-    for (void* p : {(void*)x, (void*)z, (void*)slab, (void*)part_A, (void*)part_At})
+    for (void* p : {(void*)x, (void*)z, (void*)slab, (void*)part_A, (void*)part_At, (void*)scr_scal, (void*)scr_cnt})
         if (p) (void)hipFree(p);
     return rc;
 }
@@ -2703,6 +2718,40 @@ extern "C" int zf_spmat_gap_eval(const zf_spmat* h, const double* b_dev, double 
     ZF_REQUIRE(count >= 8, "zf_spmat_gap_eval: the output buffer holds fewer than 8 doubles");
     ZF_REQUIRE(scale > 0.0 && lam >= 0.0, "zf_spmat_gap_eval: needs scale > 0 and lam >= 0");
     return zf_gap_eval_impl(nullptr, h, b_dev, h->m, h->n, scale, lam, logistic != 0, x_host, out);
+}
+
+// the gap evaluation followed by the gap-safe screen of its g (zf_kernels_screen.h): out[0 .. 8) as zf_gap_eval - the same
+// kernels in the same order, the same bits - then [r, E, r_eff, kept count]
+static int zf_screen_args(const char* who, const double* norms_dev, const double* stats_dev, int64_t max_row, int64_t max_col,
+                          uint8_t* keep_dev, int32_t* index_dev, int64_t count, zf_screen_req* rq) {
+    if (!(norms_dev && stats_dev && keep_dev && index_dev)) return zf_fail(ZF_ERR_ARG, "%s: null argument%s", who);
+    if (count < 8 + ZF_SCREEN_SCAL) return zf_fail(ZF_ERR_ARG, "%s: the output buffer holds fewer than 12 doubles%s", who);
+    if (max_row < 0 || max_col < 0) return zf_fail(ZF_ERR_ARG, "%s: the longest row and column must be >= 0%s", who);
+    *rq = zf_screen_req{norms_dev, stats_dev, max_row, max_col, keep_dev, index_dev, nullptr, nullptr};
+    return ZF_OK;
+}
+
+extern "C" int zf_gap_screen_eval(const double* A_dev, const double* b_dev, int64_t m_rows, int64_t n, double scale, double lam,
+                                  int32_t logistic, const double* x_host, double* out, int64_t count, const double* norms_dev,
+                                  const double* stats_dev, uint8_t* keep_dev, int32_t* index_dev) {
+    ZF_REQUIRE(A_dev && b_dev && x_host && out && m_rows >= 1 && n >= 1 && n <= 0x7fffffffLL, "zf_gap_screen_eval: bad argument");
+    ZF_REQUIRE(scale > 0.0 && lam >= 0.0, "zf_gap_screen_eval: needs scale > 0 and lam >= 0");
+    ZF_REQUIRE(zf_aligned16(A_dev), "zf_gap_screen_eval: A must be 16-byte aligned");
+    zf_screen_req rq;
+    const int rc = zf_screen_args("zf_gap_screen_eval", norms_dev, stats_dev, n, m_rows, keep_dev, index_dev, count, &rq);
+    if (rc) return rc;
+    return zf_gap_eval_impl(A_dev, nullptr, b_dev, m_rows, n, scale, lam, logistic != 0, x_host, out, &rq);
+}
+
+extern "C" int zf_spmat_gap_screen_eval(const zf_spmat* h, const double* b_dev, double scale, double lam, int32_t logistic,
+                                        const double* x_host, double* out, int64_t count, const double* norms_dev, const double* stats_dev,
+                                        int64_t max_row, int64_t max_col, uint8_t* keep_dev, int32_t* index_dev) {
+    ZF_REQUIRE(h && b_dev && x_host && out, "zf_spmat_gap_screen_eval: null argument");
+    ZF_REQUIRE(scale > 0.0 && lam >= 0.0, "zf_spmat_gap_screen_eval: needs scale > 0 and lam >= 0");
+    zf_screen_req rq;
+    const int rc = zf_screen_args("zf_spmat_gap_screen_eval", norms_dev, stats_dev, max_row, max_col, keep_dev, index_dev, count, &rq);
+    if (rc) return rc;
+    return zf_gap_eval_impl(nullptr, h, b_dev, h->m, h->n, scale, lam, logistic != 0, x_host, out, &rq);
 }
 
 // The gap at x_k of a live solver, on its stream: the margins A x_k are the ring's (no sweep over A), the dual candidate goes

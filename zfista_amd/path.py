@@ -12,9 +12,11 @@ import numpy as np
 from .proximal_gradient import minimize_proximal_gradient
 
 
-def l1_path(problem, lams, x0=None, gap_tol=1e-6, **solver_kwargs):
+def l1_path(problem, lams, x0=None, gap_tol=1e-6, screen=False, **solver_kwargs):
     """Solve ``problem.with_lam(l)`` for each ``l`` of ``lams`` in the order given, each from the solution of the one
     before (the first from ``x0``; default zeros), with ``minimize_proximal_gradient(..., gap_tol=gap_tol, **solver_kwargs)``.
+    ``screen=True``: each point is solved by ``zfista_amd.screening.solve_screened`` instead - gap-safe screening, and solves
+    on the kept columns only (``solver_kwargs`` may then carry its ``screen_ratio``, ``screen_shrink`` and ``max_rounds``).
 
     ``problem``: a ``LeastSquaresL1``, ``SparseLeastSquaresL1``, ``LogisticL1`` or ``SparseLogisticL1`` without bounds or a
     process group; ``gap_tol``: the absolute duality gap every point is solved to (None: the solver's own ``tol`` only).
@@ -25,7 +27,12 @@ def l1_path(problem, lams, x0=None, gap_tol=1e-6, **solver_kwargs):
     out = []
     for lam in lams:
         sib = problem.with_lam(lam)
-        res = minimize_proximal_gradient(*sib.callbacks(), x, gap_tol=gap_tol, **solver_kwargs)
+        if screen:
+            from .screening import solve_screened
+
+            res = solve_screened(sib, x, gap_tol, **solver_kwargs)
+        else:
+            res = minimize_proximal_gradient(*sib.callbacks(), x, gap_tol=gap_tol, **solver_kwargs)
         res["lam"] = float(lam)
         out.append(res)
         x = res.x

@@ -152,12 +152,122 @@ class DualityGap:
         return "DualityGap(" + ", ".join(f"{k}={getattr(self, k)!r}" for k in self.__slots__) + ")"
 
 
+class Screen(tuple):
+    """What ``problem.screen(x)`` returns: the triple ``(gap, keep, count)`` - the ``DualityGap`` at x, the device mask of the
+    columns the gap-safe rule cannot discard (a bool CUDA tensor of n_features) and their number - with, as attributes
+    beside those three, ``index`` (int32 CUDA tensor: the exclusive scan of the mask, the new number of a kept column),
+    ``radius`` = sqrt(2 L gap) and ``guard`` = E, the widening of the radius that covers the fp64 evaluation
+    (csrc/zf_kernels_screen.h)."""
+
+    def __new__(cls, gap, keep, count, index, radius, guard):
+        self = tuple.__new__(cls, (gap, keep, count))
+        self.gap, self.keep, self.count = gap, keep, count
+        self.index, self.radius, self.guard = index, np.float64(radius), np.float64(guard)
+        return self
+
+
+class _ColumnNorms:
+    """|a_j|_2 of one device matrix (a float64 CUDA tensor), [sum |a_j|^2, max |a_j|] beside it: computed by the first
+    ``column_norms()`` and shared by every ``with_lam`` sibling of the problem."""
+
+    __slots__ = ("norms", "stats")
+
+    def __init__(self):
+        self.norms = self.stats = None
+
+
+def _dp(t):
+    return C.c_void_p(t.data_ptr() if t is not None and t.numel() else None)
+
+
 class _GapMixin:
-    """Duality-gap certificate, lam_max and same-matrix siblings of the four margins classes (LeastSquaresL1,
-    SparseLeastSquaresL1, LogisticL1, SparseLogisticL1)."""
+    """Duality-gap certificate, lam_max, same-matrix siblings, gap-safe screening and column restriction of the four margins
+    classes (LeastSquaresL1, SparseLeastSquaresL1, LogisticL1, SparseLogisticL1)."""
 
     has_duality_gap = True
     _gap_logistic = 0
+
+    def column_norms(self):
+        """|a_j|_2 of every column of A: a float64 CUDA tensor of n_features, computed on the GPU once per matrix."""
+        import torch
+
+        h = self._norms
+        if h.norms is None:
+            lib = _lib.require_gpu()
+            norms = torch.empty(self.n_features, dtype=torch.float64, device="cuda")
+            stats = torch.empty(2, dtype=torch.float64, device="cuda")
+            self._norms_call(lib, norms, stats)
+            h.norms, h.stats = norms, stats
+        return h.norms
+
+    def screen(self, x):
+        """The duality gap at ``x`` and, from the same evaluation, the gap-safe screen: ``Screen`` = (gap, keep, count).
+        Column j is dropped (``keep[j]`` False) when alpha |g_j| + (r + E) |a_j|_2 < lam, r = sqrt(2 L gap): such a column is
+        zero at every optimum.  ``gap`` is, bit for bit, ``duality_gap(x)``."""
+        import torch
+
+        why = self._gap_refusal()
+        if why:
+            raise ValueError(f"screen is not available: {why}")
+        if type(x).__module__.split(".")[0] == "torch":
+            x = x.detach().cpu().numpy()
+        x = _as_host(x)
+        if x.size != self.n_features:
+            raise ValueError(f"len(x) should be equal to n_features, got {x}.")
+        lib = _lib.require_gpu()
+        self.column_norms()
+        keep = torch.empty(self.n_features, dtype=torch.uint8, device="cuda")
+        index = torch.empty(self.n_features, dtype=torch.int32, device="cuda")
+        out = np.zeros(12)
+        self._screen_call(lib, x, out, self._norms, keep, index)
+        return Screen(DualityGap(out[:8]), keep.view(torch.bool), int(out[11]), index, out[8], out[9])
+
+    def _keep_mask(self, keep):
+        """``keep`` - a Screen, a device mask, a host boolean mask or a host array of column numbers - as a uint8 CUDA tensor."""
+        import torch
+
+        n = self.n_features
+        if isinstance(keep, Screen):
+            keep = keep.keep
+        if isinstance(keep, torch.Tensor):
+            if keep.dtype not in (torch.bool, torch.uint8) or keep.ndim != 1 or keep.numel() != n:
+                raise ValueError(f"a device mask must be a bool or uint8 tensor of {n} values")
+            return keep.cuda().contiguous().view(torch.uint8)
+        a = np.asarray(keep)
+        if a.dtype == np.bool_:
+            if a.shape != (n,):
+                raise ValueError(f"a boolean mask must hold {n} values, got shape {a.shape}")
+            host = np.ascontiguousarray(a)
+        elif a.dtype.kind in "iu" and a.ndim == 1:
+            if a.size and (a.min() < 0 or a.max() >= n):
+                raise ValueError(f"column numbers must lie in [0, {n})")
+            host = np.zeros(n, dtype=np.bool_)
+            host[a] = True
+            if int(host.sum()) != a.size:
+                raise ValueError("column numbers must not repeat")
+        else:
+            raise ValueError("keep must be a mask (device or host) or a 1-D array of column numbers")
+        return torch.from_numpy(host.view(np.uint8)).cuda()
+
+    def restrict(self, keep):
+        """The problem over the columns ``keep`` alone - same class, same b (shared), ``n_features`` = the number kept - built
+        on the device from the resident matrix: the CSR of A[:, keep] and of its transpose, or the dense A[:, keep].  ``keep``:
+        the ``Screen`` of ``screen(x)``, a device mask, a host boolean mask, or a host array of column numbers (the columns
+        keep their order).  With x_full[keep] = x and zeros elsewhere, f and jac_f of the restricted problem at x are the
+        full problem's at x_full (jac_f: its kept entries).  Keeping no column is refused: that problem's solution is x = 0."""
+        why = self._gap_refusal()
+        if why:
+            raise ValueError(f"restrict is not available: {why}")
+        import copy
+
+        sub = copy.copy(self)
+        sub._norms = _ColumnNorms()
+        self._restrict_into(_lib.require_gpu(), self._keep_mask(keep), sub)
+        return sub
+
+    @staticmethod
+    def _none_kept():
+        return ValueError("no column is kept: the restricted problem has no variable (its solution is x = 0)")
 
     def _gap_refusal(self):
         """Why this problem has no duality gap (None: it has one)."""
@@ -212,6 +322,28 @@ class _DenseMarginsL1(_GapMixin, NativeProblem):
         self.box = (-np.inf, np.inf) if bounds is None else (float(bounds[0]), float(bounds[1]))
         self.m_rows, self.n_features = int(self.A.shape[0]), int(self.A.shape[1])
         self.group = None
+        self._norms = _ColumnNorms()
+
+    def _norms_call(self, lib, norms, stats):
+        _lib.check(lib.zf_dense_col_norms(_dp(self.A), self.m_rows, self.n_features, _dp(norms), _dp(stats)), "zf_dense_col_norms")
+
+    def _screen_call(self, lib, x, out, h, keep, index):
+        _lib.check(lib.zf_gap_screen_eval(_dp(self.A), _dp(self.b), self.m_rows, self.n_features, self.scale, self.lam, self._gap_logistic,
+                                          C.c_void_p(_lib.ptr(x)), C.c_void_p(_lib.ptr(out)), out.size, _dp(h.norms), _dp(h.stats),
+                                          _dp(keep), _dp(index)), "zf_gap_screen_eval")
+
+    def _restrict_into(self, lib, mask, sub):
+        import torch
+
+        n = self.n_features
+        index = torch.empty(n, dtype=torch.int32, device="cuda")
+        k = C.c_int64(0)
+        _lib.check(lib.zf_screen_scan(_dp(mask), n, _dp(index), C.byref(k)), "zf_screen_scan")
+        if k.value == 0:
+            raise self._none_kept()
+        out = torch.empty((self.m_rows, k.value), dtype=torch.float64, device="cuda")
+        _lib.check(lib.zf_dense_restrict(_dp(self.A), self.m_rows, n, _dp(mask), _dp(index), k.value, _dp(out)), "zf_dense_restrict")
+        sub.A, sub.n_features = out, int(k.value)
 
     def _ls(self, x, want_grad):
         x = _as_host(x)
@@ -285,13 +417,15 @@ class LeastSquaresL1(_DenseMarginsL1):
 class _SpmatHandle:
     """Owner of a ``zf_spmat`` handle and of the device arrays behind it."""
 
-    def __init__(self, prep):
+    def __init__(self, prep, dev=None):
+        """``prep``: what ``sparse.prepare`` returns, uploaded here - or, with ``dev`` (the six arrays, already in HBM), only
+        its sizes and the two plans."""
         import torch
 
         lib = _lib.require_gpu()
         self.lib = lib
         names = ("indptr", "indices", "data", "t_indptr", "t_indices", "t_data")
-        self.dev = {k: torch.from_numpy(prep[k]).cuda() for k in names}
+        self.dev = {k: torch.from_numpy(prep[k]).cuda() for k in names} if dev is None else {k: dev[k] for k in names}
         self.plans = []   # (the host arrays a zf_spmv_plan points to, for the duration of the call)
         for key in ("plan", "t_plan"):
             p = prep[key]
@@ -338,6 +472,51 @@ class _SparseMarginsL1(_GapMixin, NativeProblem):
         self.plan = (prep["plan"], prep["t_plan"])
         self.group = None
         self._spmat = _SpmatHandle(prep)
+        self._norms = _ColumnNorms()
+        self._longest = (int(np.diff(prep["indptr"]).max(initial=0)), int(np.diff(prep["t_indptr"]).max(initial=0)))
+
+    def _norms_call(self, lib, norms, stats):
+        _lib.check(lib.zf_spmat_col_norms(self._spmat.value, _dp(norms), _dp(stats)), "zf_spmat_col_norms")
+
+    def _screen_call(self, lib, x, out, h, keep, index):
+        _lib.check(lib.zf_spmat_gap_screen_eval(self._spmat.value, _dp(self.b), self.scale, self.lam, self._gap_logistic,
+                                                C.c_void_p(_lib.ptr(x)), C.c_void_p(_lib.ptr(out)), out.size, _dp(h.norms), _dp(h.stats),
+                                                self._longest[0], self._longest[1], _dp(keep), _dp(index)), "zf_spmat_gap_screen_eval")
+
+    def _restrict_into(self, lib, mask, sub):
+        """Counts, the two scans of the lengths (torch.cumsum), the fill; the host reads the two new row pointer arrays for the
+        plans (sparse.plan_rows) and creates the handle on the device arrays."""
+        import torch
+
+        from . import sparse
+
+        m, n, h = self.m_rows, self.n_features, self._spmat
+        i64 = dict(dtype=torch.int64, device="cuda")
+        index = torch.empty(n, dtype=torch.int32, device="cuda")
+        seg_off = torch.empty(self.plan[0]["seg_start"].size, dtype=torch.int32, device="cuda")
+        lens, t_lens = torch.empty(m, **i64), torch.empty(n, **i64)
+        k = C.c_int64(0)
+        _lib.check(lib.zf_spmat_restrict_count(h.value, _dp(mask), _dp(index), _dp(lens), _dp(t_lens), _dp(seg_off), C.byref(k)),
+                   "zf_spmat_restrict_count")
+        k = int(k.value)
+        if k == 0:
+            raise self._none_kept()
+        dev = dict(indptr=torch.zeros(m + 1, **i64), t_indptr=torch.zeros(k + 1, **i64))
+        dev["indptr"][1:] = torch.cumsum(lens, 0)
+        dev["t_indptr"][1:] = torch.cumsum(t_lens[:k], 0)
+        indptr, t_indptr = dev["indptr"].cpu().numpy(), dev["t_indptr"].cpu().numpy()
+        nnz = int(indptr[-1])
+        for key in ("indices", "t_indices"):
+            dev[key] = torch.empty(nnz, dtype=torch.int32, device="cuda")
+        for key in ("data", "t_data"):
+            dev[key] = torch.empty(nnz, dtype=torch.float64, device="cuda")
+        _lib.check(lib.zf_spmat_restrict_fill(h.value, _dp(mask), _dp(index), _dp(seg_off), k, nnz, _dp(dev["indptr"]), _dp(dev["indices"]),
+                                              _dp(dev["data"]), _dp(dev["t_indptr"]), _dp(dev["t_indices"]), _dp(dev["t_data"])),
+                   "zf_spmat_restrict_fill")
+        prep = dict(m=m, n=k, nnz=nnz, plan=sparse.plan_rows(indptr), t_plan=sparse.plan_rows(t_indptr))
+        sub.n_features, sub.nnz, sub.plan = k, nnz, (prep["plan"], prep["t_plan"])
+        sub._spmat = _SpmatHandle(prep, dev)
+        sub._longest = (int(np.diff(indptr).max(initial=0)), int(np.diff(t_indptr).max(initial=0)))
 
     def _ls(self, x, want_grad):
         x = _as_host(x)
