@@ -534,6 +534,37 @@ int zf_spmat_gap_eval(const zf_spmat* h, const double* b_dev, double scale, doub
  * one).  ZF_ERR_STATE: not initialised. */
 int zf_solver_duality_gap(zf_solver* s, double* out, int64_t count /* >= 8 */);
 
+/* ---- elastic net: g(x) = lam |x|_1 + (l2 / 2) |x|^2 (+ box) for the margins kinds 2, 4, 5, 6 ------------------------------
+ * Additive to ABI 6: no struct field, no version change.  prox_{w g}(v) = clip(soft_threshold(v, lam w) * shrink, lo, hi) with
+ * shrink = 1 / (1 + l2 w) formed once per trial as a scalar; the element is multiplied by it (no division per element), the
+ * iterate arithmetic stays uncontracted: x+ is that expression bit for bit.  The clip behind the shrink is the exact prox.
+ * zf_solver_set_l2: after zf_solver_create(_sparse), before zf_solver_enqueue_init / zf_solver_restore (ZF_ERR_STATE afterwards).
+ * ZF_ERR_ARG: another problem kind, world > 1, l2 < 0 or not finite.  With l2 > 0 every trial runs the elastic-net step kernel
+ * (zf_trial_enet_kernel: the general vector path; a matrix small enough for the two fused small-matrix launches takes the
+ * general path too, and zf_solver_ls_plan says so), F(x0) includes the ridge term, and zf_solver_duality_gap evaluates the
+ * certificate below.  l2 = 0 changes nothing: the launches, allocations and bits of a solver that was never asked.  A resumed
+ * solve sets l2 again before zf_solver_restore (the snapshot carries nothing new). */
+int zf_solver_set_l2(zf_solver* s, double l2);
+/* The certificate: the ridge term is n more rows phi(t) = (l2 / 2) t^2 at z = x.  gt = grad f(x) + l2 x, alpha = min(1, lam /
+ * |gt|_inf) (1 when gt = 0), 1 - alpha and alpha log alpha as above;
+ *   P = f + lam |x|_1 + (l2 / 2) sum x^2          D = D_loss(alpha) - (l2 / 2) alpha^2 sum x^2
+ *   ridge = (l2 / 2) (1 - alpha)^2 sum x^2        columns = sum_j (lam |x_j| + alpha gt_j x_j), term by term, clamped at 0
+ *   gap = rows + ridge + columns                  (rows: the loss part, as above)
+ * out = the eight values above with |gt|_inf in [4]; count >= 10: [8] = (l2 / 2) sum x^2, [9] = the ridge part of the gap.
+ * The |.|_inf pass forms gt on the fly from g and x (16 n bytes).  No atomics; every sum in an order fixed by m or n alone.
+ * l2 = 0 runs the evaluation above (the same kernels, the same eight values) and writes [8] = [9] = 0.  zf_solver_duality_gap
+ * of a solver with l2 > 0 writes the same ten values (count >= 10; the first eight otherwise); of any other solver the eight
+ * it wrote before, whatever count. */
+int zf_gap_eval_enet(const double* A_dev, const double* b_dev, int64_t m_rows, int64_t n, double scale, double lam, double l2,
+                     int32_t logistic, const double* x_host, double* out, int64_t count /* >= 8; 10 for all */);
+int zf_spmat_gap_eval_enet(const zf_spmat* h, const double* b_dev, double scale, double lam, double l2, int32_t logistic,
+                           const double* x_host, double* out, int64_t count /* >= 8; 10 for all */);
+/* out = clip(soft_threshold(x, tau) * shrink, lo, hi) at a host vector: the elastic-net prox with tau = lam w and the caller's
+ * scalar shrink = 1 / (1 + l2 w) */
+int zf_host_prox_enet_box(double* out_host, const double* x_host, double tau, double shrink, double lo, double hi, int64_t n);
+/* out = sum_i (lam |x_i| + (l2 / 2) x_i^2), each term two fused multiply-adds into the running sum (as the step kernel forms g(x+)) */
+int zf_host_enet_g(const double* x_host, int64_t n, double lam, double l2, double* out);
+
 /* ---- gap-safe screening and column restriction (csrc/zf_kernels_screen.h) ------------------------------------------------
  * phi_i' is L-Lipschitz (least squares L = 2 scale, logistic L = scale / 4), so the dual optimum lies within r = sqrt(2 L gap)
  * of the dual point of a gap evaluation, and column j is zero at every optimum when alpha |g_j| + r |a_j|_2 < lam.  In fp64

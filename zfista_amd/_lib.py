@@ -229,6 +229,11 @@ SIGNATURES = {
     "zf_spmat_restrict_count": (C.c_int, [_P, _P, _P, _P, _P, _P, C.POINTER(C.c_int64)]),
     "zf_spmat_restrict_fill": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int64, _P, _P, _P, _P, _P, _P]),
     "zf_dense_restrict": (C.c_int, [_P, C.c_int64, C.c_int64, _P, _P, C.c_int64, _P]),
+    "zf_solver_set_l2": (C.c_int, [_P, C.c_double]),
+    "zf_gap_eval_enet": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_int32, _P, _P, C.c_int64]),
+    "zf_spmat_gap_eval_enet": (C.c_int, [_P, _P, C.c_double, C.c_double, C.c_double, C.c_int32, _P, _P, C.c_int64]),
+    "zf_host_prox_enet_box": (C.c_int, [_P, _P, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int64]),
+    "zf_host_enet_g": (C.c_int, [_P, C.c_int64, C.c_double, C.c_double, C.POINTER(C.c_double)]),
 }
 
 _lib = None

@@ -279,6 +279,118 @@ __global__ void zf_gap_compose_kernel(int logistic, double scale, double lam, do
     out[7] = rows;
 }
 
+// ---- elastic net: g(x) = lam |x|_1 + (l2 / 2) |x|^2 ------------------------------------------------------------------------
+// The ridge term is n more rows with phi(t) = (l2 / 2) t^2 at z = x: grad phi = l2 x, so the dual point is alpha times
+// (grad phi(A x), l2 x) with alpha = min(1, lam / |gt|_inf), gt = grad f(x) + l2 x, and phi^*(alpha l2 x_j) = alpha^2 (l2 / 2) x_j^2:
+//   P = f + lam |x|_1 + (l2 / 2) sum x^2            D = D_loss(alpha) - (l2 / 2) alpha^2 sum x^2
+//   rows: the loss part as above                    ridge = (l2 / 2) (1 - alpha)^2 sum x^2
+//   columns = sum_j (lam |x_j| + alpha gt_j x_j)    gap = rows + ridge + columns, every term >= 0 as before
+// gt_j = fma(l2, x_j, g_j) is formed on the fly in both n-passes (16 n bytes each; the same expression, the same bits); the
+// column pass also sums x^2 (a third row of chunk sums).  The eight outputs keep their meaning with |gt|_inf for |g|_inf;
+// [8] = (l2 / 2) sum x^2, [9] = the ridge part of the gap.  The ten values lie in scal[ZF_GS_OUT_ENET ..], sum x^2 in
+// scal[ZF_GS_XX]: slots that the l1 evaluation leaves unused - its kernels, launches and allocations are as they were.
+enum { ZF_GS_XX = 11, ZF_GS_OUT_ENET = 14 };
+static_assert(ZF_GS_ENT < ZF_GS_XX && ZF_GS_XX < ZF_GS_OUT_ENET && ZF_GS_OUT_ENET + 10 <= ZF_GAP_SCAL, "the scalar block holds the ten outputs");
+
+__global__ __launch_bounds__(ZF_BLOCK) void zf_gap_ginf_enet_kernel(const double* __restrict__ g, const double* __restrict__ x, double l2,
+                                                                    int64_t n, double lam, double* __restrict__ part,
+                                                                    double* __restrict__ scal) {
+    __shared__ double lds[2 * ZF_WAVES];
+    int64_t lo, hi;
+    zf_gap_chunk_of(n, lo, hi);
+    double mx = 0.0, bad = 0.0;
+#pragma unroll 4
+    for (int64_t j = lo + threadIdx.x; j < hi; j += ZF_BLOCK) {
+        const double a = fabs(fma(l2, x[j], g[j]));
+        if (!(a <= DBL_MAX)) bad = 1.0;
+        mx = fmax(mx, a);
+    }
+    zf_gap_block_pair<ZF_BLOCK, true>(mx, bad, lds);
+    if (threadIdx.x == 0) {
+        if (gridDim.x == 1) {
+            zf_gap_alpha(mx, bad, lam, scal);
+        } else {
+            part[blockIdx.x] = mx;
+            part[ZF_GAP_MAX_CHUNKS + blockIdx.x] = bad;
+        }
+    }
+}
+
+// columns: sum_j (lam |x_j| + alpha gt_j x_j) term by term, sum |x_j| and sum x_j^2
+__global__ __launch_bounds__(ZF_BLOCK) void zf_gap_cols_enet_kernel(const double* __restrict__ x, const double* __restrict__ g, double l2,
+                                                                    int64_t n, double lam, double* __restrict__ part,
+                                                                    double* __restrict__ scal) {
+    __shared__ double lds[2 * ZF_WAVES];
+    const double alpha = scal[ZF_GS_ALPHA];
+    int64_t lo, hi;
+    zf_gap_chunk_of(n, lo, hi);
+    double cs = 0.0, as = 0.0, xx = 0.0;
+#pragma unroll 4
+    for (int64_t j = lo + threadIdx.x; j < hi; j += ZF_BLOCK) {
+        const double xj = x[j];
+        const double ax = fabs(xj);
+        double t = fma(alpha * fma(l2, xj, g[j]), xj, lam * ax);
+        if (t < 0.0) t = 0.0;
+        if (!(ax <= DBL_MAX)) t = NAN;
+        cs += t;
+        as += ax;
+        xx = fma(xj, xj, xx);
+    }
+    zf_gap_block_pair<ZF_BLOCK, false>(cs, as, lds);
+    __syncthreads();   // (the pair's LDS words are read by every thread: none may be rewritten before)
+    double zero = 0.0;
+    zf_gap_block_pair<ZF_BLOCK, false>(xx, zero, lds);
+    if (threadIdx.x == 0) {
+        if (gridDim.x == 1) {
+            scal[ZF_GS_COLS] = cs;
+            scal[ZF_GS_ASUM] = as;
+            scal[ZF_GS_XX] = xx;
+        } else {
+            part[blockIdx.x] = cs;
+            part[ZF_GAP_MAX_CHUNKS + blockIdx.x] = as;
+            part[2 * ZF_GAP_MAX_CHUNKS + blockIdx.x] = xx;   // (the loss kernels' row: they are done - stream order)
+        }
+    }
+}
+
+// the third row of chunk sums, added in chunk order -> scal[dst]
+__global__ __launch_bounds__(ZF_BLOCK) void zf_gap_sum_third_kernel(const double* __restrict__ part, int count, int dst,
+                                                                    double* __restrict__ scal) {
+    __shared__ double lds[2 * ZF_WAVES];
+    double a = 0.0, b = 0.0;
+    for (int i = threadIdx.x; i < count; i += ZF_BLOCK) a += part[2 * ZF_GAP_MAX_CHUNKS + i];
+    zf_gap_block_pair<ZF_BLOCK, false>(a, b, lds);
+    if (threadIdx.x == 0) scal[dst] = a;
+}
+
+// composition (one thread): [P, D, gap, alpha, |gt|_inf, f, lam |x|_1, rows gap, (l2 / 2) sum x^2, ridge gap]
+__global__ void zf_gap_compose_enet_kernel(int logistic, double scale, double lam, double l2, double* __restrict__ scal) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const double alpha = scal[ZF_GS_ALPHA], oma = scal[ZF_GS_OMA];
+    const double f = scal[ZF_GS_F], g1 = lam * scal[ZF_GS_ASUM], g2 = (0.5 * l2) * scal[ZF_GS_XX];
+    double dual, rows;
+    if (logistic) {
+        dual = -scale * scal[ZF_GS_ENT];
+        rows = scale * scal[ZF_GS_KL];
+    } else {
+        const double rr = scal[ZF_GS_RR];
+        dual = -scale * (alpha * alpha * rr + 2.0 * alpha * scal[ZF_GS_BR]);
+        rows = scale * (oma * oma) * rr;
+    }
+    const double ridge = (oma * oma) * g2;
+    double* out = scal + ZF_GS_OUT_ENET;
+    out[0] = (f + g1) + g2;
+    out[1] = dual - (alpha * alpha) * g2;
+    out[2] = (rows + ridge) + scal[ZF_GS_COLS];
+    out[3] = alpha;
+    out[4] = scal[ZF_GS_GINF];
+    out[5] = f;
+    out[6] = g1;
+    out[7] = rows;
+    out[8] = g2;
+    out[9] = ridge;
+}
+
 // ---- launches -------------------------------------------------------------------------------------------------------------
 // the workspace of one evaluation: rvec (m doubles: r or rho), g (n), part (ZF_GAP_PART), scal (ZF_GAP_SCAL)
 struct zf_gap_ws {
@@ -321,4 +433,27 @@ static inline void zf_launch_gap_tail(hipStream_t st, bool logistic, const doubl
         }
     }
     hipLaunchKernelGGL(zf_gap_compose_kernel, dim3(1), dim3(64), 0, st, logistic ? 1 : 0, scale, lam, ws.scal);
+}
+
+// steps 3 .. 6 of the elastic-net evaluation (l2 > 0), with g = grad f(x) in ws.g; the ten results are left in ws.scal + ZF_GS_OUT_ENET
+static inline void zf_launch_gap_tail_enet(hipStream_t st, bool logistic, const double* z, const double* b, const double* x, int64_t m,
+                                           int64_t n, double scale, double lam, double l2, const zf_gap_ws& ws) {
+    const int nc = zf_gap_chunks(n);
+    hipLaunchKernelGGL(zf_gap_ginf_enet_kernel, dim3(nc), dim3(ZF_BLOCK), 0, st, ws.g, x, l2, n, lam, ws.part, ws.scal);
+    if (nc > 1) hipLaunchKernelGGL(zf_gap_ginf_finish_kernel, dim3(1), dim3(ZF_BLOCK), 0, st, ws.part, nc, lam, ws.scal);
+    hipLaunchKernelGGL(zf_gap_cols_enet_kernel, dim3(nc), dim3(ZF_BLOCK), 0, st, x, ws.g, l2, n, lam, ws.part, ws.scal);
+    if (nc > 1) {
+        hipLaunchKernelGGL(zf_gap_sum_finish_kernel, dim3(1), dim3(ZF_BLOCK), 0, st, ws.part, nc, (int)ZF_GS_COLS, (int)ZF_GS_ASUM, -1.0, ws.scal);
+        hipLaunchKernelGGL(zf_gap_sum_third_kernel, dim3(1), dim3(ZF_BLOCK), 0, st, ws.part, nc, (int)ZF_GS_XX, ws.scal);
+    }
+    if (logistic) {
+        if (!zf_logit_wide(m)) {
+            hipLaunchKernelGGL(zf_gap_kl_kernel<ZF_GAP_ROWS_BLOCK>, dim3(1), dim3(ZF_GAP_ROWS_BLOCK), 0, st, z, b, m, ws.part, ws.scal);
+        } else {
+            const int chunks = zf_spmv_resid_chunks(m);
+            hipLaunchKernelGGL(zf_gap_kl_kernel<ZF_BLOCK>, dim3(chunks), dim3(ZF_BLOCK), 0, st, z, b, m, ws.part, ws.scal);
+            hipLaunchKernelGGL(zf_gap_sum_finish_kernel, dim3(1), dim3(ZF_BLOCK), 0, st, ws.part, chunks, (int)ZF_GS_KL, (int)ZF_GS_ENT, -1.0, ws.scal);
+        }
+    }
+    hipLaunchKernelGGL(zf_gap_compose_enet_kernel, dim3(1), dim3(64), 0, st, logistic ? 1 : 0, scale, lam, l2, ws.scal);
 }

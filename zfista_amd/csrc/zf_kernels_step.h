@@ -94,6 +94,28 @@ __device__ __forceinline__ double zf_elem_vec(double xk, double xo, double grad,
     return xn;
 }
 
+// The elastic-net step: g(x) = lam |x|_1 + (l2 / 2) |x|^2 (+ box), prox = clip(soft_threshold(v, lam lr) * shrink) with
+// shrink = 1 / (1 + l2 lr) formed ONCE per trial (a scalar; the element is multiplied, never divided) - x+ is, bit for bit,
+// NumPy's soft_threshold(v, lam * lr) * (1.0 / (1.0 + l2 * lr)) then the clip.  The clip behind the shrink is the exact prox: the
+// 1-D minimiser projected on the interval.  The fourth sum carries g(x+) itself - lam |x+| + hl2 x+^2, hl2 = l2 / 2 - so its
+// pack scale is 1 and lam = 0 (pure ridge) needs nothing else.  Two VALU operations more than zf_elem_vec per element.
+template <bool NESTEROV, bool BOX>
+__device__ __forceinline__ double zf_elem_vec_enet(double xk, double xo, double grad, double beta, double lr, double tau,
+                                                   double shrink, double lam, double hl2, double lo, double hi, zf_elem_acc& a) {
+    double y = xk;
+    if (NESTEROV) y = xk + beta * (xk - xo);
+    const double v = y - lr * grad;
+    double xn = zf_soft_threshold_nn(v, tau) * shrink;
+    if (BOX) xn = zf_clip(xn, lo, hi);
+    const double dx = xn - y;
+    a.dot = __builtin_fma(grad, dx, a.dot);
+    a.ss = __builtin_fma(dx, dx, a.ss);
+    a.l1 = __builtin_fma(lam, fabs(xn), a.l1);
+    a.l1 = __builtin_fma(hl2 * xn, xn, a.l1);
+    a.mx = zf_max_abs(a.mx, dx);
+    return xn;
+}
+
 // the same step with the variant chosen at run time (the operator problem's adjoint kernel runs it in its epilogue: one
 // kernel per blur size there, not per variant of the step)
 __device__ __forceinline__ double zf_elem_vec_rt(bool nesterov, bool box, double xk, double xo, double grad, double beta, double lr,
@@ -879,11 +901,15 @@ __device__ __forceinline__ zf_pass_head zf_head_of(const zf_control* c) {
 // Returns the workgroup's row: thread t < 6 S holds quantity t % 6 of fresh trial t / 6 (0 for the other threads).
 // COH: the iterates are loaded and stored agent-coherently (sc1, zf_st2_coh) - a run-ahead pass reads what a kernel
 // still running on another XCD has just stored (full chains through the DMA pipeline only; +0.7-1 % per pass, measured)
-template <bool GRAD_INLINE, bool NESTEROV, bool BOX, bool NT, int S, int MODE, bool HIST, int SP = S, bool COH = false, bool RES = false>
+// ENET: the elastic-net step (zf_elem_vec_enet; l2 is a kernel argument of its own - zf_step_args is as it was): single
+// trials on a gradient vector only.  Defaulted: every other instantiation is the one it was.
+template <bool GRAD_INLINE, bool NESTEROV, bool BOX, bool NT, int S, int MODE, bool HIST, int SP = S, bool COH = false, bool RES = false,
+          bool ENET = false>
 __device__ __forceinline__ double zf_trial_body(const zf_step_args& A, double* lds, const zf_pass_head& HD, const int lag,
-                                                const int nf, zf_d2* stage = nullptr) {
+                                                const int nf, zf_d2* stage = nullptr, const double l2 = 0.0) {
     constexpr bool FULL = (MODE == 0);          // nothing replayed, S fresh trials
     static_assert(!RES || GRAD_INLINE, "resolved differences f(x+) - f(y): the separable problem");
+    static_assert(!ENET || (!GRAD_INLINE && S == 1 && MODE == 0 && !COH), "elastic net: single trials on a gradient vector");
     static_assert(!COH || (FULL && !HIST && GRAD_INLINE && SP >= 16 && ZF_S16_GLDS != 0),
                   "coherent iterate traffic: branch-free chains of a 16-chain solver through the DMA pipeline");
     // (a run-ahead mid chain of <= ZF_MID_REG_MAX trials takes the DMA pipeline too: the coherent 16-byte load exists as DMA only)
@@ -908,6 +934,11 @@ __device__ __forceinline__ double zf_trial_body(const zf_step_args& A, double* l
     for (int j = 1; j < S; ++j)
         beta[j] = NESTEROV ? (COH ? zf_uniform_f64(A.beta_ring[(nit + j) % ZF_RING]) : A.beta_ring[(nit + j) % ZF_RING]) : 0.0;
     const double tau = A.lam * lr;   // oracle: soft_threshold(x, lam * weight)
+    double shrink = 1.0, hl2 = 0.0;  // ENET: 1 / (1 + l2 lr), once per trial; l2 / 2
+    if constexpr (ENET) {
+        shrink = 1.0 / (1.0 + l2 * lr);
+        hl2 = 0.5 * l2;
+    }
     // The lagging iterations' parameters, one iteration per LANE (lag <= 31 < 64): replay step i takes its three
     // doubles with v_readlane - no memory access inside the replay loop.  As wave-uniform scalar loads (one per step
     // and load batch) they were a dependent K$ round trip per step, amortised over the 8 element recursions of a
@@ -954,6 +985,9 @@ __device__ __forceinline__ double zf_trial_body(const zf_step_args& A, double* l
                 if (GRAD_INLINE) {
                     r.x = zf_elem_diag<NESTEROV, BOX, RES>(a.x, o.x, q.x, cc.x, beta[j], lr, tau, A.lo, A.hi, acc[j]);
                     r.y = zf_elem_diag<NESTEROV, BOX, RES>(a.y, o.y, q.y, cc.y, beta[j], lr, tau, A.lo, A.hi, acc[j]);
+                } else if constexpr (ENET) {
+                    r.x = zf_elem_vec_enet<NESTEROV, BOX>(a.x, o.x, q.x, beta[j], lr, tau, shrink, A.lam, hl2, A.lo, A.hi, acc[j]);
+                    r.y = zf_elem_vec_enet<NESTEROV, BOX>(a.y, o.y, q.y, beta[j], lr, tau, shrink, A.lam, hl2, A.lo, A.hi, acc[j]);
                 } else {
                     r.x = zf_elem_vec<NESTEROV, BOX>(a.x, o.x, q.x, beta[j], lr, tau, A.lo, A.hi, acc[j]);
                     r.y = zf_elem_vec<NESTEROV, BOX>(a.y, o.y, q.y, beta[j], lr, tau, A.lo, A.hi, acc[j]);
@@ -1235,6 +1269,8 @@ __device__ __forceinline__ double zf_trial_body(const zf_step_args& A, double* l
                     double r;
                     if (GRAD_INLINE)
                         r = zf_elem_diag<NESTEROV, BOX, RES>(a, o, q, cc, beta[j], lr, tau, A.lo, A.hi, acc[j]);
+                    else if constexpr (ENET)
+                        r = zf_elem_vec_enet<NESTEROV, BOX>(a, o, q, beta[j], lr, tau, shrink, A.lam, hl2, A.lo, A.hi, acc[j]);
                     else r = zf_elem_vec<NESTEROV, BOX>(a, o, q, beta[j], lr, tau, A.lo, A.hi, acc[j]);
                     o = a;
                     a = r;
@@ -1446,6 +1482,19 @@ __global__ __launch_bounds__(ZF_BLOCK) void zf_trial_kernel(zf_step_args A) {
         }
         zf_pass_finish<S>(A, v);
     }
+}
+
+// The elastic-net trial (zf_solver_set_l2 with l2 > 0): the single trial of zf_trial_kernel<false, ..., 1> - the same head, the
+// same tile walk, the same row of six partials stored plainly for the zf_finalize_kernel launch that follows - with the step
+// of zf_elem_vec_enet.  The fourth partial is g(x+) itself: its pack scale is 1.  Nontemporal policy; HIST as there.
+template <bool NESTEROV, bool BOX, bool HIST>
+__global__ __launch_bounds__(ZF_BLOCK) void zf_trial_enet_kernel(zf_step_args A, double l2) {
+    __shared__ double lds[ZF_WAVES * ZF_NPART];
+    if (A.ctl->status != ZF_RUNNING) return;
+    const zf_pass_head HD = zf_head_of(A.ctl);
+    if (A.pass_log && blockIdx.x == 0 && threadIdx.x == 0) A.pass_log[A.pass_slot] = A.pass_tag | zf_log_shape(0, 1, 0);
+    const double v = zf_trial_body<false, NESTEROV, BOX, true, 1, 0, HIST, 1, false, false, true>(A, lds, HD, 0, 1, nullptr, l2);
+    if (threadIdx.x < ZF_NPART) A.blk_part[(int64_t)threadIdx.x * gridDim.x + blockIdx.x] = v;   // (fin_mode 0: the vector path)
 }
 
 // A RUN-AHEAD full chain (zf_runahead_kernel).  Consecutive full-chain passes of a grid the device holds at once are launched

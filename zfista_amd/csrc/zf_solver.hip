@@ -112,6 +112,28 @@ __global__ void zf_refresh_beta_kernel(zf_control* ctl, const double* beta_ring)
 }
 
 // initial F(x0): partials [f raw, |x|_1, violations] -> init pack [f, g, 0...]
+// elastic net: g(x0) = sum (lam |x| + (l2 / 2) x^2) in the partials row of |x|_1 (zf_eval_kernel's layout: [0] unused - f comes
+// from the margins - [1] g  [2] box violations), term by term as zf_elem_vec_enet forms g(x+); zf_init_finalize_kernel
+// then takes it with lam = 1
+template <bool BOX>
+__global__ __launch_bounds__(ZF_BLOCK) void zf_eval_enet_kernel(const double* __restrict__ x, double lam, double hl2, double lo, double hi,
+                                                                int64_t n, double* partials) {
+    __shared__ double lds[ZF_WAVES * 3];
+    double g = 0.0, viol = 0.0;
+    const int64_t stride = (int64_t)gridDim.x * ZF_BLOCK;
+    for (int64_t i = (int64_t)blockIdx.x * ZF_BLOCK + threadIdx.x; i < n; i += stride) {
+        const double xv = x[i];
+        g = __builtin_fma(lam, fabs(xv), g);
+        g = __builtin_fma(hl2 * xv, xv, g);
+        if (BOX) viol += (xv < lo || xv > hi) ? 1.0 : 0.0;
+    }
+    const double sums[3] = {0.0, g, viol};
+    const double maxs[1] = {0.0};
+    double out = 0.0;
+    zf_block_reduce<3, 0, ZF_WAVES>(sums, maxs, lds, out);
+    if (threadIdx.x < 3) partials[(int64_t)threadIdx.x * gridDim.x + blockIdx.x] = out;
+}
+
 struct zf_init_args {
     const double* partials;
     int nblocks;
@@ -199,6 +221,7 @@ struct zf_solver {
     bool own_packs = true;
     bool gemv_mfma = false;       // A^T r on v_mfma_f64_16x16x4 (n % 32 == 0; ZF_GEMV_MFMA=0 disables)
     bool ls_small = false;        // cache-resident A: two fused launches per trial (zf_kernels_ls_small.h)
+    double l2 = 0.0;              // elastic net (zf_solver_set_l2): g = lam |x|_1 + (l2 / 2) |x|^2; 0: every path is the l1 one
     const zf_spmat* spmat = nullptr;   // sparse least squares: A and A^T with their plans (the caller's handle: zf_solver_create_sparse; never written through)
     double* sp_part_A = nullptr, *sp_part_At = nullptr;   // ... this solver's segment sums of the split rows of A / of A^T
     zf_op_plan op_plan = {};      // operator problem: which instantiation of the correlation kernels runs it (zf_op_make_plan)
@@ -744,7 +767,8 @@ static void zf_launch_trial_kernels(zf_solver* s, const zf_step_args& a, bool gr
     const int grid = s->grid;
     hipStream_t st = s->stream;
     if (!grad_inline) {   // least squares: one trial per pass
-        if (s->hist) zf_launch_hist(v, false, 1, 0, grid, st, a);
+        if (s->l2 > 0.0) zf_launch_enet(v, s->hist != nullptr, grid, st, a, s->l2);
+        else if (s->hist) zf_launch_hist(v, false, 1, 0, grid, st, a);
         else zf_launch_vec(v, grid, st, a);
         return;
     }
@@ -795,6 +819,7 @@ static void zf_launch_finalize(zf_solver* s, bool decide) {
     F.cnt = s->fin_cnt;
     for (int k = 0; k < ZF_NPART; ++k) F.scale[k] = 1.0;
     F.scale[3] = d.lam;               // g = lam * sum|x|
+    if (s->l2 > 0.0) F.scale[3] = 1.0;   // (elastic net: the fourth sum is g(x+) itself, zf_elem_vec_enet)
     F.f_y_ext = nullptr;
     F.f_x_ext = nullptr;
     F.r_ext = nullptr;
@@ -1553,7 +1578,14 @@ static int zf_init_ls_tail(zf_solver* s) {
                            m, s->ls_scal + 1);
     }
     const int g = zf_grid_for(n);
-    if (s->box)
+    if (s->l2 > 0.0) {   // (x0 != 0 on every warm start of a path)
+        if (s->box)
+            hipLaunchKernelGGL(zf_eval_enet_kernel<true>, dim3(g), dim3(ZF_BLOCK), 0, s->stream, s->xb[0], d.lam, 0.5 * s->l2, d.box_lo,
+                               d.box_hi, n, s->partials);
+        else
+            hipLaunchKernelGGL(zf_eval_enet_kernel<false>, dim3(g), dim3(ZF_BLOCK), 0, s->stream, s->xb[0], d.lam, 0.5 * s->l2, d.box_lo,
+                               d.box_hi, n, s->partials);
+    } else if (s->box)
         hipLaunchKernelGGL((zf_eval_kernel<false, true>), dim3(g), dim3(ZF_BLOCK), 0, s->stream, s->xb[0], nullptr,
                            nullptr, d.box_lo, d.box_hi, n, s->partials);
     else
@@ -1563,7 +1595,7 @@ static int zf_init_ls_tail(zf_solver* s) {
     I.partials = s->partials;
     I.nblocks = g;
     I.f_scale = 0.0;
-    I.lam = d.lam;
+    I.lam = s->l2 > 0.0 ? 1.0 : d.lam;
     I.f_ext = s->ls_scal + 1;
     I.pack = s->pack_local;
     I.contribute_g = (d.world == 1 || !d.row_sharded || d.rank == 0) ? 1 : 0;
@@ -1811,6 +1843,22 @@ extern "C" int zf_solver_set_history(zf_solver* s, double* hist_dev, int64_t cap
     s->hist = hist_dev;
     s->hist_cap = cap_slots;
     s->hist_stride = stride;
+    return ZF_OK;
+}
+
+// Elastic net (include/zfista_hip.h): between create and init.  l2 = 0 leaves the solver as it was created.
+extern "C" int zf_solver_set_l2(zf_solver* s, double l2) {
+    ZF_REQUIRE(s, "zf_solver_set_l2: null argument");
+    if (s->init_enqueued || s->initialised)
+        return zf_fail(ZF_ERR_STATE, "zf_solver_set_l2: call after zf_solver_create and before zf_solver_enqueue_init / zf_solver_restore%s%s");
+    const zf_problem_desc& d = s->desc;
+    ZF_REQUIRE(zf_is_dense_mat(d.kind) || zf_is_sparse_mat(d.kind),
+               "zf_solver_set_l2: only for ZF_PROBLEM_LEAST_SQUARES_L1, ZF_PROBLEM_SPARSE_LS_L1, ZF_PROBLEM_LOGISTIC_L1 and "
+               "ZF_PROBLEM_SPARSE_LOGISTIC_L1");
+    ZF_REQUIRE(d.world == 1, "zf_solver_set_l2: not for a sharded solve (world > 1)");
+    ZF_REQUIRE(l2 >= 0.0 && l2 <= DBL_MAX, "zf_solver_set_l2: l2 must be finite and >= 0");
+    s->l2 = l2;
+    if (l2 > 0.0) s->ls_small = false;   // (the fused small-matrix kernels hold the l1 step: the general path, as the logistic kind)
     return ZF_OK;
 }
 
@@ -2638,8 +2686,10 @@ static void zf_gap_ws_free(zf_gap_ws* ws) {
 // dense (h == NULL) or CSR matrix; x from the host
 // scr != NULL (zf_gap_screen_eval / zf_spmat_gap_screen_eval): the screen of zf_kernels_screen.h over the call's g behind the
 // same sequence - its four scalars follow the eight outputs; scr->cnt and scr->scal are allocated here
+// l2 > 0: the elastic-net evaluation (zf_launch_gap_tail_enet), ten outputs when out_count >= 10
 static int zf_gap_eval_impl(const double* A_dev, const zf_spmat* h, const double* b_dev, int64_t m, int64_t n, double scale, double lam,
-                            bool logistic, const double* x_host, double* out, const zf_screen_req* scr = nullptr) {
+                            bool logistic, const double* x_host, double* out, const zf_screen_req* scr = nullptr, double l2 = 0.0,
+                            int64_t out_count = 8) {
     zf_gap_ws ws = {nullptr, nullptr, nullptr, nullptr};
     double *x = nullptr, *z = nullptr, *slab = nullptr, *part_A = nullptr, *part_At = nullptr, *scr_scal = nullptr;
     int32_t* scr_cnt = nullptr;
@@ -2685,7 +2735,8 @@ static int zf_gap_eval_impl(const double* A_dev, const zf_spmat* h, const double
         } else {
             zf_gap_dense_sweep(nullptr, A_dev, ws.rvec, slab, ws.g, m, n, (int)slices, rps, n % 32 == 0 && zf_env_read().gemv_mfma, gfac);
         }
-        zf_launch_gap_tail(nullptr, logistic, z, b_dev, x, m, n, scale, lam, ws);
+        if (l2 > 0.0) zf_launch_gap_tail_enet(nullptr, logistic, z, b_dev, x, m, n, scale, lam, l2, ws);
+        else zf_launch_gap_tail(nullptr, logistic, z, b_dev, x, m, n, scale, lam, ws);
         if (scr) {
             zf_screen_req rq = *scr;
             rq.cnt = scr_cnt;
@@ -2693,7 +2744,10 @@ static int zf_gap_eval_impl(const double* A_dev, const zf_spmat* h, const double
             zf_launch_screen(nullptr, rq, ws.g, ws.scal + ZF_GS_OUT, ws.scal + ZF_GS_ASUM, ws.scal + ZF_GS_RR, m, n, scale, lam, logistic);
         }
         ZF_GAP_TRY(hipGetLastError());
-        ZF_GAP_TRY(hipMemcpyAsync(out, ws.scal + ZF_GS_OUT, sizeof(double) * 8, hipMemcpyDeviceToHost, nullptr));
+        if (l2 > 0.0)
+            ZF_GAP_TRY(hipMemcpyAsync(out, ws.scal + ZF_GS_OUT_ENET, sizeof(double) * (out_count >= 10 ? 10 : 8), hipMemcpyDeviceToHost, nullptr));
+        else
+            ZF_GAP_TRY(hipMemcpyAsync(out, ws.scal + ZF_GS_OUT, sizeof(double) * 8, hipMemcpyDeviceToHost, nullptr));
         if (scr) ZF_GAP_TRY(hipMemcpyAsync(out + 8, scr_scal, sizeof(double) * ZF_SCREEN_SCAL, hipMemcpyDeviceToHost, nullptr));
         ZF_GAP_TRY(hipStreamSynchronize(nullptr));
     }
@@ -2718,6 +2772,31 @@ extern "C" int zf_spmat_gap_eval(const zf_spmat* h, const double* b_dev, double 
     ZF_REQUIRE(count >= 8, "zf_spmat_gap_eval: the output buffer holds fewer than 8 doubles");
     ZF_REQUIRE(scale > 0.0 && lam >= 0.0, "zf_spmat_gap_eval: needs scale > 0 and lam >= 0");
     return zf_gap_eval_impl(nullptr, h, b_dev, h->m, h->n, scale, lam, logistic != 0, x_host, out);
+}
+
+// the elastic-net forms (l2 >= 0; l2 = 0 runs the l1 evaluation above - its kernels, its eight values - and writes [8] = [9] = 0)
+static void zf_gap_pad_l1(double l2, double* out, int64_t count) {
+    if (!(l2 > 0.0) && count >= 10) out[8] = out[9] = 0.0;
+}
+extern "C" int zf_gap_eval_enet(const double* A_dev, const double* b_dev, int64_t m_rows, int64_t n, double scale, double lam, double l2,
+                                int32_t logistic, const double* x_host, double* out, int64_t count) {
+    ZF_REQUIRE(A_dev && b_dev && x_host && out && m_rows >= 1 && n >= 1, "zf_gap_eval_enet: bad argument");
+    ZF_REQUIRE(count >= 8, "zf_gap_eval_enet: the output buffer holds fewer than 8 doubles");
+    ZF_REQUIRE(scale > 0.0 && lam >= 0.0 && l2 >= 0.0 && l2 <= DBL_MAX, "zf_gap_eval_enet: needs scale > 0, lam >= 0 and a finite l2 >= 0");
+    ZF_REQUIRE(zf_aligned16(A_dev), "zf_gap_eval_enet: A must be 16-byte aligned");
+    const int rc = zf_gap_eval_impl(A_dev, nullptr, b_dev, m_rows, n, scale, lam, logistic != 0, x_host, out, nullptr, l2, count);
+    if (rc == ZF_OK) zf_gap_pad_l1(l2, out, count);
+    return rc;
+}
+
+extern "C" int zf_spmat_gap_eval_enet(const zf_spmat* h, const double* b_dev, double scale, double lam, double l2, int32_t logistic,
+                                      const double* x_host, double* out, int64_t count) {
+    ZF_REQUIRE(h && b_dev && x_host && out, "zf_spmat_gap_eval_enet: null argument");
+    ZF_REQUIRE(count >= 8, "zf_spmat_gap_eval_enet: the output buffer holds fewer than 8 doubles");
+    ZF_REQUIRE(scale > 0.0 && lam >= 0.0 && l2 >= 0.0 && l2 <= DBL_MAX, "zf_spmat_gap_eval_enet: needs scale > 0, lam >= 0 and a finite l2 >= 0");
+    const int rc = zf_gap_eval_impl(nullptr, h, b_dev, h->m, h->n, scale, lam, logistic != 0, x_host, out, nullptr, l2, count);
+    if (rc == ZF_OK) zf_gap_pad_l1(l2, out, count);
+    return rc;
 }
 
 // the gap evaluation followed by the gap-safe screen of its g (zf_kernels_screen.h): out[0 .. 8) as zf_gap_eval - the same
@@ -2793,6 +2872,13 @@ extern "C" int zf_solver_duality_gap(zf_solver* s, double* out, int64_t count) {
         zf_launch_spmv(s->spmat->At, s->stream, nullptr, false, gio, -1, gfac, s->sp_part_At);
     } else {
         zf_gap_dense_sweep(s->stream, d.A, ws.rvec, s->slab, ws.g, m, n, s->slices, s->rows_per_slice, s->gemv_mfma, gfac);
+    }
+    if (s->l2 > 0.0) {   // (elastic net: ten values when the caller's buffer holds them)
+        zf_launch_gap_tail_enet(s->stream, logistic, z, d.b, x, m, n, d.scale, d.lam, s->l2, ws);
+        ZF_HIP(hipGetLastError());
+        ZF_HIP(hipMemcpyAsync(out, ws.scal + ZF_GS_OUT_ENET, sizeof(double) * (count >= 10 ? 10 : 8), hipMemcpyDeviceToHost, s->stream));
+        ZF_HIP(hipStreamSynchronize(s->stream));
+        return ZF_OK;
     }
     zf_launch_gap_tail(s->stream, logistic, z, d.b, x, m, n, d.scale, d.lam, ws);
     ZF_HIP(hipGetLastError());

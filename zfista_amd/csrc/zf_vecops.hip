@@ -461,6 +461,71 @@ extern "C" int zf_host_asum(const double* x_host, int64_t n, double* out) {
     return ZF_OK;
 }
 
+// ---- elastic net at a host point: prox and g of lam |x|_1 + (l2 / 2) |x|^2 (+ box) -------------------------------------------
+namespace {
+__global__ __launch_bounds__(ZF_BLOCK) void k_prox_enet_box(double* __restrict__ out, const double* __restrict__ x, double tau,
+                                                            double shrink, double lo, double hi, int64_t n) {
+    const int64_t stride = (int64_t)gridDim.x * ZF_BLOCK;
+    // NumPy's expression, operation by operation - sign(u) * maximum(|u| - tau, 0), times shrink, clipped - so that the
+    // callable matches the reference closure in every bit for every input: np.sign(-0.0) is +0 (the solver's threshold copies
+    // the sign of u, which differs there and only there, in the sign of a zero), NaN and inf - inf propagate
+    for (int64_t i = (int64_t)blockIdx.x * ZF_BLOCK + threadIdx.x; i < n; i += stride) {
+        const double u = x[i];
+        const double s = (u > 0.0) ? 1.0 : (u < 0.0) ? -1.0 : (u == 0.0) ? 0.0 : u;
+        double a = fabs(u) - tau;
+        a = (a < 0.0) ? 0.0 : a;
+        out[i] = zf_clip((s * a) * shrink, lo, hi);
+    }
+}
+__global__ __launch_bounds__(ZF_BLOCK) void k_enet_g(const double* __restrict__ x, int64_t n, double lam, double hl2, double* partials) {
+    __shared__ double lds[ZF_WAVES];
+    double g = 0.0;
+    const int64_t stride = (int64_t)gridDim.x * ZF_BLOCK;
+    for (int64_t i = (int64_t)blockIdx.x * ZF_BLOCK + threadIdx.x; i < n; i += stride) {
+        const double xv = x[i];
+        g = __builtin_fma(lam, fabs(xv), g);
+        g = __builtin_fma(hl2 * xv, xv, g);
+    }
+    const double sums[1] = {g};
+    const double maxs[1] = {0.0};
+    double out = 0.0;
+    zf_block_reduce<1, 0, ZF_WAVES>(sums, maxs, lds, out);
+    if (threadIdx.x == 0) partials[blockIdx.x] = out;
+}
+}  // namespace
+
+extern "C" int zf_host_prox_enet_box(double* out_host, const double* x_host, double tau, double shrink, double lo, double hi,
+                                     int64_t n) {
+    ZF_REQUIRE(out_host && x_host && n >= 0, "zf_host_prox_enet_box: bad argument");
+    if (n == 0) return ZF_OK;
+    int rc = zf_ws_reserve(n);
+    if (rc) return rc;
+    const size_t bytes = sizeof(double) * n;
+    ZF_HIP(hipMemcpyAsync(g_ws.buf[0], x_host, bytes, hipMemcpyHostToDevice, nullptr));
+    hipLaunchKernelGGL(k_prox_enet_box, dim3(zf_grid_for(n)), dim3(ZF_BLOCK), 0, nullptr, g_ws.buf[1], g_ws.buf[0], tau, shrink, lo,
+                       hi, n);
+    ZF_HIP(hipGetLastError());
+    ZF_HIP(hipMemcpyAsync(out_host, g_ws.buf[1], bytes, hipMemcpyDeviceToHost, nullptr));
+    ZF_HIP(hipStreamSynchronize(nullptr));
+    return ZF_OK;
+}
+
+extern "C" int zf_host_enet_g(const double* x_host, int64_t n, double lam, double l2, double* out) {
+    ZF_REQUIRE(x_host && out && n >= 0, "zf_host_enet_g: bad argument");
+    *out = 0.0;
+    if (n == 0) return ZF_OK;
+    int rc = zf_ws_reserve(n);
+    if (rc) return rc;
+    ZF_HIP(hipMemcpyAsync(g_ws.buf[0], x_host, sizeof(double) * n, hipMemcpyHostToDevice, nullptr));
+    const int g = zf_grid_for(n);
+    hipLaunchKernelGGL(k_enet_g, dim3(g), dim3(ZF_BLOCK), 0, nullptr, g_ws.buf[0], n, lam, 0.5 * l2, g_ws.partials);
+    hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(256), 0, nullptr, g_ws.partials, g, 1, -1, g_ws.out);
+    ZF_HIP(hipGetLastError());
+    ZF_HIP(hipMemcpyAsync(out, g_ws.out, sizeof(double), hipMemcpyDeviceToHost, nullptr));
+    ZF_HIP(hipStreamSynchronize(nullptr));
+    return ZF_OK;
+}
+
 // Release the staging workspaces of the host-pointer entry points (all threads, all devices).  Call
 // when no zf_host_* / zf_dev_* call is in flight; later calls allocate again.
 extern "C" int zf_shutdown(void) {

@@ -79,8 +79,9 @@ class DeviceSolver:
         self.stream = stream
         d = _lib.ProblemDesc()
         spmat = desc_fields.get("spmat")   # a zf_spmat handle: the matrix of a sparse problem is no descriptor field
+        l2 = float(desc_fields.get("l2", 0.0) or 0.0)   # elastic net: no descriptor field either (zf_solver_set_l2)
         for k, v in desc_fields.items():
-            if k != "spmat":
+            if k not in ("spmat", "l2"):
                 setattr(d, k, v)
         o = _lib.Options()
         for k, v in options.items():
@@ -94,6 +95,9 @@ class DeviceSolver:
             _lib.check(self.lib.zf_solver_create(C.byref(h), C.byref(d), C.byref(o), C.c_void_p(stream)),
                        "zf_solver_create")
         self.handle = h
+        self.l2 = l2
+        if l2 > 0:
+            _lib.check(self.lib.zf_solver_set_l2(h, l2), "zf_solver_set_l2")
         sub = C.c_int32(1)
         _lib.check(self.lib.zf_solver_sub_iters(h, C.byref(sub)), "zf_solver_sub_iters")
         self.sub_iters = int(sub.value)   # iterations one pass may accept (temporal blocking)
@@ -259,8 +263,8 @@ class DeviceSolver:
 
     def duality_gap(self) -> np.ndarray:
         """[P, D, gap, alpha, |grad f|_inf, f, lam |x|_1, rows gap] at the current x_k (zf_solver_duality_gap: synchronises
-        the stream; the solve is not altered)."""
-        out = np.zeros(8)
+        the stream; the solve is not altered); an elastic-net solver (l2 > 0): ten values, [(l2 / 2) |x|^2, ridge gap] behind them."""
+        out = np.zeros(10 if self.l2 > 0 else 8)
         _lib.check(self.lib.zf_solver_duality_gap(self.handle, C.c_void_p(_lib.ptr(out)), out.size), "zf_solver_duality_gap")
         return out
 

@@ -12,9 +12,11 @@ import numpy as np
 from .proximal_gradient import minimize_proximal_gradient
 
 
-def l1_path(problem, lams, x0=None, gap_tol=1e-6, screen=False, **solver_kwargs):
+def l1_path(problem, lams, x0=None, gap_tol=1e-6, screen=False, l2=None, **solver_kwargs):
     """Solve ``problem.with_lam(l)`` for each ``l`` of ``lams`` in the order given, each from the solution of the one
     before (the first from ``x0``; default zeros), with ``minimize_proximal_gradient(..., gap_tol=gap_tol, **solver_kwargs)``.
+    ``l2``: the ridge weight of an elastic-net path - a scalar, or one value per ``l`` - and the points are
+    ``problem.with_penalty(l, l2)``; None (default) keeps the problem's own ``l2``.  Not with ``screen=True`` while ``l2 > 0``.
     ``screen=True``: each point is solved by ``zfista_amd.screening.solve_screened`` instead - gap-safe screening, and solves
     on the kept columns only (``solver_kwargs`` may then carry its ``screen_ratio``, ``screen_shrink`` and ``max_rounds``).
 
@@ -24,9 +26,21 @@ def l1_path(problem, lams, x0=None, gap_tol=1e-6, screen=False, **solver_kwargs)
     if not getattr(problem, "has_duality_gap", False):
         raise ValueError("l1_path needs a LeastSquaresL1, SparseLeastSquaresL1, LogisticL1 or SparseLogisticL1")
     x = np.zeros(problem.n_features) if x0 is None else x0
+    lams = list(lams)
+    if l2 is None:
+        l2s = [None] * len(lams)
+    elif np.ndim(l2) == 0:
+        l2s = [float(l2)] * len(lams)
+    else:
+        l2s = [float(v) for v in np.asarray(l2, dtype=np.float64).reshape(-1)]
+        if len(l2s) != len(lams):
+            raise ValueError(f"l2 must be a scalar or hold one value per lam ({len(lams)}), got {len(l2s)}")
+    if screen and any((problem.l2 if v is None else v) > 0 for v in l2s):
+        raise ValueError("l1_path(screen=True) is not available with l2 > 0: the gap-safe rule of the elastic net and its rounding "
+                         "guard are not built yet")
     out = []
-    for lam in lams:
-        sib = problem.with_lam(lam)
+    for lam, ridge in zip(lams, l2s):
+        sib = problem.with_lam(lam) if ridge is None else problem.with_penalty(lam, ridge)
         if screen:
             from .screening import solve_screened
 
@@ -34,6 +48,8 @@ def l1_path(problem, lams, x0=None, gap_tol=1e-6, screen=False, **solver_kwargs)
         else:
             res = minimize_proximal_gradient(*sib.callbacks(), x, gap_tol=gap_tol, **solver_kwargs)
         res["lam"] = float(lam)
+        if sib.l2 > 0:
+            res["l2"] = float(sib.l2)
         out.append(res)
         x = res.x
     return out

@@ -140,11 +140,16 @@ class DualityGap:
     D(nu) at the dual point nu = alpha grad phi(A x), ``gap`` >= 0 - the sum of the two Fenchel-Young gaps, formed term by
     term (csrc/zf_kernels_gap.h), not ``primal - dual`` - ``alpha`` = min(1, lam / |grad f(x)|_inf) and ``grad_inf`` =
     |grad f(x)|_inf; also ``f``, ``g_l1`` = lam |x|_1 and ``rows_gap`` (the loss part of the gap; ``gap - rows_gap`` is the
-    l1 part).  ``P(x) - min P <= gap``."""
+    l1 part).  ``P(x) - min P <= gap``.
 
-    __slots__ = ("primal", "dual", "gap", "alpha", "grad_inf", "f", "g_l1", "rows_gap")
+    Elastic net (``l2 > 0``): P also holds ``g_l2`` = (l2 / 2) |x|^2, the ridge term enters the dual as n more least-squares
+    rows, ``grad_inf`` = |grad f(x) + l2 x|_inf, and ``ridge_gap`` = (l2 / 2) (1 - alpha)^2 |x|^2 is their part of the gap
+    (``gap - rows_gap - ridge_gap`` is the l1 part).  Both are 0 for an l1 problem."""
+
+    __slots__ = ("primal", "dual", "gap", "alpha", "grad_inf", "f", "g_l1", "rows_gap", "g_l2", "ridge_gap")
 
     def __init__(self, out):
+        self.g_l2 = self.ridge_gap = np.float64(0.0)
         for k, v in zip(self.__slots__, out):
             setattr(self, k, np.float64(v))
 
@@ -180,12 +185,51 @@ def _dp(t):
     return C.c_void_p(t.data_ptr() if t is not None and t.numel() else None)
 
 
+def _check_l2(l2, group=None):
+    """The ridge weight of an elastic-net penalty as a float: finite and >= 0, and 0 for a sharded problem."""
+    l2 = float(l2)
+    if not (np.isfinite(l2) and l2 >= 0):
+        raise ValueError(f"l2 must be finite and >= 0 (the weight of (l2 / 2) |x|^2 in g), got {l2!r}")
+    if l2 > 0 and group is not None:
+        raise ValueError("l2 > 0 is not available with group=: the elastic-net step and its certificate are built for one GPU")
+    return l2
+
+
 class _GapMixin:
     """Duality-gap certificate, lam_max, same-matrix siblings, gap-safe screening and column restriction of the four margins
     classes (LeastSquaresL1, SparseLeastSquaresL1, LogisticL1, SparseLogisticL1)."""
 
     has_duality_gap = True
     _gap_logistic = 0
+    l2 = 0.0   # elastic net: g(x) = lam |x|_1 + (l2 / 2) |x|^2 (+ box)
+
+    # -- g / prox with the ridge term (l2 = 0: the shared l1 forms, the same calls as before) --------------------
+    def prox_wsum_g(self, weight, x):
+        if not self.l2 > 0:
+            return NativeProblem.prox_wsum_g(self, weight, x)
+        x = _as_host(x)
+        out = np.empty_like(x)
+        lib = _lib.require_gpu()
+        shrink = 1.0 / (1.0 + self.l2 * weight)   # once, a scalar: the kernel multiplies
+        _lib.check(lib.zf_host_prox_enet_box(C.c_void_p(_lib.ptr(out)), C.c_void_p(_lib.ptr(x)), float(self.lam * weight),
+                                             float(shrink), self.box[0], self.box[1], x.size), "zf_host_prox_enet_box")
+        return out
+
+    def _eval_fg(self, x):
+        lib = _lib.require_gpu()
+        s = C.c_double(0.0)
+        if self.l2 > 0:
+            _lib.check(lib.zf_host_enet_g(C.c_void_p(_lib.ptr(x)), x.size, self.lam, self.l2, C.byref(s)), "zf_host_enet_g")
+            return None, np.float64(s.value)
+        _lib.check(lib.zf_host_asum(C.c_void_p(_lib.ptr(x)), x.size, C.byref(s)), "zf_host_asum")
+        return None, np.float64(self.lam * s.value)
+
+    def _screen_refusal(self):
+        """Why this problem cannot be screened (None: it can)."""
+        if self.l2 > 0:
+            return ("l2 > 0: the gap-safe rule of the elastic net (alpha |gt_j| against sqrt(2 gap) sqrt(L |a_j|^2 + l2)) and its "
+                    "rounding guard are not built yet")
+        return self._gap_refusal()
 
     def column_norms(self):
         """|a_j|_2 of every column of A: a float64 CUDA tensor of n_features, computed on the GPU once per matrix."""
@@ -206,7 +250,7 @@ class _GapMixin:
         zero at every optimum.  ``gap`` is, bit for bit, ``duality_gap(x)``."""
         import torch
 
-        why = self._gap_refusal()
+        why = self._screen_refusal()
         if why:
             raise ValueError(f"screen is not available: {why}")
         if type(x).__module__.split(".")[0] == "torch":
@@ -287,7 +331,7 @@ class _GapMixin:
         x = _as_host(x)
         if x.size != self.n_features:
             raise ValueError(f"len(x) should be equal to n_features, got {x}.")
-        out = np.zeros(8)
+        out = np.zeros(10 if self.l2 > 0 else 8)
         self._gap_call(_lib.require_gpu(), x, out)
         return DualityGap(out)
 
@@ -304,16 +348,24 @@ class _GapMixin:
         sib.lam = float(lam)
         return sib
 
+    def with_penalty(self, lam, l2):
+        """``with_lam`` for both weights of the elastic net: the sibling with g = lam |x|_1 + (l2 / 2) |x|^2 on the same device
+        matrix, b and matrix handle; nothing is uploaded."""
+        sib = self.with_lam(lam)
+        sib.l2 = _check_l2(l2, getattr(self, "group", None))
+        return sib
+
 
 class _DenseMarginsL1(_GapMixin, NativeProblem):
-    """What the dense single-GPU problems f(x) = scale * sum_i loss_i((Ax)_i), g = lam |x|_1 (+ box) share: A (m x n, dense
+    """What the dense single-GPU problems f(x) = scale * sum_i loss_i((Ax)_i), g = lam |x|_1 (+ (l2 / 2) |x|^2) (+ box) share: A (m x n, dense
     row-major) and the m-vector b in HBM, f / jac_f at a host vector through the entry point the subclass names, the
     descriptor of one GPU.  The loss is the subclass's: its ``kind``, its ``_eval_name``, what b means."""
 
     kind = None
     _eval_name = None   # f and jac_f at a host vector
 
-    def _set(self, A, b, lam, scale, bounds):
+    def _set(self, A, b, lam, scale, bounds, l2=0.0):
+        self.l2 = _check_l2(l2)
         self.A = _to_device(A, "A")
         self.b = _to_device(b, "b")
         if self.A.ndim != 2 or self.b.ndim != 1 or self.A.shape[0] != self.b.shape[0]:
@@ -359,6 +411,11 @@ class _DenseMarginsL1(_GapMixin, NativeProblem):
         return np.float64(fval.value), grad
 
     def _gap_call(self, lib, x, out):
+        if self.l2 > 0:
+            _lib.check(lib.zf_gap_eval_enet(C.c_void_p(self.A.data_ptr()), C.c_void_p(self.b.data_ptr()), self.m_rows, self.n_features,
+                                            self.scale, self.lam, self.l2, self._gap_logistic, C.c_void_p(_lib.ptr(x)),
+                                            C.c_void_p(_lib.ptr(out)), out.size), "zf_gap_eval_enet")
+            return
         _lib.check(lib.zf_gap_eval(C.c_void_p(self.A.data_ptr()), C.c_void_p(self.b.data_ptr()), self.m_rows, self.n_features,
                                    self.scale, self.lam, self._gap_logistic, C.c_void_p(_lib.ptr(x)), C.c_void_p(_lib.ptr(out)),
                                    out.size), "zf_gap_eval")
@@ -369,16 +426,12 @@ class _DenseMarginsL1(_GapMixin, NativeProblem):
     def jac_f(self, x):
         return self._ls(x, True)[1]
 
-    def _eval_fg(self, x):
-        lib = _lib.require_gpu()
-        s = C.c_double(0.0)
-        _lib.check(lib.zf_host_asum(C.c_void_p(_lib.ptr(x)), x.size, C.byref(s)), "zf_host_asum")
-        return None, np.float64(self.lam * s.value)
-
     def _descriptor(self, rank=0, world=1, row_sharded=0):
         fields = dict(kind=self.kind, world=world, rank=rank, n=self.n_features, m_rows=self.m_rows, row_sharded=row_sharded,
                       d=None, c=None, A=self.A.data_ptr(), b=self.b.data_ptr(),
                       scale=self.scale, lam=self.lam, box_lo=self.box[0], box_hi=self.box[1])
+        if self.l2 > 0:
+            fields["l2"] = self.l2   # (no descriptor field: the engine calls zf_solver_set_l2)
         return fields, (self.A, self.b)
 
 
@@ -393,7 +446,7 @@ class LeastSquaresL1(_DenseMarginsL1):
     _eval_name = "zf_ls_eval"
     taylor_remainder = True   # acceptance="remainder": R = scale |A (x+ - y)|^2 from the residual kernels at x+
 
-    def __init__(self, A, b, lam, scale=0.5, bounds=None, group=None, shard="columns"):
+    def __init__(self, A, b, lam, scale=0.5, bounds=None, group=None, shard="columns", l2=0.0):
         """With ``group`` set and ``shard="columns"`` (default), ``A`` is this rank's column block A_p
         (m x n_p, row-major) of a matrix whose columns - and the decision vector - are partitioned
         over the ranks of that process group; ``b`` is replicated; the solve exchanges the m-vector
@@ -404,7 +457,8 @@ class LeastSquaresL1(_DenseMarginsL1):
         if shard not in ("columns", "rows"):
             raise ValueError("shard must be 'columns' or 'rows'")
         self.shard = shard
-        self._set(A, b, lam, scale, bounds)
+        _check_l2(l2, group)
+        self._set(A, b, lam, scale, bounds, l2)
         self.group = group
 
     def _descriptor(self):
@@ -458,10 +512,12 @@ class _SparseMarginsL1(_GapMixin, NativeProblem):
     kind = None
     _eval_name = None
 
-    def _set(self, A, b, lam, scale, bounds):
+    def _set(self, A, b, lam, scale, bounds, l2=0.0):
         import torch
 
         from . import sparse
+
+        self.l2 = _check_l2(l2)
 
         b_host = b.detach().cpu().numpy() if isinstance(b, torch.Tensor) else b
         prep = sparse.prepare(A, b_host)   # (every ValueError comes from here, before anything touches the device)
@@ -530,6 +586,11 @@ class _SparseMarginsL1(_GapMixin, NativeProblem):
         return np.float64(fval.value), grad
 
     def _gap_call(self, lib, x, out):
+        if self.l2 > 0:
+            _lib.check(lib.zf_spmat_gap_eval_enet(self._spmat.value, C.c_void_p(self.b.data_ptr()), self.scale, self.lam, self.l2,
+                                                  self._gap_logistic, C.c_void_p(_lib.ptr(x)), C.c_void_p(_lib.ptr(out)), out.size),
+                       "zf_spmat_gap_eval_enet")
+            return
         _lib.check(lib.zf_spmat_gap_eval(self._spmat.value, C.c_void_p(self.b.data_ptr()), self.scale, self.lam, self._gap_logistic,
                                          C.c_void_p(_lib.ptr(x)), C.c_void_p(_lib.ptr(out)), out.size), "zf_spmat_gap_eval")
 
@@ -539,16 +600,12 @@ class _SparseMarginsL1(_GapMixin, NativeProblem):
     def jac_f(self, x):
         return self._ls(x, True)[1]
 
-    def _eval_fg(self, x):
-        lib = _lib.require_gpu()
-        s = C.c_double(0.0)
-        _lib.check(lib.zf_host_asum(C.c_void_p(_lib.ptr(x)), x.size, C.byref(s)), "zf_host_asum")
-        return None, np.float64(self.lam * s.value)
-
     def _descriptor(self):
         fields = dict(kind=self.kind, world=1, rank=0, n=self.n_features, m_rows=self.m_rows, row_sharded=0,
                       d=None, c=None, A=None, b=self.b.data_ptr(), scale=self.scale, lam=self.lam,
                       box_lo=self.box[0], box_hi=self.box[1], spmat=self._spmat.value.value)
+        if self.l2 > 0:
+            fields["l2"] = self.l2   # (no descriptor field: the engine calls zf_solver_set_l2)
         return fields, (self._spmat, self.b)
 
 
@@ -566,8 +623,8 @@ class SparseLeastSquaresL1(_SparseMarginsL1):
     _eval_name = "zf_spmat_eval"
     taylor_remainder = True   # acceptance="remainder": R = scale |A (x+ - y)|^2 from the residual kernels at x+
 
-    def __init__(self, A, b, lam, scale=0.5, bounds=None):
-        self._set(A, b, lam, scale, bounds)
+    def __init__(self, A, b, lam, scale=0.5, bounds=None, l2=0.0):
+        self._set(A, b, lam, scale, bounds, l2)
 
 
 def _check_labels(b, m=None):
@@ -586,7 +643,7 @@ class LogisticL1(_DenseMarginsL1):
     row-major: L1-regularised logistic regression on the device-resident trial of ``LeastSquaresL1`` - same keywords,
     same result fields.  grad f = scale A^T rho, rho_i = -b_i sigma(-b_i (Ax)_i) (csrc/zf_kernels_loss.h: one
     exp(-|t|) per row feeds both, finite for every finite margin).  Labels other than exactly -1 / +1 raise ValueError.
-    Single GPU."""
+    Single GPU.  The elastic net: ``LogisticL1(A, b, lam).with_penalty(lam, l2)`` (the constructor's parameter list is fixed)."""
 
     kind = _lib.ZF_PROBLEM_LOGISTIC_L1
     _eval_name = "zf_logistic_eval"

@@ -39,7 +39,7 @@ def solve_screened(problem, x0, gap_tol, screen_ratio=0.1, screen_shrink=0.5, ma
     gap the round started from), ``kept`` and ``restricted`` (whether a restriction was made in that round)."""
     if not getattr(problem, "has_duality_gap", False):
         raise ValueError("solve_screened needs a LeastSquaresL1, SparseLeastSquaresL1, LogisticL1 or SparseLogisticL1")
-    why = problem._gap_refusal()
+    why = problem._screen_refusal()
     if why:
         raise ValueError(f"solve_screened is not available: {why}")
     if solver_kwargs.get("return_all"):
