@@ -604,6 +604,49 @@ int zf_spmat_restrict_fill(const zf_spmat* h, const uint8_t* keep_dev, const int
 int zf_dense_restrict(const double* A_dev, int64_t m_rows, int64_t n, const uint8_t* keep_dev, int32_t* index_dev, int64_t k,
                       double* out_dev);
 
+/* ---- Huber's loss on the least-squares kinds 2 and 4 (csrc/zf_kernels_huber.h) -------------------------------------------
+ * f(x) = scale sum_i H(r_i), r = A x - b, H(r) = r^2 for |r| <= delta and delta (2 |r| - delta) beyond (scale = 1/2: the textbook
+ * function); grad f = 2 scale A^T c, c = clip(r, -delta, delta).  Every kernel forms c = copysign(min(|r|, delta), r) - exact
+ * given r - and H = c (2 r - c): two roundings, never negative, r r on an unclipped row.  The sum is a plain sum.  A NaN margin
+ * gives a NaN f.  Additive to ABI 6: no problem kind, no struct field, no version change.
+ * zf_solver_set_huber: after zf_solver_create(_sparse), before zf_solver_enqueue_init / zf_solver_restore (ZF_ERR_STATE
+ * afterwards).  ZF_ERR_ARG: a kind other than ZF_PROBLEM_LEAST_SQUARES_L1 / ZF_PROBLEM_SPARSE_LS_L1, world > 1, delta not finite
+ * or <= 0, a solver created with ZF_ACCEPT_REMAINDER (scale |A (x+ - y)|^2 is not this loss's Taylor remainder).  A trial then
+ * runs the loss kernels where it ran the residual kernels - at y (c to the residual buffer, f(y)) and at x+ (f(x+)); the A^T
+ * sweep (with the same 2 scale), the prox step (zf_solver_set_l2 composes, in either order), the decision, history and
+ * snapshots are the least-squares kinds' own.  A matrix small enough for the two fused small-matrix launches takes the general
+ * path, and zf_solver_ls_plan says so.  A solver that was never asked launches and allocates what it did.  A resumed solve
+ * sets delta again before zf_solver_restore. */
+int zf_solver_set_huber(zf_solver* s, double delta);
+/* f and (grad_out_host != NULL) grad at a host vector: zf_ls_eval / zf_spmat_eval with the loss kernels the solver runs.
+ * ZF_ERR_ARG before anything else: a null pointer, m_rows or n < 1, delta not finite or <= 0, a misaligned A. */
+int zf_huber_eval(const double* A_dev, const double* b_dev, int64_t m_rows, int64_t n, double scale, double delta,
+                  const double* x_host, double* f_out, double* grad_out_host);
+int zf_spmat_huber_eval(const zf_spmat* h, const double* b_dev, double scale, double delta, const double* x_host, double* f_out,
+                        double* grad_out_host);
+/* The certificate.  phi_i^*(nu) = nu b_i + nu^2 / (4 scale) on |nu| <= 2 scale delta, and nu = alpha 2 scale c never leaves that
+ * interval.  One rows pass stores c and returns sum H, sum c^2, sum b c and T = sum |c| (|r| - |c|) (every term >= 0, exactly 0
+ * on an unclipped row); none depends on alpha:
+ *   P = scale sum H + lam |x|_1                    D = -scale (alpha^2 sum c^2 + 2 alpha sum b c)
+ *   rows = scale (1 - alpha) ((1 - alpha) sum c^2 + 2 T)         columns, alpha, 1 - alpha: as zf_gap_eval
+ *   gap = rows + columns   (+ the ridge part, gt = fma(l2, x, g) and the two further outputs of zf_gap_eval_enet when l2 > 0)
+ * out: the eight slots of zf_gap_eval; count >= 10 and l2 > 0: the ten of zf_gap_eval_enet (l2 = 0: [8] = [9] = 0).
+ * zf_solver_duality_gap of a solver with zf_solver_set_huber writes the same values, bit for bit.  delta >= max |r| gives the
+ * least-squares rows gap scale (1 - alpha)^2 |r|^2.  ZF_ERR_ARG as zf_gap_eval_enet, and for delta not finite or <= 0. */
+int zf_gap_eval_huber(const double* A_dev, const double* b_dev, int64_t m_rows, int64_t n, double scale, double lam, double l2,
+                      double delta, const double* x_host, double* out, int64_t count /* >= 8; 10 for all */);
+int zf_spmat_gap_eval_huber(const zf_spmat* h, const double* b_dev, double scale, double lam, double l2, double delta,
+                            const double* x_host, double* out, int64_t count /* >= 8; 10 for all */);
+/* The screen (l2 = 0): zf_gap_screen_eval's rule with L = 2 scale and its guard with c for r, |c|_2 = sqrt(sum c^2) - the clip
+ * is exact and 1-Lipschitz.  The radius, mask, scan and restriction kernels are the same.  Arguments and outputs as
+ * zf_gap_screen_eval / zf_spmat_gap_screen_eval, with delta where they take `logistic`. */
+int zf_gap_screen_eval_huber(const double* A_dev, const double* b_dev, int64_t m_rows, int64_t n, double scale, double lam, double delta,
+                             const double* x_host, double* out, int64_t count /* >= 12 */, const double* norms_dev,
+                             const double* stats_dev, uint8_t* keep_dev, int32_t* index_dev);
+int zf_spmat_gap_screen_eval_huber(const zf_spmat* h, const double* b_dev, double scale, double lam, double delta, const double* x_host,
+                                   double* out, int64_t count /* >= 12 */, const double* norms_dev, const double* stats_dev,
+                                   int64_t max_row, int64_t max_col, uint8_t* keep_dev, int32_t* index_dev);
+
 /* ---- multi-objective trial (m >= 2), device side ---------------------------
  * The dual of the scalarised subproblem is minimised on the host by SciPy exactly
  * as the reference does (proximal_gradient.py:179-205); every O(n) expression runs

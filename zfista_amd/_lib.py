@@ -234,6 +234,14 @@ SIGNATURES = {
     "zf_spmat_gap_eval_enet": (C.c_int, [_P, _P, C.c_double, C.c_double, C.c_double, C.c_int32, _P, _P, C.c_int64]),
     "zf_host_prox_enet_box": (C.c_int, [_P, _P, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int64]),
     "zf_host_enet_g": (C.c_int, [_P, C.c_int64, C.c_double, C.c_double, C.POINTER(C.c_double)]),
+    "zf_solver_set_huber": (C.c_int, [_P, C.c_double]),
+    "zf_huber_eval": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_double, C.c_double, _P, C.POINTER(C.c_double), _P]),
+    "zf_spmat_huber_eval": (C.c_int, [_P, _P, C.c_double, C.c_double, _P, C.POINTER(C.c_double), _P]),
+    "zf_gap_eval_huber": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, _P, _P, C.c_int64]),
+    "zf_spmat_gap_eval_huber": (C.c_int, [_P, _P, C.c_double, C.c_double, C.c_double, C.c_double, _P, _P, C.c_int64]),
+    "zf_gap_screen_eval_huber": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_double, _P, _P, C.c_int64, _P, _P, _P, _P]),
+    "zf_spmat_gap_screen_eval_huber": (C.c_int, [_P, _P, C.c_double, C.c_double, C.c_double, _P, _P, C.c_int64, _P, _P, C.c_int64,
+                                                 C.c_int64, _P, _P]),
 }
 
 _lib = None

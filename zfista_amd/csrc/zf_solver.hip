@@ -23,6 +23,7 @@
 #include "zf_screen.h"
 #include "zf_kernels_loss.h"
 #include "zf_kernels_gap.h"
+#include "zf_kernels_huber.h"
 #include "zf_kernels_step.h"
 #include "zf_trial_launch.h"
 
@@ -221,6 +222,7 @@ struct zf_solver {
     bool own_packs = true;
     bool gemv_mfma = false;       // A^T r on v_mfma_f64_16x16x4 (n % 32 == 0; ZF_GEMV_MFMA=0 disables)
     bool ls_small = false;        // cache-resident A: two fused launches per trial (zf_kernels_ls_small.h)
+    double huber = 0.0;           // Huber's loss (zf_solver_set_huber): delta > 0 swaps the residual kernels for zf_kernels_huber.h; 0: the squared loss
     double l2 = 0.0;              // elastic net (zf_solver_set_l2): g = lam |x|_1 + (l2 / 2) |x|^2; 0: every path is the l1 one
     const zf_spmat* spmat = nullptr;   // sparse least squares: A and A^T with their plans (the caller's handle: zf_solver_create_sparse; never written through)
     double* sp_part_A = nullptr, *sp_part_At = nullptr;   // ... this solver's segment sums of the split rows of A / of A^T
@@ -1356,9 +1358,14 @@ static int zf_launch_trial(zf_solver* s, bool decide_in_launch, bool dry = false
         // (1) r = A y - b by linearity, f(y); grad = 2 scale A^T r   [only when y changed]
         // (sparse matrices have 1e5 .. 1e7 rows: beyond what one workgroup should walk, the residuals take many - zf_kernels_spmv.h)
         const bool wide_resid = d.kind == ZF_PROBLEM_SPARSE_LS_L1 && m > ZF_SPMV_WIDE_RESID_MIN_ROWS;
+        // Huber's loss on a least-squares kind (zf_kernels_huber.h): c(y), f(y) and f(x+); grad = 2 scale A^T c by the same sweep
+        const bool huber = s->huber > 0.0;
         if (logistic)
             zf_launch_logit_y(s->stream, s->ctl, s->sring.p[0], s->sring.p[1], s->sring.p[2], d.b, s->resid, d.scale, m, (int)s->opt.nesterov,
                               s->row_part, s->ls_scal + 0);
+        else if (huber)
+            zf_launch_huber_y(s->stream, s->ctl, s->sring.p[0], s->sring.p[1], s->sring.p[2], d.b, s->resid, d.scale, s->huber, m,
+                              (int)s->opt.nesterov, s->row_part, s->ls_scal + 0);
         else if (wide_resid)
             zf_launch_spmv_resid_y(s->stream, s->ctl, s->sring.p[0], s->sring.p[1], s->sring.p[2], d.b, s->resid, d.scale, m,
                                    (int)s->opt.nesterov, s->row_part, s->ls_scal + 0);
@@ -1444,6 +1451,9 @@ static int zf_launch_trial(zf_solver* s, bool decide_in_launch, bool dry = false
             if (logistic)
                 zf_launch_logit_x(s->stream, s->ctl, s->sring.p[0], s->sring.p[1], s->sring.p[2], 1, d.b, d.scale, m,
                                   s->row_part + ZF_SPMV_RESID_MAX_CHUNKS, s->ls_scal + 1);
+            else if (huber)
+                zf_launch_huber_x(s->stream, s->ctl, s->sring.p[0], s->sring.p[1], s->sring.p[2], 1, d.b, d.scale, s->huber, m,
+                                  s->row_part + ZF_SPMV_RESID_MAX_CHUNKS, s->ls_scal + 1);
             else if (wide_resid && s->rem)
                 zf_launch_spmv_resid_x_rem(s->stream, s->ctl, s->sring.p[0], s->sring.p[1], s->sring.p[2], 1, d.b, d.scale, m,
                                            (int)s->opt.nesterov, 0.0, s->row_part + ZF_SPMV_RESID_MAX_CHUNKS,
@@ -1509,6 +1519,9 @@ static int zf_launch_trial(zf_solver* s, bool decide_in_launch, bool dry = false
             if (logistic)
                 zf_launch_logit_x(s->stream, s->ctl, s->sring.p[0], s->sring.p[1], s->sring.p[2], 1, d.b, d.scale, m,
                                   s->row_part + ZF_SPMV_RESID_MAX_CHUNKS, s->ls_scal + 1);
+            else if (huber)
+                zf_launch_huber_x(s->stream, s->ctl, s->sring.p[0], s->sring.p[1], s->sring.p[2], 1, d.b, d.scale, s->huber, m,
+                                  s->row_part + ZF_SPMV_RESID_MAX_CHUNKS, s->ls_scal + 1);
             else
                 zf_launch_resid_x(s);
             zf_launch_finalize(s, decide_in_launch);
@@ -1569,6 +1582,8 @@ static int zf_init_ls_tail(zf_solver* s) {
     ZF_HIP(hipMemcpyAsync(s->sring.p[2], s->sring.p[0], sizeof(double) * m, hipMemcpyDeviceToDevice, s->stream));
     if (zf_is_logistic(d.kind)) {   // the same loss, in the order the loop sums f(x+) (zf_kernels_loss.h)
         zf_launch_logit_x(s->stream, nullptr, s0.p[0], s0.p[0], s0.p[0], -1, d.b, d.scale, m, s->row_part, s->ls_scal + 1);
+    } else if (s->huber > 0.0) {   // (zf_kernels_huber.h, likewise)
+        zf_launch_huber_x(s->stream, nullptr, s0.p[0], s0.p[0], s0.p[0], -1, d.b, d.scale, s->huber, m, s->row_part, s->ls_scal + 1);
     } else if (m > (int64_t)1 << 18) {   // long residuals (the operator problem at image sizes beyond 512 x 512): two launches, many workgroups
         const int wgs = zf_grid_for(m / 8);
         hipLaunchKernelGGL(zf_resid_x_wide_kernel, dim3(wgs), dim3(ZF_BLOCK), 0, s->stream, s0.p[0], d.b, m, s->partials);
@@ -1859,6 +1874,29 @@ extern "C" int zf_solver_set_l2(zf_solver* s, double l2) {
     ZF_REQUIRE(l2 >= 0.0 && l2 <= DBL_MAX, "zf_solver_set_l2: l2 must be finite and >= 0");
     s->l2 = l2;
     if (l2 > 0.0) s->ls_small = false;   // (the fused small-matrix kernels hold the l1 step: the general path, as the logistic kind)
+    return ZF_OK;
+}
+
+// Huber's loss (include/zfista_hip.h): between create and init, on the two least-squares kinds.
+extern "C" int zf_solver_set_huber(zf_solver* s, double delta) {
+    ZF_REQUIRE(s, "zf_solver_set_huber: null argument");
+    if (s->init_enqueued || s->initialised)
+        return zf_fail(ZF_ERR_STATE, "zf_solver_set_huber: call after zf_solver_create and before zf_solver_enqueue_init / zf_solver_restore%s%s");
+    const zf_problem_desc& d = s->desc;
+    ZF_REQUIRE(d.kind == ZF_PROBLEM_LEAST_SQUARES_L1 || d.kind == ZF_PROBLEM_SPARSE_LS_L1,
+               "zf_solver_set_huber: only for ZF_PROBLEM_LEAST_SQUARES_L1 and ZF_PROBLEM_SPARSE_LS_L1");
+    ZF_REQUIRE(d.world == 1, "zf_solver_set_huber: not for a sharded solve (world > 1)");
+    ZF_REQUIRE(delta > 0.0 && delta <= DBL_MAX, "zf_solver_set_huber: delta must be finite and > 0");
+    ZF_REQUIRE(!s->rem, "zf_solver_set_huber: not with ZF_ACCEPT_REMAINDER (scale |A (x+ - y)|^2 is not the Taylor remainder of this loss)");
+    if (d.kind == ZF_PROBLEM_LEAST_SQUARES_L1 && s->huber == 0.0) {
+        // chunk sums of the loss at y and at x+, as the dense logistic kind holds them (the fused small-matrix path's are shorter)
+        double* part = nullptr;
+        ZF_HIP(hipMalloc(&part, sizeof(double) * 2 * ZF_SPMV_RESID_MAX_CHUNKS));
+        if (s->row_part) (void)hipFree(s->row_part);
+        s->row_part = part;
+    }
+    s->huber = delta;
+    s->ls_small = false;   // (the fused small-matrix kernels hold the squared loss: the general path, as the logistic kind)
     return ZF_OK;
 }
 
@@ -2438,7 +2476,9 @@ extern "C" int zf_ls_remainder_eval(const double* s_plus_host, const double* s_k
 // logistic: the loss of zf_kernels_loss.h on the same sweeps (zf_logistic_eval) - rho = -b sigma(-b s) takes the place of
 // r = s - b, scale that of 2 scale
 static int zf_dense_eval(const double* A_dev, const double* b_dev, int64_t m_rows, int64_t n, double scale,
-                         const double* x_host, double* f_out, double* grad_out_host, bool logistic) {
+                         const double* x_host, double* f_out, double* grad_out_host, bool logistic, double delta = 0.0) {
+    // (delta > 0: Huber's loss of zf_kernels_huber.h - c = clip(s - b) takes the place of r, the factor stays 2 scale)
+    const bool huber = delta > 0.0, own_rows = logistic || huber;
     const int V = (n % 2 == 0) ? 2 : 1;
     const int64_t nv = n / V;
     const int64_t panels = (nv + ZF_BLOCK - 1) / ZF_BLOCK;
@@ -2459,7 +2499,7 @@ static int zf_dense_eval(const double* A_dev, const double* b_dev, int64_t m_row
     ZF_LS(hipMalloc(&x, sizeof(double) * (n + 2)));
     ZF_LS(hipMalloc(&s, sizeof(double) * (m_rows + 2)));
     ZF_LS(hipMalloc(&fdev, sizeof(double) * 2));
-    if (logistic) {
+    if (own_rows) {
         ZF_LS(hipMalloc(&part, sizeof(double) * ZF_SPMV_RESID_MAX_CHUNKS));
         if (grad_out_host) ZF_LS(hipMalloc(&rho, sizeof(double) * m_rows));
     }
@@ -2478,7 +2518,11 @@ static int zf_dense_eval(const double* A_dev, const double* b_dev, int64_t m_row
         else
             hipLaunchKernelGGL(zf_gemv_rows_kernel<1>, dim3(gr), dim3(ZF_BLOCK), 0, nullptr, nullptr, A_dev, xr, sr,
                                -1, m_rows, n);
-        if (!logistic)
+        if (huber && grad_out_host)
+            zf_launch_huber_y(nullptr, nullptr, s, s, s, b_dev, rho, scale, delta, m_rows, 0, part, fdev);
+        else if (huber)
+            zf_launch_huber_x(nullptr, nullptr, s, s, s, -1, b_dev, scale, delta, m_rows, part, fdev);
+        else if (!logistic)
             hipLaunchKernelGGL(zf_resid_x_kernel, dim3(1), dim3(RESID_BLOCK), 0, nullptr, nullptr, sr, -1, b_dev, scale,
                                m_rows, fdev);
         else if (grad_out_host)
@@ -2487,10 +2531,10 @@ static int zf_dense_eval(const double* A_dev, const double* b_dev, int64_t m_row
             zf_launch_logit_x(nullptr, nullptr, s, s, s, -1, b_dev, scale, m_rows, part, fdev);
         if (grad_out_host) {
             // r = s - b in place, then column sums
-            if (!logistic)
+            if (!own_rows)
                 hipLaunchKernelGGL(zf_axmb_kernel, dim3(zf_grid_for(m_rows)), dim3(ZF_BLOCK), 0, nullptr, s, b_dev,
                                    m_rows);
-            const double* rv = logistic ? rho : s;
+            const double* rv = own_rows ? rho : s;
             dim3 gT((unsigned)panels, (unsigned)slices);
             if (V == 2)
                 hipLaunchKernelGGL(zf_gemvT_partial_kernel<2>, gT, dim3(ZF_BLOCK), 0, nullptr, nullptr, A_dev, rv,
@@ -2530,7 +2574,8 @@ extern "C" int zf_logistic_eval(const double* A_dev, const double* b_dev, int64_
 
 // the same for a CSR matrix behind a handle (zf_spmat_create), on the two sweeps the solver runs
 static int zf_sparse_eval(const zf_spmat* h, const double* b_dev, double scale, const double* x_host, double* f_out,
-                          double* grad_out_host, bool logistic) {
+                          double* grad_out_host, bool logistic, double delta = 0.0) {
+    const bool huber = delta > 0.0, own_rows = logistic || huber;   // (as zf_dense_eval)
     const int64_t m = h->m, n = h->n;
     double *x = nullptr, *sv = nullptr, *grad = nullptr, *fdev = nullptr, *part_A = nullptr, *part_At = nullptr, *rho = nullptr, *part = nullptr;
     int rc = ZF_OK;
@@ -2544,7 +2589,7 @@ static int zf_sparse_eval(const zf_spmat* h, const double* b_dev, double scale, 
     ZF_SP(hipMalloc(&sv, sizeof(double) * m));
     ZF_SP(hipMalloc(&fdev, sizeof(double) * 2));
     if (grad_out_host) ZF_SP(hipMalloc(&grad, sizeof(double) * n));
-    if (logistic) {
+    if (own_rows) {
         ZF_SP(hipMalloc(&part, sizeof(double) * ZF_SPMV_RESID_MAX_CHUNKS));
         if (grad_out_host) ZF_SP(hipMalloc(&rho, sizeof(double) * m));
     }
@@ -2556,15 +2601,19 @@ static int zf_sparse_eval(const zf_spmat* h, const double* b_dev, double scale, 
         zf_ring3 sr = {{sv, sv, sv}};
         const zf_spmv_io aio = {{x, x, x}, {sv, sv, sv}};
         zf_launch_spmv(h->A, nullptr, nullptr, false, aio, -1, 1.0, part_A);
-        if (!logistic)
+        if (huber && grad_out_host)
+            zf_launch_huber_y(nullptr, nullptr, sv, sv, sv, b_dev, rho, scale, delta, m, 0, part, fdev);
+        else if (huber)
+            zf_launch_huber_x(nullptr, nullptr, sv, sv, sv, -1, b_dev, scale, delta, m, part, fdev);
+        else if (!logistic)
             hipLaunchKernelGGL(zf_resid_x_kernel, dim3(1), dim3(RESID_BLOCK), 0, nullptr, nullptr, sr, -1, b_dev, scale, m, fdev);
         else if (grad_out_host)
             zf_launch_logit_y(nullptr, nullptr, sv, sv, sv, b_dev, rho, scale, m, 0, part, fdev);
         else
             zf_launch_logit_x(nullptr, nullptr, sv, sv, sv, -1, b_dev, scale, m, part, fdev);
         if (grad_out_host) {
-            if (!logistic) hipLaunchKernelGGL(zf_axmb_kernel, dim3(zf_grid_for(m)), dim3(ZF_BLOCK), 0, nullptr, sv, b_dev, m);
-            const double* rv = logistic ? rho : sv;
+            if (!own_rows) hipLaunchKernelGGL(zf_axmb_kernel, dim3(zf_grid_for(m)), dim3(ZF_BLOCK), 0, nullptr, sv, b_dev, m);
+            const double* rv = own_rows ? rho : sv;
             const zf_spmv_io gio = {{rv, rv, rv}, {grad, grad, grad}};
             zf_launch_spmv(h->At, nullptr, nullptr, false, gio, -1, logistic ? scale : 2 * scale, part_At);
             ZF_SP(hipMemcpyAsync(grad_out_host, grad, sizeof(double) * n, hipMemcpyDeviceToHost, nullptr));
@@ -2590,6 +2639,22 @@ extern "C" int zf_spmat_logistic_eval(const zf_spmat* h, const double* b_dev, do
                                       double* grad_out_host) {
     ZF_REQUIRE(h && b_dev && x_host && f_out, "zf_spmat_logistic_eval: null argument");
     return zf_sparse_eval(h, b_dev, scale, x_host, f_out, grad_out_host, true);
+}
+
+// Huber's loss (zf_kernels_huber.h) on the same sweeps: f = scale sum H_delta(A x - b), grad = 2 scale A^T clip(A x - b)
+extern "C" int zf_huber_eval(const double* A_dev, const double* b_dev, int64_t m_rows, int64_t n, double scale, double delta,
+                             const double* x_host, double* f_out, double* grad_out_host) {
+    ZF_REQUIRE(A_dev && b_dev && x_host && f_out && m_rows >= 1 && n >= 1, "zf_huber_eval: bad argument");
+    ZF_REQUIRE(delta > 0.0 && delta <= DBL_MAX, "zf_huber_eval: delta must be finite and > 0");
+    ZF_REQUIRE(zf_aligned16(A_dev), "zf_huber_eval: A must be 16-byte aligned");
+    return zf_dense_eval(A_dev, b_dev, m_rows, n, scale, x_host, f_out, grad_out_host, false, delta);
+}
+
+extern "C" int zf_spmat_huber_eval(const zf_spmat* h, const double* b_dev, double scale, double delta, const double* x_host, double* f_out,
+                                   double* grad_out_host) {
+    ZF_REQUIRE(h && b_dev && x_host && f_out, "zf_spmat_huber_eval: null argument");
+    ZF_REQUIRE(delta > 0.0 && delta <= DBL_MAX, "zf_spmat_huber_eval: delta must be finite and > 0");
+    return zf_sparse_eval(h, b_dev, scale, x_host, f_out, grad_out_host, false, delta);
 }
 
 // f(x) = scale |B W^-1 x - b|^2 and (optionally) jac_f(x) = 2 scale W B (B W^-1 x - b) of the operator problem
@@ -2669,11 +2734,12 @@ static void zf_gap_dense_sweep(hipStream_t st, const double* A, const double* rv
             rc = zf_fail(ZF_ERR_HIP, "%s: %s", #expr, hipGetErrorString(_e));     \
     } while (0)
 
-static int zf_gap_ws_alloc(zf_gap_ws* ws, int64_t m, int64_t n) {
+// (huber: a fourth row of chunk sums for the rows pass of zf_kernels_huber.h; otherwise what it always took)
+static int zf_gap_ws_alloc(zf_gap_ws* ws, int64_t m, int64_t n, bool huber = false) {
     int rc = ZF_OK;
     ZF_GAP_TRY(hipMalloc(&ws->rvec, sizeof(double) * m));
     ZF_GAP_TRY(hipMalloc(&ws->g, sizeof(double) * n));
-    ZF_GAP_TRY(hipMalloc(&ws->part, sizeof(double) * ZF_GAP_PART));
+    ZF_GAP_TRY(hipMalloc(&ws->part, sizeof(double) * (huber ? ZF_GAP_PART_HUBER : ZF_GAP_PART)));
     ZF_GAP_TRY(hipMalloc(&ws->scal, sizeof(double) * ZF_GAP_SCAL));
     return rc;
 }
@@ -2687,14 +2753,16 @@ static void zf_gap_ws_free(zf_gap_ws* ws) {
 // scr != NULL (zf_gap_screen_eval / zf_spmat_gap_screen_eval): the screen of zf_kernels_screen.h over the call's g behind the
 // same sequence - its four scalars follow the eight outputs; scr->cnt and scr->scal are allocated here
 // l2 > 0: the elastic-net evaluation (zf_launch_gap_tail_enet), ten outputs when out_count >= 10
+// delta > 0 (logistic false): Huber's loss - its rows pass and composition (zf_kernels_huber.h) around the same sweeps and n-passes
 static int zf_gap_eval_impl(const double* A_dev, const zf_spmat* h, const double* b_dev, int64_t m, int64_t n, double scale, double lam,
                             bool logistic, const double* x_host, double* out, const zf_screen_req* scr = nullptr, double l2 = 0.0,
-                            int64_t out_count = 8) {
+                            int64_t out_count = 8, double delta = 0.0) {
+    const bool huber = delta > 0.0;
     zf_gap_ws ws = {nullptr, nullptr, nullptr, nullptr};
     double *x = nullptr, *z = nullptr, *slab = nullptr, *part_A = nullptr, *part_At = nullptr, *scr_scal = nullptr;
     int32_t* scr_cnt = nullptr;
     int64_t slices = 1, rps = m;
-    int rc = zf_gap_ws_alloc(&ws, m, n);
+    int rc = zf_gap_ws_alloc(&ws, m, n, huber);
     if (scr) {
         ZF_GAP_TRY(hipMalloc(&scr_scal, sizeof(double) * ZF_SCREEN_SCAL));
         ZF_GAP_TRY(hipMalloc(&scr_cnt, sizeof(int32_t) * (ZF_SCREEN_MAX_CHUNKS + 1)));
@@ -2728,14 +2796,16 @@ static int zf_gap_eval_impl(const double* A_dev, const zf_spmat* h, const double
             if (n % 2 == 0) hipLaunchKernelGGL(zf_gemv_rows_kernel<2>, dim3(gr), dim3(ZF_BLOCK), 0, nullptr, nullptr, A_dev, xr, sr, -1, m, n);
             else hipLaunchKernelGGL(zf_gemv_rows_kernel<1>, dim3(gr), dim3(ZF_BLOCK), 0, nullptr, nullptr, A_dev, xr, sr, -1, m, n);
         }
-        zf_launch_gap_rows(nullptr, logistic, z, b_dev, m, scale, ws);
+        if (huber) zf_launch_gap_huber_rows(nullptr, z, b_dev, m, scale, delta, ws);
+        else zf_launch_gap_rows(nullptr, logistic, z, b_dev, m, scale, ws);
         if (h) {
             const zf_spmv_io gio = {{ws.rvec, ws.rvec, ws.rvec}, {ws.g, ws.g, ws.g}};
             zf_launch_spmv(h->At, nullptr, nullptr, false, gio, -1, gfac, part_At);
         } else {
             zf_gap_dense_sweep(nullptr, A_dev, ws.rvec, slab, ws.g, m, n, (int)slices, rps, n % 32 == 0 && zf_env_read().gemv_mfma, gfac);
         }
-        if (l2 > 0.0) zf_launch_gap_tail_enet(nullptr, logistic, z, b_dev, x, m, n, scale, lam, l2, ws);
+        if (huber) zf_launch_gap_tail_huber(nullptr, x, n, scale, lam, l2, ws);
+        else if (l2 > 0.0) zf_launch_gap_tail_enet(nullptr, logistic, z, b_dev, x, m, n, scale, lam, l2, ws);
         else zf_launch_gap_tail(nullptr, logistic, z, b_dev, x, m, n, scale, lam, ws);
         if (scr) {
             zf_screen_req rq = *scr;
@@ -2833,6 +2903,63 @@ extern "C" int zf_spmat_gap_screen_eval(const zf_spmat* h, const double* b_dev, 
     return zf_gap_eval_impl(nullptr, h, b_dev, h->m, h->n, scale, lam, logistic != 0, x_host, out, &rq);
 }
 
+// Huber's loss (zf_kernels_huber.h): the certificate and the screen of the least-squares kinds with c = clip(A x - b) for r
+static int zf_huber_gap_args(const char* who, double scale, double lam, double l2, double delta, int64_t count) {
+    if (count < 8) return zf_fail(ZF_ERR_ARG, "%s: the output buffer holds fewer than 8 doubles%s", who);
+    if (!(scale > 0.0 && lam >= 0.0 && l2 >= 0.0 && l2 <= DBL_MAX)) return zf_fail(ZF_ERR_ARG, "%s: needs scale > 0, lam >= 0 and a finite l2 >= 0%s", who);
+    if (!(delta > 0.0 && delta <= DBL_MAX)) return zf_fail(ZF_ERR_ARG, "%s: delta must be finite and > 0%s", who);
+    return ZF_OK;
+}
+
+extern "C" int zf_gap_eval_huber(const double* A_dev, const double* b_dev, int64_t m_rows, int64_t n, double scale, double lam, double l2,
+                                 double delta, const double* x_host, double* out, int64_t count) {
+    ZF_REQUIRE(A_dev && b_dev && x_host && out && m_rows >= 1 && n >= 1, "zf_gap_eval_huber: bad argument");
+    int rc = zf_huber_gap_args("zf_gap_eval_huber", scale, lam, l2, delta, count);
+    if (rc) return rc;
+    ZF_REQUIRE(zf_aligned16(A_dev), "zf_gap_eval_huber: A must be 16-byte aligned");
+    rc = zf_gap_eval_impl(A_dev, nullptr, b_dev, m_rows, n, scale, lam, false, x_host, out, nullptr, l2, count, delta);
+    if (rc == ZF_OK) zf_gap_pad_l1(l2, out, count);
+    return rc;
+}
+
+extern "C" int zf_spmat_gap_eval_huber(const zf_spmat* h, const double* b_dev, double scale, double lam, double l2, double delta,
+                                       const double* x_host, double* out, int64_t count) {
+    ZF_REQUIRE(h && b_dev && x_host && out, "zf_spmat_gap_eval_huber: null argument");
+    int rc = zf_huber_gap_args("zf_spmat_gap_eval_huber", scale, lam, l2, delta, count);
+    if (rc) return rc;
+    rc = zf_gap_eval_impl(nullptr, h, b_dev, h->m, h->n, scale, lam, false, x_host, out, nullptr, l2, count, delta);
+    if (rc == ZF_OK) zf_gap_pad_l1(l2, out, count);
+    return rc;
+}
+
+// the screen (l2 = 0 only): the rule, the guard and the four screen launches are the least-squares kinds' - L = 2 scale, |c|_2 from
+// sum c^2 where they read sum r^2 (the clip is exact and 1-Lipschitz; tests/huber_cases.py derives the guard line by line)
+extern "C" int zf_gap_screen_eval_huber(const double* A_dev, const double* b_dev, int64_t m_rows, int64_t n, double scale, double lam,
+                                        double delta, const double* x_host, double* out, int64_t count, const double* norms_dev,
+                                        const double* stats_dev, uint8_t* keep_dev, int32_t* index_dev) {
+    ZF_REQUIRE(A_dev && b_dev && x_host && out && m_rows >= 1 && n >= 1 && n <= 0x7fffffffLL, "zf_gap_screen_eval_huber: bad argument");
+    int rc = zf_huber_gap_args("zf_gap_screen_eval_huber", scale, lam, 0.0, delta, count);
+    if (rc) return rc;
+    ZF_REQUIRE(zf_aligned16(A_dev), "zf_gap_screen_eval_huber: A must be 16-byte aligned");
+    zf_screen_req rq;
+    rc = zf_screen_args("zf_gap_screen_eval_huber", norms_dev, stats_dev, n, m_rows, keep_dev, index_dev, count, &rq);
+    if (rc) return rc;
+    return zf_gap_eval_impl(A_dev, nullptr, b_dev, m_rows, n, scale, lam, false, x_host, out, &rq, 0.0, 8, delta);
+}
+
+extern "C" int zf_spmat_gap_screen_eval_huber(const zf_spmat* h, const double* b_dev, double scale, double lam, double delta,
+                                              const double* x_host, double* out, int64_t count, const double* norms_dev,
+                                              const double* stats_dev, int64_t max_row, int64_t max_col, uint8_t* keep_dev,
+                                              int32_t* index_dev) {
+    ZF_REQUIRE(h && b_dev && x_host && out, "zf_spmat_gap_screen_eval_huber: null argument");
+    int rc = zf_huber_gap_args("zf_spmat_gap_screen_eval_huber", scale, lam, 0.0, delta, count);
+    if (rc) return rc;
+    zf_screen_req rq;
+    rc = zf_screen_args("zf_spmat_gap_screen_eval_huber", norms_dev, stats_dev, max_row, max_col, keep_dev, index_dev, count, &rq);
+    if (rc) return rc;
+    return zf_gap_eval_impl(nullptr, h, b_dev, h->m, h->n, scale, lam, false, x_host, out, &rq, 0.0, 8, delta);
+}
+
 // The gap at x_k of a live solver, on its stream: the margins A x_k are the ring's (no sweep over A), the dual candidate goes
 // to the call's own m-vector, g = grad f(x_k) through the solver's column sweep to its own n-vector.  Reads the iterate and
 // margin rings, A, b; writes only its workspace (and the scratch of a sweep - the slab, the segment sums of split rows -
@@ -2851,7 +2978,7 @@ extern "C" int zf_solver_duality_gap(zf_solver* s, double* out, int64_t count) {
     if (!s->initialised) return zf_fail(ZF_ERR_STATE, "zf_solver_duality_gap: solver not initialised%s%s");
     const int64_t m = d.m_rows, n = d.n;
     if (!s->gap.scal) {
-        int rc = zf_gap_ws_alloc(&s->gap, m, n);
+        int rc = zf_gap_ws_alloc(&s->gap, m, n, s->huber > 0.0);
         if (rc) {
             zf_gap_ws_free(&s->gap);
             return rc;
@@ -2866,7 +2993,8 @@ extern "C" int zf_solver_duality_gap(zf_solver* s, double* out, int64_t count) {
     const double* x = s->xb[c.cur];
     const double* z = s->sring.p[c.cur];   // A x_k: every path of these kinds keeps it there (the fused small-matrix path too)
     const zf_gap_ws& ws = s->gap;
-    zf_launch_gap_rows(s->stream, logistic, z, d.b, m, d.scale, ws);
+    if (s->huber > 0.0) zf_launch_gap_huber_rows(s->stream, z, d.b, m, d.scale, s->huber, ws);
+    else zf_launch_gap_rows(s->stream, logistic, z, d.b, m, d.scale, ws);
     if (zf_is_sparse_mat(d.kind)) {
         const zf_spmv_io gio = {{ws.rvec, ws.rvec, ws.rvec}, {ws.g, ws.g, ws.g}};
         zf_launch_spmv(s->spmat->At, s->stream, nullptr, false, gio, -1, gfac, s->sp_part_At);
@@ -2874,13 +3002,15 @@ extern "C" int zf_solver_duality_gap(zf_solver* s, double* out, int64_t count) {
         zf_gap_dense_sweep(s->stream, d.A, ws.rvec, s->slab, ws.g, m, n, s->slices, s->rows_per_slice, s->gemv_mfma, gfac);
     }
     if (s->l2 > 0.0) {   // (elastic net: ten values when the caller's buffer holds them)
-        zf_launch_gap_tail_enet(s->stream, logistic, z, d.b, x, m, n, d.scale, d.lam, s->l2, ws);
+        if (s->huber > 0.0) zf_launch_gap_tail_huber(s->stream, x, n, d.scale, d.lam, s->l2, ws);
+        else zf_launch_gap_tail_enet(s->stream, logistic, z, d.b, x, m, n, d.scale, d.lam, s->l2, ws);
         ZF_HIP(hipGetLastError());
         ZF_HIP(hipMemcpyAsync(out, ws.scal + ZF_GS_OUT_ENET, sizeof(double) * (count >= 10 ? 10 : 8), hipMemcpyDeviceToHost, s->stream));
         ZF_HIP(hipStreamSynchronize(s->stream));
         return ZF_OK;
     }
-    zf_launch_gap_tail(s->stream, logistic, z, d.b, x, m, n, d.scale, d.lam, ws);
+    if (s->huber > 0.0) zf_launch_gap_tail_huber(s->stream, x, n, d.scale, d.lam, 0.0, ws);
+    else zf_launch_gap_tail(s->stream, logistic, z, d.b, x, m, n, d.scale, d.lam, ws);
     ZF_HIP(hipGetLastError());
     ZF_HIP(hipMemcpyAsync(out, ws.scal + ZF_GS_OUT, sizeof(double) * 8, hipMemcpyDeviceToHost, s->stream));
     ZF_HIP(hipStreamSynchronize(s->stream));

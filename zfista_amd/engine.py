@@ -80,8 +80,9 @@ class DeviceSolver:
         d = _lib.ProblemDesc()
         spmat = desc_fields.get("spmat")   # a zf_spmat handle: the matrix of a sparse problem is no descriptor field
         l2 = float(desc_fields.get("l2", 0.0) or 0.0)   # elastic net: no descriptor field either (zf_solver_set_l2)
+        huber = float(desc_fields.get("huber_delta", 0.0) or 0.0)   # Huber's loss on a least-squares kind: likewise (zf_solver_set_huber)
         for k, v in desc_fields.items():
-            if k not in ("spmat", "l2"):
+            if k not in ("spmat", "l2", "huber_delta"):
                 setattr(d, k, v)
         o = _lib.Options()
         for k, v in options.items():
@@ -98,6 +99,8 @@ class DeviceSolver:
         self.l2 = l2
         if l2 > 0:
             _lib.check(self.lib.zf_solver_set_l2(h, l2), "zf_solver_set_l2")
+        if huber > 0:
+            _lib.check(self.lib.zf_solver_set_huber(h, huber), "zf_solver_set_huber")
         sub = C.c_int32(1)
         _lib.check(self.lib.zf_solver_sub_iters(h, C.byref(sub)), "zf_solver_sub_iters")
         self.sub_iters = int(sub.value)   # iterations one pass may accept (temporal blocking)

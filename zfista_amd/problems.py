@@ -196,8 +196,8 @@ def _check_l2(l2, group=None):
 
 
 class _GapMixin:
-    """Duality-gap certificate, lam_max, same-matrix siblings, gap-safe screening and column restriction of the four margins
-    classes (LeastSquaresL1, SparseLeastSquaresL1, LogisticL1, SparseLogisticL1)."""
+    """Duality-gap certificate, lam_max, same-matrix siblings, gap-safe screening and column restriction of the six margins
+    classes (LeastSquaresL1, SparseLeastSquaresL1, LogisticL1, SparseLogisticL1, HuberL1, SparseHuberL1)."""
 
     has_duality_gap = True
     _gap_logistic = 0
@@ -669,6 +669,102 @@ class SparseLogisticL1(_SparseMarginsL1):
     def __init__(self, A, b, lam, scale=1.0, bounds=None):
         _check_labels(b)
         self._set(A, b, lam, scale, bounds)
+
+
+def _check_delta(delta):
+    """The threshold of Huber's loss as a float: finite and > 0."""
+    delta = float(delta)
+    if not (np.isfinite(delta) and delta > 0):
+        raise ValueError(f"delta must be finite and > 0 (the residual size beyond which Huber's loss is linear), got {delta!r}")
+    return delta
+
+
+class _HuberMixin:
+    """Huber's loss on the trial of a least-squares class: f(x) = scale sum_i H(r_i), r = A x - b, H(r) = r^2 for
+    |r| <= delta and delta (2 |r| - delta) beyond; grad f = 2 scale A^T clip(r, -delta, delta) (csrc/zf_kernels_huber.h).  The
+    problem kind is the least-squares one; ``huber_delta`` in the descriptor fields makes the engine call
+    ``zf_solver_set_huber``.  No ``taylor_remainder``: scale |A (x+ - y)|^2 is not this loss's remainder, so
+    ``acceptance="remainder"`` is refused as for the logistic classes."""
+
+    def _descriptor(self):
+        fields, keep = super()._descriptor()
+        fields["huber_delta"] = self.delta   # (no descriptor field: the engine calls zf_solver_set_huber)
+        return fields, keep
+
+    @staticmethod
+    def _refuse_group(group):
+        if group is not None:
+            raise ValueError("group= is not available: the Huber loss kernels, their certificate and zf_solver_set_huber are built "
+                             "for one GPU (world = 1)")
+
+
+class HuberL1(_HuberMixin, _DenseMarginsL1):
+    r"""f(x) = scale \sum_i H_delta((Ax - b)_i),  g(x) = lam \|x\|_1 (+ (l2 / 2) \|x\|^2) (+ optional box); A dense row-major:
+    robust L1 regression on the device-resident trial of ``LeastSquaresL1`` - same keywords, same result fields, with the
+    duality-gap certificate, ``gap_tol``, ``l1_path``, screening (l2 = 0) and the elastic net.  ``scale = 0.5`` is the
+    textbook Huber function (r^2 / 2 inside, delta |r| - delta^2 / 2 beyond).  Single GPU."""
+
+    kind = _lib.ZF_PROBLEM_LEAST_SQUARES_L1
+
+    def __init__(self, A, b, lam, delta, scale=0.5, bounds=None, l2=0.0, *, group=None):
+        self._refuse_group(group)
+        self.delta = _check_delta(delta)
+        self._set(A, b, lam, scale, bounds, l2)
+
+    def _ls(self, x, want_grad):
+        x = _as_host(x)
+        if x.size != self.n_features:
+            raise ValueError(f"len(x) should be equal to n_features, got {x}.")
+        lib = _lib.require_gpu()
+        fval = C.c_double(0.0)
+        grad = np.empty_like(x) if want_grad else None
+        _lib.check(lib.zf_huber_eval(_dp(self.A), _dp(self.b), self.m_rows, self.n_features, self.scale, self.delta,
+                                     C.c_void_p(_lib.ptr(x)), C.byref(fval), C.c_void_p(_lib.ptr(grad)) if want_grad else None),
+                   "zf_huber_eval")
+        return np.float64(fval.value), grad
+
+    def _gap_call(self, lib, x, out):
+        _lib.check(lib.zf_gap_eval_huber(_dp(self.A), _dp(self.b), self.m_rows, self.n_features, self.scale, self.lam, self.l2,
+                                         self.delta, C.c_void_p(_lib.ptr(x)), C.c_void_p(_lib.ptr(out)), out.size), "zf_gap_eval_huber")
+
+    def _screen_call(self, lib, x, out, h, keep, index):
+        _lib.check(lib.zf_gap_screen_eval_huber(_dp(self.A), _dp(self.b), self.m_rows, self.n_features, self.scale, self.lam, self.delta,
+                                                C.c_void_p(_lib.ptr(x)), C.c_void_p(_lib.ptr(out)), out.size, _dp(h.norms), _dp(h.stats),
+                                                _dp(keep), _dp(index)), "zf_gap_screen_eval_huber")
+
+
+class SparseHuberL1(_HuberMixin, _SparseMarginsL1):
+    r"""``HuberL1`` with a SPARSE A (any scipy.sparse matrix): the matrix is prepared, stored and swept exactly as for
+    ``SparseLeastSquaresL1``; the loss kernels are the dense class's and sum the rows of the same m in the same order.
+    Single GPU."""
+
+    kind = _lib.ZF_PROBLEM_SPARSE_LS_L1
+
+    def __init__(self, A, b, lam, delta, scale=0.5, bounds=None, l2=0.0, *, group=None):
+        self._refuse_group(group)
+        self.delta = _check_delta(delta)
+        self._set(A, b, lam, scale, bounds, l2)
+
+    def _ls(self, x, want_grad):
+        x = _as_host(x)
+        if x.size != self.n_features:
+            raise ValueError(f"len(x) should be equal to n_features, got {x}.")
+        lib = _lib.require_gpu()
+        fval = C.c_double(0.0)
+        grad = np.empty_like(x) if want_grad else None
+        _lib.check(lib.zf_spmat_huber_eval(self._spmat.value, _dp(self.b), self.scale, self.delta, C.c_void_p(_lib.ptr(x)),
+                                           C.byref(fval), C.c_void_p(_lib.ptr(grad)) if want_grad else None), "zf_spmat_huber_eval")
+        return np.float64(fval.value), grad
+
+    def _gap_call(self, lib, x, out):
+        _lib.check(lib.zf_spmat_gap_eval_huber(self._spmat.value, _dp(self.b), self.scale, self.lam, self.l2, self.delta,
+                                               C.c_void_p(_lib.ptr(x)), C.c_void_p(_lib.ptr(out)), out.size), "zf_spmat_gap_eval_huber")
+
+    def _screen_call(self, lib, x, out, h, keep, index):
+        _lib.check(lib.zf_spmat_gap_screen_eval_huber(self._spmat.value, _dp(self.b), self.scale, self.lam, self.delta,
+                                                      C.c_void_p(_lib.ptr(x)), C.c_void_p(_lib.ptr(out)), out.size, _dp(h.norms),
+                                                      _dp(h.stats), self._longest[0], self._longest[1], _dp(keep), _dp(index)),
+                   "zf_spmat_gap_screen_eval_huber")
 
 
 class BlurHaarL1(NativeProblem):
