@@ -29,6 +29,7 @@ import logistic_cases as L
 import screen_cases as SC
 import sparse_cases as S
 from conftest import ROOT
+from restrict_cases import _callbacks_agree, _same_as_prepare
 
 pytestmark = pytest.mark.gpu
 U = 2.0 ** -53
@@ -186,36 +187,6 @@ def test_a_non_finite_point_keeps_everything():
 
 
 # ---- (3) restriction ---------------------------------------------------------------------------------------------------------------
-def _same_as_prepare(sub, A, cols):
-    from zfista_amd import sparse
-
-    want = sparse.prepare(A[:, cols])
-    assert (sub.m_rows, sub.n_features, sub.nnz) == (want["m"], want["n"], want["nnz"])
-    for key in ("indptr", "indices", "data", "t_indptr", "t_indices", "t_data"):
-        got = sub._spmat.dev[key].cpu().numpy()
-        assert got.dtype == want[key].dtype and np.array_equal(got, want[key]), key
-        if key.endswith("data"):
-            assert np.array_equal(got.view(np.uint64), want[key].view(np.uint64)), key
-    for got, key in zip(sub.plan, ("plan", "t_plan")):
-        assert got["lanes"] == want[key]["lanes"] and got["threshold"] == want[key]["threshold"]
-        for name in ("split_row", "split_first", "seg_start"):
-            assert np.array_equal(got[name], want[key][name]), (key, name)
-    return want
-
-
-def _callbacks_agree(prob, sub, cols, seed):
-    rng = np.random.default_rng(seed)
-    x = rng.standard_normal(cols.size) * (rng.random(cols.size) < 0.5)
-    full = np.zeros(prob.n_features)
-    full[cols] = x
-    f_sub, f_full = sub.f(x), prob.f(full)
-    assert abs(f_sub - f_full) <= 1e-12 * abs(f_full)
-    j_sub, j_full = sub.jac_f(x), prob.jac_f(full)[cols]
-    assert np.linalg.norm(j_sub - j_full) <= 1e-12 * np.linalg.norm(j_full)
-    gp_sub, gp_full = sub.duality_gap(x), prob.duality_gap(full)
-    assert abs(gp_sub.primal - gp_full.primal) <= 1e-12 * abs(gp_full.primal)
-
-
 def _keep_sets_small0(m, n):
     rng = np.random.default_rng(12)
     dense_col = n // 5
