@@ -647,6 +647,41 @@ int zf_spmat_gap_screen_eval_huber(const zf_spmat* h, const double* b_dev, doubl
                                    double* out, int64_t count /* >= 12 */, const double* norms_dev, const double* stats_dev,
                                    int64_t max_row, int64_t max_col, uint8_t* keep_dev, int32_t* index_dev);
 
+/* ---- per-row sample weights on the four margins kinds 2, 4, 5, 6 (csrc/zf_kernels_wloss.h) -----------------------------------
+ * f(x) = scale sum_i w_i phi_i(z_i) - a weighted SUM, not a mean; the weights are used as given - and
+ * grad f = gfac A^T (w o psi(z)), gfac = 2 scale (square, Huber) | scale (logistic), phi and psi per row as the unweighted
+ * kernels form them, then one product for each output: rho_i = w_i psi_i, acc += w_i phi_i (two roundings per row).  The sum is a
+ * plain sum times scale (the sqrt()^2 of the unweighted squared loss is not used).  A row with w_i == 0 is a row that is not
+ * there: rho_i = +0 and its term +0 whatever b_i holds, NaN and Inf included.  No guarantee for non-finite entries of A.
+ * w_dev: m_rows doubles in device memory, finite and >= 0 with at least one > 0 (the caller's check: the library does not read
+ * them on the host).  Additive to ABI 6: no problem kind, no struct field, no version change. */
+enum { ZF_LOSS_SQUARE = 0, ZF_LOSS_LOGISTIC = 1, ZF_LOSS_HUBER = 2 };
+/* zf_solver_set_row_weights: after zf_solver_create(_sparse), before zf_solver_enqueue_init / zf_solver_restore (ZF_ERR_STATE
+ * afterwards).  ZF_ERR_ARG: a null argument, a kind other than the four margins kinds, world > 1, a solver created with
+ * ZF_ACCEPT_REMAINDER or ZF_ACCEPT_RESOLVED.  The pointer is borrowed, as b is.  Composes with zf_solver_set_huber and
+ * zf_solver_set_l2 in any order.  The three loss sites of a trial, f of the initial point and zf_solver_duality_gap then take
+ * the weighted kernels; the two sweeps, the prox step, the decision, history and snapshots stay as they are.  A matrix small
+ * enough for the two fused small-matrix launches takes the general path, and zf_solver_ls_plan says so.  A solver that was
+ * never asked launches and allocates what it did.  A resumed solve sets the weights again before zf_solver_restore. */
+int zf_solver_set_row_weights(zf_solver* s, const double* w_dev);
+/* f and (grad_out_host != NULL) grad at a host vector with the weighted loss kernels the solver runs.  loss: ZF_LOSS_*; delta
+ * must be finite and > 0 for ZF_LOSS_HUBER and is ignored otherwise.  ZF_ERR_ARG before anything else: a null pointer, m_rows or
+ * n < 1, an unknown loss, a bad delta, a misaligned A. */
+int zf_wloss_eval(const double* A_dev, const double* b_dev, const double* w_dev, int64_t m_rows, int64_t n, double scale, int32_t loss,
+                  double delta, const double* x_host, double* f_out, double* grad_out_host);
+int zf_spmat_wloss_eval(const zf_spmat* h, const double* b_dev, const double* w_dev, double scale, int32_t loss, double delta,
+                        const double* x_host, double* f_out, double* grad_out_host);
+/* The certificate with every row term times w_i ((w phi)^*(w u) = w phi^*(u); the dual point is nu = alpha grad phi(z) as
+ * before): square sum w r^2, sum w b r; Huber sum w H, sum w c^2, sum w b c, sum w |c| (|r| - |c|); logistic sum w KL,
+ * sum w [p log p + (1 - p) log(1 - p)].  The n-passes and the compositions are those of zf_gap_eval / zf_gap_eval_enet /
+ * zf_gap_eval_huber.  out: the eight slots of zf_gap_eval; count >= 10 and l2 > 0: the ten of zf_gap_eval_enet (l2 = 0:
+ * [8] = [9] = 0).  zf_solver_duality_gap of a solver with zf_solver_set_row_weights writes the same values, bit for bit. */
+int zf_gap_eval_weighted(const double* A_dev, const double* b_dev, const double* w_dev, int64_t m_rows, int64_t n, double scale,
+                         double lam, double l2, int32_t loss, double delta, const double* x_host, double* out,
+                         int64_t count /* >= 8; 10 for all */);
+int zf_spmat_gap_eval_weighted(const zf_spmat* h, const double* b_dev, const double* w_dev, double scale, double lam, double l2,
+                               int32_t loss, double delta, const double* x_host, double* out, int64_t count /* >= 8; 10 for all */);
+
 /* ---- multi-objective trial (m >= 2), device side ---------------------------
  * The dual of the scalarised subproblem is minimised on the host by SciPy exactly
  * as the reference does (proximal_gradient.py:179-205); every O(n) expression runs

@@ -24,6 +24,7 @@
 #include "zf_kernels_loss.h"
 #include "zf_kernels_gap.h"
 #include "zf_kernels_huber.h"
+#include "zf_kernels_wloss.h"
 #include "zf_kernels_step.h"
 #include "zf_trial_launch.h"
 
@@ -223,6 +224,8 @@ struct zf_solver {
     bool gemv_mfma = false;       // A^T r on v_mfma_f64_16x16x4 (n % 32 == 0; ZF_GEMV_MFMA=0 disables)
     bool ls_small = false;        // cache-resident A: two fused launches per trial (zf_kernels_ls_small.h)
     double huber = 0.0;           // Huber's loss (zf_solver_set_huber): delta > 0 swaps the residual kernels for zf_kernels_huber.h; 0: the squared loss
+    bool loss_part = false;       // the dense least-squares kind holds the 2 x ZF_SPMV_RESID_MAX_CHUNKS chunk sums of the loss kernels (zf_loss_part)
+    const double* roww = nullptr; // per-row sample weights (zf_solver_set_row_weights; borrowed as b is): the loss sites take zf_kernels_wloss.h; NULL: what ran before
     double l2 = 0.0;              // elastic net (zf_solver_set_l2): g = lam |x|_1 + (l2 / 2) |x|^2; 0: every path is the l1 one
     const zf_spmat* spmat = nullptr;   // sparse least squares: A and A^T with their plans (the caller's handle: zf_solver_create_sparse; never written through)
     double* sp_part_A = nullptr, *sp_part_At = nullptr;   // ... this solver's segment sums of the split rows of A / of A^T
@@ -1360,7 +1363,12 @@ static int zf_launch_trial(zf_solver* s, bool decide_in_launch, bool dry = false
         const bool wide_resid = d.kind == ZF_PROBLEM_SPARSE_LS_L1 && m > ZF_SPMV_WIDE_RESID_MIN_ROWS;
         // Huber's loss on a least-squares kind (zf_kernels_huber.h): c(y), f(y) and f(x+); grad = 2 scale A^T c by the same sweep
         const bool huber = s->huber > 0.0;
-        if (logistic)
+        // per-row weights (zf_kernels_wloss.h): the same three places with w o psi and sum w phi; the sweeps stay as they are
+        const int wloss = logistic ? ZF_LOSS_LOGISTIC : huber ? ZF_LOSS_HUBER : ZF_LOSS_SQUARE;
+        if (s->roww)
+            zf_launch_wloss_y(s->stream, s->ctl, s->sring.p[0], s->sring.p[1], s->sring.p[2], d.b, s->roww, s->resid, d.scale, wloss, s->huber,
+                              m, (int)s->opt.nesterov, s->row_part, s->ls_scal + 0);
+        else if (logistic)
             zf_launch_logit_y(s->stream, s->ctl, s->sring.p[0], s->sring.p[1], s->sring.p[2], d.b, s->resid, d.scale, m, (int)s->opt.nesterov,
                               s->row_part, s->ls_scal + 0);
         else if (huber)
@@ -1448,7 +1456,10 @@ static int zf_launch_trial(zf_solver* s, bool decide_in_launch, bool dry = false
             zf_launch_trial_kernels(s, a, false);
             zf_ring3 xr3 = {{s->xb[0], s->xb[1], s->xb[2]}};
             zf_launch_apply_A(s, s->ctl, xr3, s->sring, 1);
-            if (logistic)
+            if (s->roww)
+                zf_launch_wloss_x(s->stream, s->ctl, s->sring.p[0], s->sring.p[1], s->sring.p[2], 1, d.b, s->roww, d.scale, wloss, s->huber, m,
+                                  s->row_part + ZF_SPMV_RESID_MAX_CHUNKS, s->ls_scal + 1);
+            else if (logistic)
                 zf_launch_logit_x(s->stream, s->ctl, s->sring.p[0], s->sring.p[1], s->sring.p[2], 1, d.b, d.scale, m,
                                   s->row_part + ZF_SPMV_RESID_MAX_CHUNKS, s->ls_scal + 1);
             else if (huber)
@@ -1516,7 +1527,10 @@ static int zf_launch_trial(zf_solver* s, bool decide_in_launch, bool dry = false
             hipLaunchKernelGGL(zf_gemv_rows_kernel<1>, dim3(gr), dim3(ZF_BLOCK), 0, s->stream, s->ctl, d.A,
                                xr, sout, 1, m, n);
         if (d.world == 1) {
-            if (logistic)
+            if (s->roww)
+                zf_launch_wloss_x(s->stream, s->ctl, s->sring.p[0], s->sring.p[1], s->sring.p[2], 1, d.b, s->roww, d.scale, wloss, s->huber, m,
+                                  s->row_part + ZF_SPMV_RESID_MAX_CHUNKS, s->ls_scal + 1);
+            else if (logistic)
                 zf_launch_logit_x(s->stream, s->ctl, s->sring.p[0], s->sring.p[1], s->sring.p[2], 1, d.b, d.scale, m,
                                   s->row_part + ZF_SPMV_RESID_MAX_CHUNKS, s->ls_scal + 1);
             else if (huber)
@@ -1580,7 +1594,11 @@ static int zf_init_ls_tail(zf_solver* s) {
     const int64_t n = d.n, m = d.m_rows;
     zf_ring3 s0 = {{s->sring.p[0], s->sring.p[0], s->sring.p[0]}};
     ZF_HIP(hipMemcpyAsync(s->sring.p[2], s->sring.p[0], sizeof(double) * m, hipMemcpyDeviceToDevice, s->stream));
-    if (zf_is_logistic(d.kind)) {   // the same loss, in the order the loop sums f(x+) (zf_kernels_loss.h)
+    if (s->roww) {   // (zf_kernels_wloss.h: the weighted loss, in the order the loop sums f(x+))
+        const int wloss = zf_is_logistic(d.kind) ? ZF_LOSS_LOGISTIC : s->huber > 0.0 ? ZF_LOSS_HUBER : ZF_LOSS_SQUARE;
+        zf_launch_wloss_x(s->stream, nullptr, s0.p[0], s0.p[0], s0.p[0], -1, d.b, s->roww, d.scale, wloss, s->huber, m, s->row_part,
+                          s->ls_scal + 1);
+    } else if (zf_is_logistic(d.kind)) {   // the same loss, in the order the loop sums f(x+) (zf_kernels_loss.h)
         zf_launch_logit_x(s->stream, nullptr, s0.p[0], s0.p[0], s0.p[0], -1, d.b, d.scale, m, s->row_part, s->ls_scal + 1);
     } else if (s->huber > 0.0) {   // (zf_kernels_huber.h, likewise)
         zf_launch_huber_x(s->stream, nullptr, s0.p[0], s0.p[0], s0.p[0], -1, d.b, d.scale, s->huber, m, s->row_part, s->ls_scal + 1);
@@ -1877,6 +1895,18 @@ extern "C" int zf_solver_set_l2(zf_solver* s, double l2) {
     return ZF_OK;
 }
 
+// chunk sums of the loss at y and at x+ for the dense least-squares kind, as the dense logistic kind holds them (the fused
+// small-matrix path's are shorter): allocated once, by the first of zf_solver_set_huber / zf_solver_set_row_weights
+static int zf_loss_part(zf_solver* s) {
+    if (s->desc.kind != ZF_PROBLEM_LEAST_SQUARES_L1 || s->loss_part) return ZF_OK;
+    double* part = nullptr;
+    ZF_HIP(hipMalloc(&part, sizeof(double) * 2 * ZF_SPMV_RESID_MAX_CHUNKS));
+    if (s->row_part) (void)hipFree(s->row_part);
+    s->row_part = part;
+    s->loss_part = true;
+    return ZF_OK;
+}
+
 // Huber's loss (include/zfista_hip.h): between create and init, on the two least-squares kinds.
 extern "C" int zf_solver_set_huber(zf_solver* s, double delta) {
     ZF_REQUIRE(s, "zf_solver_set_huber: null argument");
@@ -1888,15 +1918,29 @@ extern "C" int zf_solver_set_huber(zf_solver* s, double delta) {
     ZF_REQUIRE(d.world == 1, "zf_solver_set_huber: not for a sharded solve (world > 1)");
     ZF_REQUIRE(delta > 0.0 && delta <= DBL_MAX, "zf_solver_set_huber: delta must be finite and > 0");
     ZF_REQUIRE(!s->rem, "zf_solver_set_huber: not with ZF_ACCEPT_REMAINDER (scale |A (x+ - y)|^2 is not the Taylor remainder of this loss)");
-    if (d.kind == ZF_PROBLEM_LEAST_SQUARES_L1 && s->huber == 0.0) {
-        // chunk sums of the loss at y and at x+, as the dense logistic kind holds them (the fused small-matrix path's are shorter)
-        double* part = nullptr;
-        ZF_HIP(hipMalloc(&part, sizeof(double) * 2 * ZF_SPMV_RESID_MAX_CHUNKS));
-        if (s->row_part) (void)hipFree(s->row_part);
-        s->row_part = part;
-    }
+    const int rc = zf_loss_part(s);
+    if (rc) return rc;
     s->huber = delta;
     s->ls_small = false;   // (the fused small-matrix kernels hold the squared loss: the general path, as the logistic kind)
+    return ZF_OK;
+}
+
+// Per-row sample weights (include/zfista_hip.h): between create and init, on the four margins kinds.
+extern "C" int zf_solver_set_row_weights(zf_solver* s, const double* w_dev) {
+    ZF_REQUIRE(s && w_dev, "zf_solver_set_row_weights: null argument");
+    if (s->init_enqueued || s->initialised)
+        return zf_fail(ZF_ERR_STATE, "zf_solver_set_row_weights: call after zf_solver_create and before zf_solver_enqueue_init / zf_solver_restore%s%s");
+    const zf_problem_desc& d = s->desc;
+    ZF_REQUIRE(zf_is_dense_mat(d.kind) || zf_is_sparse_mat(d.kind),
+               "zf_solver_set_row_weights: only for ZF_PROBLEM_LEAST_SQUARES_L1, ZF_PROBLEM_SPARSE_LS_L1, ZF_PROBLEM_LOGISTIC_L1 and "
+               "ZF_PROBLEM_SPARSE_LOGISTIC_L1");
+    ZF_REQUIRE(d.world == 1, "zf_solver_set_row_weights: not for a sharded solve (world > 1)");
+    ZF_REQUIRE(!s->rem, "zf_solver_set_row_weights: not with ZF_ACCEPT_REMAINDER (the residual kernels that form scale |A (x+ - y)|^2 carry no weights)");
+    ZF_REQUIRE(!s->res, "zf_solver_set_row_weights: not with ZF_ACCEPT_RESOLVED");
+    const int rc = zf_loss_part(s);
+    if (rc) return rc;
+    s->roww = w_dev;
+    s->ls_small = false;   // (the fused small-matrix kernels hold the unweighted squared loss: the general path, as the logistic kind)
     return ZF_OK;
 }
 
@@ -2476,9 +2520,12 @@ extern "C" int zf_ls_remainder_eval(const double* s_plus_host, const double* s_k
 // logistic: the loss of zf_kernels_loss.h on the same sweeps (zf_logistic_eval) - rho = -b sigma(-b s) takes the place of
 // r = s - b, scale that of 2 scale
 static int zf_dense_eval(const double* A_dev, const double* b_dev, int64_t m_rows, int64_t n, double scale,
-                         const double* x_host, double* f_out, double* grad_out_host, bool logistic, double delta = 0.0) {
+                         const double* x_host, double* f_out, double* grad_out_host, bool logistic, double delta = 0.0,
+                         const double* w_dev = nullptr) {
     // (delta > 0: Huber's loss of zf_kernels_huber.h - c = clip(s - b) takes the place of r, the factor stays 2 scale)
-    const bool huber = delta > 0.0, own_rows = logistic || huber;
+    // (w_dev: the weighted kernels of zf_kernels_wloss.h for the loss the two flags name)
+    const bool huber = delta > 0.0, own_rows = logistic || huber || w_dev;
+    const int wloss = logistic ? ZF_LOSS_LOGISTIC : huber ? ZF_LOSS_HUBER : ZF_LOSS_SQUARE;
     const int V = (n % 2 == 0) ? 2 : 1;
     const int64_t nv = n / V;
     const int64_t panels = (nv + ZF_BLOCK - 1) / ZF_BLOCK;
@@ -2518,7 +2565,11 @@ static int zf_dense_eval(const double* A_dev, const double* b_dev, int64_t m_row
         else
             hipLaunchKernelGGL(zf_gemv_rows_kernel<1>, dim3(gr), dim3(ZF_BLOCK), 0, nullptr, nullptr, A_dev, xr, sr,
                                -1, m_rows, n);
-        if (huber && grad_out_host)
+        if (w_dev && grad_out_host)
+            zf_launch_wloss_y(nullptr, nullptr, s, s, s, b_dev, w_dev, rho, scale, wloss, delta, m_rows, 0, part, fdev);
+        else if (w_dev)
+            zf_launch_wloss_x(nullptr, nullptr, s, s, s, -1, b_dev, w_dev, scale, wloss, delta, m_rows, part, fdev);
+        else if (huber && grad_out_host)
             zf_launch_huber_y(nullptr, nullptr, s, s, s, b_dev, rho, scale, delta, m_rows, 0, part, fdev);
         else if (huber)
             zf_launch_huber_x(nullptr, nullptr, s, s, s, -1, b_dev, scale, delta, m_rows, part, fdev);
@@ -2574,8 +2625,9 @@ extern "C" int zf_logistic_eval(const double* A_dev, const double* b_dev, int64_
 
 // the same for a CSR matrix behind a handle (zf_spmat_create), on the two sweeps the solver runs
 static int zf_sparse_eval(const zf_spmat* h, const double* b_dev, double scale, const double* x_host, double* f_out,
-                          double* grad_out_host, bool logistic, double delta = 0.0) {
-    const bool huber = delta > 0.0, own_rows = logistic || huber;   // (as zf_dense_eval)
+                          double* grad_out_host, bool logistic, double delta = 0.0, const double* w_dev = nullptr) {
+    const bool huber = delta > 0.0, own_rows = logistic || huber || w_dev;   // (as zf_dense_eval)
+    const int wloss = logistic ? ZF_LOSS_LOGISTIC : huber ? ZF_LOSS_HUBER : ZF_LOSS_SQUARE;
     const int64_t m = h->m, n = h->n;
     double *x = nullptr, *sv = nullptr, *grad = nullptr, *fdev = nullptr, *part_A = nullptr, *part_At = nullptr, *rho = nullptr, *part = nullptr;
     int rc = ZF_OK;
@@ -2601,7 +2653,11 @@ static int zf_sparse_eval(const zf_spmat* h, const double* b_dev, double scale, 
         zf_ring3 sr = {{sv, sv, sv}};
         const zf_spmv_io aio = {{x, x, x}, {sv, sv, sv}};
         zf_launch_spmv(h->A, nullptr, nullptr, false, aio, -1, 1.0, part_A);
-        if (huber && grad_out_host)
+        if (w_dev && grad_out_host)
+            zf_launch_wloss_y(nullptr, nullptr, sv, sv, sv, b_dev, w_dev, rho, scale, wloss, delta, m, 0, part, fdev);
+        else if (w_dev)
+            zf_launch_wloss_x(nullptr, nullptr, sv, sv, sv, -1, b_dev, w_dev, scale, wloss, delta, m, part, fdev);
+        else if (huber && grad_out_host)
             zf_launch_huber_y(nullptr, nullptr, sv, sv, sv, b_dev, rho, scale, delta, m, 0, part, fdev);
         else if (huber)
             zf_launch_huber_x(nullptr, nullptr, sv, sv, sv, -1, b_dev, scale, delta, m, part, fdev);
@@ -2655,6 +2711,34 @@ extern "C" int zf_spmat_huber_eval(const zf_spmat* h, const double* b_dev, doubl
     ZF_REQUIRE(h && b_dev && x_host && f_out, "zf_spmat_huber_eval: null argument");
     ZF_REQUIRE(delta > 0.0 && delta <= DBL_MAX, "zf_spmat_huber_eval: delta must be finite and > 0");
     return zf_sparse_eval(h, b_dev, scale, x_host, f_out, grad_out_host, false, delta);
+}
+
+// per-row sample weights (zf_kernels_wloss.h) on the same sweeps: f = scale sum w phi, grad = gfac A^T (w o psi)
+static int zf_wloss_args(const char* who, int32_t loss, double delta, double* delta_eff) {
+    if (loss != ZF_LOSS_SQUARE && loss != ZF_LOSS_LOGISTIC && loss != ZF_LOSS_HUBER)
+        return zf_fail(ZF_ERR_ARG, "%s: loss must be ZF_LOSS_SQUARE, ZF_LOSS_LOGISTIC or ZF_LOSS_HUBER%s", who);
+    if (loss == ZF_LOSS_HUBER && !(delta > 0.0 && delta <= DBL_MAX)) return zf_fail(ZF_ERR_ARG, "%s: delta must be finite and > 0%s", who);
+    *delta_eff = loss == ZF_LOSS_HUBER ? delta : 0.0;
+    return ZF_OK;
+}
+
+extern "C" int zf_wloss_eval(const double* A_dev, const double* b_dev, const double* w_dev, int64_t m_rows, int64_t n, double scale,
+                             int32_t loss, double delta, const double* x_host, double* f_out, double* grad_out_host) {
+    ZF_REQUIRE(A_dev && b_dev && w_dev && x_host && f_out && m_rows >= 1 && n >= 1, "zf_wloss_eval: bad argument");
+    double de = 0.0;
+    const int rc = zf_wloss_args("zf_wloss_eval", loss, delta, &de);
+    if (rc) return rc;
+    ZF_REQUIRE(zf_aligned16(A_dev), "zf_wloss_eval: A must be 16-byte aligned");
+    return zf_dense_eval(A_dev, b_dev, m_rows, n, scale, x_host, f_out, grad_out_host, loss == ZF_LOSS_LOGISTIC, de, w_dev);
+}
+
+extern "C" int zf_spmat_wloss_eval(const zf_spmat* h, const double* b_dev, const double* w_dev, double scale, int32_t loss, double delta,
+                                   const double* x_host, double* f_out, double* grad_out_host) {
+    ZF_REQUIRE(h && b_dev && w_dev && x_host && f_out, "zf_spmat_wloss_eval: null argument");
+    double de = 0.0;
+    const int rc = zf_wloss_args("zf_spmat_wloss_eval", loss, delta, &de);
+    if (rc) return rc;
+    return zf_sparse_eval(h, b_dev, scale, x_host, f_out, grad_out_host, loss == ZF_LOSS_LOGISTIC, de, w_dev);
 }
 
 // f(x) = scale |B W^-1 x - b|^2 and (optionally) jac_f(x) = 2 scale W B (B W^-1 x - b) of the operator problem
@@ -2756,8 +2840,10 @@ static void zf_gap_ws_free(zf_gap_ws* ws) {
 // delta > 0 (logistic false): Huber's loss - its rows pass and composition (zf_kernels_huber.h) around the same sweeps and n-passes
 static int zf_gap_eval_impl(const double* A_dev, const zf_spmat* h, const double* b_dev, int64_t m, int64_t n, double scale, double lam,
                             bool logistic, const double* x_host, double* out, const zf_screen_req* scr = nullptr, double l2 = 0.0,
-                            int64_t out_count = 8, double delta = 0.0) {
+                            int64_t out_count = 8, double delta = 0.0, const double* w_dev = nullptr) {
+    // (w_dev: the weighted rows passes of zf_kernels_wloss.h around the same sweeps, n-passes and compositions)
     const bool huber = delta > 0.0;
+    const int wloss = logistic ? ZF_LOSS_LOGISTIC : huber ? ZF_LOSS_HUBER : ZF_LOSS_SQUARE;
     zf_gap_ws ws = {nullptr, nullptr, nullptr, nullptr};
     double *x = nullptr, *z = nullptr, *slab = nullptr, *part_A = nullptr, *part_At = nullptr, *scr_scal = nullptr;
     int32_t* scr_cnt = nullptr;
@@ -2796,7 +2882,8 @@ static int zf_gap_eval_impl(const double* A_dev, const zf_spmat* h, const double
             if (n % 2 == 0) hipLaunchKernelGGL(zf_gemv_rows_kernel<2>, dim3(gr), dim3(ZF_BLOCK), 0, nullptr, nullptr, A_dev, xr, sr, -1, m, n);
             else hipLaunchKernelGGL(zf_gemv_rows_kernel<1>, dim3(gr), dim3(ZF_BLOCK), 0, nullptr, nullptr, A_dev, xr, sr, -1, m, n);
         }
-        if (huber) zf_launch_gap_huber_rows(nullptr, z, b_dev, m, scale, delta, ws);
+        if (w_dev) zf_launch_gap_wrows(nullptr, wloss, z, b_dev, w_dev, m, scale, delta, ws);
+        else if (huber) zf_launch_gap_huber_rows(nullptr, z, b_dev, m, scale, delta, ws);
         else zf_launch_gap_rows(nullptr, logistic, z, b_dev, m, scale, ws);
         if (h) {
             const zf_spmv_io gio = {{ws.rvec, ws.rvec, ws.rvec}, {ws.g, ws.g, ws.g}};
@@ -2804,7 +2891,8 @@ static int zf_gap_eval_impl(const double* A_dev, const zf_spmat* h, const double
         } else {
             zf_gap_dense_sweep(nullptr, A_dev, ws.rvec, slab, ws.g, m, n, (int)slices, rps, n % 32 == 0 && zf_env_read().gemv_mfma, gfac);
         }
-        if (huber) zf_launch_gap_tail_huber(nullptr, x, n, scale, lam, l2, ws);
+        if (w_dev) zf_launch_gap_wtail(nullptr, wloss, z, b_dev, w_dev, x, m, n, scale, lam, l2, ws);
+        else if (huber) zf_launch_gap_tail_huber(nullptr, x, n, scale, lam, l2, ws);
         else if (l2 > 0.0) zf_launch_gap_tail_enet(nullptr, logistic, z, b_dev, x, m, n, scale, lam, l2, ws);
         else zf_launch_gap_tail(nullptr, logistic, z, b_dev, x, m, n, scale, lam, ws);
         if (scr) {
@@ -2932,6 +3020,40 @@ extern "C" int zf_spmat_gap_eval_huber(const zf_spmat* h, const double* b_dev, d
     return rc;
 }
 
+// per-row sample weights (zf_kernels_wloss.h): the certificate with every row term times w_i
+static int zf_wgap_args(const char* who, double scale, double lam, double l2, int64_t count) {
+    if (count < 8) return zf_fail(ZF_ERR_ARG, "%s: the output buffer holds fewer than 8 doubles%s", who);
+    if (!(scale > 0.0 && lam >= 0.0 && l2 >= 0.0 && l2 <= DBL_MAX)) return zf_fail(ZF_ERR_ARG, "%s: needs scale > 0, lam >= 0 and a finite l2 >= 0%s", who);
+    return ZF_OK;
+}
+
+extern "C" int zf_gap_eval_weighted(const double* A_dev, const double* b_dev, const double* w_dev, int64_t m_rows, int64_t n, double scale,
+                                    double lam, double l2, int32_t loss, double delta, const double* x_host, double* out, int64_t count) {
+    ZF_REQUIRE(A_dev && b_dev && w_dev && x_host && out && m_rows >= 1 && n >= 1, "zf_gap_eval_weighted: bad argument");
+    int rc = zf_wgap_args("zf_gap_eval_weighted", scale, lam, l2, count);
+    if (rc) return rc;
+    double de = 0.0;
+    rc = zf_wloss_args("zf_gap_eval_weighted", loss, delta, &de);
+    if (rc) return rc;
+    ZF_REQUIRE(zf_aligned16(A_dev), "zf_gap_eval_weighted: A must be 16-byte aligned");
+    rc = zf_gap_eval_impl(A_dev, nullptr, b_dev, m_rows, n, scale, lam, loss == ZF_LOSS_LOGISTIC, x_host, out, nullptr, l2, count, de, w_dev);
+    if (rc == ZF_OK) zf_gap_pad_l1(l2, out, count);
+    return rc;
+}
+
+extern "C" int zf_spmat_gap_eval_weighted(const zf_spmat* h, const double* b_dev, const double* w_dev, double scale, double lam, double l2,
+                                          int32_t loss, double delta, const double* x_host, double* out, int64_t count) {
+    ZF_REQUIRE(h && b_dev && w_dev && x_host && out, "zf_spmat_gap_eval_weighted: null argument");
+    int rc = zf_wgap_args("zf_spmat_gap_eval_weighted", scale, lam, l2, count);
+    if (rc) return rc;
+    double de = 0.0;
+    rc = zf_wloss_args("zf_spmat_gap_eval_weighted", loss, delta, &de);
+    if (rc) return rc;
+    rc = zf_gap_eval_impl(nullptr, h, b_dev, h->m, h->n, scale, lam, loss == ZF_LOSS_LOGISTIC, x_host, out, nullptr, l2, count, de, w_dev);
+    if (rc == ZF_OK) zf_gap_pad_l1(l2, out, count);
+    return rc;
+}
+
 // the screen (l2 = 0 only): the rule, the guard and the four screen launches are the least-squares kinds' - L = 2 scale, |c|_2 from
 // sum c^2 where they read sum r^2 (the clip is exact and 1-Lipschitz; tests/huber_cases.py derives the guard line by line)
 extern "C" int zf_gap_screen_eval_huber(const double* A_dev, const double* b_dev, int64_t m_rows, int64_t n, double scale, double lam,
@@ -2993,7 +3115,9 @@ extern "C" int zf_solver_duality_gap(zf_solver* s, double* out, int64_t count) {
     const double* x = s->xb[c.cur];
     const double* z = s->sring.p[c.cur];   // A x_k: every path of these kinds keeps it there (the fused small-matrix path too)
     const zf_gap_ws& ws = s->gap;
-    if (s->huber > 0.0) zf_launch_gap_huber_rows(s->stream, z, d.b, m, d.scale, s->huber, ws);
+    const int wloss = logistic ? ZF_LOSS_LOGISTIC : s->huber > 0.0 ? ZF_LOSS_HUBER : ZF_LOSS_SQUARE;
+    if (s->roww) zf_launch_gap_wrows(s->stream, wloss, z, d.b, s->roww, m, d.scale, s->huber, ws);
+    else if (s->huber > 0.0) zf_launch_gap_huber_rows(s->stream, z, d.b, m, d.scale, s->huber, ws);
     else zf_launch_gap_rows(s->stream, logistic, z, d.b, m, d.scale, ws);
     if (zf_is_sparse_mat(d.kind)) {
         const zf_spmv_io gio = {{ws.rvec, ws.rvec, ws.rvec}, {ws.g, ws.g, ws.g}};
@@ -3002,14 +3126,16 @@ extern "C" int zf_solver_duality_gap(zf_solver* s, double* out, int64_t count) {
         zf_gap_dense_sweep(s->stream, d.A, ws.rvec, s->slab, ws.g, m, n, s->slices, s->rows_per_slice, s->gemv_mfma, gfac);
     }
     if (s->l2 > 0.0) {   // (elastic net: ten values when the caller's buffer holds them)
-        if (s->huber > 0.0) zf_launch_gap_tail_huber(s->stream, x, n, d.scale, d.lam, s->l2, ws);
+        if (s->roww) zf_launch_gap_wtail(s->stream, wloss, z, d.b, s->roww, x, m, n, d.scale, d.lam, s->l2, ws);
+        else if (s->huber > 0.0) zf_launch_gap_tail_huber(s->stream, x, n, d.scale, d.lam, s->l2, ws);
         else zf_launch_gap_tail_enet(s->stream, logistic, z, d.b, x, m, n, d.scale, d.lam, s->l2, ws);
         ZF_HIP(hipGetLastError());
         ZF_HIP(hipMemcpyAsync(out, ws.scal + ZF_GS_OUT_ENET, sizeof(double) * (count >= 10 ? 10 : 8), hipMemcpyDeviceToHost, s->stream));
         ZF_HIP(hipStreamSynchronize(s->stream));
         return ZF_OK;
     }
-    if (s->huber > 0.0) zf_launch_gap_tail_huber(s->stream, x, n, d.scale, d.lam, 0.0, ws);
+    if (s->roww) zf_launch_gap_wtail(s->stream, wloss, z, d.b, s->roww, x, m, n, d.scale, d.lam, 0.0, ws);
+    else if (s->huber > 0.0) zf_launch_gap_tail_huber(s->stream, x, n, d.scale, d.lam, 0.0, ws);
     else zf_launch_gap_tail(s->stream, logistic, z, d.b, x, m, n, d.scale, d.lam, ws);
     ZF_HIP(hipGetLastError());
     ZF_HIP(hipMemcpyAsync(out, ws.scal + ZF_GS_OUT, sizeof(double) * 8, hipMemcpyDeviceToHost, s->stream));

@@ -81,8 +81,9 @@ class DeviceSolver:
         spmat = desc_fields.get("spmat")   # a zf_spmat handle: the matrix of a sparse problem is no descriptor field
         l2 = float(desc_fields.get("l2", 0.0) or 0.0)   # elastic net: no descriptor field either (zf_solver_set_l2)
         huber = float(desc_fields.get("huber_delta", 0.0) or 0.0)   # Huber's loss on a least-squares kind: likewise (zf_solver_set_huber)
+        roww = desc_fields.get("row_weights")   # per-row sample weights (a device pointer): likewise (zf_solver_set_row_weights)
         for k, v in desc_fields.items():
-            if k not in ("spmat", "l2", "huber_delta"):
+            if k not in ("spmat", "l2", "huber_delta", "row_weights"):
                 setattr(d, k, v)
         o = _lib.Options()
         for k, v in options.items():
@@ -101,6 +102,8 @@ class DeviceSolver:
             _lib.check(self.lib.zf_solver_set_l2(h, l2), "zf_solver_set_l2")
         if huber > 0:
             _lib.check(self.lib.zf_solver_set_huber(h, huber), "zf_solver_set_huber")
+        if roww:
+            _lib.check(self.lib.zf_solver_set_row_weights(h, C.c_void_p(roww)), "zf_solver_set_row_weights")
         sub = C.c_int32(1)
         _lib.check(self.lib.zf_solver_sub_iters(h, C.byref(sub)), "zf_solver_sub_iters")
         self.sub_iters = int(sub.value)   # iterations one pass may accept (temporal blocking)

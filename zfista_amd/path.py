@@ -38,6 +38,9 @@ def l1_path(problem, lams, x0=None, gap_tol=1e-6, screen=False, l2=None, **solve
     if screen and any((problem.l2 if v is None else v) > 0 for v in l2s):
         raise ValueError("l1_path(screen=True) is not available with l2 > 0: the gap-safe rule of the elastic net and its rounding "
                          "guard are not built yet")
+    if screen and getattr(problem, "sample_weight", None) is not None:
+        raise ValueError("l1_path(screen=True) is not available with sample_weight: the weighted screening rule needs "
+                         "sum_i w_i a_ij^2 for |a_j|^2 and a re-derived rounding guard, which are not built yet")
     out = []
     for lam, ridge in zip(lams, l2s):
         sib = problem.with_lam(lam) if ridge is None else problem.with_penalty(lam, ridge)
@@ -52,4 +55,108 @@ def l1_path(problem, lams, x0=None, gap_tol=1e-6, screen=False, l2=None, **solve
             res["l2"] = float(sib.l2)
         out.append(res)
         x = res.x
+    return out
+
+
+def cv_fold_ids(m, folds, seed=0):
+    """The fold number of each of ``m`` rows.  ``folds``: an int K >= 2 - ``p = numpy.random.default_rng(seed).permutation(m)``
+    and fold k takes the rows ``p[k::K]`` - or an integer array of m fold numbers, used as given."""
+    if np.ndim(folds) == 0:
+        K = int(folds)
+        if K != folds or K < 2 or K > m:
+            raise ValueError(f"folds must be an integer in [2, m = {m}] or an array of m fold numbers, got {folds!r}")
+        perm = np.random.default_rng(seed).permutation(m)
+        ids = np.empty(m, dtype=np.int64)
+        for k in range(K):
+            ids[perm[k::K]] = k
+        return ids
+    ids = np.asarray(folds)
+    if ids.dtype.kind not in "iu" or ids.shape != (m,):
+        raise ValueError(f"fold numbers must be an integer array of m = {m} values, got dtype {ids.dtype}, shape {ids.shape}")
+    return ids.astype(np.int64)
+
+
+class L1CV:
+    """What ``l1_cv`` returns: ``lams``, ``fold_ids`` (m), ``folds`` (the fold numbers, in the order of the rows of ``scores``),
+    ``scores`` and ``nnz`` (K x L: the held-out loss per unit of held-out weight, and the number of non-zeros, of fold k at
+    ``lams[l]``), ``mean`` and ``se`` (over the folds: the mean and its standard error, ``std(ddof=1) / sqrt(K)``), ``best``
+    (the index of the smallest mean; the first, i.e. the largest lam of the order given, on a tie), ``lam_best``, ``lam_1se``
+    (the largest lam whose mean is <= ``mean[best] + se[best]``), ``path`` (``l1_path`` on all rows at ``lams``, or None) and
+    ``paths`` (the K fold paths when asked for, else None) and, with them, ``problems`` (the K training siblings and, last, the
+    problem of ``path``: all on one device matrix)."""
+
+    __slots__ = ("lams", "fold_ids", "folds", "scores", "nnz", "mean", "se", "best", "lam_best", "lam_1se", "path", "paths", "problems")
+
+    def __repr__(self):
+        return f"L1CV(lam_best={self.lam_best!r}, lam_1se={self.lam_1se!r}, folds={len(self.folds)}, lams={len(self.lams)})"
+
+
+def cv_summary(lams, scores):
+    """(mean, se, best, lam_best, lam_1se) of a K x L score table: see ``L1CV``."""
+    lams = np.asarray(lams, dtype=np.float64)
+    scores = np.asarray(scores, dtype=np.float64)
+    K = scores.shape[0]
+    mean = scores.mean(axis=0)
+    se = scores.std(axis=0, ddof=1) / np.sqrt(K) if K > 1 else np.zeros_like(mean)
+    best = int(np.argmin(mean))
+    lam_1se = float(lams[mean <= mean[best] + se[best]].max())
+    return mean, se, best, float(lams[best]), lam_1se
+
+
+def l1_cv(problem, lams, folds=5, seed=0, x0=None, gap_tol=1e-6, refit=True, return_paths=False, **solver_kwargs):
+    """K-fold cross-validation of the l1 weight on ONE resident matrix: a fold is the same device matrix with 0 / 1 row
+    weights (``problem.with_sample_weight``), so nothing but K pairs of m-vectors is uploaded.
+
+    ``folds``: an int K, or an integer array of m fold numbers (``cv_fold_ids``).  For each fold number k the training
+    weights are ``w_base * (ids != k)`` (``w_base``: the problem's own ``sample_weight``, or ones) and ``l1_path`` runs on that
+    sibling over ``lams`` (warm-started along the path from ``x0``; ``gap_tol`` and ``solver_kwargs`` as in ``l1_path``;
+    ``gap_tol=None`` is allowed).  The score of each point is the unpenalised loss on the held-out rows per unit of held-out
+    weight, ``with_sample_weight(w_base * (ids == k)).f(x) / sum(w_base[ids == k])``.  Every fold must leave positive training
+    weight and hold positive weight itself.  ``refit``: also solve the path on all rows (``path``).  Returns an ``L1CV``.
+    The folds run one after the other; there is no intercept; screening is not available with weights."""
+    if not getattr(problem, "has_duality_gap", False) or not hasattr(problem, "with_sample_weight"):
+        raise ValueError("l1_cv needs one of the six margins classes (LeastSquaresL1, SparseLeastSquaresL1, LogisticL1, "
+                         "SparseLogisticL1, HuberL1, SparseHuberL1)")
+    if solver_kwargs.get("screen"):
+        raise ValueError("l1_cv(screen=True) is not available: a fold is a sample_weight sibling, and the weighted screening rule "
+                         "is not built yet")
+    lams = [float(v) for v in lams]
+    if not lams:
+        raise ValueError("lams must hold at least one value")
+    m = problem.m_rows
+    ids = cv_fold_ids(m, folds, seed)
+    base = problem.sample_weight
+    w_base = np.ones(m) if base is None else base
+    labels = [int(k) for k in np.unique(ids)]
+    if len(labels) < 2:
+        raise ValueError("l1_cv needs at least two folds")
+    for k in labels:   # (before any solve)
+        if not np.any(w_base * (ids != k) > 0):
+            raise ValueError(f"fold {k} leaves no training weight: every row with a positive weight lies in it")
+    for k in labels:
+        if not np.any(w_base * (ids == k) > 0):
+            raise ValueError(f"fold {k} holds no weight: no held-out row to score on")
+    scores = np.empty((len(labels), len(lams)))
+    nnz = np.zeros((len(labels), len(lams)), dtype=np.int64)
+    paths, sibs = [], []
+    for r, k in enumerate(labels):
+        w_test = w_base * (ids == k)
+        train = problem.with_sample_weight(w_base * (ids != k))
+        test = problem.with_sample_weight(w_test)
+        wsum = w_test.sum()
+        path = l1_path(train, lams, x0=x0, gap_tol=gap_tol, **solver_kwargs)
+        for l, res in enumerate(path):
+            scores[r, l] = test.f(res.x) / wsum
+            nnz[r, l] = int(np.count_nonzero(res.x))
+        if return_paths:
+            paths.append(path)
+            sibs.append(train)
+    out = L1CV()
+    out.lams = np.asarray(lams, dtype=np.float64)
+    out.fold_ids, out.folds = ids, labels
+    out.scores, out.nnz = scores, nnz
+    out.mean, out.se, out.best, out.lam_best, out.lam_1se = cv_summary(lams, scores)
+    out.path = l1_path(problem, lams, x0=x0, gap_tol=gap_tol, **solver_kwargs) if refit else None
+    out.paths = paths if return_paths else None
+    out.problems = sibs + [problem] if return_paths else None
     return out

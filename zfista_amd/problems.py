@@ -195,6 +195,25 @@ def _check_l2(l2, group=None):
     return l2
 
 
+def _check_weights(w, m, group=None):
+    """Per-row sample weights as a host float64 vector: m of them, finite and >= 0, at least one > 0.  ValueError otherwise -
+    on the host, before anything touches the device (a torch tensor is copied to the host for the check)."""
+    if group is not None:
+        raise ValueError("sample_weight is not available with group=: the weighted loss kernels, their certificate and "
+                         "zf_solver_set_row_weights are built for one GPU (world = 1)")
+    host = w.detach().cpu().numpy() if hasattr(w, "detach") else np.asarray(w)
+    if np.dtype(host.dtype).kind not in "biuf":
+        raise ValueError(f"sample_weight must be real numbers, got dtype {host.dtype}")
+    host = np.array(host, dtype=np.float64, order="C", copy=True)   # (the problem's own copy: never the caller's array)
+    if host.ndim != 1 or host.shape[0] != m:
+        raise ValueError(f"sample_weight must be a vector of {m} weights (one per row of A), got shape {host.shape}")
+    if not np.all(np.isfinite(host)) or np.any(host < 0):
+        raise ValueError("sample_weight must be finite and >= 0")
+    if not np.any(host > 0):
+        raise ValueError("sample_weight must hold at least one weight > 0 (no row is left)")
+    return host
+
+
 class _GapMixin:
     """Duality-gap certificate, lam_max, same-matrix siblings, gap-safe screening and column restriction of the six margins
     classes (LeastSquaresL1, SparseLeastSquaresL1, LogisticL1, SparseLogisticL1, HuberL1, SparseHuberL1)."""
@@ -202,6 +221,44 @@ class _GapMixin:
     has_duality_gap = True
     _gap_logistic = 0
     l2 = 0.0   # elastic net: g(x) = lam |x|_1 + (l2 / 2) |x|^2 (+ box)
+    # per-row sample weights: f(x) = scale sum_i w_i loss_i - a weighted SUM, not a mean; the weights are used as given
+    # (csrc/zf_kernels_wloss.h).  _w: the device vector, shared by every sibling; None: the unweighted problem, every call as before
+    _w = None
+    _w_host = None
+    _loss = _lib.ZF_LOSS_SQUARE
+
+    @property
+    def sample_weight(self):
+        """The per-row sample weights (a host copy), or None."""
+        return None if self._w_host is None else self._w_host.copy()
+
+    def with_sample_weight(self, w):
+        """A sibling problem with the per-row weights ``w`` (m values, finite and >= 0, at least one > 0; used as given:
+        f = scale sum_i w_i loss_i) that SHARES the device matrix, b and (sparse classes) the matrix handle: only w is
+        uploaded.  A row with w_i = 0 is a row that is not there, whatever its b_i holds.  ``None``: the unweighted sibling."""
+        import copy
+
+        sib = copy.copy(self)
+        sib._set_weights(w)
+        return sib
+
+    def _set_weights(self, w):
+        if w is None:
+            self._w = self._w_host = None
+            self.__dict__.pop("taylor_remainder", None)
+            return
+        host = _check_weights(w, self.m_rows, getattr(self, "group", None))
+        self._w_host = host
+        self._w = _to_device(host, "sample_weight")
+        self.taylor_remainder = False   # (the residual kernels that form scale |A (x+ - y)|^2 carry no weights)
+
+    def _weights_refusal(self, what):
+        if self._w is not None:
+            raise ValueError(f"{what} is not available with sample_weight: the weighted screening rule needs sum_i w_i a_ij^2 for "
+                             "|a_j|^2 and a re-derived rounding guard, which are not built yet")
+
+    def _w_delta(self):
+        return float(getattr(self, "delta", 0.0)) if self._loss == _lib.ZF_LOSS_HUBER else 0.0
 
     # -- g / prox with the ridge term (l2 = 0: the shared l1 forms, the same calls as before) --------------------
     def prox_wsum_g(self, weight, x):
@@ -226,6 +283,9 @@ class _GapMixin:
 
     def _screen_refusal(self):
         """Why this problem cannot be screened (None: it can)."""
+        if self._w is not None:
+            return ("sample_weight is set: the weighted rule needs sum_i w_i a_ij^2 for |a_j|^2 and a re-derived rounding guard, "
+                    "which are not built yet")
         if self.l2 > 0:
             return ("l2 > 0: the gap-safe rule of the elastic net (alpha |gt_j| against sqrt(2 gap) sqrt(L |a_j|^2 + l2)) and its "
                     "rounding guard are not built yet")
@@ -235,6 +295,7 @@ class _GapMixin:
         """|a_j|_2 of every column of A: a float64 CUDA tensor of n_features, computed on the GPU once per matrix."""
         import torch
 
+        self._weights_refusal("column_norms")
         h = self._norms
         if h.norms is None:
             lib = _lib.require_gpu()
@@ -299,6 +360,7 @@ class _GapMixin:
         the ``Screen`` of ``screen(x)``, a device mask, a host boolean mask, or a host array of column numbers (the columns
         keep their order).  With x_full[keep] = x and zeros elsewhere, f and jac_f of the restricted problem at x are the
         full problem's at x_full (jac_f: its kept entries).  Keeping no column is refused: that problem's solution is x = 0."""
+        self._weights_refusal("restrict")
         why = self._gap_refusal()
         if why:
             raise ValueError(f"restrict is not available: {why}")
@@ -364,8 +426,10 @@ class _DenseMarginsL1(_GapMixin, NativeProblem):
     kind = None
     _eval_name = None   # f and jac_f at a host vector
 
-    def _set(self, A, b, lam, scale, bounds, l2=0.0):
+    def _set(self, A, b, lam, scale, bounds, l2=0.0, sample_weight=None, group=None):
         self.l2 = _check_l2(l2)
+        if sample_weight is not None:   # (every ValueError before anything touches the device)
+            sample_weight = _check_weights(sample_weight, int(np.shape(b)[0]) if np.ndim(b) == 1 else -1, group)
         self.A = _to_device(A, "A")
         self.b = _to_device(b, "b")
         if self.A.ndim != 2 or self.b.ndim != 1 or self.A.shape[0] != self.b.shape[0]:
@@ -375,6 +439,7 @@ class _DenseMarginsL1(_GapMixin, NativeProblem):
         self.m_rows, self.n_features = int(self.A.shape[0]), int(self.A.shape[1])
         self.group = None
         self._norms = _ColumnNorms()
+        self._set_weights(sample_weight)
 
     def _norms_call(self, lib, norms, stats):
         _lib.check(lib.zf_dense_col_norms(_dp(self.A), self.m_rows, self.n_features, _dp(norms), _dp(stats)), "zf_dense_col_norms")
@@ -397,7 +462,27 @@ class _DenseMarginsL1(_GapMixin, NativeProblem):
         _lib.check(lib.zf_dense_restrict(_dp(self.A), self.m_rows, n, _dp(mask), _dp(index), k.value, _dp(out)), "zf_dense_restrict")
         sub.A, sub.n_features = out, int(k.value)
 
+    def _w_ls(self, x, want_grad):
+        """f and jac_f with sample weights (zf_wloss_eval)."""
+        x = _as_host(x)
+        if x.size != self.n_features:
+            raise ValueError(f"len(x) should be equal to n_features, got {x}.")
+        lib = _lib.require_gpu()
+        fval = C.c_double(0.0)
+        grad = np.empty_like(x) if want_grad else None
+        _lib.check(lib.zf_wloss_eval(_dp(self.A), _dp(self.b), _dp(self._w), self.m_rows, self.n_features, self.scale, self._loss,
+                                     self._w_delta(), C.c_void_p(_lib.ptr(x)), C.byref(fval),
+                                     C.c_void_p(_lib.ptr(grad)) if want_grad else None), "zf_wloss_eval")
+        return np.float64(fval.value), grad
+
+    def _w_gap_call(self, lib, x, out):
+        _lib.check(lib.zf_gap_eval_weighted(_dp(self.A), _dp(self.b), _dp(self._w), self.m_rows, self.n_features, self.scale, self.lam,
+                                            self.l2, self._loss, self._w_delta(), C.c_void_p(_lib.ptr(x)), C.c_void_p(_lib.ptr(out)),
+                                            out.size), "zf_gap_eval_weighted")
+
     def _ls(self, x, want_grad):
+        if self._w is not None:
+            return self._w_ls(x, want_grad)
         x = _as_host(x)
         if x.size != self.n_features:
             raise ValueError(f"len(x) should be equal to n_features, got {x}.")
@@ -411,6 +496,8 @@ class _DenseMarginsL1(_GapMixin, NativeProblem):
         return np.float64(fval.value), grad
 
     def _gap_call(self, lib, x, out):
+        if self._w is not None:
+            return self._w_gap_call(lib, x, out)
         if self.l2 > 0:
             _lib.check(lib.zf_gap_eval_enet(C.c_void_p(self.A.data_ptr()), C.c_void_p(self.b.data_ptr()), self.m_rows, self.n_features,
                                             self.scale, self.lam, self.l2, self._gap_logistic, C.c_void_p(_lib.ptr(x)),
@@ -432,7 +519,9 @@ class _DenseMarginsL1(_GapMixin, NativeProblem):
                       scale=self.scale, lam=self.lam, box_lo=self.box[0], box_hi=self.box[1])
         if self.l2 > 0:
             fields["l2"] = self.l2   # (no descriptor field: the engine calls zf_solver_set_l2)
-        return fields, (self.A, self.b)
+        if self._w is not None:
+            fields["row_weights"] = self._w.data_ptr()   # (likewise: zf_solver_set_row_weights)
+        return fields, (self.A, self.b) if self._w is None else (self.A, self.b, self._w)
 
 
 class LeastSquaresL1(_DenseMarginsL1):
@@ -446,7 +535,7 @@ class LeastSquaresL1(_DenseMarginsL1):
     _eval_name = "zf_ls_eval"
     taylor_remainder = True   # acceptance="remainder": R = scale |A (x+ - y)|^2 from the residual kernels at x+
 
-    def __init__(self, A, b, lam, scale=0.5, bounds=None, group=None, shard="columns", l2=0.0):
+    def __init__(self, A, b, lam, scale=0.5, bounds=None, group=None, shard="columns", l2=0.0, *, sample_weight=None):
         """With ``group`` set and ``shard="columns"`` (default), ``A`` is this rank's column block A_p
         (m x n_p, row-major) of a matrix whose columns - and the decision vector - are partitioned
         over the ranks of that process group; ``b`` is replicated; the solve exchanges the m-vector
@@ -458,7 +547,7 @@ class LeastSquaresL1(_DenseMarginsL1):
             raise ValueError("shard must be 'columns' or 'rows'")
         self.shard = shard
         _check_l2(l2, group)
-        self._set(A, b, lam, scale, bounds, l2)
+        self._set(A, b, lam, scale, bounds, l2, sample_weight, group)
         self.group = group
 
     def _descriptor(self):
@@ -512,12 +601,14 @@ class _SparseMarginsL1(_GapMixin, NativeProblem):
     kind = None
     _eval_name = None
 
-    def _set(self, A, b, lam, scale, bounds, l2=0.0):
+    def _set(self, A, b, lam, scale, bounds, l2=0.0, sample_weight=None):
         import torch
 
         from . import sparse
 
         self.l2 = _check_l2(l2)
+        if sample_weight is not None:   # (every ValueError before anything touches the device)
+            sample_weight = _check_weights(sample_weight, int(A.shape[0]))
 
         b_host = b.detach().cpu().numpy() if isinstance(b, torch.Tensor) else b
         prep = sparse.prepare(A, b_host)   # (every ValueError comes from here, before anything touches the device)
@@ -530,6 +621,7 @@ class _SparseMarginsL1(_GapMixin, NativeProblem):
         self._spmat = _SpmatHandle(prep)
         self._norms = _ColumnNorms()
         self._longest = (int(np.diff(prep["indptr"]).max(initial=0)), int(np.diff(prep["t_indptr"]).max(initial=0)))
+        self._set_weights(sample_weight)
 
     def _norms_call(self, lib, norms, stats):
         _lib.check(lib.zf_spmat_col_norms(self._spmat.value, _dp(norms), _dp(stats)), "zf_spmat_col_norms")
@@ -574,7 +666,27 @@ class _SparseMarginsL1(_GapMixin, NativeProblem):
         sub._spmat = _SpmatHandle(prep, dev)
         sub._longest = (int(np.diff(indptr).max(initial=0)), int(np.diff(t_indptr).max(initial=0)))
 
+    def _w_ls(self, x, want_grad):
+        """f and jac_f with sample weights (zf_spmat_wloss_eval)."""
+        x = _as_host(x)
+        if x.size != self.n_features:
+            raise ValueError(f"len(x) should be equal to n_features, got {x}.")
+        lib = _lib.require_gpu()
+        fval = C.c_double(0.0)
+        grad = np.empty_like(x) if want_grad else None
+        _lib.check(lib.zf_spmat_wloss_eval(self._spmat.value, _dp(self.b), _dp(self._w), self.scale, self._loss, self._w_delta(),
+                                           C.c_void_p(_lib.ptr(x)), C.byref(fval), C.c_void_p(_lib.ptr(grad)) if want_grad else None),
+                   "zf_spmat_wloss_eval")
+        return np.float64(fval.value), grad
+
+    def _w_gap_call(self, lib, x, out):
+        _lib.check(lib.zf_spmat_gap_eval_weighted(self._spmat.value, _dp(self.b), _dp(self._w), self.scale, self.lam, self.l2, self._loss,
+                                                  self._w_delta(), C.c_void_p(_lib.ptr(x)), C.c_void_p(_lib.ptr(out)), out.size),
+                   "zf_spmat_gap_eval_weighted")
+
     def _ls(self, x, want_grad):
+        if self._w is not None:
+            return self._w_ls(x, want_grad)
         x = _as_host(x)
         if x.size != self.n_features:
             raise ValueError(f"len(x) should be equal to n_features, got {x}.")
@@ -586,6 +698,8 @@ class _SparseMarginsL1(_GapMixin, NativeProblem):
         return np.float64(fval.value), grad
 
     def _gap_call(self, lib, x, out):
+        if self._w is not None:
+            return self._w_gap_call(lib, x, out)
         if self.l2 > 0:
             _lib.check(lib.zf_spmat_gap_eval_enet(self._spmat.value, C.c_void_p(self.b.data_ptr()), self.scale, self.lam, self.l2,
                                                   self._gap_logistic, C.c_void_p(_lib.ptr(x)), C.c_void_p(_lib.ptr(out)), out.size),
@@ -606,7 +720,9 @@ class _SparseMarginsL1(_GapMixin, NativeProblem):
                       box_lo=self.box[0], box_hi=self.box[1], spmat=self._spmat.value.value)
         if self.l2 > 0:
             fields["l2"] = self.l2   # (no descriptor field: the engine calls zf_solver_set_l2)
-        return fields, (self._spmat, self.b)
+        if self._w is not None:
+            fields["row_weights"] = self._w.data_ptr()   # (likewise: zf_solver_set_row_weights)
+        return fields, (self._spmat, self.b) if self._w is None else (self._spmat, self.b, self._w)
 
 
 class SparseLeastSquaresL1(_SparseMarginsL1):
@@ -623,8 +739,8 @@ class SparseLeastSquaresL1(_SparseMarginsL1):
     _eval_name = "zf_spmat_eval"
     taylor_remainder = True   # acceptance="remainder": R = scale |A (x+ - y)|^2 from the residual kernels at x+
 
-    def __init__(self, A, b, lam, scale=0.5, bounds=None, l2=0.0):
-        self._set(A, b, lam, scale, bounds, l2)
+    def __init__(self, A, b, lam, scale=0.5, bounds=None, l2=0.0, *, sample_weight=None):
+        self._set(A, b, lam, scale, bounds, l2, sample_weight)
 
 
 def _check_labels(b, m=None):
@@ -643,11 +759,13 @@ class LogisticL1(_DenseMarginsL1):
     row-major: L1-regularised logistic regression on the device-resident trial of ``LeastSquaresL1`` - same keywords,
     same result fields.  grad f = scale A^T rho, rho_i = -b_i sigma(-b_i (Ax)_i) (csrc/zf_kernels_loss.h: one
     exp(-|t|) per row feeds both, finite for every finite margin).  Labels other than exactly -1 / +1 raise ValueError.
-    Single GPU.  The elastic net: ``LogisticL1(A, b, lam).with_penalty(lam, l2)`` (the constructor's parameter list is fixed)."""
+    Single GPU.  The elastic net: ``LogisticL1(A, b, lam).with_penalty(lam, l2)``; sample weights:
+    ``LogisticL1(A, b, lam).with_sample_weight(w)`` (the constructor's parameter list is fixed)."""
 
     kind = _lib.ZF_PROBLEM_LOGISTIC_L1
     _eval_name = "zf_logistic_eval"
     _gap_logistic = 1
+    _loss = _lib.ZF_LOSS_LOGISTIC
 
     def __init__(self, A, b, lam, scale=1.0, bounds=None):
         shape = tuple(getattr(A, "shape", np.shape(A)))
@@ -665,6 +783,7 @@ class SparseLogisticL1(_SparseMarginsL1):
     kind = _lib.ZF_PROBLEM_SPARSE_LOGISTIC_L1
     _eval_name = "zf_spmat_logistic_eval"
     _gap_logistic = 1
+    _loss = _lib.ZF_LOSS_LOGISTIC
 
     def __init__(self, A, b, lam, scale=1.0, bounds=None):
         _check_labels(b)
@@ -686,6 +805,8 @@ class _HuberMixin:
     ``zf_solver_set_huber``.  No ``taylor_remainder``: scale |A (x+ - y)|^2 is not this loss's remainder, so
     ``acceptance="remainder"`` is refused as for the logistic classes."""
 
+    _loss = _lib.ZF_LOSS_HUBER
+
     def _descriptor(self):
         fields, keep = super()._descriptor()
         fields["huber_delta"] = self.delta   # (no descriptor field: the engine calls zf_solver_set_huber)
@@ -706,12 +827,14 @@ class HuberL1(_HuberMixin, _DenseMarginsL1):
 
     kind = _lib.ZF_PROBLEM_LEAST_SQUARES_L1
 
-    def __init__(self, A, b, lam, delta, scale=0.5, bounds=None, l2=0.0, *, group=None):
+    def __init__(self, A, b, lam, delta, scale=0.5, bounds=None, l2=0.0, *, group=None, sample_weight=None):
         self._refuse_group(group)
         self.delta = _check_delta(delta)
-        self._set(A, b, lam, scale, bounds, l2)
+        self._set(A, b, lam, scale, bounds, l2, sample_weight)
 
     def _ls(self, x, want_grad):
+        if self._w is not None:
+            return self._w_ls(x, want_grad)
         x = _as_host(x)
         if x.size != self.n_features:
             raise ValueError(f"len(x) should be equal to n_features, got {x}.")
@@ -724,6 +847,8 @@ class HuberL1(_HuberMixin, _DenseMarginsL1):
         return np.float64(fval.value), grad
 
     def _gap_call(self, lib, x, out):
+        if self._w is not None:
+            return self._w_gap_call(lib, x, out)
         _lib.check(lib.zf_gap_eval_huber(_dp(self.A), _dp(self.b), self.m_rows, self.n_features, self.scale, self.lam, self.l2,
                                          self.delta, C.c_void_p(_lib.ptr(x)), C.c_void_p(_lib.ptr(out)), out.size), "zf_gap_eval_huber")
 
@@ -740,12 +865,14 @@ class SparseHuberL1(_HuberMixin, _SparseMarginsL1):
 
     kind = _lib.ZF_PROBLEM_SPARSE_LS_L1
 
-    def __init__(self, A, b, lam, delta, scale=0.5, bounds=None, l2=0.0, *, group=None):
+    def __init__(self, A, b, lam, delta, scale=0.5, bounds=None, l2=0.0, *, group=None, sample_weight=None):
         self._refuse_group(group)
         self.delta = _check_delta(delta)
-        self._set(A, b, lam, scale, bounds, l2)
+        self._set(A, b, lam, scale, bounds, l2, sample_weight)
 
     def _ls(self, x, want_grad):
+        if self._w is not None:
+            return self._w_ls(x, want_grad)
         x = _as_host(x)
         if x.size != self.n_features:
             raise ValueError(f"len(x) should be equal to n_features, got {x}.")
@@ -757,6 +884,8 @@ class SparseHuberL1(_HuberMixin, _SparseMarginsL1):
         return np.float64(fval.value), grad
 
     def _gap_call(self, lib, x, out):
+        if self._w is not None:
+            return self._w_gap_call(lib, x, out)
         _lib.check(lib.zf_spmat_gap_eval_huber(self._spmat.value, _dp(self.b), self.scale, self.lam, self.l2, self.delta,
                                                C.c_void_p(_lib.ptr(x)), C.c_void_p(_lib.ptr(out)), out.size), "zf_spmat_gap_eval_huber")
 

@@ -180,6 +180,12 @@ def minimize_proximal_gradient(
     if native is not None and not (lr > 0 and decay_rate > 0 and native.lam >= 0):
         native = None   # the fused kernels assume a threshold lam * lr >= 0; the callback path does not
     native_multi = match_native_multi(f, g, jac_f, prox_wsum_g)
+    if acceptance in ("resolved", "remainder") and native is not None and getattr(native, "sample_weight", None) is not None:
+        if accept_from_env:
+            opts["acceptance"] = acceptance = "reference"   # (the environment asks for what this problem has not: the reference's test runs)
+        else:
+            raise ValueError(f"acceptance={acceptance!r} is not available with sample_weight: the kernels that form the Taylor remainder "
+                             "scale |A (x+ - y)|^2 (and the element-wise difference of 'resolved') carry no row weights")
     if acceptance == "resolved" and not (native is not None and getattr(native, "separable", False)):
         if accept_from_env:
             opts["acceptance"] = acceptance = "reference"   # (the environment asks for what this problem has not: the reference's test runs)
