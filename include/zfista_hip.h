@@ -417,7 +417,13 @@ int zf_host_model_terms(const double* jac_host, const double* x_host, const doub
 int zf_host_momentum(double* y_out_host, const double* x_host, const double* x_old_host,
                      double beta, int64_t n);
 /* the same three expressions on device vectors (callbacks written against device tensors:
- * iterates stay in HBM; zf_dev_model_terms synchronises `stream` to return its three scalars) */
+ * iterates stay in HBM; zf_dev_model_terms synchronises `stream` to return its three scalars).
+ * Sharing: the zf_dev_* calls and zf_eval_diag_l1 of ONE host thread share, per device, one buffer of block
+ * partials and one 8-double result block (the staging workspace of the zf_host_* calls, which zf_shutdown
+ * releases).  A call only enqueues work on `stream`, so two calls of one thread on DIFFERENT streams would
+ * overwrite each other's partials: the caller orders them against each other (an event, a synchronisation, or
+ * simply one stream per thread).  Calls of different host threads never share: solve_on_streams gives each
+ * stream a thread of its own. */
 int zf_dev_grad_step(double* v_dev, const double* y_dev, const double* jac_dev, double lr, int64_t n, void* stream);
 int zf_dev_model_terms(const double* jac_dev, const double* x_dev, const double* y_dev, int64_t n,
                        double out3_host[3], void* stream);
