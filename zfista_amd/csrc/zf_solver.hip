@@ -25,10 +25,19 @@
 #include "zf_kernels_gap.h"
 #include "zf_kernels_huber.h"
 #include "zf_kernels_wloss.h"
+#include "zf_loss_dispatch.h"
 #include "zf_kernels_step.h"
 #include "zf_trial_launch.h"
 
 thread_local char zf_errbuf[512] = "";
+
+// for the entry points that allocate, launch and free in one call: run everything, keep the first HIP error in `rc`
+#define ZF_KEEP_FIRST(expr)                                                       \
+    do {                                                                          \
+        hipError_t _e = (expr);                                                   \
+        if (_e != hipSuccess && rc == ZF_OK)                                      \
+            rc = zf_fail(ZF_ERR_HIP, "%s: %s", #expr, hipGetErrorString(_e));     \
+    } while (0)
 
 // ---------------------------------------------------------------------------
 // finalize / decide kernels
@@ -403,6 +412,22 @@ static bool zf_is_dense_mat(int kind) { return kind == ZF_PROBLEM_LEAST_SQUARES_
 static bool zf_is_sparse_mat(int kind) { return kind == ZF_PROBLEM_SPARSE_LS_L1 || kind == ZF_PROBLEM_SPARSE_LOGISTIC_L1; }
 // f is a loss of A x: the margins of x_k, x_{k-1} are kept in a ring and A y follows by linearity
 static bool zf_has_margins(int kind) { return zf_is_ls(kind) || zf_is_logistic(kind); }
+// the loss of a solver (zf_loss_dispatch.h): the one place that reads the problem kind, zf_solver_set_huber and zf_solver_set_row_weights for it
+static zf_loss zf_loss_of(const zf_solver* s) {
+    const int kind = zf_is_logistic(s->desc.kind) ? ZF_LOSS_LOGISTIC : s->huber > 0.0 ? ZF_LOSS_HUBER : ZF_LOSS_SQUARE;
+    return zf_loss{kind, s->huber, s->roww};
+}
+// row slices of the dense column sweep A^T r: enough that panels x slices fills the chip (>= ~2048 workgroups)
+static void zf_dense_slices(int64_t m, int64_t n, int* slices_out, int64_t* rows_per_slice) {
+    const int V = (n % 2 == 0) ? 2 : 1;
+    const int64_t panels = (n / V + ZF_BLOCK - 1) / ZF_BLOCK;
+    int64_t slices = (ZF_MAX_GRID + panels - 1) / panels;
+    if (slices > (m + 7) / 8) slices = (m + 7) / 8;
+    if (slices < 1) slices = 1;
+    if (slices > 64) slices = 64;
+    *rows_per_slice = (m + slices - 1) / slices;
+    *slices_out = (int)((m + *rows_per_slice - 1) / *rows_per_slice);
+}
 static zf_op_args zf_op_of(const zf_problem_desc& d, const zf_control* ctl, const zf_op_plan& pl, const double* taps, const double* sep) {
     zf_op_args P;
     P.ctl = ctl;
@@ -697,15 +722,7 @@ static int zf_solver_create_impl(zf_solver** out, const zf_problem_desc* desc, c
     if (zf_is_dense_mat(desc->kind)) {
         const int64_t m = desc->m_rows;
         const int64_t m_pad = (m + 63) & ~int64_t(63);
-        // enough row slices that panels x slices fills the chip (>= ~2048 workgroups)
-        const int V = (n % 2 == 0) ? 2 : 1;
-        const int64_t panels = (n / V + ZF_BLOCK - 1) / ZF_BLOCK;
-        int64_t slices = (ZF_MAX_GRID + panels - 1) / panels;
-        if (slices > (m + 7) / 8) slices = (m + 7) / 8;
-        if (slices < 1) slices = 1;
-        if (slices > 64) slices = 64;
-        s->rows_per_slice = (m + slices - 1) / slices;
-        s->slices = (int)((m + s->rows_per_slice - 1) / s->rows_per_slice);
+        zf_dense_slices(m, n, &s->slices, &s->rows_per_slice);
         s->gemv_mfma = (n % 32 == 0) && s->env.gemv_mfma;
         ZF_TRY(hipMalloc(&s->grad, sizeof(double) * n_pad));
         ZF_TRY(hipMalloc(&s->sbuf, sizeof(double) * 3 * m_pad));
@@ -1354,33 +1371,23 @@ static int zf_launch_trial(zf_solver* s, bool decide_in_launch, bool dry = false
         const int V = (n % 2 == 0) ? 2 : 1;
         // (the sparse kind times the whole trial - the event pair brackets every launch of it, not the prox step alone)
         const bool time_whole = zf_is_sparse_mat(d.kind);
-        // the logistic kinds: rho(y), f(y) and f(x+) from zf_kernels_loss.h, and grad = scale A^T rho
-        const bool logistic = zf_is_logistic(d.kind);
-        const double gfac = logistic ? d.scale : 2 * d.scale;
+        // every loss but the unweighted squared one: psi(y), f(y) and f(x+) from its rows kernels, grad = gfac A^T psi by the same sweeps
+        const zf_loss loss = zf_loss_of(s);
+        const double gfac = zf_gfac(loss, d.scale);
         if (time_whole && e0) ZF_HIP(hipEventRecord(e0, s->stream));
         // (1) r = A y - b by linearity, f(y); grad = 2 scale A^T r   [only when y changed]
         // (sparse matrices have 1e5 .. 1e7 rows: beyond what one workgroup should walk, the residuals take many - zf_kernels_spmv.h)
         const bool wide_resid = d.kind == ZF_PROBLEM_SPARSE_LS_L1 && m > ZF_SPMV_WIDE_RESID_MIN_ROWS;
-        // Huber's loss on a least-squares kind (zf_kernels_huber.h): c(y), f(y) and f(x+); grad = 2 scale A^T c by the same sweep
-        const bool huber = s->huber > 0.0;
-        // per-row weights (zf_kernels_wloss.h): the same three places with w o psi and sum w phi; the sweeps stay as they are
-        const int wloss = logistic ? ZF_LOSS_LOGISTIC : huber ? ZF_LOSS_HUBER : ZF_LOSS_SQUARE;
-        if (s->roww)
-            zf_launch_wloss_y(s->stream, s->ctl, s->sring.p[0], s->sring.p[1], s->sring.p[2], d.b, s->roww, s->resid, d.scale, wloss, s->huber,
-                              m, (int)s->opt.nesterov, s->row_part, s->ls_scal + 0);
-        else if (logistic)
-            zf_launch_logit_y(s->stream, s->ctl, s->sring.p[0], s->sring.p[1], s->sring.p[2], d.b, s->resid, d.scale, m, (int)s->opt.nesterov,
-                              s->row_part, s->ls_scal + 0);
-        else if (huber)
-            zf_launch_huber_y(s->stream, s->ctl, s->sring.p[0], s->sring.p[1], s->sring.p[2], d.b, s->resid, d.scale, s->huber, m,
-                              (int)s->opt.nesterov, s->row_part, s->ls_scal + 0);
-        else if (wide_resid)
-            zf_launch_spmv_resid_y(s->stream, s->ctl, s->sring.p[0], s->sring.p[1], s->sring.p[2], d.b, s->resid, d.scale, m,
-                                   (int)s->opt.nesterov, s->row_part, s->ls_scal + 0);
-        else if (d.kind != ZF_PROBLEM_BLUR_HAAR_L1)   // (the operator problem forms r inside its adjoint kernel)
-            hipLaunchKernelGGL(zf_resid_y_kernel, dim3(1), dim3(RESID_BLOCK), 0, s->stream, s->ctl,
-                               s->beta_ring, s->sring, d.b, s->resid, d.scale, m, s->ls_scal + 0,
-                               (int)s->opt.nesterov);
+        if (!zf_launch_loss_y(s->stream, s->ctl, s->sring.p[0], s->sring.p[1], s->sring.p[2], d.b, loss, s->resid, d.scale, m,
+                              (int)s->opt.nesterov, s->row_part, s->ls_scal + 0)) {
+            if (wide_resid)
+                zf_launch_spmv_resid_y(s->stream, s->ctl, s->sring.p[0], s->sring.p[1], s->sring.p[2], d.b, s->resid, d.scale, m,
+                                       (int)s->opt.nesterov, s->row_part, s->ls_scal + 0);
+            else if (d.kind != ZF_PROBLEM_BLUR_HAAR_L1)   // (the operator problem forms r inside its adjoint kernel)
+                hipLaunchKernelGGL(zf_resid_y_kernel, dim3(1), dim3(RESID_BLOCK), 0, s->stream, s->ctl,
+                                   s->beta_ring, s->sring, d.b, s->resid, d.scale, m, s->ls_scal + 0,
+                                   (int)s->opt.nesterov);
+        }
         const int64_t nv = n / V;
         dim3 gT((unsigned)((nv + ZF_BLOCK - 1) / ZF_BLOCK), (unsigned)s->slices);
         if (d.kind == ZF_PROBLEM_BLUR_HAAR_L1) {
@@ -1456,24 +1463,18 @@ static int zf_launch_trial(zf_solver* s, bool decide_in_launch, bool dry = false
             zf_launch_trial_kernels(s, a, false);
             zf_ring3 xr3 = {{s->xb[0], s->xb[1], s->xb[2]}};
             zf_launch_apply_A(s, s->ctl, xr3, s->sring, 1);
-            if (s->roww)
-                zf_launch_wloss_x(s->stream, s->ctl, s->sring.p[0], s->sring.p[1], s->sring.p[2], 1, d.b, s->roww, d.scale, wloss, s->huber, m,
-                                  s->row_part + ZF_SPMV_RESID_MAX_CHUNKS, s->ls_scal + 1);
-            else if (logistic)
-                zf_launch_logit_x(s->stream, s->ctl, s->sring.p[0], s->sring.p[1], s->sring.p[2], 1, d.b, d.scale, m,
-                                  s->row_part + ZF_SPMV_RESID_MAX_CHUNKS, s->ls_scal + 1);
-            else if (huber)
-                zf_launch_huber_x(s->stream, s->ctl, s->sring.p[0], s->sring.p[1], s->sring.p[2], 1, d.b, d.scale, s->huber, m,
-                                  s->row_part + ZF_SPMV_RESID_MAX_CHUNKS, s->ls_scal + 1);
-            else if (wide_resid && s->rem)
-                zf_launch_spmv_resid_x_rem(s->stream, s->ctl, s->sring.p[0], s->sring.p[1], s->sring.p[2], 1, d.b, d.scale, m,
-                                           (int)s->opt.nesterov, 0.0, s->row_part + ZF_SPMV_RESID_MAX_CHUNKS,
-                                           s->row_part + 2 * ZF_SPMV_RESID_MAX_CHUNKS, s->ls_scal + 1, s->ls_scal + 2);
-            else if (wide_resid)
-                zf_launch_spmv_resid_x(s->stream, s->ctl, s->sring.p[0], s->sring.p[1], s->sring.p[2], 1, d.b, d.scale, m,
-                                       s->row_part + ZF_SPMV_RESID_MAX_CHUNKS, s->ls_scal + 1);
-            else
-                zf_launch_resid_x(s);
+            if (!zf_launch_loss_x(s->stream, s->ctl, s->sring.p[0], s->sring.p[1], s->sring.p[2], 1, d.b, loss, d.scale, m,
+                                  s->row_part + ZF_SPMV_RESID_MAX_CHUNKS, s->ls_scal + 1)) {
+                if (wide_resid && s->rem)
+                    zf_launch_spmv_resid_x_rem(s->stream, s->ctl, s->sring.p[0], s->sring.p[1], s->sring.p[2], 1, d.b, d.scale, m,
+                                               (int)s->opt.nesterov, 0.0, s->row_part + ZF_SPMV_RESID_MAX_CHUNKS,
+                                               s->row_part + 2 * ZF_SPMV_RESID_MAX_CHUNKS, s->ls_scal + 1, s->ls_scal + 2);
+                else if (wide_resid)
+                    zf_launch_spmv_resid_x(s->stream, s->ctl, s->sring.p[0], s->sring.p[1], s->sring.p[2], 1, d.b, d.scale, m,
+                                           s->row_part + ZF_SPMV_RESID_MAX_CHUNKS, s->ls_scal + 1);
+                else
+                    zf_launch_resid_x(s);
+            }
             zf_launch_finalize(s, decide_in_launch);
             if (e1) ZF_HIP(hipEventRecord(e1, s->stream));
             ZF_HIP(hipGetLastError());
@@ -1527,16 +1528,8 @@ static int zf_launch_trial(zf_solver* s, bool decide_in_launch, bool dry = false
             hipLaunchKernelGGL(zf_gemv_rows_kernel<1>, dim3(gr), dim3(ZF_BLOCK), 0, s->stream, s->ctl, d.A,
                                xr, sout, 1, m, n);
         if (d.world == 1) {
-            if (s->roww)
-                zf_launch_wloss_x(s->stream, s->ctl, s->sring.p[0], s->sring.p[1], s->sring.p[2], 1, d.b, s->roww, d.scale, wloss, s->huber, m,
-                                  s->row_part + ZF_SPMV_RESID_MAX_CHUNKS, s->ls_scal + 1);
-            else if (logistic)
-                zf_launch_logit_x(s->stream, s->ctl, s->sring.p[0], s->sring.p[1], s->sring.p[2], 1, d.b, d.scale, m,
-                                  s->row_part + ZF_SPMV_RESID_MAX_CHUNKS, s->ls_scal + 1);
-            else if (huber)
-                zf_launch_huber_x(s->stream, s->ctl, s->sring.p[0], s->sring.p[1], s->sring.p[2], 1, d.b, d.scale, s->huber, m,
-                                  s->row_part + ZF_SPMV_RESID_MAX_CHUNKS, s->ls_scal + 1);
-            else
+            if (!zf_launch_loss_x(s->stream, s->ctl, s->sring.p[0], s->sring.p[1], s->sring.p[2], 1, d.b, loss, d.scale, m,
+                                  s->row_part + ZF_SPMV_RESID_MAX_CHUNKS, s->ls_scal + 1))
                 zf_launch_resid_x(s);
             zf_launch_finalize(s, decide_in_launch);
         }
@@ -1594,19 +1587,14 @@ static int zf_init_ls_tail(zf_solver* s) {
     const int64_t n = d.n, m = d.m_rows;
     zf_ring3 s0 = {{s->sring.p[0], s->sring.p[0], s->sring.p[0]}};
     ZF_HIP(hipMemcpyAsync(s->sring.p[2], s->sring.p[0], sizeof(double) * m, hipMemcpyDeviceToDevice, s->stream));
-    if (s->roww) {   // (zf_kernels_wloss.h: the weighted loss, in the order the loop sums f(x+))
-        const int wloss = zf_is_logistic(d.kind) ? ZF_LOSS_LOGISTIC : s->huber > 0.0 ? ZF_LOSS_HUBER : ZF_LOSS_SQUARE;
-        zf_launch_wloss_x(s->stream, nullptr, s0.p[0], s0.p[0], s0.p[0], -1, d.b, s->roww, d.scale, wloss, s->huber, m, s->row_part,
-                          s->ls_scal + 1);
-    } else if (zf_is_logistic(d.kind)) {   // the same loss, in the order the loop sums f(x+) (zf_kernels_loss.h)
-        zf_launch_logit_x(s->stream, nullptr, s0.p[0], s0.p[0], s0.p[0], -1, d.b, d.scale, m, s->row_part, s->ls_scal + 1);
-    } else if (s->huber > 0.0) {   // (zf_kernels_huber.h, likewise)
-        zf_launch_huber_x(s->stream, nullptr, s0.p[0], s0.p[0], s0.p[0], -1, d.b, d.scale, s->huber, m, s->row_part, s->ls_scal + 1);
-    } else if (m > (int64_t)1 << 18) {   // long residuals (the operator problem at image sizes beyond 512 x 512): two launches, many workgroups
+    // (a loss with rows kernels of its own: in the order the loop sums f(x+))
+    const bool own_rows = zf_launch_loss_x(s->stream, nullptr, s0.p[0], s0.p[0], s0.p[0], -1, d.b, zf_loss_of(s), d.scale, m, s->row_part,
+                                           s->ls_scal + 1);
+    if (!own_rows && m > (int64_t)1 << 18) {   // long residuals (the operator problem at image sizes beyond 512 x 512): two launches, many workgroups
         const int wgs = zf_grid_for(m / 8);
         hipLaunchKernelGGL(zf_resid_x_wide_kernel, dim3(wgs), dim3(ZF_BLOCK), 0, s->stream, s0.p[0], d.b, m, s->partials);
         hipLaunchKernelGGL(zf_resid_x_finish_kernel, dim3(1), dim3(RESID_BLOCK), 0, s->stream, s->partials, wgs, d.scale, s->ls_scal + 1);
-    } else {
+    } else if (!own_rows) {
         hipLaunchKernelGGL(zf_resid_x_kernel, dim3(1), dim3(RESID_BLOCK), 0, s->stream, nullptr, s0, -1, d.b, d.scale,
                            m, s->ls_scal + 1);
     }
@@ -2483,20 +2471,14 @@ extern "C" int zf_ls_remainder_eval(const double* s_plus_host, const double* s_k
     double *sv = nullptr, *b = nullptr, *part = nullptr, *out = nullptr;
     const int64_t m_pad = (m + 63) & ~int64_t(63);
     int rc = ZF_OK;
-#define ZF_RM(expr)                                                               \
-    do {                                                                          \
-        hipError_t _e = (expr);                                                   \
-        if (_e != hipSuccess && rc == ZF_OK)                                      \
-            rc = zf_fail(ZF_ERR_HIP, "%s: %s", #expr, hipGetErrorString(_e));     \
-    } while (0)
-    ZF_RM(hipMalloc(&sv, sizeof(double) * 3 * m_pad));
-    ZF_RM(hipMalloc(&b, sizeof(double) * m_pad));
-    ZF_RM(hipMalloc(&part, sizeof(double) * 2 * ZF_SPMV_RESID_MAX_CHUNKS));
-    ZF_RM(hipMalloc(&out, sizeof(double) * 2));
+    ZF_KEEP_FIRST(hipMalloc(&sv, sizeof(double) * 3 * m_pad));
+    ZF_KEEP_FIRST(hipMalloc(&b, sizeof(double) * m_pad));
+    ZF_KEEP_FIRST(hipMalloc(&part, sizeof(double) * 2 * ZF_SPMV_RESID_MAX_CHUNKS));
+    ZF_KEEP_FIRST(hipMalloc(&out, sizeof(double) * 2));
     if (rc == ZF_OK) {
         const double* src[3] = {s_plus_host, s_k_host, s_km1_host};
-        for (int k = 0; k < 3; ++k) ZF_RM(hipMemcpyAsync(sv + k * m_pad, src[k], sizeof(double) * m, hipMemcpyHostToDevice, nullptr));
-        ZF_RM(hipMemsetAsync(b, 0, sizeof(double) * m_pad, nullptr));   // (f(x+) of the same kernels is not asked for here)
+        for (int k = 0; k < 3; ++k) ZF_KEEP_FIRST(hipMemcpyAsync(sv + k * m_pad, src[k], sizeof(double) * m, hipMemcpyHostToDevice, nullptr));
+        ZF_KEEP_FIRST(hipMemsetAsync(b, 0, sizeof(double) * m_pad, nullptr));   // (f(x+) of the same kernels is not asked for here)
         const zf_ring3 sr = {{sv, sv + m_pad, sv + 2 * m_pad}};
         if (wide)
             zf_launch_spmv_resid_x_rem(nullptr, nullptr, sr.p[0], sr.p[1], sr.p[2], -1, b, scale, m, nesterov ? 1 : 0, beta, part,
@@ -2504,241 +2486,210 @@ extern "C" int zf_ls_remainder_eval(const double* s_plus_host, const double* s_k
         else
             hipLaunchKernelGGL(zf_resid_x_rem_kernel, dim3(1), dim3(RESID_BLOCK), 0, nullptr, nullptr, sr, -1, b, scale, m, out + 0,
                                nesterov ? 1 : 0, beta, out + 1);
-        ZF_RM(hipGetLastError());
-        ZF_RM(hipMemcpyAsync(r_out, out + 1, sizeof(double), hipMemcpyDeviceToHost, nullptr));
-        ZF_RM(hipStreamSynchronize(nullptr));
+        ZF_KEEP_FIRST(hipGetLastError());
+        ZF_KEEP_FIRST(hipMemcpyAsync(r_out, out + 1, sizeof(double), hipMemcpyDeviceToHost, nullptr));
+        ZF_KEEP_FIRST(hipStreamSynchronize(nullptr));
     }
-#undef ZF_RM
     for (void* p : {(void*)sv, (void*)b, (void*)part, (void*)out})
         if (p) (void)hipFree(p);
     return rc;
 }
 
 // ---------------------------------------------------------------------------
-// least-squares operator at a host point (callback contract, not the hot loop)
+// A as the evaluations outside the loop see it: dense row-major, or CSR behind a handle - and its two sweeps
 // ---------------------------------------------------------------------------
-// logistic: the loss of zf_kernels_loss.h on the same sweeps (zf_logistic_eval) - rho = -b sigma(-b s) takes the place of
-// r = s - b, scale that of 2 scale
-static int zf_dense_eval(const double* A_dev, const double* b_dev, int64_t m_rows, int64_t n, double scale,
-                         const double* x_host, double* f_out, double* grad_out_host, bool logistic, double delta = 0.0,
-                         const double* w_dev = nullptr) {
-    // (delta > 0: Huber's loss of zf_kernels_huber.h - c = clip(s - b) takes the place of r, the factor stays 2 scale)
-    // (w_dev: the weighted kernels of zf_kernels_wloss.h for the loss the two flags name)
-    const bool huber = delta > 0.0, own_rows = logistic || huber || w_dev;
-    const int wloss = logistic ? ZF_LOSS_LOGISTIC : huber ? ZF_LOSS_HUBER : ZF_LOSS_SQUARE;
-    const int V = (n % 2 == 0) ? 2 : 1;
-    const int64_t nv = n / V;
-    const int64_t panels = (nv + ZF_BLOCK - 1) / ZF_BLOCK;
-    int64_t slices = (ZF_MAX_GRID + panels - 1) / panels;
-    if (slices > (m_rows + 7) / 8) slices = (m_rows + 7) / 8;
-    if (slices < 1) slices = 1;
-    if (slices > 64) slices = 64;
-    const int64_t rps = (m_rows + slices - 1) / slices;
-    slices = (m_rows + rps - 1) / rps;
-    double *x = nullptr, *s = nullptr, *slab = nullptr, *grad = nullptr, *fdev = nullptr, *rho = nullptr, *part = nullptr;
+struct zf_matview {
+    const double* A;     // dense: m x n row-major (device), 16-byte aligned; NULL for CSR
+    int64_t m, n;        // (CSR: the handle's, filled in by zf_loss_args once the handle is known not to be NULL)
+    const zf_spmat* h;   // CSR: A and A^T with their plans; NULL for dense
+    bool csr;
+};
+static zf_matview zf_dense_view(const double* A, int64_t m, int64_t n) { return zf_matview{A, m, n, nullptr, false}; }
+static zf_matview zf_csr_view(const zf_spmat* h) { return zf_matview{nullptr, 0, 0, h, true}; }
+
+// what the sweeps write between their launches: the slab of the dense column sweep and its slices, or the segment sums of the
+// split rows of A / A^T (a call's own, or a solver's: the handle is shared with live solvers on other streams)
+struct zf_sweep_ws {
+    double* slab;
+    int slices;
+    int64_t rows_per_slice;
+    double *part_A, *part_At;
+};
+// (adjoint false: what z = A x alone needs)
+static int zf_sweep_ws_alloc(const zf_matview& V, bool adjoint, zf_sweep_ws* W) {
     int rc = ZF_OK;
-#define ZF_LS(expr)                                                               \
-    do {                                                                          \
-        hipError_t _e = (expr);                                                   \
-        if (_e != hipSuccess && rc == ZF_OK)                                      \
-            rc = zf_fail(ZF_ERR_HIP, "%s: %s", #expr, hipGetErrorString(_e));     \
-    } while (0)
-    ZF_LS(hipMalloc(&x, sizeof(double) * (n + 2)));
-    ZF_LS(hipMalloc(&s, sizeof(double) * (m_rows + 2)));
-    ZF_LS(hipMalloc(&fdev, sizeof(double) * 2));
+    *W = zf_sweep_ws{nullptr, 1, V.m, nullptr, nullptr};
+    if (V.csr) {
+        if (V.h->A.nseg > 0) ZF_KEEP_FIRST(hipMalloc(&W->part_A, sizeof(double) * V.h->A.nseg));
+        if (adjoint && V.h->At.nseg > 0) ZF_KEEP_FIRST(hipMalloc(&W->part_At, sizeof(double) * V.h->At.nseg));
+    } else if (adjoint) {
+        zf_dense_slices(V.m, V.n, &W->slices, &W->rows_per_slice);
+        ZF_KEEP_FIRST(hipMalloc(&W->slab, sizeof(double) * W->slices * V.n));
+    }
+    return rc;
+}
+static void zf_sweep_ws_free(zf_sweep_ws* W) {
+    for (void* p : {(void*)W->slab, (void*)W->part_A, (void*)W->part_At})
+        if (p) (void)hipFree(p);
+}
+
+// z = A x, outside the loop (ctl = NULL)
+static void zf_launch_view_apply(const zf_matview& V, hipStream_t st, double* x, double* z, const zf_sweep_ws& W) {
+    if (V.csr) {
+        const zf_spmv_io aio = {{x, x, x}, {z, z, z}};
+        zf_launch_spmv(V.h->A, st, nullptr, false, aio, -1, 1.0, W.part_A);
+        return;
+    }
+    zf_ring3 xr = {{x, x, x}}, sr = {{z, z, z}};
+    int gr = (int)((V.m + GEMV_ROWS - 1) / GEMV_ROWS);
+    if (gr > 8 * ZF_MAX_GRID) gr = 8 * ZF_MAX_GRID;
+    if (V.n % 2 == 0) hipLaunchKernelGGL(zf_gemv_rows_kernel<2>, dim3(gr), dim3(ZF_BLOCK), 0, st, nullptr, V.A, xr, sr, -1, V.m, V.n);
+    else hipLaunchKernelGGL(zf_gemv_rows_kernel<1>, dim3(gr), dim3(ZF_BLOCK), 0, st, nullptr, V.A, xr, sr, -1, V.m, V.n);
+}
+
+// g = factor * A^T r, outside the loop.  Dense: the column sweep over W's slices - on v_mfma_f64_16x16x4 when `mfma` (the caller
+// knows n % 32 == 0 and asked the environment), else the VALU sweep; the two sum in different orders - and the slice combine.
+static void zf_launch_view_adjoint(const zf_matview& V, hipStream_t st, const double* r, double* g, double factor, bool mfma,
+                                   const zf_sweep_ws& W) {
+    if (V.csr) {
+        const zf_spmv_io gio = {{r, r, r}, {g, g, g}};
+        zf_launch_spmv(V.h->At, st, nullptr, false, gio, -1, factor, W.part_At);
+        return;
+    }
+    const int64_t m = V.m, n = V.n;
+    const int vw = (n % 2 == 0) ? 2 : 1;
+    if (mfma) {
+        dim3 gM((unsigned)((n + GEMVT_MFMA_COLS - 1) / GEMVT_MFMA_COLS), (unsigned)W.slices);
+        hipLaunchKernelGGL(zf_gemvT_partial_mfma_kernel, gM, dim3(ZF_BLOCK), 0, st, nullptr, V.A, r, W.slab, m, n, W.rows_per_slice);
+    } else {
+        dim3 gT((unsigned)((n / vw + ZF_BLOCK - 1) / ZF_BLOCK), (unsigned)W.slices);
+        if (vw == 2) hipLaunchKernelGGL(zf_gemvT_partial_kernel<2>, gT, dim3(ZF_BLOCK), 0, st, nullptr, V.A, r, W.slab, m, n, W.rows_per_slice);
+        else hipLaunchKernelGGL(zf_gemvT_partial_kernel<1>, gT, dim3(ZF_BLOCK), 0, st, nullptr, V.A, r, W.slab, m, n, W.rows_per_slice);
+    }
+    hipLaunchKernelGGL(zf_gemvT_combine_kernel, dim3(zf_grid_for(n)), dim3(ZF_BLOCK), 0, st, nullptr, W.slab, g, factor, n, W.slices);
+}
+
+// The checks every evaluation entry point shares (`who`: the entry's name).  First its pointers (`ok`) and its matrix ...
+static int zf_view_args(const char* who, const zf_matview& V, bool ok) {
+    if (V.csr && !(ok && V.h)) return zf_fail(ZF_ERR_ARG, "%s: null argument%s", who);
+    if (!V.csr && !(ok && V.A && V.m >= 1 && V.n >= 1)) return zf_fail(ZF_ERR_ARG, "%s: bad argument%s", who);
+    return ZF_OK;
+}
+// ... then, behind zf_view_args, the loss code, Huber's delta and the alignment of a dense A; leaves the entry's loss in *L
+static int zf_loss_args(const char* who, zf_matview* V, int32_t kind, double delta, const double* w_dev, zf_loss* L) {
+    if (kind != ZF_LOSS_SQUARE && kind != ZF_LOSS_LOGISTIC && kind != ZF_LOSS_HUBER)
+        return zf_fail(ZF_ERR_ARG, "%s: loss must be ZF_LOSS_SQUARE, ZF_LOSS_LOGISTIC or ZF_LOSS_HUBER%s", who);
+    if (kind == ZF_LOSS_HUBER && !(delta > 0.0 && delta <= DBL_MAX)) return zf_fail(ZF_ERR_ARG, "%s: delta must be finite and > 0%s", who);
+    if (!V->csr && !zf_aligned16(V->A)) return zf_fail(ZF_ERR_ARG, "%s: A must be 16-byte aligned%s", who);
+    if (V->csr) V->m = V->h->m, V->n = V->h->n;
+    *L = zf_loss{kind, kind == ZF_LOSS_HUBER ? delta : 0.0, w_dev};
+    return ZF_OK;
+}
+
+// ---------------------------------------------------------------------------
+// f and grad f at a host point (callback contract, not the hot loop)
+// ---------------------------------------------------------------------------
+// f = scale sum w phi(A x) and (grad_out_host != NULL) grad = gfac A^T (w o psi(A x)), on the rows kernels and the sweeps a solver
+// of this loss runs.  The column sweep of a dense A is always the VALU one: jac_f has the same bits whatever n % 32 is.
+static int zf_point_eval(const zf_matview& V, const double* b_dev, double scale, const zf_loss& L, const double* x_host, double* f_out,
+                         double* grad_out_host) {
+    const int64_t m = V.m, n = V.n;
+    const bool own_rows = L.w || L.kind != ZF_LOSS_SQUARE;   // (zf_launch_loss_y / _x return true)
+    double *x = nullptr, *z = nullptr, *grad = nullptr, *fdev = nullptr, *rho = nullptr, *part = nullptr;
+    zf_sweep_ws W;
+    int rc = zf_sweep_ws_alloc(V, grad_out_host != nullptr, &W);
+    ZF_KEEP_FIRST(hipMalloc(&x, sizeof(double) * (n + 2)));   // (the dense rows kernel reads its two-wide tail; nothing reads the pad for CSR)
+    ZF_KEEP_FIRST(hipMalloc(&z, sizeof(double) * (m + 2)));
+    ZF_KEEP_FIRST(hipMalloc(&fdev, sizeof(double) * 2));
     if (own_rows) {
-        ZF_LS(hipMalloc(&part, sizeof(double) * ZF_SPMV_RESID_MAX_CHUNKS));
-        if (grad_out_host) ZF_LS(hipMalloc(&rho, sizeof(double) * m_rows));
+        ZF_KEEP_FIRST(hipMalloc(&part, sizeof(double) * ZF_SPMV_RESID_MAX_CHUNKS));
+        if (grad_out_host) ZF_KEEP_FIRST(hipMalloc(&rho, sizeof(double) * m));
     }
-    if (grad_out_host) {
-        ZF_LS(hipMalloc(&slab, sizeof(double) * slices * n));
-        ZF_LS(hipMalloc(&grad, sizeof(double) * n));
-    }
+    if (grad_out_host) ZF_KEEP_FIRST(hipMalloc(&grad, sizeof(double) * n));
     if (rc == ZF_OK) {
-        ZF_LS(hipMemcpyAsync(x, x_host, sizeof(double) * n, hipMemcpyHostToDevice, nullptr));
-        zf_ring3 xr = {{x, x, x}}, sr = {{s, s, s}};
-        int gr = (int)((m_rows + GEMV_ROWS - 1) / GEMV_ROWS);
-        if (gr > 8 * ZF_MAX_GRID) gr = 8 * ZF_MAX_GRID;
-        if (V == 2)
-            hipLaunchKernelGGL(zf_gemv_rows_kernel<2>, dim3(gr), dim3(ZF_BLOCK), 0, nullptr, nullptr, A_dev, xr, sr,
-                               -1, m_rows, n);
-        else
-            hipLaunchKernelGGL(zf_gemv_rows_kernel<1>, dim3(gr), dim3(ZF_BLOCK), 0, nullptr, nullptr, A_dev, xr, sr,
-                               -1, m_rows, n);
-        if (w_dev && grad_out_host)
-            zf_launch_wloss_y(nullptr, nullptr, s, s, s, b_dev, w_dev, rho, scale, wloss, delta, m_rows, 0, part, fdev);
-        else if (w_dev)
-            zf_launch_wloss_x(nullptr, nullptr, s, s, s, -1, b_dev, w_dev, scale, wloss, delta, m_rows, part, fdev);
-        else if (huber && grad_out_host)
-            zf_launch_huber_y(nullptr, nullptr, s, s, s, b_dev, rho, scale, delta, m_rows, 0, part, fdev);
-        else if (huber)
-            zf_launch_huber_x(nullptr, nullptr, s, s, s, -1, b_dev, scale, delta, m_rows, part, fdev);
-        else if (!logistic)
-            hipLaunchKernelGGL(zf_resid_x_kernel, dim3(1), dim3(RESID_BLOCK), 0, nullptr, nullptr, sr, -1, b_dev, scale,
-                               m_rows, fdev);
-        else if (grad_out_host)
-            zf_launch_logit_y(nullptr, nullptr, s, s, s, b_dev, rho, scale, m_rows, 0, part, fdev);
-        else
-            zf_launch_logit_x(nullptr, nullptr, s, s, s, -1, b_dev, scale, m_rows, part, fdev);
-        if (grad_out_host) {
-            // r = s - b in place, then column sums
-            if (!own_rows)
-                hipLaunchKernelGGL(zf_axmb_kernel, dim3(zf_grid_for(m_rows)), dim3(ZF_BLOCK), 0, nullptr, s, b_dev,
-                                   m_rows);
-            const double* rv = own_rows ? rho : s;
-            dim3 gT((unsigned)panels, (unsigned)slices);
-            if (V == 2)
-                hipLaunchKernelGGL(zf_gemvT_partial_kernel<2>, gT, dim3(ZF_BLOCK), 0, nullptr, nullptr, A_dev, rv,
-                                   slab, m_rows, n, rps);
-            else
-                hipLaunchKernelGGL(zf_gemvT_partial_kernel<1>, gT, dim3(ZF_BLOCK), 0, nullptr, nullptr, A_dev, rv,
-                                   slab, m_rows, n, rps);
-            hipLaunchKernelGGL(zf_gemvT_combine_kernel, dim3(zf_grid_for(n)), dim3(ZF_BLOCK), 0, nullptr, nullptr,
-                               slab, grad, logistic ? scale : 2 * scale, n, (int)slices);
-            ZF_LS(hipMemcpyAsync(grad_out_host, grad, sizeof(double) * n, hipMemcpyDeviceToHost, nullptr));
+        ZF_KEEP_FIRST(hipMemcpyAsync(x, x_host, sizeof(double) * n, hipMemcpyHostToDevice, nullptr));
+        zf_launch_view_apply(V, nullptr, x, z, W);
+        const bool launched = grad_out_host ? zf_launch_loss_y(nullptr, nullptr, z, z, z, b_dev, L, rho, scale, m, 0, part, fdev)
+                                            : zf_launch_loss_x(nullptr, nullptr, z, z, z, -1, b_dev, L, scale, m, part, fdev);
+        if (!launched) {   // the unweighted squared loss: f from the residual kernel, then r = z - b in place for the sweep
+            zf_ring3 sr = {{z, z, z}};
+            hipLaunchKernelGGL(zf_resid_x_kernel, dim3(1), dim3(RESID_BLOCK), 0, nullptr, nullptr, sr, -1, b_dev, scale, m, fdev);
+            if (grad_out_host) hipLaunchKernelGGL(zf_axmb_kernel, dim3(zf_grid_for(m)), dim3(ZF_BLOCK), 0, nullptr, z, b_dev, m);
         }
-        ZF_LS(hipGetLastError());
-        ZF_LS(hipMemcpyAsync(f_out, fdev, sizeof(double), hipMemcpyDeviceToHost, nullptr));
-        ZF_LS(hipStreamSynchronize(nullptr));
+        if (grad_out_host) {
+            zf_launch_view_adjoint(V, nullptr, launched ? rho : z, grad, zf_gfac(L, scale), false, W);
+            ZF_KEEP_FIRST(hipMemcpyAsync(grad_out_host, grad, sizeof(double) * n, hipMemcpyDeviceToHost, nullptr));
+        }
+        ZF_KEEP_FIRST(hipGetLastError());
+        ZF_KEEP_FIRST(hipMemcpyAsync(f_out, fdev, sizeof(double), hipMemcpyDeviceToHost, nullptr));
+        ZF_KEEP_FIRST(hipStreamSynchronize(nullptr));
     }
-#undef ZF_LS
-    for (void* p : {(void*)x, (void*)s, (void*)slab, (void*)grad, (void*)fdev, (void*)rho, (void*)part})
+    zf_sweep_ws_free(&W);
+    for (void* p : {(void*)x, (void*)z, (void*)grad, (void*)fdev, (void*)rho, (void*)part})
         if (p) (void)hipFree(p);
     return rc;
 }
 
+// the point evaluation of one entry: the checks, then the launches.  kind / delta / w_dev: the entry's loss (w_dev NULL: unweighted)
+static int zf_point_entry(const char* who, zf_matview V, const double* b_dev, bool w_ok, const double* w_dev, double scale, int32_t kind,
+                          double delta, const double* x_host, double* f_out, double* grad_out_host) {
+    zf_loss L;
+    int rc = zf_view_args(who, V, b_dev && w_ok && x_host && f_out);
+    if (rc == ZF_OK) rc = zf_loss_args(who, &V, kind, delta, w_dev, &L);
+    return rc ? rc : zf_point_eval(V, b_dev, scale, L, x_host, f_out, grad_out_host);
+}
+
 extern "C" int zf_ls_eval(const double* A_dev, const double* b_dev, int64_t m_rows, int64_t n, double scale,
                           const double* x_host, double* f_out, double* grad_out_host) {
-    ZF_REQUIRE(A_dev && b_dev && x_host && f_out && m_rows >= 1 && n >= 1, "zf_ls_eval: bad argument");
-    ZF_REQUIRE(zf_aligned16(A_dev), "zf_ls_eval: A must be 16-byte aligned");
-    return zf_dense_eval(A_dev, b_dev, m_rows, n, scale, x_host, f_out, grad_out_host, false);
+    return zf_point_entry("zf_ls_eval", zf_dense_view(A_dev, m_rows, n), b_dev, true, nullptr, scale, ZF_LOSS_SQUARE, 0.0, x_host, f_out,
+                          grad_out_host);
 }
 
 // f = scale sum softplus(-b (A x)) and (grad_out_host != NULL) grad = scale A^T rho of ZF_PROBLEM_LOGISTIC_L1 for a host
 // vector: the callback bodies of zfista_amd.problems.LogisticL1, on the loss kernels the solver runs
 extern "C" int zf_logistic_eval(const double* A_dev, const double* b_dev, int64_t m_rows, int64_t n, double scale,
                                 const double* x_host, double* f_out, double* grad_out_host) {
-    ZF_REQUIRE(A_dev && b_dev && x_host && f_out && m_rows >= 1 && n >= 1, "zf_logistic_eval: bad argument");
-    ZF_REQUIRE(zf_aligned16(A_dev), "zf_logistic_eval: A must be 16-byte aligned");
-    return zf_dense_eval(A_dev, b_dev, m_rows, n, scale, x_host, f_out, grad_out_host, true);
+    return zf_point_entry("zf_logistic_eval", zf_dense_view(A_dev, m_rows, n), b_dev, true, nullptr, scale, ZF_LOSS_LOGISTIC, 0.0, x_host,
+                          f_out, grad_out_host);
 }
 
-// the same for a CSR matrix behind a handle (zf_spmat_create), on the two sweeps the solver runs
-static int zf_sparse_eval(const zf_spmat* h, const double* b_dev, double scale, const double* x_host, double* f_out,
-                          double* grad_out_host, bool logistic, double delta = 0.0, const double* w_dev = nullptr) {
-    const bool huber = delta > 0.0, own_rows = logistic || huber || w_dev;   // (as zf_dense_eval)
-    const int wloss = logistic ? ZF_LOSS_LOGISTIC : huber ? ZF_LOSS_HUBER : ZF_LOSS_SQUARE;
-    const int64_t m = h->m, n = h->n;
-    double *x = nullptr, *sv = nullptr, *grad = nullptr, *fdev = nullptr, *part_A = nullptr, *part_At = nullptr, *rho = nullptr, *part = nullptr;
-    int rc = ZF_OK;
-#define ZF_SP(expr)                                                               \
-    do {                                                                          \
-        hipError_t _e = (expr);                                                   \
-        if (_e != hipSuccess && rc == ZF_OK)                                      \
-            rc = zf_fail(ZF_ERR_HIP, "%s: %s", #expr, hipGetErrorString(_e));     \
-    } while (0)
-    ZF_SP(hipMalloc(&x, sizeof(double) * n));
-    ZF_SP(hipMalloc(&sv, sizeof(double) * m));
-    ZF_SP(hipMalloc(&fdev, sizeof(double) * 2));
-    if (grad_out_host) ZF_SP(hipMalloc(&grad, sizeof(double) * n));
-    if (own_rows) {
-        ZF_SP(hipMalloc(&part, sizeof(double) * ZF_SPMV_RESID_MAX_CHUNKS));
-        if (grad_out_host) ZF_SP(hipMalloc(&rho, sizeof(double) * m));
-    }
-    // (the segment sums of split rows are this call's own: the handle is shared with solvers running on other streams)
-    if (h->A.nseg > 0) ZF_SP(hipMalloc(&part_A, sizeof(double) * h->A.nseg));
-    if (grad_out_host && h->At.nseg > 0) ZF_SP(hipMalloc(&part_At, sizeof(double) * h->At.nseg));
-    if (rc == ZF_OK) {
-        ZF_SP(hipMemcpyAsync(x, x_host, sizeof(double) * n, hipMemcpyHostToDevice, nullptr));
-        zf_ring3 sr = {{sv, sv, sv}};
-        const zf_spmv_io aio = {{x, x, x}, {sv, sv, sv}};
-        zf_launch_spmv(h->A, nullptr, nullptr, false, aio, -1, 1.0, part_A);
-        if (w_dev && grad_out_host)
-            zf_launch_wloss_y(nullptr, nullptr, sv, sv, sv, b_dev, w_dev, rho, scale, wloss, delta, m, 0, part, fdev);
-        else if (w_dev)
-            zf_launch_wloss_x(nullptr, nullptr, sv, sv, sv, -1, b_dev, w_dev, scale, wloss, delta, m, part, fdev);
-        else if (huber && grad_out_host)
-            zf_launch_huber_y(nullptr, nullptr, sv, sv, sv, b_dev, rho, scale, delta, m, 0, part, fdev);
-        else if (huber)
-            zf_launch_huber_x(nullptr, nullptr, sv, sv, sv, -1, b_dev, scale, delta, m, part, fdev);
-        else if (!logistic)
-            hipLaunchKernelGGL(zf_resid_x_kernel, dim3(1), dim3(RESID_BLOCK), 0, nullptr, nullptr, sr, -1, b_dev, scale, m, fdev);
-        else if (grad_out_host)
-            zf_launch_logit_y(nullptr, nullptr, sv, sv, sv, b_dev, rho, scale, m, 0, part, fdev);
-        else
-            zf_launch_logit_x(nullptr, nullptr, sv, sv, sv, -1, b_dev, scale, m, part, fdev);
-        if (grad_out_host) {
-            if (!own_rows) hipLaunchKernelGGL(zf_axmb_kernel, dim3(zf_grid_for(m)), dim3(ZF_BLOCK), 0, nullptr, sv, b_dev, m);
-            const double* rv = own_rows ? rho : sv;
-            const zf_spmv_io gio = {{rv, rv, rv}, {grad, grad, grad}};
-            zf_launch_spmv(h->At, nullptr, nullptr, false, gio, -1, logistic ? scale : 2 * scale, part_At);
-            ZF_SP(hipMemcpyAsync(grad_out_host, grad, sizeof(double) * n, hipMemcpyDeviceToHost, nullptr));
-        }
-        ZF_SP(hipGetLastError());
-        ZF_SP(hipMemcpyAsync(f_out, fdev, sizeof(double), hipMemcpyDeviceToHost, nullptr));
-        ZF_SP(hipStreamSynchronize(nullptr));
-    }
-#undef ZF_SP
-    for (void* p : {(void*)x, (void*)sv, (void*)grad, (void*)fdev, (void*)part_A, (void*)part_At, (void*)rho, (void*)part})
-        if (p) (void)hipFree(p);
-    return rc;
-}
-
+// the same for a CSR matrix behind a handle (zf_spmat_create)
 extern "C" int zf_spmat_eval(const zf_spmat* h, const double* b_dev, double scale, const double* x_host, double* f_out,
                              double* grad_out_host) {
-    ZF_REQUIRE(h && b_dev && x_host && f_out, "zf_spmat_eval: null argument");
-    return zf_sparse_eval(h, b_dev, scale, x_host, f_out, grad_out_host, false);
+    return zf_point_entry("zf_spmat_eval", zf_csr_view(h), b_dev, true, nullptr, scale, ZF_LOSS_SQUARE, 0.0, x_host, f_out, grad_out_host);
 }
 
 // the logistic loss (ZF_PROBLEM_SPARSE_LOGISTIC_L1) over the same handle: zf_logistic_eval for a CSR matrix
 extern "C" int zf_spmat_logistic_eval(const zf_spmat* h, const double* b_dev, double scale, const double* x_host, double* f_out,
                                       double* grad_out_host) {
-    ZF_REQUIRE(h && b_dev && x_host && f_out, "zf_spmat_logistic_eval: null argument");
-    return zf_sparse_eval(h, b_dev, scale, x_host, f_out, grad_out_host, true);
+    return zf_point_entry("zf_spmat_logistic_eval", zf_csr_view(h), b_dev, true, nullptr, scale, ZF_LOSS_LOGISTIC, 0.0, x_host, f_out,
+                          grad_out_host);
 }
 
 // Huber's loss (zf_kernels_huber.h) on the same sweeps: f = scale sum H_delta(A x - b), grad = 2 scale A^T clip(A x - b)
 extern "C" int zf_huber_eval(const double* A_dev, const double* b_dev, int64_t m_rows, int64_t n, double scale, double delta,
                              const double* x_host, double* f_out, double* grad_out_host) {
-    ZF_REQUIRE(A_dev && b_dev && x_host && f_out && m_rows >= 1 && n >= 1, "zf_huber_eval: bad argument");
-    ZF_REQUIRE(delta > 0.0 && delta <= DBL_MAX, "zf_huber_eval: delta must be finite and > 0");
-    ZF_REQUIRE(zf_aligned16(A_dev), "zf_huber_eval: A must be 16-byte aligned");
-    return zf_dense_eval(A_dev, b_dev, m_rows, n, scale, x_host, f_out, grad_out_host, false, delta);
+    return zf_point_entry("zf_huber_eval", zf_dense_view(A_dev, m_rows, n), b_dev, true, nullptr, scale, ZF_LOSS_HUBER, delta, x_host, f_out,
+                          grad_out_host);
 }
 
 extern "C" int zf_spmat_huber_eval(const zf_spmat* h, const double* b_dev, double scale, double delta, const double* x_host, double* f_out,
                                    double* grad_out_host) {
-    ZF_REQUIRE(h && b_dev && x_host && f_out, "zf_spmat_huber_eval: null argument");
-    ZF_REQUIRE(delta > 0.0 && delta <= DBL_MAX, "zf_spmat_huber_eval: delta must be finite and > 0");
-    return zf_sparse_eval(h, b_dev, scale, x_host, f_out, grad_out_host, false, delta);
+    return zf_point_entry("zf_spmat_huber_eval", zf_csr_view(h), b_dev, true, nullptr, scale, ZF_LOSS_HUBER, delta, x_host, f_out,
+                          grad_out_host);
 }
 
 // per-row sample weights (zf_kernels_wloss.h) on the same sweeps: f = scale sum w phi, grad = gfac A^T (w o psi)
-static int zf_wloss_args(const char* who, int32_t loss, double delta, double* delta_eff) {
-    if (loss != ZF_LOSS_SQUARE && loss != ZF_LOSS_LOGISTIC && loss != ZF_LOSS_HUBER)
-        return zf_fail(ZF_ERR_ARG, "%s: loss must be ZF_LOSS_SQUARE, ZF_LOSS_LOGISTIC or ZF_LOSS_HUBER%s", who);
-    if (loss == ZF_LOSS_HUBER && !(delta > 0.0 && delta <= DBL_MAX)) return zf_fail(ZF_ERR_ARG, "%s: delta must be finite and > 0%s", who);
-    *delta_eff = loss == ZF_LOSS_HUBER ? delta : 0.0;
-    return ZF_OK;
-}
-
 extern "C" int zf_wloss_eval(const double* A_dev, const double* b_dev, const double* w_dev, int64_t m_rows, int64_t n, double scale,
                              int32_t loss, double delta, const double* x_host, double* f_out, double* grad_out_host) {
-    ZF_REQUIRE(A_dev && b_dev && w_dev && x_host && f_out && m_rows >= 1 && n >= 1, "zf_wloss_eval: bad argument");
-    double de = 0.0;
-    const int rc = zf_wloss_args("zf_wloss_eval", loss, delta, &de);
-    if (rc) return rc;
-    ZF_REQUIRE(zf_aligned16(A_dev), "zf_wloss_eval: A must be 16-byte aligned");
-    return zf_dense_eval(A_dev, b_dev, m_rows, n, scale, x_host, f_out, grad_out_host, loss == ZF_LOSS_LOGISTIC, de, w_dev);
+    return zf_point_entry("zf_wloss_eval", zf_dense_view(A_dev, m_rows, n), b_dev, w_dev != nullptr, w_dev, scale, loss, delta, x_host, f_out,
+                          grad_out_host);
 }
 
 extern "C" int zf_spmat_wloss_eval(const zf_spmat* h, const double* b_dev, const double* w_dev, double scale, int32_t loss, double delta,
                                    const double* x_host, double* f_out, double* grad_out_host) {
-    ZF_REQUIRE(h && b_dev && w_dev && x_host && f_out, "zf_spmat_wloss_eval: null argument");
-    double de = 0.0;
-    const int rc = zf_wloss_args("zf_spmat_wloss_eval", loss, delta, &de);
-    if (rc) return rc;
-    return zf_sparse_eval(h, b_dev, scale, x_host, f_out, grad_out_host, loss == ZF_LOSS_LOGISTIC, de, w_dev);
+    return zf_point_entry("zf_spmat_wloss_eval", zf_csr_view(h), b_dev, w_dev != nullptr, w_dev, scale, loss, delta, x_host, f_out,
+                          grad_out_host);
 }
 
 // f(x) = scale |B W^-1 x - b|^2 and (optionally) jac_f(x) = 2 scale W B (B W^-1 x - b) of the operator problem
@@ -2761,31 +2712,24 @@ extern "C" int zf_op_eval(const double* taps_dev, int32_t k, const double* b_dev
     const double *taps = nullptr, *sep = nullptr;
     int rc = zf_op_prepare(zf_env_read(), taps_dev, (int)k, h, w, nullptr, &pl, &opbuf, &taps, &sep);
     if (rc) return rc;
-#define ZF_OP(expr)                                                               \
-    do {                                                                          \
-        hipError_t _e = (expr);                                                   \
-        if (_e != hipSuccess && rc == ZF_OK)                                      \
-            rc = zf_fail(ZF_ERR_HIP, "%s: %s", #expr, hipGetErrorString(_e));     \
-    } while (0)
-    ZF_OP(hipMalloc(&x, sizeof(double) * n));
-    ZF_OP(hipMalloc(&sv, sizeof(double) * n));
-    ZF_OP(hipMalloc(&fdev, sizeof(double) * 2));
-    if (grad_out_host) ZF_OP(hipMalloc(&grad, sizeof(double) * n));
+    ZF_KEEP_FIRST(hipMalloc(&x, sizeof(double) * n));
+    ZF_KEEP_FIRST(hipMalloc(&sv, sizeof(double) * n));
+    ZF_KEEP_FIRST(hipMalloc(&fdev, sizeof(double) * 2));
+    if (grad_out_host) ZF_KEEP_FIRST(hipMalloc(&grad, sizeof(double) * n));
     if (rc == ZF_OK) {
-        ZF_OP(hipMemcpyAsync(x, x_host, sizeof(double) * n, hipMemcpyHostToDevice, nullptr));
+        ZF_KEEP_FIRST(hipMemcpyAsync(x, x_host, sizeof(double) * n, hipMemcpyHostToDevice, nullptr));
         zf_ring3 sr = {{sv, sv, sv}};
         zf_launch_op_apply(pl, nullptr, zf_op_of(d, nullptr, pl, taps, sep), x, x, x, sv, sv, sv, -1, zf_op_no_fuse());
         hipLaunchKernelGGL(zf_resid_x_kernel, dim3(1), dim3(RESID_BLOCK), 0, nullptr, nullptr, sr, -1, b_dev, scale, n, fdev);
         if (grad_out_host) {
             hipLaunchKernelGGL(zf_axmb_kernel, dim3(zf_grid_for(n)), dim3(ZF_BLOCK), 0, nullptr, sv, b_dev, n);
             zf_launch_op_adjoint(pl, nullptr, zf_op_of(d, nullptr, pl, taps, sep), sv, grad, 2 * scale, zf_op_no_fuse());
-            ZF_OP(hipMemcpyAsync(grad_out_host, grad, sizeof(double) * n, hipMemcpyDeviceToHost, nullptr));
+            ZF_KEEP_FIRST(hipMemcpyAsync(grad_out_host, grad, sizeof(double) * n, hipMemcpyDeviceToHost, nullptr));
         }
-        ZF_OP(hipGetLastError());
-        ZF_OP(hipMemcpyAsync(f_out, fdev, sizeof(double), hipMemcpyDeviceToHost, nullptr));
-        ZF_OP(hipStreamSynchronize(nullptr));
+        ZF_KEEP_FIRST(hipGetLastError());
+        ZF_KEEP_FIRST(hipMemcpyAsync(f_out, fdev, sizeof(double), hipMemcpyDeviceToHost, nullptr));
+        ZF_KEEP_FIRST(hipStreamSynchronize(nullptr));
     }
-#undef ZF_OP
     for (void* p : {(void*)x, (void*)sv, (void*)grad, (void*)fdev, (void*)opbuf})
         if (p) (void)hipFree(p);
     return rc;
@@ -2794,37 +2738,12 @@ extern "C" int zf_op_eval(const double* taps_dev, int32_t k, const double* b_dev
 // ---------------------------------------------------------------------------
 // duality gap (zf_kernels_gap.h): standalone at a host point, and at x_k of a live solver
 // ---------------------------------------------------------------------------
-// g = factor * A^T rvec for a dense row-major A: the column sweep a solver of this shape runs (MFMA when n % 32 == 0 and
-// ZF_GEMV_MFMA is not 0, else the VALU sweep) and the slice combine, outside the loop (ctl = NULL)
-static void zf_gap_dense_sweep(hipStream_t st, const double* A, const double* rvec, double* slab, double* g, int64_t m, int64_t n,
-                               int slices, int64_t rows_per_slice, bool mfma, double factor) {
-    const int V = (n % 2 == 0) ? 2 : 1;
-    const int64_t nv = n / V;
-    if (mfma) {
-        dim3 gM((unsigned)((n + GEMVT_MFMA_COLS - 1) / GEMVT_MFMA_COLS), (unsigned)slices);
-        hipLaunchKernelGGL(zf_gemvT_partial_mfma_kernel, gM, dim3(ZF_BLOCK), 0, st, nullptr, A, rvec, slab, m, n, rows_per_slice);
-    } else {
-        dim3 gT((unsigned)((nv + ZF_BLOCK - 1) / ZF_BLOCK), (unsigned)slices);
-        if (V == 2) hipLaunchKernelGGL(zf_gemvT_partial_kernel<2>, gT, dim3(ZF_BLOCK), 0, st, nullptr, A, rvec, slab, m, n, rows_per_slice);
-        else hipLaunchKernelGGL(zf_gemvT_partial_kernel<1>, gT, dim3(ZF_BLOCK), 0, st, nullptr, A, rvec, slab, m, n, rows_per_slice);
-    }
-    hipLaunchKernelGGL(zf_gemvT_combine_kernel, dim3(zf_grid_for(n)), dim3(ZF_BLOCK), 0, st, nullptr, slab, g, factor, n, slices);
-}
-
-#define ZF_GAP_TRY(expr)                                                          \
-    do {                                                                          \
-        hipError_t _e = (expr);                                                   \
-        if (_e != hipSuccess && rc == ZF_OK)                                      \
-            rc = zf_fail(ZF_ERR_HIP, "%s: %s", #expr, hipGetErrorString(_e));     \
-    } while (0)
-
-// (huber: a fourth row of chunk sums for the rows pass of zf_kernels_huber.h; otherwise what it always took)
-static int zf_gap_ws_alloc(zf_gap_ws* ws, int64_t m, int64_t n, bool huber = false) {
+static int zf_gap_ws_alloc(zf_gap_ws* ws, int64_t m, int64_t n, const zf_loss& L) {
     int rc = ZF_OK;
-    ZF_GAP_TRY(hipMalloc(&ws->rvec, sizeof(double) * m));
-    ZF_GAP_TRY(hipMalloc(&ws->g, sizeof(double) * n));
-    ZF_GAP_TRY(hipMalloc(&ws->part, sizeof(double) * (huber ? ZF_GAP_PART_HUBER : ZF_GAP_PART)));
-    ZF_GAP_TRY(hipMalloc(&ws->scal, sizeof(double) * ZF_GAP_SCAL));
+    ZF_KEEP_FIRST(hipMalloc(&ws->rvec, sizeof(double) * m));
+    ZF_KEEP_FIRST(hipMalloc(&ws->g, sizeof(double) * n));
+    ZF_KEEP_FIRST(hipMalloc(&ws->part, sizeof(double) * zf_gap_part_len(L)));
+    ZF_KEEP_FIRST(hipMalloc(&ws->scal, sizeof(double) * ZF_GAP_SCAL));
     return rc;
 }
 static void zf_gap_ws_free(zf_gap_ws* ws) {
@@ -2833,132 +2752,130 @@ static void zf_gap_ws_free(zf_gap_ws* ws) {
     *ws = zf_gap_ws{nullptr, nullptr, nullptr, nullptr};
 }
 
-// dense (h == NULL) or CSR matrix; x from the host
-// scr != NULL (zf_gap_screen_eval / zf_spmat_gap_screen_eval): the screen of zf_kernels_screen.h over the call's g behind the
-// same sequence - its four scalars follow the eight outputs; scr->cnt and scr->scal are allocated here
-// l2 > 0: the elastic-net evaluation (zf_launch_gap_tail_enet), ten outputs when out_count >= 10
-// delta > 0 (logistic false): Huber's loss - its rows pass and composition (zf_kernels_huber.h) around the same sweeps and n-passes
-static int zf_gap_eval_impl(const double* A_dev, const zf_spmat* h, const double* b_dev, int64_t m, int64_t n, double scale, double lam,
-                            bool logistic, const double* x_host, double* out, const zf_screen_req* scr = nullptr, double l2 = 0.0,
-                            int64_t out_count = 8, double delta = 0.0, const double* w_dev = nullptr) {
-    // (w_dev: the weighted rows passes of zf_kernels_wloss.h around the same sweeps, n-passes and compositions)
-    const bool huber = delta > 0.0;
-    const int wloss = logistic ? ZF_LOSS_LOGISTIC : huber ? ZF_LOSS_HUBER : ZF_LOSS_SQUARE;
+// The gap at a host point x: z = A x, the rows pass of the loss, g = grad f(x) by the column sweep a solver of this shape runs
+// (dense: MFMA when n % 32 == 0 and ZF_GEMV_MFMA is not 0), the n-passes and the composition; l2 > 0: the elastic-net evaluation.
+// scr != NULL (the *_screen_eval entries): the screen of zf_kernels_screen.h over the call's g behind the same sequence - its four
+// scalars follow the eight outputs; scr->cnt and scr->scal are allocated here
+static int zf_gap_eval_impl(const zf_matview& V, const double* b_dev, double scale, double lam, double l2, const zf_loss& L,
+                            const double* x_host, double* out, int64_t out_count, const zf_screen_req* scr) {
+    const int64_t m = V.m, n = V.n;
     zf_gap_ws ws = {nullptr, nullptr, nullptr, nullptr};
-    double *x = nullptr, *z = nullptr, *slab = nullptr, *part_A = nullptr, *part_At = nullptr, *scr_scal = nullptr;
+    zf_sweep_ws W = {nullptr, 1, m, nullptr, nullptr};
+    double *x = nullptr, *z = nullptr, *scr_scal = nullptr;
     int32_t* scr_cnt = nullptr;
-    int64_t slices = 1, rps = m;
-    int rc = zf_gap_ws_alloc(&ws, m, n, huber);
+    int rc = zf_gap_ws_alloc(&ws, m, n, L);
+    if (rc == ZF_OK) rc = zf_sweep_ws_alloc(V, true, &W);
     if (scr) {
-        ZF_GAP_TRY(hipMalloc(&scr_scal, sizeof(double) * ZF_SCREEN_SCAL));
-        ZF_GAP_TRY(hipMalloc(&scr_cnt, sizeof(int32_t) * (ZF_SCREEN_MAX_CHUNKS + 1)));
+        ZF_KEEP_FIRST(hipMalloc(&scr_scal, sizeof(double) * ZF_SCREEN_SCAL));
+        ZF_KEEP_FIRST(hipMalloc(&scr_cnt, sizeof(int32_t) * (ZF_SCREEN_MAX_CHUNKS + 1)));
     }
-    ZF_GAP_TRY(hipMalloc(&x, sizeof(double) * (n + 2)));
-    ZF_GAP_TRY(hipMalloc(&z, sizeof(double) * (m + 2)));
-    if (h) {
-        if (h->A.nseg > 0) ZF_GAP_TRY(hipMalloc(&part_A, sizeof(double) * h->A.nseg));
-        if (h->At.nseg > 0) ZF_GAP_TRY(hipMalloc(&part_At, sizeof(double) * h->At.nseg));
-    } else {   // the slices of zf_solver_create
-        const int V = (n % 2 == 0) ? 2 : 1;
-        const int64_t panels = (n / V + ZF_BLOCK - 1) / ZF_BLOCK;
-        slices = (ZF_MAX_GRID + panels - 1) / panels;
-        if (slices > (m + 7) / 8) slices = (m + 7) / 8;
-        if (slices < 1) slices = 1;
-        if (slices > 64) slices = 64;
-        rps = (m + slices - 1) / slices;
-        slices = (m + rps - 1) / rps;
-        ZF_GAP_TRY(hipMalloc(&slab, sizeof(double) * slices * n));
-    }
+    ZF_KEEP_FIRST(hipMalloc(&x, sizeof(double) * (n + 2)));
+    ZF_KEEP_FIRST(hipMalloc(&z, sizeof(double) * (m + 2)));
     if (rc == ZF_OK) {
-        const double gfac = logistic ? scale : 2 * scale;
-        ZF_GAP_TRY(hipMemcpyAsync(x, x_host, sizeof(double) * n, hipMemcpyHostToDevice, nullptr));
-        if (h) {
-            const zf_spmv_io aio = {{x, x, x}, {z, z, z}};
-            zf_launch_spmv(h->A, nullptr, nullptr, false, aio, -1, 1.0, part_A);
-        } else {
-            zf_ring3 xr = {{x, x, x}}, sr = {{z, z, z}};
-            int gr = (int)((m + GEMV_ROWS - 1) / GEMV_ROWS);
-            if (gr > 8 * ZF_MAX_GRID) gr = 8 * ZF_MAX_GRID;
-            if (n % 2 == 0) hipLaunchKernelGGL(zf_gemv_rows_kernel<2>, dim3(gr), dim3(ZF_BLOCK), 0, nullptr, nullptr, A_dev, xr, sr, -1, m, n);
-            else hipLaunchKernelGGL(zf_gemv_rows_kernel<1>, dim3(gr), dim3(ZF_BLOCK), 0, nullptr, nullptr, A_dev, xr, sr, -1, m, n);
-        }
-        if (w_dev) zf_launch_gap_wrows(nullptr, wloss, z, b_dev, w_dev, m, scale, delta, ws);
-        else if (huber) zf_launch_gap_huber_rows(nullptr, z, b_dev, m, scale, delta, ws);
-        else zf_launch_gap_rows(nullptr, logistic, z, b_dev, m, scale, ws);
-        if (h) {
-            const zf_spmv_io gio = {{ws.rvec, ws.rvec, ws.rvec}, {ws.g, ws.g, ws.g}};
-            zf_launch_spmv(h->At, nullptr, nullptr, false, gio, -1, gfac, part_At);
-        } else {
-            zf_gap_dense_sweep(nullptr, A_dev, ws.rvec, slab, ws.g, m, n, (int)slices, rps, n % 32 == 0 && zf_env_read().gemv_mfma, gfac);
-        }
-        if (w_dev) zf_launch_gap_wtail(nullptr, wloss, z, b_dev, w_dev, x, m, n, scale, lam, l2, ws);
-        else if (huber) zf_launch_gap_tail_huber(nullptr, x, n, scale, lam, l2, ws);
-        else if (l2 > 0.0) zf_launch_gap_tail_enet(nullptr, logistic, z, b_dev, x, m, n, scale, lam, l2, ws);
-        else zf_launch_gap_tail(nullptr, logistic, z, b_dev, x, m, n, scale, lam, ws);
+        const bool mfma = !V.csr && n % 32 == 0 && zf_env_read().gemv_mfma;
+        ZF_KEEP_FIRST(hipMemcpyAsync(x, x_host, sizeof(double) * n, hipMemcpyHostToDevice, nullptr));
+        zf_launch_view_apply(V, nullptr, x, z, W);
+        zf_launch_loss_gap_rows(nullptr, L, z, b_dev, m, scale, ws);
+        zf_launch_view_adjoint(V, nullptr, ws.rvec, ws.g, zf_gfac(L, scale), mfma, W);
+        const zf_gap_out res = zf_launch_loss_gap_tail(nullptr, L, z, b_dev, x, m, n, scale, lam, l2, ws, out_count);
         if (scr) {
             zf_screen_req rq = *scr;
             rq.cnt = scr_cnt;
             rq.scal = scr_scal;
-            zf_launch_screen(nullptr, rq, ws.g, ws.scal + ZF_GS_OUT, ws.scal + ZF_GS_ASUM, ws.scal + ZF_GS_RR, m, n, scale, lam, logistic);
+            zf_launch_screen(nullptr, rq, ws.g, ws.scal + ZF_GS_OUT, ws.scal + ZF_GS_ASUM, ws.scal + ZF_GS_RR, m, n, scale, lam,
+                             L.kind == ZF_LOSS_LOGISTIC);
         }
-        ZF_GAP_TRY(hipGetLastError());
-        if (l2 > 0.0)
-            ZF_GAP_TRY(hipMemcpyAsync(out, ws.scal + ZF_GS_OUT_ENET, sizeof(double) * (out_count >= 10 ? 10 : 8), hipMemcpyDeviceToHost, nullptr));
-        else
-            ZF_GAP_TRY(hipMemcpyAsync(out, ws.scal + ZF_GS_OUT, sizeof(double) * 8, hipMemcpyDeviceToHost, nullptr));
-        if (scr) ZF_GAP_TRY(hipMemcpyAsync(out + 8, scr_scal, sizeof(double) * ZF_SCREEN_SCAL, hipMemcpyDeviceToHost, nullptr));
-        ZF_GAP_TRY(hipStreamSynchronize(nullptr));
+        ZF_KEEP_FIRST(hipGetLastError());
+        ZF_KEEP_FIRST(hipMemcpyAsync(out, ws.scal + res.slot, sizeof(double) * res.count, hipMemcpyDeviceToHost, nullptr));
+        if (scr) ZF_KEEP_FIRST(hipMemcpyAsync(out + 8, scr_scal, sizeof(double) * ZF_SCREEN_SCAL, hipMemcpyDeviceToHost, nullptr));
+        ZF_KEEP_FIRST(hipStreamSynchronize(nullptr));
     }
     zf_gap_ws_free(&ws);
-    for (void* p : {(void*)x, (void*)z, (void*)slab, (void*)part_A, (void*)part_At, (void*)scr_scal, (void*)scr_cnt})
+    zf_sweep_ws_free(&W);
+    for (void* p : {(void*)x, (void*)z, (void*)scr_scal, (void*)scr_cnt})
         if (p) (void)hipFree(p);
     return rc;
 }
 
+// The checks every gap entry shares, in front of those of zf_loss_args: the capacity of `out`, scale, lam and l2.  l2_arg: the entry
+// takes l2 (its message names it); the others pass l2 = 0.
+static int zf_gap_args(const char* who, zf_matview* V, bool ok, double scale, double lam, bool l2_arg, double l2, int64_t count, int32_t kind,
+                       double delta, const double* w_dev, zf_loss* L) {
+    const int rc = zf_view_args(who, *V, ok);
+    if (rc) return rc;
+    if (count < 8) return zf_fail(ZF_ERR_ARG, "%s: the output buffer holds fewer than 8 doubles%s", who);
+    if (!(scale > 0.0 && lam >= 0.0 && l2 >= 0.0 && l2 <= DBL_MAX))
+        return zf_fail(ZF_ERR_ARG, l2_arg ? "%s: needs scale > 0, lam >= 0 and a finite l2 >= 0%s" : "%s: needs scale > 0 and lam >= 0%s", who);
+    return zf_loss_args(who, V, kind, delta, w_dev, L);
+}
+
+// a gap entry without the screen; the elastic-net forms (l2_arg) run the l1 evaluation for l2 = 0 - its kernels, its eight values -
+// and write [8] = [9] = 0 when the buffer holds ten
+static int zf_gap_entry(const char* who, zf_matview V, const double* b_dev, bool w_ok, const double* w_dev, double scale, double lam,
+                        bool l2_arg, double l2, int32_t kind, double delta, const double* x_host, double* out, int64_t count) {
+    zf_loss L;
+    int rc = zf_gap_args(who, &V, b_dev && w_ok && x_host && out, scale, lam, l2_arg, l2, count, kind, delta, w_dev, &L);
+    if (rc) return rc;
+    rc = zf_gap_eval_impl(V, b_dev, scale, lam, l2, L, x_host, out, count, nullptr);
+    if (rc == ZF_OK && l2_arg && !(l2 > 0.0) && count >= 10) out[8] = out[9] = 0.0;
+    return rc;
+}
+static int32_t zf_loss_of_flag(int32_t logistic) { return logistic != 0 ? ZF_LOSS_LOGISTIC : ZF_LOSS_SQUARE; }
+
 extern "C" int zf_gap_eval(const double* A_dev, const double* b_dev, int64_t m_rows, int64_t n, double scale, double lam,
                            int32_t logistic, const double* x_host, double* out, int64_t count) {
-    ZF_REQUIRE(A_dev && b_dev && x_host && out && m_rows >= 1 && n >= 1, "zf_gap_eval: bad argument");
-    ZF_REQUIRE(count >= 8, "zf_gap_eval: the output buffer holds fewer than 8 doubles");
-    ZF_REQUIRE(scale > 0.0 && lam >= 0.0, "zf_gap_eval: needs scale > 0 and lam >= 0");
-    ZF_REQUIRE(zf_aligned16(A_dev), "zf_gap_eval: A must be 16-byte aligned");
-    return zf_gap_eval_impl(A_dev, nullptr, b_dev, m_rows, n, scale, lam, logistic != 0, x_host, out);
+    return zf_gap_entry("zf_gap_eval", zf_dense_view(A_dev, m_rows, n), b_dev, true, nullptr, scale, lam, false, 0.0, zf_loss_of_flag(logistic),
+                        0.0, x_host, out, count);
 }
 
 extern "C" int zf_spmat_gap_eval(const zf_spmat* h, const double* b_dev, double scale, double lam, int32_t logistic,
                                  const double* x_host, double* out, int64_t count) {
-    ZF_REQUIRE(h && b_dev && x_host && out, "zf_spmat_gap_eval: null argument");
-    ZF_REQUIRE(count >= 8, "zf_spmat_gap_eval: the output buffer holds fewer than 8 doubles");
-    ZF_REQUIRE(scale > 0.0 && lam >= 0.0, "zf_spmat_gap_eval: needs scale > 0 and lam >= 0");
-    return zf_gap_eval_impl(nullptr, h, b_dev, h->m, h->n, scale, lam, logistic != 0, x_host, out);
+    return zf_gap_entry("zf_spmat_gap_eval", zf_csr_view(h), b_dev, true, nullptr, scale, lam, false, 0.0, zf_loss_of_flag(logistic), 0.0,
+                        x_host, out, count);
 }
 
-// the elastic-net forms (l2 >= 0; l2 = 0 runs the l1 evaluation above - its kernels, its eight values - and writes [8] = [9] = 0)
-static void zf_gap_pad_l1(double l2, double* out, int64_t count) {
-    if (!(l2 > 0.0) && count >= 10) out[8] = out[9] = 0.0;
-}
 extern "C" int zf_gap_eval_enet(const double* A_dev, const double* b_dev, int64_t m_rows, int64_t n, double scale, double lam, double l2,
                                 int32_t logistic, const double* x_host, double* out, int64_t count) {
-    ZF_REQUIRE(A_dev && b_dev && x_host && out && m_rows >= 1 && n >= 1, "zf_gap_eval_enet: bad argument");
-    ZF_REQUIRE(count >= 8, "zf_gap_eval_enet: the output buffer holds fewer than 8 doubles");
-    ZF_REQUIRE(scale > 0.0 && lam >= 0.0 && l2 >= 0.0 && l2 <= DBL_MAX, "zf_gap_eval_enet: needs scale > 0, lam >= 0 and a finite l2 >= 0");
-    ZF_REQUIRE(zf_aligned16(A_dev), "zf_gap_eval_enet: A must be 16-byte aligned");
-    const int rc = zf_gap_eval_impl(A_dev, nullptr, b_dev, m_rows, n, scale, lam, logistic != 0, x_host, out, nullptr, l2, count);
-    if (rc == ZF_OK) zf_gap_pad_l1(l2, out, count);
-    return rc;
+    return zf_gap_entry("zf_gap_eval_enet", zf_dense_view(A_dev, m_rows, n), b_dev, true, nullptr, scale, lam, true, l2,
+                        zf_loss_of_flag(logistic), 0.0, x_host, out, count);
 }
 
 extern "C" int zf_spmat_gap_eval_enet(const zf_spmat* h, const double* b_dev, double scale, double lam, double l2, int32_t logistic,
                                       const double* x_host, double* out, int64_t count) {
-    ZF_REQUIRE(h && b_dev && x_host && out, "zf_spmat_gap_eval_enet: null argument");
-    ZF_REQUIRE(count >= 8, "zf_spmat_gap_eval_enet: the output buffer holds fewer than 8 doubles");
-    ZF_REQUIRE(scale > 0.0 && lam >= 0.0 && l2 >= 0.0 && l2 <= DBL_MAX, "zf_spmat_gap_eval_enet: needs scale > 0, lam >= 0 and a finite l2 >= 0");
-    const int rc = zf_gap_eval_impl(nullptr, h, b_dev, h->m, h->n, scale, lam, logistic != 0, x_host, out, nullptr, l2, count);
-    if (rc == ZF_OK) zf_gap_pad_l1(l2, out, count);
-    return rc;
+    return zf_gap_entry("zf_spmat_gap_eval_enet", zf_csr_view(h), b_dev, true, nullptr, scale, lam, true, l2, zf_loss_of_flag(logistic), 0.0,
+                        x_host, out, count);
 }
 
-// the gap evaluation followed by the gap-safe screen of its g (zf_kernels_screen.h): out[0 .. 8) as zf_gap_eval - the same
-// kernels in the same order, the same bits - then [r, E, r_eff, kept count]
+// Huber's loss (zf_kernels_huber.h): the certificate of the least-squares kinds with c = clip(A x - b) for r
+extern "C" int zf_gap_eval_huber(const double* A_dev, const double* b_dev, int64_t m_rows, int64_t n, double scale, double lam, double l2,
+                                 double delta, const double* x_host, double* out, int64_t count) {
+    return zf_gap_entry("zf_gap_eval_huber", zf_dense_view(A_dev, m_rows, n), b_dev, true, nullptr, scale, lam, true, l2, ZF_LOSS_HUBER, delta,
+                        x_host, out, count);
+}
+
+extern "C" int zf_spmat_gap_eval_huber(const zf_spmat* h, const double* b_dev, double scale, double lam, double l2, double delta,
+                                       const double* x_host, double* out, int64_t count) {
+    return zf_gap_entry("zf_spmat_gap_eval_huber", zf_csr_view(h), b_dev, true, nullptr, scale, lam, true, l2, ZF_LOSS_HUBER, delta, x_host,
+                        out, count);
+}
+
+// per-row sample weights (zf_kernels_wloss.h): the certificate with every row term times w_i
+extern "C" int zf_gap_eval_weighted(const double* A_dev, const double* b_dev, const double* w_dev, int64_t m_rows, int64_t n, double scale,
+                                    double lam, double l2, int32_t loss, double delta, const double* x_host, double* out, int64_t count) {
+    return zf_gap_entry("zf_gap_eval_weighted", zf_dense_view(A_dev, m_rows, n), b_dev, w_dev != nullptr, w_dev, scale, lam, true, l2, loss,
+                        delta, x_host, out, count);
+}
+
+extern "C" int zf_spmat_gap_eval_weighted(const zf_spmat* h, const double* b_dev, const double* w_dev, double scale, double lam, double l2,
+                                          int32_t loss, double delta, const double* x_host, double* out, int64_t count) {
+    return zf_gap_entry("zf_spmat_gap_eval_weighted", zf_csr_view(h), b_dev, w_dev != nullptr, w_dev, scale, lam, true, l2, loss, delta,
+                        x_host, out, count);
+}
+
+// the gap evaluation followed by the gap-safe screen of its g (zf_kernels_screen.h), l2 = 0 only: out[0 .. 8) as zf_gap_eval - the
+// same kernels in the same order, the same bits - then [r, E, r_eff, kept count].  Huber's loss: the rule, the guard and the four
+// screen launches are the least-squares kinds' - L = 2 scale, |c|_2 from sum c^2 where they read sum r^2 (the clip is exact and
+// 1-Lipschitz; tests/huber_cases.py derives the guard line by line)
 static int zf_screen_args(const char* who, const double* norms_dev, const double* stats_dev, int64_t max_row, int64_t max_col,
                           uint8_t* keep_dev, int32_t* index_dev, int64_t count, zf_screen_req* rq) {
     if (!(norms_dev && stats_dev && keep_dev && index_dev)) return zf_fail(ZF_ERR_ARG, "%s: null argument%s", who);
@@ -2968,118 +2885,46 @@ static int zf_screen_args(const char* who, const double* norms_dev, const double
     return ZF_OK;
 }
 
+// a screen entry.  gap_count: what zf_gap_args checks against 8 - the Huber entries' `count`; the two older entries pass 8 and
+// report every short buffer through zf_screen_args ("fewer than 12")
+static int zf_screen_entry(const char* who, zf_matview V, const double* b_dev, double scale, double lam, bool l2_arg, int64_t gap_count,
+                           int32_t kind, double delta, const double* x_host, double* out, int64_t count, const double* norms_dev,
+                           const double* stats_dev, int64_t max_row, int64_t max_col, uint8_t* keep_dev, int32_t* index_dev) {
+    zf_loss L;
+    zf_screen_req rq;
+    int rc = zf_gap_args(who, &V, b_dev && x_host && out && (V.csr || V.n <= 0x7fffffffLL), scale, lam, l2_arg, 0.0, gap_count, kind, delta,
+                         nullptr, &L);
+    if (rc == ZF_OK) rc = zf_screen_args(who, norms_dev, stats_dev, max_row, max_col, keep_dev, index_dev, count, &rq);
+    return rc ? rc : zf_gap_eval_impl(V, b_dev, scale, lam, 0.0, L, x_host, out, 8, &rq);
+}
+
 extern "C" int zf_gap_screen_eval(const double* A_dev, const double* b_dev, int64_t m_rows, int64_t n, double scale, double lam,
                                   int32_t logistic, const double* x_host, double* out, int64_t count, const double* norms_dev,
                                   const double* stats_dev, uint8_t* keep_dev, int32_t* index_dev) {
-    ZF_REQUIRE(A_dev && b_dev && x_host && out && m_rows >= 1 && n >= 1 && n <= 0x7fffffffLL, "zf_gap_screen_eval: bad argument");
-    ZF_REQUIRE(scale > 0.0 && lam >= 0.0, "zf_gap_screen_eval: needs scale > 0 and lam >= 0");
-    ZF_REQUIRE(zf_aligned16(A_dev), "zf_gap_screen_eval: A must be 16-byte aligned");
-    zf_screen_req rq;
-    const int rc = zf_screen_args("zf_gap_screen_eval", norms_dev, stats_dev, n, m_rows, keep_dev, index_dev, count, &rq);
-    if (rc) return rc;
-    return zf_gap_eval_impl(A_dev, nullptr, b_dev, m_rows, n, scale, lam, logistic != 0, x_host, out, &rq);
+    return zf_screen_entry("zf_gap_screen_eval", zf_dense_view(A_dev, m_rows, n), b_dev, scale, lam, false, 8, zf_loss_of_flag(logistic), 0.0,
+                           x_host, out, count, norms_dev, stats_dev, n, m_rows, keep_dev, index_dev);
 }
 
 extern "C" int zf_spmat_gap_screen_eval(const zf_spmat* h, const double* b_dev, double scale, double lam, int32_t logistic,
                                         const double* x_host, double* out, int64_t count, const double* norms_dev, const double* stats_dev,
                                         int64_t max_row, int64_t max_col, uint8_t* keep_dev, int32_t* index_dev) {
-    ZF_REQUIRE(h && b_dev && x_host && out, "zf_spmat_gap_screen_eval: null argument");
-    ZF_REQUIRE(scale > 0.0 && lam >= 0.0, "zf_spmat_gap_screen_eval: needs scale > 0 and lam >= 0");
-    zf_screen_req rq;
-    const int rc = zf_screen_args("zf_spmat_gap_screen_eval", norms_dev, stats_dev, max_row, max_col, keep_dev, index_dev, count, &rq);
-    if (rc) return rc;
-    return zf_gap_eval_impl(nullptr, h, b_dev, h->m, h->n, scale, lam, logistic != 0, x_host, out, &rq);
+    return zf_screen_entry("zf_spmat_gap_screen_eval", zf_csr_view(h), b_dev, scale, lam, false, 8, zf_loss_of_flag(logistic), 0.0, x_host,
+                           out, count, norms_dev, stats_dev, max_row, max_col, keep_dev, index_dev);
 }
 
-// Huber's loss (zf_kernels_huber.h): the certificate and the screen of the least-squares kinds with c = clip(A x - b) for r
-static int zf_huber_gap_args(const char* who, double scale, double lam, double l2, double delta, int64_t count) {
-    if (count < 8) return zf_fail(ZF_ERR_ARG, "%s: the output buffer holds fewer than 8 doubles%s", who);
-    if (!(scale > 0.0 && lam >= 0.0 && l2 >= 0.0 && l2 <= DBL_MAX)) return zf_fail(ZF_ERR_ARG, "%s: needs scale > 0, lam >= 0 and a finite l2 >= 0%s", who);
-    if (!(delta > 0.0 && delta <= DBL_MAX)) return zf_fail(ZF_ERR_ARG, "%s: delta must be finite and > 0%s", who);
-    return ZF_OK;
-}
-
-extern "C" int zf_gap_eval_huber(const double* A_dev, const double* b_dev, int64_t m_rows, int64_t n, double scale, double lam, double l2,
-                                 double delta, const double* x_host, double* out, int64_t count) {
-    ZF_REQUIRE(A_dev && b_dev && x_host && out && m_rows >= 1 && n >= 1, "zf_gap_eval_huber: bad argument");
-    int rc = zf_huber_gap_args("zf_gap_eval_huber", scale, lam, l2, delta, count);
-    if (rc) return rc;
-    ZF_REQUIRE(zf_aligned16(A_dev), "zf_gap_eval_huber: A must be 16-byte aligned");
-    rc = zf_gap_eval_impl(A_dev, nullptr, b_dev, m_rows, n, scale, lam, false, x_host, out, nullptr, l2, count, delta);
-    if (rc == ZF_OK) zf_gap_pad_l1(l2, out, count);
-    return rc;
-}
-
-extern "C" int zf_spmat_gap_eval_huber(const zf_spmat* h, const double* b_dev, double scale, double lam, double l2, double delta,
-                                       const double* x_host, double* out, int64_t count) {
-    ZF_REQUIRE(h && b_dev && x_host && out, "zf_spmat_gap_eval_huber: null argument");
-    int rc = zf_huber_gap_args("zf_spmat_gap_eval_huber", scale, lam, l2, delta, count);
-    if (rc) return rc;
-    rc = zf_gap_eval_impl(nullptr, h, b_dev, h->m, h->n, scale, lam, false, x_host, out, nullptr, l2, count, delta);
-    if (rc == ZF_OK) zf_gap_pad_l1(l2, out, count);
-    return rc;
-}
-
-// per-row sample weights (zf_kernels_wloss.h): the certificate with every row term times w_i
-static int zf_wgap_args(const char* who, double scale, double lam, double l2, int64_t count) {
-    if (count < 8) return zf_fail(ZF_ERR_ARG, "%s: the output buffer holds fewer than 8 doubles%s", who);
-    if (!(scale > 0.0 && lam >= 0.0 && l2 >= 0.0 && l2 <= DBL_MAX)) return zf_fail(ZF_ERR_ARG, "%s: needs scale > 0, lam >= 0 and a finite l2 >= 0%s", who);
-    return ZF_OK;
-}
-
-extern "C" int zf_gap_eval_weighted(const double* A_dev, const double* b_dev, const double* w_dev, int64_t m_rows, int64_t n, double scale,
-                                    double lam, double l2, int32_t loss, double delta, const double* x_host, double* out, int64_t count) {
-    ZF_REQUIRE(A_dev && b_dev && w_dev && x_host && out && m_rows >= 1 && n >= 1, "zf_gap_eval_weighted: bad argument");
-    int rc = zf_wgap_args("zf_gap_eval_weighted", scale, lam, l2, count);
-    if (rc) return rc;
-    double de = 0.0;
-    rc = zf_wloss_args("zf_gap_eval_weighted", loss, delta, &de);
-    if (rc) return rc;
-    ZF_REQUIRE(zf_aligned16(A_dev), "zf_gap_eval_weighted: A must be 16-byte aligned");
-    rc = zf_gap_eval_impl(A_dev, nullptr, b_dev, m_rows, n, scale, lam, loss == ZF_LOSS_LOGISTIC, x_host, out, nullptr, l2, count, de, w_dev);
-    if (rc == ZF_OK) zf_gap_pad_l1(l2, out, count);
-    return rc;
-}
-
-extern "C" int zf_spmat_gap_eval_weighted(const zf_spmat* h, const double* b_dev, const double* w_dev, double scale, double lam, double l2,
-                                          int32_t loss, double delta, const double* x_host, double* out, int64_t count) {
-    ZF_REQUIRE(h && b_dev && w_dev && x_host && out, "zf_spmat_gap_eval_weighted: null argument");
-    int rc = zf_wgap_args("zf_spmat_gap_eval_weighted", scale, lam, l2, count);
-    if (rc) return rc;
-    double de = 0.0;
-    rc = zf_wloss_args("zf_spmat_gap_eval_weighted", loss, delta, &de);
-    if (rc) return rc;
-    rc = zf_gap_eval_impl(nullptr, h, b_dev, h->m, h->n, scale, lam, loss == ZF_LOSS_LOGISTIC, x_host, out, nullptr, l2, count, de, w_dev);
-    if (rc == ZF_OK) zf_gap_pad_l1(l2, out, count);
-    return rc;
-}
-
-// the screen (l2 = 0 only): the rule, the guard and the four screen launches are the least-squares kinds' - L = 2 scale, |c|_2 from
-// sum c^2 where they read sum r^2 (the clip is exact and 1-Lipschitz; tests/huber_cases.py derives the guard line by line)
 extern "C" int zf_gap_screen_eval_huber(const double* A_dev, const double* b_dev, int64_t m_rows, int64_t n, double scale, double lam,
                                         double delta, const double* x_host, double* out, int64_t count, const double* norms_dev,
                                         const double* stats_dev, uint8_t* keep_dev, int32_t* index_dev) {
-    ZF_REQUIRE(A_dev && b_dev && x_host && out && m_rows >= 1 && n >= 1 && n <= 0x7fffffffLL, "zf_gap_screen_eval_huber: bad argument");
-    int rc = zf_huber_gap_args("zf_gap_screen_eval_huber", scale, lam, 0.0, delta, count);
-    if (rc) return rc;
-    ZF_REQUIRE(zf_aligned16(A_dev), "zf_gap_screen_eval_huber: A must be 16-byte aligned");
-    zf_screen_req rq;
-    rc = zf_screen_args("zf_gap_screen_eval_huber", norms_dev, stats_dev, n, m_rows, keep_dev, index_dev, count, &rq);
-    if (rc) return rc;
-    return zf_gap_eval_impl(A_dev, nullptr, b_dev, m_rows, n, scale, lam, false, x_host, out, &rq, 0.0, 8, delta);
+    return zf_screen_entry("zf_gap_screen_eval_huber", zf_dense_view(A_dev, m_rows, n), b_dev, scale, lam, true, count, ZF_LOSS_HUBER, delta,
+                           x_host, out, count, norms_dev, stats_dev, n, m_rows, keep_dev, index_dev);
 }
 
 extern "C" int zf_spmat_gap_screen_eval_huber(const zf_spmat* h, const double* b_dev, double scale, double lam, double delta,
                                               const double* x_host, double* out, int64_t count, const double* norms_dev,
                                               const double* stats_dev, int64_t max_row, int64_t max_col, uint8_t* keep_dev,
                                               int32_t* index_dev) {
-    ZF_REQUIRE(h && b_dev && x_host && out, "zf_spmat_gap_screen_eval_huber: null argument");
-    int rc = zf_huber_gap_args("zf_spmat_gap_screen_eval_huber", scale, lam, 0.0, delta, count);
-    if (rc) return rc;
-    zf_screen_req rq;
-    rc = zf_screen_args("zf_spmat_gap_screen_eval_huber", norms_dev, stats_dev, max_row, max_col, keep_dev, index_dev, count, &rq);
-    if (rc) return rc;
-    return zf_gap_eval_impl(nullptr, h, b_dev, h->m, h->n, scale, lam, false, x_host, out, &rq, 0.0, 8, delta);
+    return zf_screen_entry("zf_spmat_gap_screen_eval_huber", zf_csr_view(h), b_dev, scale, lam, true, count, ZF_LOSS_HUBER, delta, x_host,
+                           out, count, norms_dev, stats_dev, max_row, max_col, keep_dev, index_dev);
 }
 
 // The gap at x_k of a live solver, on its stream: the margins A x_k are the ring's (no sweep over A), the dual candidate goes
@@ -3099,8 +2944,9 @@ extern "C" int zf_solver_duality_gap(zf_solver* s, double* out, int64_t count) {
     ZF_REQUIRE(d.scale > 0.0, "zf_solver_duality_gap: needs scale > 0");
     if (!s->initialised) return zf_fail(ZF_ERR_STATE, "zf_solver_duality_gap: solver not initialised%s%s");
     const int64_t m = d.m_rows, n = d.n;
+    const zf_loss loss = zf_loss_of(s);
     if (!s->gap.scal) {
-        int rc = zf_gap_ws_alloc(&s->gap, m, n, s->huber > 0.0);
+        int rc = zf_gap_ws_alloc(&s->gap, m, n, loss);
         if (rc) {
             zf_gap_ws_free(&s->gap);
             return rc;
@@ -3110,36 +2956,16 @@ extern "C" int zf_solver_duality_gap(zf_solver* s, double* out, int64_t count) {
     ZF_HIP(hipMemcpyAsync(&c, s->ctl, sizeof(c), hipMemcpyDeviceToHost, s->stream));
     ZF_HIP(hipStreamSynchronize(s->stream));
     if (c.lag != 0 || c.cur < 0 || c.cur > 2) return zf_fail(ZF_ERR_STATE, "zf_solver_duality_gap: the iterate ring does not hold x_k%s%s");
-    const bool logistic = zf_is_logistic(d.kind);
-    const double gfac = logistic ? d.scale : 2 * d.scale;
     const double* x = s->xb[c.cur];
     const double* z = s->sring.p[c.cur];   // A x_k: every path of these kinds keeps it there (the fused small-matrix path too)
     const zf_gap_ws& ws = s->gap;
-    const int wloss = logistic ? ZF_LOSS_LOGISTIC : s->huber > 0.0 ? ZF_LOSS_HUBER : ZF_LOSS_SQUARE;
-    if (s->roww) zf_launch_gap_wrows(s->stream, wloss, z, d.b, s->roww, m, d.scale, s->huber, ws);
-    else if (s->huber > 0.0) zf_launch_gap_huber_rows(s->stream, z, d.b, m, d.scale, s->huber, ws);
-    else zf_launch_gap_rows(s->stream, logistic, z, d.b, m, d.scale, ws);
-    if (zf_is_sparse_mat(d.kind)) {
-        const zf_spmv_io gio = {{ws.rvec, ws.rvec, ws.rvec}, {ws.g, ws.g, ws.g}};
-        zf_launch_spmv(s->spmat->At, s->stream, nullptr, false, gio, -1, gfac, s->sp_part_At);
-    } else {
-        zf_gap_dense_sweep(s->stream, d.A, ws.rvec, s->slab, ws.g, m, n, s->slices, s->rows_per_slice, s->gemv_mfma, gfac);
-    }
-    if (s->l2 > 0.0) {   // (elastic net: ten values when the caller's buffer holds them)
-        if (s->roww) zf_launch_gap_wtail(s->stream, wloss, z, d.b, s->roww, x, m, n, d.scale, d.lam, s->l2, ws);
-        else if (s->huber > 0.0) zf_launch_gap_tail_huber(s->stream, x, n, d.scale, d.lam, s->l2, ws);
-        else zf_launch_gap_tail_enet(s->stream, logistic, z, d.b, x, m, n, d.scale, d.lam, s->l2, ws);
-        ZF_HIP(hipGetLastError());
-        ZF_HIP(hipMemcpyAsync(out, ws.scal + ZF_GS_OUT_ENET, sizeof(double) * (count >= 10 ? 10 : 8), hipMemcpyDeviceToHost, s->stream));
-        ZF_HIP(hipStreamSynchronize(s->stream));
-        return ZF_OK;
-    }
-    if (s->roww) zf_launch_gap_wtail(s->stream, wloss, z, d.b, s->roww, x, m, n, d.scale, d.lam, 0.0, ws);
-    else if (s->huber > 0.0) zf_launch_gap_tail_huber(s->stream, x, n, d.scale, d.lam, 0.0, ws);
-    else zf_launch_gap_tail(s->stream, logistic, z, d.b, x, m, n, d.scale, d.lam, ws);
+    const zf_matview V = {d.A, m, n, s->spmat, zf_is_sparse_mat(d.kind)};
+    const zf_sweep_ws W = {s->slab, s->slices, s->rows_per_slice, s->sp_part_A, s->sp_part_At};
+    zf_launch_loss_gap_rows(s->stream, loss, z, d.b, m, d.scale, ws);
+    zf_launch_view_adjoint(V, s->stream, ws.rvec, ws.g, zf_gfac(loss, d.scale), s->gemv_mfma, W);
+    const zf_gap_out res = zf_launch_loss_gap_tail(s->stream, loss, z, d.b, x, m, n, d.scale, d.lam, s->l2, ws, count);
     ZF_HIP(hipGetLastError());
-    ZF_HIP(hipMemcpyAsync(out, ws.scal + ZF_GS_OUT, sizeof(double) * 8, hipMemcpyDeviceToHost, s->stream));
+    ZF_HIP(hipMemcpyAsync(out, ws.scal + res.slot, sizeof(double) * res.count, hipMemcpyDeviceToHost, s->stream));
     ZF_HIP(hipStreamSynchronize(s->stream));
     return ZF_OK;
 }
-#undef ZF_GAP_TRY

@@ -214,18 +214,85 @@ def _check_weights(w, m, group=None):
     return host
 
 
+class _classattr:
+    """A read-only attribute computed from the class: it reads the same on the class and on an instance."""
+
+    def __init__(self, fn):
+        self.fn = fn
+
+    def __get__(self, obj, cls):
+        return self.fn(cls)
+
+
 class _GapMixin:
-    """Duality-gap certificate, lam_max, same-matrix siblings, gap-safe screening and column restriction of the six margins
-    classes (LeastSquaresL1, SparseLeastSquaresL1, LogisticL1, SparseLogisticL1, HuberL1, SparseHuberL1)."""
+    """What the six margins classes (LeastSquaresL1, SparseLeastSquaresL1, LogisticL1, SparseLogisticL1, HuberL1, SparseHuberL1)
+    share: f / jac_f at a host vector, the duality-gap certificate, lam_max, same-matrix siblings, gap-safe screening and column
+    restriction.  Which C entry point a call reaches is decided HERE, from the loss (``_loss``), the weights (``_w``) and ``l2``;
+    the storage class below supplies the entry names (``_ENTRY``) and the matrix arguments they start with (``_lead``)."""
 
     has_duality_gap = True
-    _gap_logistic = 0
     l2 = 0.0   # elastic net: g(x) = lam |x|_1 + (l2 / 2) |x|^2 (+ box)
     # per-row sample weights: f(x) = scale sum_i w_i loss_i - a weighted SUM, not a mean; the weights are used as given
     # (csrc/zf_kernels_wloss.h).  _w: the device vector, shared by every sibling; None: the unweighted problem, every call as before
     _w = None
     _w_host = None
-    _loss = _lib.ZF_LOSS_SQUARE
+    _loss = _lib.ZF_LOSS_SQUARE   # the loss of the class: everything below that depends on it reads this one attribute
+    _gap_logistic = _classattr(lambda cls: int(cls._loss == _lib.ZF_LOSS_LOGISTIC))
+    _eval_name = _classattr(lambda cls: cls._ENTRY["eval"][cls._loss])   # f and jac_f of the unweighted problem
+    _longest = ()   # (sparse classes: the longest row and column, which their screen entries take)
+
+    def _ls(self, x, want_grad):
+        """(f, jac_f or None) at a host vector."""
+        x = _as_host(x)
+        if x.size != self.n_features:
+            raise ValueError(f"len(x) should be equal to n_features, got {x}.")
+        lib = _lib.require_gpu()
+        fval = C.c_double(0.0)
+        grad = np.empty_like(x) if want_grad else None
+        if self._w is not None:
+            name, args = self._ENTRY["weval"], self._lead(_dp(self._w)) + (self.scale, self._loss, self._w_delta())
+        else:   # (unweighted least squares stays on its own entry: other kernels, other bits than the weighted ones with w = 1)
+            name, args = self._eval_name, self._lead() + (self.scale,) + ((self.delta,) if self._loss == _lib.ZF_LOSS_HUBER else ())
+        _lib.check(getattr(lib, name)(*args, C.c_void_p(_lib.ptr(x)), C.byref(fval), C.c_void_p(_lib.ptr(grad)) if want_grad else None),
+                   name)
+        return np.float64(fval.value), grad
+
+    def f(self, x):
+        return self._ls(x, False)[0]
+
+    def jac_f(self, x):
+        return self._ls(x, True)[1]
+
+    def _gap_call(self, lib, x, out):
+        if self._w is not None:
+            name, args = "gap_weighted", self._lead(_dp(self._w)) + (self.scale, self.lam, self.l2, self._loss, self._w_delta())
+        elif self._loss == _lib.ZF_LOSS_HUBER:
+            name, args = "gap_huber", self._lead() + (self.scale, self.lam, self.l2, self.delta)
+        elif self.l2 > 0:
+            name, args = "gap_enet", self._lead() + (self.scale, self.lam, self.l2, self._gap_logistic)
+        else:
+            name, args = "gap", self._lead() + (self.scale, self.lam, self._gap_logistic)
+        name = self._ENTRY[name]
+        _lib.check(getattr(lib, name)(*args, C.c_void_p(_lib.ptr(x)), C.c_void_p(_lib.ptr(out)), out.size), name)
+
+    def _screen_call(self, lib, x, out, h, keep, index):
+        huber = self._loss == _lib.ZF_LOSS_HUBER
+        name = self._ENTRY["screen_huber" if huber else "screen"]
+        _lib.check(getattr(lib, name)(*self._lead(), self.scale, self.lam, self.delta if huber else self._gap_logistic,
+                                      C.c_void_p(_lib.ptr(x)), C.c_void_p(_lib.ptr(out)), out.size, _dp(h.norms), _dp(h.stats),
+                                      *self._longest, _dp(keep), _dp(index)), name)
+
+    def _finish_descriptor(self, fields, keep):
+        """The descriptor of a storage class with what has no field of zf_problem_desc: the engine calls zf_solver_set_l2 /
+        zf_solver_set_row_weights / zf_solver_set_huber for these three."""
+        if self.l2 > 0:
+            fields["l2"] = self.l2
+        if self._w is not None:
+            fields["row_weights"] = self._w.data_ptr()
+            keep = keep + (self._w,)
+        if self._loss == _lib.ZF_LOSS_HUBER:
+            fields["huber_delta"] = self.delta
+        return fields, keep
 
     @property
     def sample_weight(self):
@@ -420,11 +487,17 @@ class _GapMixin:
 
 class _DenseMarginsL1(_GapMixin, NativeProblem):
     """What the dense single-GPU problems f(x) = scale * sum_i loss_i((Ax)_i), g = lam |x|_1 (+ (l2 / 2) |x|^2) (+ box) share: A (m x n, dense
-    row-major) and the m-vector b in HBM, f / jac_f at a host vector through the entry point the subclass names, the
-    descriptor of one GPU.  The loss is the subclass's: its ``kind``, its ``_eval_name``, what b means."""
+    row-major) and the m-vector b in HBM, the dense entry points and their leading arguments, the descriptor of one GPU.  The
+    loss is the subclass's: its ``kind``, its ``_loss``, what b means."""
 
     kind = None
-    _eval_name = None   # f and jac_f at a host vector
+    _ENTRY = dict(eval=("zf_ls_eval", "zf_logistic_eval", "zf_huber_eval"), weval="zf_wloss_eval",   # (eval: by ZF_LOSS_* code)
+                  gap="zf_gap_eval", gap_enet="zf_gap_eval_enet", gap_huber="zf_gap_eval_huber", gap_weighted="zf_gap_eval_weighted",
+                  screen="zf_gap_screen_eval", screen_huber="zf_gap_screen_eval_huber")
+
+    def _lead(self, *w):
+        """What every dense entry point starts with: A, b, (the weights,) m, n."""
+        return (_dp(self.A), _dp(self.b), *w, self.m_rows, self.n_features)
 
     def _set(self, A, b, lam, scale, bounds, l2=0.0, sample_weight=None, group=None):
         self.l2 = _check_l2(l2)
@@ -444,11 +517,6 @@ class _DenseMarginsL1(_GapMixin, NativeProblem):
     def _norms_call(self, lib, norms, stats):
         _lib.check(lib.zf_dense_col_norms(_dp(self.A), self.m_rows, self.n_features, _dp(norms), _dp(stats)), "zf_dense_col_norms")
 
-    def _screen_call(self, lib, x, out, h, keep, index):
-        _lib.check(lib.zf_gap_screen_eval(_dp(self.A), _dp(self.b), self.m_rows, self.n_features, self.scale, self.lam, self._gap_logistic,
-                                          C.c_void_p(_lib.ptr(x)), C.c_void_p(_lib.ptr(out)), out.size, _dp(h.norms), _dp(h.stats),
-                                          _dp(keep), _dp(index)), "zf_gap_screen_eval")
-
     def _restrict_into(self, lib, mask, sub):
         import torch
 
@@ -462,66 +530,11 @@ class _DenseMarginsL1(_GapMixin, NativeProblem):
         _lib.check(lib.zf_dense_restrict(_dp(self.A), self.m_rows, n, _dp(mask), _dp(index), k.value, _dp(out)), "zf_dense_restrict")
         sub.A, sub.n_features = out, int(k.value)
 
-    def _w_ls(self, x, want_grad):
-        """f and jac_f with sample weights (zf_wloss_eval)."""
-        x = _as_host(x)
-        if x.size != self.n_features:
-            raise ValueError(f"len(x) should be equal to n_features, got {x}.")
-        lib = _lib.require_gpu()
-        fval = C.c_double(0.0)
-        grad = np.empty_like(x) if want_grad else None
-        _lib.check(lib.zf_wloss_eval(_dp(self.A), _dp(self.b), _dp(self._w), self.m_rows, self.n_features, self.scale, self._loss,
-                                     self._w_delta(), C.c_void_p(_lib.ptr(x)), C.byref(fval),
-                                     C.c_void_p(_lib.ptr(grad)) if want_grad else None), "zf_wloss_eval")
-        return np.float64(fval.value), grad
-
-    def _w_gap_call(self, lib, x, out):
-        _lib.check(lib.zf_gap_eval_weighted(_dp(self.A), _dp(self.b), _dp(self._w), self.m_rows, self.n_features, self.scale, self.lam,
-                                            self.l2, self._loss, self._w_delta(), C.c_void_p(_lib.ptr(x)), C.c_void_p(_lib.ptr(out)),
-                                            out.size), "zf_gap_eval_weighted")
-
-    def _ls(self, x, want_grad):
-        if self._w is not None:
-            return self._w_ls(x, want_grad)
-        x = _as_host(x)
-        if x.size != self.n_features:
-            raise ValueError(f"len(x) should be equal to n_features, got {x}.")
-        lib = _lib.require_gpu()
-        fval = C.c_double(0.0)
-        grad = np.empty_like(x) if want_grad else None
-        _lib.check(getattr(lib, self._eval_name)(C.c_void_p(self.A.data_ptr()), C.c_void_p(self.b.data_ptr()),
-                                                 self.m_rows, self.n_features, self.scale, C.c_void_p(_lib.ptr(x)),
-                                                 C.byref(fval), C.c_void_p(_lib.ptr(grad)) if want_grad else None),
-                   self._eval_name)
-        return np.float64(fval.value), grad
-
-    def _gap_call(self, lib, x, out):
-        if self._w is not None:
-            return self._w_gap_call(lib, x, out)
-        if self.l2 > 0:
-            _lib.check(lib.zf_gap_eval_enet(C.c_void_p(self.A.data_ptr()), C.c_void_p(self.b.data_ptr()), self.m_rows, self.n_features,
-                                            self.scale, self.lam, self.l2, self._gap_logistic, C.c_void_p(_lib.ptr(x)),
-                                            C.c_void_p(_lib.ptr(out)), out.size), "zf_gap_eval_enet")
-            return
-        _lib.check(lib.zf_gap_eval(C.c_void_p(self.A.data_ptr()), C.c_void_p(self.b.data_ptr()), self.m_rows, self.n_features,
-                                   self.scale, self.lam, self._gap_logistic, C.c_void_p(_lib.ptr(x)), C.c_void_p(_lib.ptr(out)),
-                                   out.size), "zf_gap_eval")
-
-    def f(self, x):
-        return self._ls(x, False)[0]
-
-    def jac_f(self, x):
-        return self._ls(x, True)[1]
-
     def _descriptor(self, rank=0, world=1, row_sharded=0):
         fields = dict(kind=self.kind, world=world, rank=rank, n=self.n_features, m_rows=self.m_rows, row_sharded=row_sharded,
                       d=None, c=None, A=self.A.data_ptr(), b=self.b.data_ptr(),
                       scale=self.scale, lam=self.lam, box_lo=self.box[0], box_hi=self.box[1])
-        if self.l2 > 0:
-            fields["l2"] = self.l2   # (no descriptor field: the engine calls zf_solver_set_l2)
-        if self._w is not None:
-            fields["row_weights"] = self._w.data_ptr()   # (likewise: zf_solver_set_row_weights)
-        return fields, (self.A, self.b) if self._w is None else (self.A, self.b, self._w)
+        return self._finish_descriptor(fields, (self.A, self.b))
 
 
 class LeastSquaresL1(_DenseMarginsL1):
@@ -532,7 +545,6 @@ class LeastSquaresL1(_DenseMarginsL1):
     """
 
     kind = _lib.ZF_PROBLEM_LEAST_SQUARES_L1
-    _eval_name = "zf_ls_eval"
     taylor_remainder = True   # acceptance="remainder": R = scale |A (x+ - y)|^2 from the residual kernels at x+
 
     def __init__(self, A, b, lam, scale=0.5, bounds=None, group=None, shard="columns", l2=0.0, *, sample_weight=None):
@@ -595,11 +607,18 @@ class _SpmatHandle:
 
 class _SparseMarginsL1(_GapMixin, NativeProblem):
     """What the sparse single-GPU problems f(x) = scale * sum_i loss_i((Ax)_i), g = lam |x|_1 (+ box) share: the canonical
-    CSR of A and of A^T behind one immutable handle, b in HBM, f / jac_f at a host vector through the entry point the
-    subclass names, the descriptor.  The loss is the subclass's: its ``kind``, its ``_eval_name``, what b means."""
+    CSR of A and of A^T behind one immutable handle, b in HBM, the sparse entry points and their leading arguments, the
+    descriptor.  The loss is the subclass's: its ``kind``, its ``_loss``, what b means."""
 
     kind = None
-    _eval_name = None
+    _ENTRY = dict(eval=("zf_spmat_eval", "zf_spmat_logistic_eval", "zf_spmat_huber_eval"), weval="zf_spmat_wloss_eval",
+                  gap="zf_spmat_gap_eval", gap_enet="zf_spmat_gap_eval_enet", gap_huber="zf_spmat_gap_eval_huber",
+                  gap_weighted="zf_spmat_gap_eval_weighted", screen="zf_spmat_gap_screen_eval",
+                  screen_huber="zf_spmat_gap_screen_eval_huber")
+
+    def _lead(self, *w):
+        """What every sparse entry point starts with: the matrix handle, b (, the weights)."""
+        return (self._spmat.value, _dp(self.b), *w)
 
     def _set(self, A, b, lam, scale, bounds, l2=0.0, sample_weight=None):
         import torch
@@ -625,11 +644,6 @@ class _SparseMarginsL1(_GapMixin, NativeProblem):
 
     def _norms_call(self, lib, norms, stats):
         _lib.check(lib.zf_spmat_col_norms(self._spmat.value, _dp(norms), _dp(stats)), "zf_spmat_col_norms")
-
-    def _screen_call(self, lib, x, out, h, keep, index):
-        _lib.check(lib.zf_spmat_gap_screen_eval(self._spmat.value, _dp(self.b), self.scale, self.lam, self._gap_logistic,
-                                                C.c_void_p(_lib.ptr(x)), C.c_void_p(_lib.ptr(out)), out.size, _dp(h.norms), _dp(h.stats),
-                                                self._longest[0], self._longest[1], _dp(keep), _dp(index)), "zf_spmat_gap_screen_eval")
 
     def _restrict_into(self, lib, mask, sub):
         """Counts, the two scans of the lengths (torch.cumsum), the fill; the host reads the two new row pointer arrays for the
@@ -666,63 +680,11 @@ class _SparseMarginsL1(_GapMixin, NativeProblem):
         sub._spmat = _SpmatHandle(prep, dev)
         sub._longest = (int(np.diff(indptr).max(initial=0)), int(np.diff(t_indptr).max(initial=0)))
 
-    def _w_ls(self, x, want_grad):
-        """f and jac_f with sample weights (zf_spmat_wloss_eval)."""
-        x = _as_host(x)
-        if x.size != self.n_features:
-            raise ValueError(f"len(x) should be equal to n_features, got {x}.")
-        lib = _lib.require_gpu()
-        fval = C.c_double(0.0)
-        grad = np.empty_like(x) if want_grad else None
-        _lib.check(lib.zf_spmat_wloss_eval(self._spmat.value, _dp(self.b), _dp(self._w), self.scale, self._loss, self._w_delta(),
-                                           C.c_void_p(_lib.ptr(x)), C.byref(fval), C.c_void_p(_lib.ptr(grad)) if want_grad else None),
-                   "zf_spmat_wloss_eval")
-        return np.float64(fval.value), grad
-
-    def _w_gap_call(self, lib, x, out):
-        _lib.check(lib.zf_spmat_gap_eval_weighted(self._spmat.value, _dp(self.b), _dp(self._w), self.scale, self.lam, self.l2, self._loss,
-                                                  self._w_delta(), C.c_void_p(_lib.ptr(x)), C.c_void_p(_lib.ptr(out)), out.size),
-                   "zf_spmat_gap_eval_weighted")
-
-    def _ls(self, x, want_grad):
-        if self._w is not None:
-            return self._w_ls(x, want_grad)
-        x = _as_host(x)
-        if x.size != self.n_features:
-            raise ValueError(f"len(x) should be equal to n_features, got {x}.")
-        lib = _lib.require_gpu()
-        fval = C.c_double(0.0)
-        grad = np.empty_like(x) if want_grad else None
-        _lib.check(getattr(lib, self._eval_name)(self._spmat.value, C.c_void_p(self.b.data_ptr()), self.scale, C.c_void_p(_lib.ptr(x)),
-                                                 C.byref(fval), C.c_void_p(_lib.ptr(grad)) if want_grad else None), self._eval_name)
-        return np.float64(fval.value), grad
-
-    def _gap_call(self, lib, x, out):
-        if self._w is not None:
-            return self._w_gap_call(lib, x, out)
-        if self.l2 > 0:
-            _lib.check(lib.zf_spmat_gap_eval_enet(self._spmat.value, C.c_void_p(self.b.data_ptr()), self.scale, self.lam, self.l2,
-                                                  self._gap_logistic, C.c_void_p(_lib.ptr(x)), C.c_void_p(_lib.ptr(out)), out.size),
-                       "zf_spmat_gap_eval_enet")
-            return
-        _lib.check(lib.zf_spmat_gap_eval(self._spmat.value, C.c_void_p(self.b.data_ptr()), self.scale, self.lam, self._gap_logistic,
-                                         C.c_void_p(_lib.ptr(x)), C.c_void_p(_lib.ptr(out)), out.size), "zf_spmat_gap_eval")
-
-    def f(self, x):
-        return self._ls(x, False)[0]
-
-    def jac_f(self, x):
-        return self._ls(x, True)[1]
-
     def _descriptor(self):
         fields = dict(kind=self.kind, world=1, rank=0, n=self.n_features, m_rows=self.m_rows, row_sharded=0,
                       d=None, c=None, A=None, b=self.b.data_ptr(), scale=self.scale, lam=self.lam,
                       box_lo=self.box[0], box_hi=self.box[1], spmat=self._spmat.value.value)
-        if self.l2 > 0:
-            fields["l2"] = self.l2   # (no descriptor field: the engine calls zf_solver_set_l2)
-        if self._w is not None:
-            fields["row_weights"] = self._w.data_ptr()   # (likewise: zf_solver_set_row_weights)
-        return fields, (self._spmat, self.b) if self._w is None else (self._spmat, self.b, self._w)
+        return self._finish_descriptor(fields, (self._spmat, self.b))
 
 
 class SparseLeastSquaresL1(_SparseMarginsL1):
@@ -736,7 +698,6 @@ class SparseLeastSquaresL1(_SparseMarginsL1):
     stored element in total.  A matrix with no stored element is legal.  Single GPU."""
 
     kind = _lib.ZF_PROBLEM_SPARSE_LS_L1
-    _eval_name = "zf_spmat_eval"
     taylor_remainder = True   # acceptance="remainder": R = scale |A (x+ - y)|^2 from the residual kernels at x+
 
     def __init__(self, A, b, lam, scale=0.5, bounds=None, l2=0.0, *, sample_weight=None):
@@ -763,8 +724,6 @@ class LogisticL1(_DenseMarginsL1):
     ``LogisticL1(A, b, lam).with_sample_weight(w)`` (the constructor's parameter list is fixed)."""
 
     kind = _lib.ZF_PROBLEM_LOGISTIC_L1
-    _eval_name = "zf_logistic_eval"
-    _gap_logistic = 1
     _loss = _lib.ZF_LOSS_LOGISTIC
 
     def __init__(self, A, b, lam, scale=1.0, bounds=None):
@@ -781,8 +740,6 @@ class SparseLogisticL1(_SparseMarginsL1):
     class's.  Single GPU."""
 
     kind = _lib.ZF_PROBLEM_SPARSE_LOGISTIC_L1
-    _eval_name = "zf_spmat_logistic_eval"
-    _gap_logistic = 1
     _loss = _lib.ZF_LOSS_LOGISTIC
 
     def __init__(self, A, b, lam, scale=1.0, bounds=None):
@@ -807,11 +764,6 @@ class _HuberMixin:
 
     _loss = _lib.ZF_LOSS_HUBER
 
-    def _descriptor(self):
-        fields, keep = super()._descriptor()
-        fields["huber_delta"] = self.delta   # (no descriptor field: the engine calls zf_solver_set_huber)
-        return fields, keep
-
     @staticmethod
     def _refuse_group(group):
         if group is not None:
@@ -832,31 +784,6 @@ class HuberL1(_HuberMixin, _DenseMarginsL1):
         self.delta = _check_delta(delta)
         self._set(A, b, lam, scale, bounds, l2, sample_weight)
 
-    def _ls(self, x, want_grad):
-        if self._w is not None:
-            return self._w_ls(x, want_grad)
-        x = _as_host(x)
-        if x.size != self.n_features:
-            raise ValueError(f"len(x) should be equal to n_features, got {x}.")
-        lib = _lib.require_gpu()
-        fval = C.c_double(0.0)
-        grad = np.empty_like(x) if want_grad else None
-        _lib.check(lib.zf_huber_eval(_dp(self.A), _dp(self.b), self.m_rows, self.n_features, self.scale, self.delta,
-                                     C.c_void_p(_lib.ptr(x)), C.byref(fval), C.c_void_p(_lib.ptr(grad)) if want_grad else None),
-                   "zf_huber_eval")
-        return np.float64(fval.value), grad
-
-    def _gap_call(self, lib, x, out):
-        if self._w is not None:
-            return self._w_gap_call(lib, x, out)
-        _lib.check(lib.zf_gap_eval_huber(_dp(self.A), _dp(self.b), self.m_rows, self.n_features, self.scale, self.lam, self.l2,
-                                         self.delta, C.c_void_p(_lib.ptr(x)), C.c_void_p(_lib.ptr(out)), out.size), "zf_gap_eval_huber")
-
-    def _screen_call(self, lib, x, out, h, keep, index):
-        _lib.check(lib.zf_gap_screen_eval_huber(_dp(self.A), _dp(self.b), self.m_rows, self.n_features, self.scale, self.lam, self.delta,
-                                                C.c_void_p(_lib.ptr(x)), C.c_void_p(_lib.ptr(out)), out.size, _dp(h.norms), _dp(h.stats),
-                                                _dp(keep), _dp(index)), "zf_gap_screen_eval_huber")
-
 
 class SparseHuberL1(_HuberMixin, _SparseMarginsL1):
     r"""``HuberL1`` with a SPARSE A (any scipy.sparse matrix): the matrix is prepared, stored and swept exactly as for
@@ -869,31 +796,6 @@ class SparseHuberL1(_HuberMixin, _SparseMarginsL1):
         self._refuse_group(group)
         self.delta = _check_delta(delta)
         self._set(A, b, lam, scale, bounds, l2, sample_weight)
-
-    def _ls(self, x, want_grad):
-        if self._w is not None:
-            return self._w_ls(x, want_grad)
-        x = _as_host(x)
-        if x.size != self.n_features:
-            raise ValueError(f"len(x) should be equal to n_features, got {x}.")
-        lib = _lib.require_gpu()
-        fval = C.c_double(0.0)
-        grad = np.empty_like(x) if want_grad else None
-        _lib.check(lib.zf_spmat_huber_eval(self._spmat.value, _dp(self.b), self.scale, self.delta, C.c_void_p(_lib.ptr(x)),
-                                           C.byref(fval), C.c_void_p(_lib.ptr(grad)) if want_grad else None), "zf_spmat_huber_eval")
-        return np.float64(fval.value), grad
-
-    def _gap_call(self, lib, x, out):
-        if self._w is not None:
-            return self._w_gap_call(lib, x, out)
-        _lib.check(lib.zf_spmat_gap_eval_huber(self._spmat.value, _dp(self.b), self.scale, self.lam, self.l2, self.delta,
-                                               C.c_void_p(_lib.ptr(x)), C.c_void_p(_lib.ptr(out)), out.size), "zf_spmat_gap_eval_huber")
-
-    def _screen_call(self, lib, x, out, h, keep, index):
-        _lib.check(lib.zf_spmat_gap_screen_eval_huber(self._spmat.value, _dp(self.b), self.scale, self.lam, self.delta,
-                                                      C.c_void_p(_lib.ptr(x)), C.c_void_p(_lib.ptr(out)), out.size, _dp(h.norms),
-                                                      _dp(h.stats), self._longest[0], self._longest[1], _dp(keep), _dp(index)),
-                   "zf_spmat_gap_screen_eval_huber")
 
 
 class BlurHaarL1(NativeProblem):
