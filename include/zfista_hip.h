@@ -671,7 +671,9 @@ enum { ZF_LOSS_SQUARE = 0, ZF_LOSS_LOGISTIC = 1, ZF_LOSS_HUBER = 2 };
  * never asked launches and allocates what it did.  A resumed solve sets the weights again before zf_solver_restore. */
 int zf_solver_set_row_weights(zf_solver* s, const double* w_dev);
 /* f and (grad_out_host != NULL) grad at a host vector with the weighted loss kernels the solver runs.  loss: ZF_LOSS_*; delta
- * must be finite and > 0 for ZF_LOSS_HUBER and is ignored otherwise.  ZF_ERR_ARG before anything else: a null pointer, m_rows or
+ * must be finite and > 0 for ZF_LOSS_HUBER and is ignored otherwise.  The three codes above only: the Poisson loss takes its
+ * weights through its own entry points (below), and ZF_LOSS_POISSON is refused here as every other code is.  ZF_ERR_ARG before
+ * anything else: a null pointer, m_rows or
  * n < 1, an unknown loss, a bad delta, a misaligned A. */
 int zf_wloss_eval(const double* A_dev, const double* b_dev, const double* w_dev, int64_t m_rows, int64_t n, double scale, int32_t loss,
                   double delta, const double* x_host, double* f_out, double* grad_out_host);
@@ -687,6 +689,46 @@ int zf_gap_eval_weighted(const double* A_dev, const double* b_dev, const double*
                          int64_t count /* >= 8; 10 for all */);
 int zf_spmat_gap_eval_weighted(const zf_spmat* h, const double* b_dev, const double* w_dev, double scale, double lam, double l2,
                                int32_t loss, double delta, const double* x_host, double* out, int64_t count /* >= 8; 10 for all */);
+
+/* ---- the Poisson loss with a log link on the least-squares kinds 2 and 4 (csrc/zf_kernels_poisson.h) ------------------------
+ * f(x) = scale sum_i w_i (exp(z_i) - b_i z_i), z = A x, with counts b_i >= 0, finite, not necessarily integers (a rate
+ * count / exposure with the exposure as the row weight is the exposure model); the constant log b! is dropped.
+ * grad f = scale A^T (w o psi), psi_i = exp(z_i) - b_i.  Every kernel forms ONE e = exp(z) per row, psi = e - b and
+ * phi = e - b z (two roundings); the sum is a plain sum times scale.  A margin beyond the range of exp gives f = +inf, never NaN:
+ * the acceptance test rejects such a trial and the line search backtracks.  A NaN margin gives a NaN f.  The library does not
+ * read b on the host: b >= 0 is the caller's check.  Additive to ABI 6: no problem kind, no struct field, no version change.
+ * zf_solver_set_poisson: after zf_solver_create(_sparse), before zf_solver_enqueue_init / zf_solver_restore (ZF_ERR_STATE
+ * afterwards).  ZF_ERR_ARG: a kind other than ZF_PROBLEM_LEAST_SQUARES_L1 / ZF_PROBLEM_SPARSE_LS_L1, world > 1, a solver
+ * created with ZF_ACCEPT_REMAINDER or ZF_ACCEPT_RESOLVED, a solver that has Huber's loss (and zf_solver_set_huber after this
+ * call likewise).  Composes with zf_solver_set_l2 and zf_solver_set_row_weights in any order.  A trial then runs the loss
+ * kernels where it ran the residual kernels - at y (psi to the residual buffer, f(y)) and at x+ (f(x+)); the A^T sweep runs with
+ * `scale` for `2 scale`; the prox step, the decision, history and snapshots are the least-squares kinds' own.  A matrix small
+ * enough for the two fused small-matrix launches takes the general path, and zf_solver_ls_plan says so.  A solver that was never
+ * asked launches and allocates what it did.  A resumed solve calls it again before zf_solver_restore. */
+enum { ZF_LOSS_POISSON = 3 };   /* the fourth ZF_LOSS_* code (struct zf_loss of csrc/zf_loss_dispatch.h) */
+int zf_solver_set_poisson(zf_solver* s);
+/* f and (grad_out_host != NULL) grad at a host vector: zf_ls_eval / zf_spmat_eval with the loss kernels the solver runs.
+ * w_dev: the row weights (m_rows doubles in device memory, as zf_solver_set_row_weights takes them) or NULL for the unweighted
+ * loss - the weighted form of this loss is reached here, not through zf_wloss_eval.  ZF_ERR_ARG before anything else: a null
+ * pointer (but w_dev), m_rows or n < 1, a misaligned A. */
+int zf_poisson_eval(const double* A_dev, const double* b_dev, const double* w_dev, int64_t m_rows, int64_t n, double scale,
+                    const double* x_host, double* f_out, double* grad_out_host);
+int zf_spmat_poisson_eval(const zf_spmat* h, const double* b_dev, const double* w_dev, double scale, const double* x_host, double* f_out,
+                          double* grad_out_host);
+/* The certificate.  h(z) = e^z - b z has h^*(u) = v log v - v, v = u + b >= 0 (0 log 0 = 0); with nu = alpha grad phi(z),
+ * v = alpha e^z + (1 - alpha) b >= 0 always.
+ *   P = f + lam |x|_1                                D = -scale sum w (v log v - v)
+ *   rows = scale sum w [e^z - v + v (log v - z)]     every term >= 0, exactly 0 at alpha = 1; columns, alpha: as zf_gap_eval
+ *   gap = rows + columns   (+ the ridge part, gt = fma(l2, x, g) and the two further outputs of zf_gap_eval_enet when l2 > 0)
+ * The row terms depend on alpha: a second rows pass follows the n-passes, as for the logistic loss.  out: the eight slots of
+ * zf_gap_eval; count >= 10 and l2 > 0: the ten of zf_gap_eval_enet (l2 = 0: [8] = [9] = 0).  w_dev: the row weights or NULL, as
+ * above.  zf_solver_duality_gap of a solver with zf_solver_set_poisson (and zf_solver_set_row_weights) writes the same values,
+ * bit for bit.  ZF_ERR_ARG as zf_gap_eval_enet.  There is no screen entry: exp is not globally Lipschitz, so the
+ * gap-safe radius of zf_gap_screen_eval does not apply. */
+int zf_gap_eval_poisson(const double* A_dev, const double* b_dev, const double* w_dev, int64_t m_rows, int64_t n, double scale, double lam,
+                        double l2, const double* x_host, double* out, int64_t count /* >= 8; 10 for all */);
+int zf_spmat_gap_eval_poisson(const zf_spmat* h, const double* b_dev, const double* w_dev, double scale, double lam, double l2,
+                              const double* x_host, double* out, int64_t count /* >= 8; 10 for all */);
 
 /* ---- multi-objective trial (m >= 2), device side ---------------------------
  * The dual of the scalarised subproblem is minimised on the host by SciPy exactly

@@ -22,7 +22,7 @@ ZF_RUNNING, ZF_CONVERGED, ZF_MAXITER, ZF_BACKTRACK_FAILED = 0, 1, 2, 3
 ZF_PROBLEM_DIAG_QUAD_L1, ZF_PROBLEM_LEAST_SQUARES_L1, ZF_PROBLEM_BLUR_HAAR_L1 = 1, 2, 3
 ZF_PROBLEM_SPARSE_LS_L1 = 4
 ZF_PROBLEM_LOGISTIC_L1, ZF_PROBLEM_SPARSE_LOGISTIC_L1 = 5, 6
-ZF_LOSS_SQUARE, ZF_LOSS_LOGISTIC, ZF_LOSS_HUBER = 0, 1, 2   # the loss of the weighted entry points (csrc/zf_kernels_wloss.h)
+ZF_LOSS_SQUARE, ZF_LOSS_LOGISTIC, ZF_LOSS_HUBER, ZF_LOSS_POISSON = 0, 1, 2, 3   # the loss of the weighted entry points (csrc/zf_kernels_wloss.h)
 ZF_MO_GENERIC, ZF_MO_JOS1, ZF_MO_FDS = 0, 1, 2
 ZF_PACK_LEN, ZF_TRACE_COLS, ZF_RING = 8, 8, 1024
 ZF_MAX_SUB_ITERS = 16
@@ -249,6 +249,11 @@ SIGNATURES = {
     "zf_gap_eval_weighted": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_double, _P, _P,
                                        C.c_int64]),
     "zf_spmat_gap_eval_weighted": (C.c_int, [_P, _P, _P, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_double, _P, _P, C.c_int64]),
+    "zf_solver_set_poisson": (C.c_int, [_P]),
+    "zf_poisson_eval": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_double, _P, C.POINTER(C.c_double), _P]),
+    "zf_spmat_poisson_eval": (C.c_int, [_P, _P, _P, C.c_double, _P, C.POINTER(C.c_double), _P]),
+    "zf_gap_eval_poisson": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_double, _P, _P, C.c_int64]),
+    "zf_spmat_gap_eval_poisson": (C.c_int, [_P, _P, _P, C.c_double, C.c_double, C.c_double, _P, _P, C.c_int64]),
 }
 
 _lib = None

@@ -5,6 +5,7 @@
 //   ZF_LOSS_SQUARE    r = z - b              psi = r                          phi = r * r
 //   ZF_LOSS_HUBER     r = z - b              psi = c = zf_huber_clip(r)       phi = zf_huber_of(r, c) = c (2 r - c)
 //   ZF_LOSS_LOGISTIC  t = -b z, e = exp(-|t|) psi = -b zf_sigmoid_of(t, e)     phi = zf_softplus_of(t, e)
+//   ZF_LOSS_POISSON   e = exp(z)             psi = e - b                      phi = e - b z       (zf_poisson_row)
 // then ONE product for each output: rho_i = w_i * psi_i and acc += w_i * phi_i (-ffp-contract=off: two roundings per row,
 // which NumPy reproduces bit for bit).  The sum is a plain sum, multiplied by scale once at the end - not the sqrt()^2 of the
 // unweighted squared loss.  w_i == 0 is a row that is not there: rho_i = +0 and its term +0 by a select, whatever b_i holds
@@ -23,11 +24,13 @@
 //   square    sum w r^2, sum w b r                       f = scale sum w r^2
 //   Huber     sum w H, sum w c^2, sum w b c, sum w |c| (|r| - |c|)
 //   logistic  sum w KL(alpha q || q), sum w [p log p + (1 - p) log(1 - p)]
+//   Poisson   sum w [row gap], sum w (v log v - v)       (zf_gap_poisson_kernel with w, zf_kernels_poisson.h)
 // (included by zf_solver.hip alone, behind zf_kernels_huber.h)
 #pragma once
 #include "zf_kernels_huber.h"
+#include "zf_kernels_poisson.h"
 
-// (include/zfista_hip.h: ZF_LOSS_SQUARE = 0, ZF_LOSS_LOGISTIC = 1, ZF_LOSS_HUBER = 2)
+// (include/zfista_hip.h: ZF_LOSS_SQUARE = 0, ZF_LOSS_LOGISTIC = 1, ZF_LOSS_HUBER = 2, ZF_LOSS_POISSON = 3)
 
 // psi and phi of one row; b is read only here, so a zero-weight row's b never reaches an output
 template <int LOSS>
@@ -41,6 +44,8 @@ __device__ __forceinline__ void zf_wloss_row(double z, double bi, double delta, 
         const double rv = z - bi;
         psi = zf_huber_clip(rv, delta);
         phi = zf_huber_of(rv, psi);
+    } else if (LOSS == ZF_LOSS_POISSON) {
+        zf_poisson_row(z, bi, psi, phi);
     } else {
         psi = z - bi;
         phi = psi * psi;
@@ -118,6 +123,8 @@ static inline void zf_launch_wloss_y(hipStream_t st, const zf_control* ctl, cons
         zf_launch_wloss_shape<ZF_LOSS_LOGISTIC, 0>(st, ctl, ctl, s0, s1, s2, 0, b, w, r, scale, delta, m, nesterov, part, f_out);
     else if (loss == ZF_LOSS_HUBER)
         zf_launch_wloss_shape<ZF_LOSS_HUBER, 0>(st, ctl, ctl, s0, s1, s2, 0, b, w, r, scale, delta, m, nesterov, part, f_out);
+    else if (loss == ZF_LOSS_POISSON)
+        zf_launch_wloss_shape<ZF_LOSS_POISSON, 0>(st, ctl, ctl, s0, s1, s2, 0, b, w, r, scale, delta, m, nesterov, part, f_out);
     else
         zf_launch_wloss_shape<ZF_LOSS_SQUARE, 0>(st, ctl, ctl, s0, s1, s2, 0, b, w, r, scale, delta, m, nesterov, part, f_out);
 }
@@ -131,6 +138,8 @@ static inline void zf_launch_wloss_x(hipStream_t st, const zf_control* ctl, cons
         zf_launch_wloss_shape<ZF_LOSS_LOGISTIC, 1>(st, ctl, fin, s0, s1, s2, slot, b, w, nullptr, scale, delta, m, 0, part, f_out);
     else if (loss == ZF_LOSS_HUBER)
         zf_launch_wloss_shape<ZF_LOSS_HUBER, 1>(st, ctl, fin, s0, s1, s2, slot, b, w, nullptr, scale, delta, m, 0, part, f_out);
+    else if (loss == ZF_LOSS_POISSON)
+        zf_launch_wloss_shape<ZF_LOSS_POISSON, 1>(st, ctl, fin, s0, s1, s2, slot, b, w, nullptr, scale, delta, m, 0, part, f_out);
     else
         zf_launch_wloss_shape<ZF_LOSS_SQUARE, 1>(st, ctl, fin, s0, s1, s2, slot, b, w, nullptr, scale, delta, m, 0, part, f_out);
 }
@@ -254,8 +263,8 @@ __global__ __launch_bounds__(BLOCK) void zf_gap_wkl_kernel(const double* __restr
 // ZF_GAP_PART_HUBER for Huber's loss)
 static inline void zf_launch_gap_wrows(hipStream_t st, int loss, const double* z, const double* b, const double* w, int64_t m, double scale,
                                        double delta, const zf_gap_ws& ws) {
-    if (loss == ZF_LOSS_LOGISTIC) {   // w rho and f by the loss kernels of a trial, called outside the loop
-        zf_launch_wloss_y(st, nullptr, z, z, z, b, w, ws.rvec, scale, ZF_LOSS_LOGISTIC, 0.0, m, 0, ws.part + 2 * ZF_GAP_MAX_CHUNKS,
+    if (loss == ZF_LOSS_LOGISTIC || loss == ZF_LOSS_POISSON) {   // w psi and f by the loss kernels of a trial, called outside the loop
+        zf_launch_wloss_y(st, nullptr, z, z, z, b, w, ws.rvec, scale, loss, 0.0, m, 0, ws.part + 2 * ZF_GAP_MAX_CHUNKS,
                           ws.scal + ZF_GS_F);
         return;
     }
@@ -290,6 +299,10 @@ static inline void zf_launch_gap_wtail(hipStream_t st, int loss, const double* z
                                        int64_t m, int64_t n, double scale, double lam, double l2, const zf_gap_ws& ws) {
     if (loss == ZF_LOSS_HUBER) {   // (no row pass behind the n-passes: its composition reads the four sums of step 1)
         zf_launch_gap_tail_huber(st, x, n, scale, lam, l2, ws);
+        return;
+    }
+    if (loss == ZF_LOSS_POISSON) {   // (its second rows pass takes the weights itself)
+        zf_launch_gap_tail_poisson(st, z, b, w, x, m, n, scale, lam, l2, ws);
         return;
     }
     const int nc = zf_gap_chunks(n);

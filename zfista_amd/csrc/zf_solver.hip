@@ -24,6 +24,7 @@
 #include "zf_kernels_loss.h"
 #include "zf_kernels_gap.h"
 #include "zf_kernels_huber.h"
+#include "zf_kernels_poisson.h"
 #include "zf_kernels_wloss.h"
 #include "zf_loss_dispatch.h"
 #include "zf_kernels_step.h"
@@ -233,6 +234,7 @@ struct zf_solver {
     bool gemv_mfma = false;       // A^T r on v_mfma_f64_16x16x4 (n % 32 == 0; ZF_GEMV_MFMA=0 disables)
     bool ls_small = false;        // cache-resident A: two fused launches per trial (zf_kernels_ls_small.h)
     double huber = 0.0;           // Huber's loss (zf_solver_set_huber): delta > 0 swaps the residual kernels for zf_kernels_huber.h; 0: the squared loss
+    bool poisson = false;         // the Poisson loss (zf_solver_set_poisson): the residual kernels swapped for zf_kernels_poisson.h
     bool loss_part = false;       // the dense least-squares kind holds the 2 x ZF_SPMV_RESID_MAX_CHUNKS chunk sums of the loss kernels (zf_loss_part)
     const double* roww = nullptr; // per-row sample weights (zf_solver_set_row_weights; borrowed as b is): the loss sites take zf_kernels_wloss.h; NULL: what ran before
     double l2 = 0.0;              // elastic net (zf_solver_set_l2): g = lam |x|_1 + (l2 / 2) |x|^2; 0: every path is the l1 one
@@ -412,9 +414,13 @@ static bool zf_is_dense_mat(int kind) { return kind == ZF_PROBLEM_LEAST_SQUARES_
 static bool zf_is_sparse_mat(int kind) { return kind == ZF_PROBLEM_SPARSE_LS_L1 || kind == ZF_PROBLEM_SPARSE_LOGISTIC_L1; }
 // f is a loss of A x: the margins of x_k, x_{k-1} are kept in a ring and A y follows by linearity
 static bool zf_has_margins(int kind) { return zf_is_ls(kind) || zf_is_logistic(kind); }
-// the loss of a solver (zf_loss_dispatch.h): the one place that reads the problem kind, zf_solver_set_huber and zf_solver_set_row_weights for it
+// the loss of a solver (zf_loss_dispatch.h): the one place that reads the problem kind, zf_solver_set_huber, zf_solver_set_poisson and
+// zf_solver_set_row_weights for it
 static zf_loss zf_loss_of(const zf_solver* s) {
-    const int kind = zf_is_logistic(s->desc.kind) ? ZF_LOSS_LOGISTIC : s->huber > 0.0 ? ZF_LOSS_HUBER : ZF_LOSS_SQUARE;
+    const int kind = zf_is_logistic(s->desc.kind) ? ZF_LOSS_LOGISTIC
+                     : s->huber > 0.0            ? ZF_LOSS_HUBER
+                     : s->poisson                ? ZF_LOSS_POISSON
+                                                 : ZF_LOSS_SQUARE;
     return zf_loss{kind, s->huber, s->roww};
 }
 // row slices of the dense column sweep A^T r: enough that panels x slices fills the chip (>= ~2048 workgroups)
@@ -1884,7 +1890,8 @@ extern "C" int zf_solver_set_l2(zf_solver* s, double l2) {
 }
 
 // chunk sums of the loss at y and at x+ for the dense least-squares kind, as the dense logistic kind holds them (the fused
-// small-matrix path's are shorter): allocated once, by the first of zf_solver_set_huber / zf_solver_set_row_weights
+// small-matrix path's are shorter): allocated once, by the first of zf_solver_set_huber / zf_solver_set_poisson /
+// zf_solver_set_row_weights
 static int zf_loss_part(zf_solver* s) {
     if (s->desc.kind != ZF_PROBLEM_LEAST_SQUARES_L1 || s->loss_part) return ZF_OK;
     double* part = nullptr;
@@ -1906,9 +1913,29 @@ extern "C" int zf_solver_set_huber(zf_solver* s, double delta) {
     ZF_REQUIRE(d.world == 1, "zf_solver_set_huber: not for a sharded solve (world > 1)");
     ZF_REQUIRE(delta > 0.0 && delta <= DBL_MAX, "zf_solver_set_huber: delta must be finite and > 0");
     ZF_REQUIRE(!s->rem, "zf_solver_set_huber: not with ZF_ACCEPT_REMAINDER (scale |A (x+ - y)|^2 is not the Taylor remainder of this loss)");
+    ZF_REQUIRE(!s->poisson, "zf_solver_set_huber: the solver already has the Poisson loss (zf_solver_set_poisson)");
     const int rc = zf_loss_part(s);
     if (rc) return rc;
     s->huber = delta;
+    s->ls_small = false;   // (the fused small-matrix kernels hold the squared loss: the general path, as the logistic kind)
+    return ZF_OK;
+}
+
+// The Poisson loss (include/zfista_hip.h): between create and init, on the two least-squares kinds.
+extern "C" int zf_solver_set_poisson(zf_solver* s) {
+    ZF_REQUIRE(s, "zf_solver_set_poisson: null argument");
+    if (s->init_enqueued || s->initialised)
+        return zf_fail(ZF_ERR_STATE, "zf_solver_set_poisson: call after zf_solver_create and before zf_solver_enqueue_init / zf_solver_restore%s%s");
+    const zf_problem_desc& d = s->desc;
+    ZF_REQUIRE(d.kind == ZF_PROBLEM_LEAST_SQUARES_L1 || d.kind == ZF_PROBLEM_SPARSE_LS_L1,
+               "zf_solver_set_poisson: only for ZF_PROBLEM_LEAST_SQUARES_L1 and ZF_PROBLEM_SPARSE_LS_L1");
+    ZF_REQUIRE(d.world == 1, "zf_solver_set_poisson: not for a sharded solve (world > 1)");
+    ZF_REQUIRE(!s->rem, "zf_solver_set_poisson: not with ZF_ACCEPT_REMAINDER (scale |A (x+ - y)|^2 is not the Taylor remainder of this loss)");
+    ZF_REQUIRE(!s->res, "zf_solver_set_poisson: not with ZF_ACCEPT_RESOLVED");
+    ZF_REQUIRE(!(s->huber > 0.0), "zf_solver_set_poisson: the solver already has Huber's loss (zf_solver_set_huber)");
+    const int rc = zf_loss_part(s);
+    if (rc) return rc;
+    s->poisson = true;
     s->ls_small = false;   // (the fused small-matrix kernels hold the squared loss: the general path, as the logistic kind)
     return ZF_OK;
 }
@@ -2577,8 +2604,8 @@ static int zf_view_args(const char* who, const zf_matview& V, bool ok) {
 }
 // ... then, behind zf_view_args, the loss code, Huber's delta and the alignment of a dense A; leaves the entry's loss in *L
 static int zf_loss_args(const char* who, zf_matview* V, int32_t kind, double delta, const double* w_dev, zf_loss* L) {
-    if (kind != ZF_LOSS_SQUARE && kind != ZF_LOSS_LOGISTIC && kind != ZF_LOSS_HUBER)
-        return zf_fail(ZF_ERR_ARG, "%s: loss must be ZF_LOSS_SQUARE, ZF_LOSS_LOGISTIC or ZF_LOSS_HUBER%s", who);
+    if (kind != ZF_LOSS_SQUARE && kind != ZF_LOSS_LOGISTIC && kind != ZF_LOSS_HUBER && kind != ZF_LOSS_POISSON)
+        return zf_fail(ZF_ERR_ARG, "%s: loss must be ZF_LOSS_SQUARE, ZF_LOSS_LOGISTIC, ZF_LOSS_HUBER or ZF_LOSS_POISSON%s", who);
     if (kind == ZF_LOSS_HUBER && !(delta > 0.0 && delta <= DBL_MAX)) return zf_fail(ZF_ERR_ARG, "%s: delta must be finite and > 0%s", who);
     if (!V->csr && !zf_aligned16(V->A)) return zf_fail(ZF_ERR_ARG, "%s: A must be 16-byte aligned%s", who);
     if (V->csr) V->m = V->h->m, V->n = V->h->n;
@@ -2679,16 +2706,34 @@ extern "C" int zf_spmat_huber_eval(const zf_spmat* h, const double* b_dev, doubl
                           grad_out_host);
 }
 
+// the Poisson loss (zf_kernels_poisson.h) on the same sweeps: f = scale sum (exp(A x) - b o A x), grad = scale A^T (exp(A x) - b)
+// (w_dev: the row weights or NULL - the weighted form of this loss has no other entry)
+extern "C" int zf_poisson_eval(const double* A_dev, const double* b_dev, const double* w_dev, int64_t m_rows, int64_t n, double scale,
+                               const double* x_host, double* f_out, double* grad_out_host) {
+    return zf_point_entry("zf_poisson_eval", zf_dense_view(A_dev, m_rows, n), b_dev, true, w_dev, scale, ZF_LOSS_POISSON, 0.0, x_host, f_out,
+                          grad_out_host);
+}
+
+extern "C" int zf_spmat_poisson_eval(const zf_spmat* h, const double* b_dev, const double* w_dev, double scale, const double* x_host,
+                                     double* f_out, double* grad_out_host) {
+    return zf_point_entry("zf_spmat_poisson_eval", zf_csr_view(h), b_dev, true, w_dev, scale, ZF_LOSS_POISSON, 0.0, x_host, f_out,
+                          grad_out_host);
+}
+
+// the loss code of the four weighted entries below: the three losses they were built for.  The Poisson loss takes its weights through
+// its own entries, so its code is refused here as every unknown code is (zf_loss_args names the codes)
+static int32_t zf_wloss_code(int32_t loss) { return loss == ZF_LOSS_POISSON ? -1 : loss; }
+
 // per-row sample weights (zf_kernels_wloss.h) on the same sweeps: f = scale sum w phi, grad = gfac A^T (w o psi)
 extern "C" int zf_wloss_eval(const double* A_dev, const double* b_dev, const double* w_dev, int64_t m_rows, int64_t n, double scale,
                              int32_t loss, double delta, const double* x_host, double* f_out, double* grad_out_host) {
-    return zf_point_entry("zf_wloss_eval", zf_dense_view(A_dev, m_rows, n), b_dev, w_dev != nullptr, w_dev, scale, loss, delta, x_host, f_out,
+    return zf_point_entry("zf_wloss_eval", zf_dense_view(A_dev, m_rows, n), b_dev, w_dev != nullptr, w_dev, scale, zf_wloss_code(loss), delta, x_host, f_out,
                           grad_out_host);
 }
 
 extern "C" int zf_spmat_wloss_eval(const zf_spmat* h, const double* b_dev, const double* w_dev, double scale, int32_t loss, double delta,
                                    const double* x_host, double* f_out, double* grad_out_host) {
-    return zf_point_entry("zf_spmat_wloss_eval", zf_csr_view(h), b_dev, w_dev != nullptr, w_dev, scale, loss, delta, x_host, f_out,
+    return zf_point_entry("zf_spmat_wloss_eval", zf_csr_view(h), b_dev, w_dev != nullptr, w_dev, scale, zf_wloss_code(loss), delta, x_host, f_out,
                           grad_out_host);
 }
 
@@ -2859,17 +2904,31 @@ extern "C" int zf_spmat_gap_eval_huber(const zf_spmat* h, const double* b_dev, d
                         out, count);
 }
 
+// the Poisson loss (zf_kernels_poisson.h): the certificate with the conjugate v log v - v, v = alpha exp(z) + (1 - alpha) b
+// (w_dev: the row weights or NULL)
+extern "C" int zf_gap_eval_poisson(const double* A_dev, const double* b_dev, const double* w_dev, int64_t m_rows, int64_t n, double scale,
+                                   double lam, double l2, const double* x_host, double* out, int64_t count) {
+    return zf_gap_entry("zf_gap_eval_poisson", zf_dense_view(A_dev, m_rows, n), b_dev, true, w_dev, scale, lam, true, l2, ZF_LOSS_POISSON, 0.0,
+                        x_host, out, count);
+}
+
+extern "C" int zf_spmat_gap_eval_poisson(const zf_spmat* h, const double* b_dev, const double* w_dev, double scale, double lam, double l2,
+                                         const double* x_host, double* out, int64_t count) {
+    return zf_gap_entry("zf_spmat_gap_eval_poisson", zf_csr_view(h), b_dev, true, w_dev, scale, lam, true, l2, ZF_LOSS_POISSON, 0.0, x_host,
+                        out, count);
+}
+
 // per-row sample weights (zf_kernels_wloss.h): the certificate with every row term times w_i
 extern "C" int zf_gap_eval_weighted(const double* A_dev, const double* b_dev, const double* w_dev, int64_t m_rows, int64_t n, double scale,
                                     double lam, double l2, int32_t loss, double delta, const double* x_host, double* out, int64_t count) {
-    return zf_gap_entry("zf_gap_eval_weighted", zf_dense_view(A_dev, m_rows, n), b_dev, w_dev != nullptr, w_dev, scale, lam, true, l2, loss,
-                        delta, x_host, out, count);
+    return zf_gap_entry("zf_gap_eval_weighted", zf_dense_view(A_dev, m_rows, n), b_dev, w_dev != nullptr, w_dev, scale, lam, true, l2,
+                        zf_wloss_code(loss), delta, x_host, out, count);
 }
 
 extern "C" int zf_spmat_gap_eval_weighted(const zf_spmat* h, const double* b_dev, const double* w_dev, double scale, double lam, double l2,
                                           int32_t loss, double delta, const double* x_host, double* out, int64_t count) {
-    return zf_gap_entry("zf_spmat_gap_eval_weighted", zf_csr_view(h), b_dev, w_dev != nullptr, w_dev, scale, lam, true, l2, loss, delta,
-                        x_host, out, count);
+    return zf_gap_entry("zf_spmat_gap_eval_weighted", zf_csr_view(h), b_dev, w_dev != nullptr, w_dev, scale, lam, true, l2, zf_wloss_code(loss),
+                        delta, x_host, out, count);
 }
 
 // the gap evaluation followed by the gap-safe screen of its g (zf_kernels_screen.h), l2 = 0 only: out[0 .. 8) as zf_gap_eval - the

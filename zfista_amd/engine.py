@@ -81,9 +81,10 @@ class DeviceSolver:
         spmat = desc_fields.get("spmat")   # a zf_spmat handle: the matrix of a sparse problem is no descriptor field
         l2 = float(desc_fields.get("l2", 0.0) or 0.0)   # elastic net: no descriptor field either (zf_solver_set_l2)
         huber = float(desc_fields.get("huber_delta", 0.0) or 0.0)   # Huber's loss on a least-squares kind: likewise (zf_solver_set_huber)
+        poisson = bool(desc_fields.get("poisson", False))   # the Poisson loss on a least-squares kind: likewise (zf_solver_set_poisson)
         roww = desc_fields.get("row_weights")   # per-row sample weights (a device pointer): likewise (zf_solver_set_row_weights)
         for k, v in desc_fields.items():
-            if k not in ("spmat", "l2", "huber_delta", "row_weights"):
+            if k not in ("spmat", "l2", "huber_delta", "poisson", "row_weights"):
                 setattr(d, k, v)
         o = _lib.Options()
         for k, v in options.items():
@@ -102,6 +103,8 @@ class DeviceSolver:
             _lib.check(self.lib.zf_solver_set_l2(h, l2), "zf_solver_set_l2")
         if huber > 0:
             _lib.check(self.lib.zf_solver_set_huber(h, huber), "zf_solver_set_huber")
+        if poisson:
+            _lib.check(self.lib.zf_solver_set_poisson(h), "zf_solver_set_poisson")
         if roww:
             _lib.check(self.lib.zf_solver_set_row_weights(h, C.c_void_p(roww)), "zf_solver_set_row_weights")
         sub = C.c_int32(1)

@@ -115,8 +115,8 @@ def l1_cv(problem, lams, folds=5, seed=0, x0=None, gap_tol=1e-6, refit=True, ret
     weight and hold positive weight itself.  ``refit``: also solve the path on all rows (``path``).  Returns an ``L1CV``.
     The folds run one after the other; there is no intercept; screening is not available with weights."""
     if not getattr(problem, "has_duality_gap", False) or not hasattr(problem, "with_sample_weight"):
-        raise ValueError("l1_cv needs one of the six margins classes (LeastSquaresL1, SparseLeastSquaresL1, LogisticL1, "
-                         "SparseLogisticL1, HuberL1, SparseHuberL1)")
+        raise ValueError("l1_cv needs one of the margins classes (LeastSquaresL1, SparseLeastSquaresL1, LogisticL1, "
+                         "SparseLogisticL1, HuberL1, SparseHuberL1, PoissonL1, SparsePoissonL1)")
     if solver_kwargs.get("screen"):
         raise ValueError("l1_cv(screen=True) is not available: a fold is a sample_weight sibling, and the weighted screening rule "
                          "is not built yet")

@@ -225,8 +225,8 @@ class _classattr:
 
 
 class _GapMixin:
-    """What the six margins classes (LeastSquaresL1, SparseLeastSquaresL1, LogisticL1, SparseLogisticL1, HuberL1, SparseHuberL1)
-    share: f / jac_f at a host vector, the duality-gap certificate, lam_max, same-matrix siblings, gap-safe screening and column
+    """What the eight margins classes (LeastSquaresL1, SparseLeastSquaresL1, LogisticL1, SparseLogisticL1, HuberL1, SparseHuberL1,
+    PoissonL1, SparsePoissonL1) share: f / jac_f at a host vector, the duality-gap certificate, lam_max, same-matrix siblings, gap-safe screening and column
     restriction.  Which C entry point a call reaches is decided HERE, from the loss (``_loss``), the weights (``_w``) and ``l2``;
     the storage class below supplies the entry names (``_ENTRY``) and the matrix arguments they start with (``_lead``)."""
 
@@ -249,7 +249,9 @@ class _GapMixin:
         lib = _lib.require_gpu()
         fval = C.c_double(0.0)
         grad = np.empty_like(x) if want_grad else None
-        if self._w is not None:
+        if self._loss == _lib.ZF_LOSS_POISSON:   # (its entries take the weights, or NULL)
+            name, args = self._eval_name, self._lead(_dp(self._w)) + (self.scale,)
+        elif self._w is not None:
             name, args = self._ENTRY["weval"], self._lead(_dp(self._w)) + (self.scale, self._loss, self._w_delta())
         else:   # (unweighted least squares stays on its own entry: other kernels, other bits than the weighted ones with w = 1)
             name, args = self._eval_name, self._lead() + (self.scale,) + ((self.delta,) if self._loss == _lib.ZF_LOSS_HUBER else ())
@@ -264,7 +266,9 @@ class _GapMixin:
         return self._ls(x, True)[1]
 
     def _gap_call(self, lib, x, out):
-        if self._w is not None:
+        if self._loss == _lib.ZF_LOSS_POISSON:   # (its entries take the weights, or NULL)
+            name, args = "gap_poisson", self._lead(_dp(self._w)) + (self.scale, self.lam, self.l2)
+        elif self._w is not None:
             name, args = "gap_weighted", self._lead(_dp(self._w)) + (self.scale, self.lam, self.l2, self._loss, self._w_delta())
         elif self._loss == _lib.ZF_LOSS_HUBER:
             name, args = "gap_huber", self._lead() + (self.scale, self.lam, self.l2, self.delta)
@@ -284,7 +288,7 @@ class _GapMixin:
 
     def _finish_descriptor(self, fields, keep):
         """The descriptor of a storage class with what has no field of zf_problem_desc: the engine calls zf_solver_set_l2 /
-        zf_solver_set_row_weights / zf_solver_set_huber for these three."""
+        zf_solver_set_row_weights / zf_solver_set_huber / zf_solver_set_poisson for these."""
         if self.l2 > 0:
             fields["l2"] = self.l2
         if self._w is not None:
@@ -292,6 +296,8 @@ class _GapMixin:
             keep = keep + (self._w,)
         if self._loss == _lib.ZF_LOSS_HUBER:
             fields["huber_delta"] = self.delta
+        if self._loss == _lib.ZF_LOSS_POISSON:
+            fields["poisson"] = True
         return fields, keep
 
     @property
@@ -491,8 +497,9 @@ class _DenseMarginsL1(_GapMixin, NativeProblem):
     loss is the subclass's: its ``kind``, its ``_loss``, what b means."""
 
     kind = None
-    _ENTRY = dict(eval=("zf_ls_eval", "zf_logistic_eval", "zf_huber_eval"), weval="zf_wloss_eval",   # (eval: by ZF_LOSS_* code)
+    _ENTRY = dict(eval=("zf_ls_eval", "zf_logistic_eval", "zf_huber_eval", "zf_poisson_eval"), weval="zf_wloss_eval",   # (eval: by ZF_LOSS_* code)
                   gap="zf_gap_eval", gap_enet="zf_gap_eval_enet", gap_huber="zf_gap_eval_huber", gap_weighted="zf_gap_eval_weighted",
+                  gap_poisson="zf_gap_eval_poisson",
                   screen="zf_gap_screen_eval", screen_huber="zf_gap_screen_eval_huber")
 
     def _lead(self, *w):
@@ -611,7 +618,8 @@ class _SparseMarginsL1(_GapMixin, NativeProblem):
     descriptor.  The loss is the subclass's: its ``kind``, its ``_loss``, what b means."""
 
     kind = None
-    _ENTRY = dict(eval=("zf_spmat_eval", "zf_spmat_logistic_eval", "zf_spmat_huber_eval"), weval="zf_spmat_wloss_eval",
+    _ENTRY = dict(eval=("zf_spmat_eval", "zf_spmat_logistic_eval", "zf_spmat_huber_eval", "zf_spmat_poisson_eval"),
+                  weval="zf_spmat_wloss_eval", gap_poisson="zf_spmat_gap_eval_poisson",
                   gap="zf_spmat_gap_eval", gap_enet="zf_spmat_gap_eval_enet", gap_huber="zf_spmat_gap_eval_huber",
                   gap_weighted="zf_spmat_gap_eval_weighted", screen="zf_spmat_gap_screen_eval",
                   screen_huber="zf_spmat_gap_screen_eval_huber")
@@ -795,6 +803,86 @@ class SparseHuberL1(_HuberMixin, _SparseMarginsL1):
     def __init__(self, A, b, lam, delta, scale=0.5, bounds=None, l2=0.0, *, group=None, sample_weight=None):
         self._refuse_group(group)
         self.delta = _check_delta(delta)
+        self._set(A, b, lam, scale, bounds, l2, sample_weight)
+
+
+def _check_counts(b, m=None):
+    """The counts of a Poisson problem as a host vector: finite and >= 0, one per row (not necessarily integers).  ValueError
+    otherwise - on the host, before anything touches the device (a torch tensor is copied to the host for the check)."""
+    host = b.detach().cpu().numpy() if hasattr(b, "detach") else np.asarray(b)
+    if host.ndim != 1 or (m is not None and host.shape[0] != m):
+        raise ValueError(f"b must be a vector of {'m' if m is None else m} counts (the rows of A), got shape {host.shape}")
+    if np.dtype(host.dtype).kind not in "biuf" or not np.all(np.isfinite(host)) or np.any(host < 0):
+        raise ValueError("the counts b must be finite and >= 0")
+    return host
+
+
+class _PoissonMixin:
+    """The Poisson loss with a log link on the trial of a least-squares class: f(x) = scale sum_i w_i (exp(z_i) - b_i z_i),
+    z = A x; grad f = scale A^T (w o (exp(z) - b)) (csrc/zf_kernels_poisson.h: one exp per row).  The problem kind is the
+    least-squares one; ``poisson`` in the descriptor fields makes the engine call ``zf_solver_set_poisson``.  No
+    ``taylor_remainder`` and not separable: ``acceptance="remainder"`` / ``"resolved"`` are refused.  No screening: exp is not
+    globally Lipschitz, so the gap-safe radius sqrt(2 L gap) does not apply."""
+
+    _loss = _lib.ZF_LOSS_POISSON
+
+    @staticmethod
+    def _refuse_group(group):
+        if group is not None:
+            raise ValueError("group= is not available: the Poisson loss kernels, their certificate and zf_solver_set_poisson are "
+                             "built for one GPU (world = 1)")
+
+    def _screen_refusal(self):
+        return ("the Poisson loss has no globally Lipschitz gradient, so the gap-safe radius sqrt(2 L gap) does not apply "
+                "(a level-set bound is not built)")
+
+    def _no_screening(self, what):
+        raise ValueError(f"{what} is not available: {self._screen_refusal()}")
+
+    def column_norms(self):
+        self._no_screening("column_norms")
+
+    def restrict(self, keep):
+        self._no_screening("restrict")
+
+    def lam_max(self):
+        """|grad f(0)|_inf = scale |A^T (w o (1 - b))|_inf: the smallest lam for which x = 0 is optimal."""
+        return super().lam_max()
+
+
+class PoissonL1(_PoissonMixin, _DenseMarginsL1):
+    r"""f(x) = scale \sum_i w_i (exp((Ax)_i) - b_i (Ax)_i),  g(x) = lam \|x\|_1 (+ (l2 / 2) \|x\|^2) (+ optional box); A dense
+    row-major: L1-regularised Poisson regression with a log link on the device-resident trial of ``LeastSquaresL1`` - same
+    keywords, same result fields, with the duality-gap certificate, ``gap_tol``, ``l1_path``, ``l1_cv``, the elastic net and
+    sample weights.  The negative log-likelihood up to the constant log b!.
+
+    ``b``: the counts, finite and >= 0.  They need not be integers: with an exposure t_i per row, pass the RATE
+    ``b = count / t`` and ``sample_weight = t`` - w_i (exp(z_i) - (count_i / t_i) z_i) is the likelihood of
+    count_i ~ Poisson(t_i exp(z_i)) up to a constant, so exposure is exactly a sample weight.  A trial whose margins leave
+    the range of exp has f = +inf and is rejected: the line search backtracks.  No screening (``column_norms``, ``screen``,
+    ``restrict``, ``solve_screened``, ``l1_path(screen=True)``): exp is not globally Lipschitz.  Single GPU."""
+
+    kind = _lib.ZF_PROBLEM_LEAST_SQUARES_L1
+
+    def __init__(self, A, b, lam, scale=1.0, bounds=None, l2=0.0, *, group=None, sample_weight=None):
+        self._refuse_group(group)
+        shape = tuple(getattr(A, "shape", np.shape(A)))
+        if len(shape) != 2:
+            raise ValueError("A must be (m, n) and b (m,)")
+        _check_counts(b, shape[0])
+        self._set(A, b, lam, scale, bounds, l2, sample_weight)
+
+
+class SparsePoissonL1(_PoissonMixin, _SparseMarginsL1):
+    r"""``PoissonL1`` with a SPARSE A (any scipy.sparse matrix): the matrix is prepared, stored and swept exactly as for
+    ``SparseLeastSquaresL1``; the loss kernels are the dense class's and sum the rows of the same m in the same order.
+    Single GPU."""
+
+    kind = _lib.ZF_PROBLEM_SPARSE_LS_L1
+
+    def __init__(self, A, b, lam, scale=1.0, bounds=None, l2=0.0, *, group=None, sample_weight=None):
+        self._refuse_group(group)
+        _check_counts(b)
         self._set(A, b, lam, scale, bounds, l2, sample_weight)
 
 
