@@ -730,6 +730,36 @@ int zf_gap_eval_poisson(const double* A_dev, const double* b_dev, const double* 
 int zf_spmat_gap_eval_poisson(const zf_spmat* h, const double* b_dev, const double* w_dev, double scale, double lam, double l2,
                               const double* x_host, double* out, int64_t count /* >= 8; 10 for all */);
 
+/* ---- per-column penalty factors on the four margins kinds 2, 4, 5, 6 --------------------------------------------------------
+ * g(x) = lam sum_j p_j |x_j| (+ box), p_j >= 0: p_j = 0 leaves column j unpenalised (an intercept: a column of ones with p = 0).
+ * Additive to ABI 6: no struct field, no version change.  p_dev: n doubles in device memory, 16-byte aligned, borrowed as b is
+ * (it must outlive the solver); its values are the caller's responsibility (finite, >= 0; > 0 for the certificate).
+ * prox_{w g}(v)_j = clip(soft_threshold(v_j, (lam w) p_j), lo, hi): t = lam w once per trial, tau_j = t * p_j per element, the
+ * fourth running sum takes fma(p_j, |x+_j|, sum) and keeps its scale lam (zf_trial_pf_kernel; 8 n bytes more per trial).  p = 1
+ * gives the iterates and packs of a solver that was never asked, bit for bit; p_j = 0 gives x+_j = v_j exactly.
+ * zf_solver_set_penalty_factors: after zf_solver_create(_sparse), before zf_solver_enqueue_init / zf_solver_restore
+ * (ZF_ERR_STATE afterwards).  ZF_ERR_ARG: a null pointer, a misaligned one, another problem kind, world > 1, and together with
+ * l2 > 0 in either call order (the ridge term would need the factors too; not built).  Every trial then runs the general vector
+ * path (a matrix small enough for the two fused small-matrix launches too, and zf_solver_ls_plan says so).  Composes with
+ * zf_solver_set_huber / _poisson / _row_weights in any order, and with ZF_ACCEPT_REMAINDER, which touches f only.  A resumed
+ * solve sets the factors again before zf_solver_restore (the snapshot carries nothing new). */
+int zf_solver_set_penalty_factors(zf_solver* s, const double* p_dev);
+/* The certificate with p > 0: the dual constraint is |a_j^T theta| <= lam p_j.  With g'_j = g_j / p_j and x'_j = x_j p_j every
+ * quantity is that of the unfactored evaluation of this loss at (g', x'): one n-pass writes g' and x' (an IEEE division and a
+ * multiplication per element) between g = grad f(x) and the tails, which run unchanged.  out: the eight slots of zf_gap_eval with
+ * [4] = max_j |g_j| / p_j and [6] = lam sum p_j |x_j| = g(x).  loss: ZF_LOSS_SQUARE / _LOGISTIC / _HUBER (delta) / _POISSON;
+ * w_dev: the row weights or NULL.  A p_j = 0 divides by zero: the dual candidate cannot be made feasible by scaling (it needs
+ * a_j^T theta = 0 exactly), and the callers above this level refuse.  zf_solver_duality_gap of a solver with
+ * zf_solver_set_penalty_factors writes the same values, bit for bit.  ZF_ERR_ARG as zf_gap_eval_weighted. */
+int zf_gap_eval_pf(const double* A_dev, const double* b_dev, const double* w_dev, const double* p_dev, int64_t m_rows, int64_t n,
+                   double scale, double lam, int32_t loss, double delta, const double* x_host, double* out, int64_t count /* >= 8 */);
+int zf_spmat_gap_eval_pf(const zf_spmat* h, const double* b_dev, const double* w_dev, const double* p_dev, double scale, double lam,
+                         int32_t loss, double delta, const double* x_host, double* out, int64_t count /* >= 8 */);
+/* out = clip(sign(x) * max(|x| - t * p, 0), lo, hi) at host vectors, NumPy's expression operation by operation */
+int zf_host_prox_pf_box(double* out_host, const double* x_host, const double* p_host, double t, double lo, double hi, int64_t n);
+/* out = lam * sum_i p_i |x_i|, each term one fused multiply-add into the running sum (as the step kernel forms it) */
+int zf_host_pf_g(const double* x_host, const double* p_host, int64_t n, double lam, double* out);
+
 /* ---- multi-objective trial (m >= 2), device side ---------------------------
  * The dual of the scalarised subproblem is minimised on the host by SciPy exactly
  * as the reference does (proximal_gradient.py:179-205); every O(n) expression runs

@@ -414,6 +414,23 @@ static inline void zf_launch_gap_rows(hipStream_t st, bool logistic, const doubl
     hipLaunchKernelGGL(zf_gap_sum_finish_kernel, dim3(1), dim3(ZF_BLOCK), 0, st, ws.part, chunks, (int)ZF_GS_RR, (int)ZF_GS_BR, scale, ws.scal);
 }
 
+// Penalty factors p > 0 (g(x) = lam sum p_j |x_j|, dual constraint |a_j^T theta| <= lam p_j): with g'_j = g_j / p_j and
+// x'_j = x_j p_j every quantity of the certificate is that of the unfactored problem at (g', x') - alpha = min(1, lam / |g'|_inf),
+// columns = sum (lam |x'_j| + alpha g'_j x'_j), lam |x'|_1 = g(x).  One n-pass between step 2 and the tails: an IEEE division and a
+// multiplication per element; g is scaled in place, xp may be x itself (32 n bytes).  The tails then run unchanged.
+__global__ __launch_bounds__(ZF_BLOCK) void zf_gap_pf_scale_kernel(double* g, const double* x, const double* __restrict__ p, double* xp,
+                                                                   int64_t n) {
+    const int64_t stride = (int64_t)gridDim.x * ZF_BLOCK;
+    for (int64_t i = (int64_t)blockIdx.x * ZF_BLOCK + threadIdx.x; i < n; i += stride) {
+        const double pj = p[i];
+        g[i] = g[i] / pj;
+        xp[i] = x[i] * pj;
+    }
+}
+static inline void zf_launch_gap_pf_scale(hipStream_t st, double* g, const double* x, const double* p, double* xp, int64_t n) {
+    hipLaunchKernelGGL(zf_gap_pf_scale_kernel, dim3(zf_grid_for(n)), dim3(ZF_BLOCK), 0, st, g, x, p, xp, n);
+}
+
 // steps 3 .. 6, with g = grad f(x) in ws.g; the eight results are left in ws.scal + ZF_GS_OUT
 static inline void zf_launch_gap_tail(hipStream_t st, bool logistic, const double* z, const double* b, const double* x, int64_t m,
                                       int64_t n, double scale, double lam, const zf_gap_ws& ws) {

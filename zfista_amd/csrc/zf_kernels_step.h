@@ -116,6 +116,27 @@ __device__ __forceinline__ double zf_elem_vec_enet(double xk, double xo, double 
     return xn;
 }
 
+// The penalty-factor step: g(x) = lam sum_j p_j |x_j| (+ box), p_j >= 0 per column (zf_solver_set_penalty_factors).  t = lam lr
+// is formed once per trial as in zf_elem_vec; the element's threshold is tau_j = t * p_j and the fourth sum takes
+// fma(p_j, |x+|, sum), pack scale lam as before.  p = 1: t * 1 == t and fma(1, a, s) == a + s - the bits of zf_elem_vec.
+// p = 0: zf_soft_threshold_nn(v, 0) = copysign(|v| - min(|v|, 0), v) = v - the column is not thresholded (NaN and inf stay).
+// One multiplication more than zf_elem_vec per element (the fma replaces the addition).
+template <bool NESTEROV, bool BOX>
+__device__ __forceinline__ double zf_elem_vec_pf(double xk, double xo, double grad, double pj, double beta, double lr, double t,
+                                                 double lo, double hi, zf_elem_acc& a) {
+    double y = xk;
+    if (NESTEROV) y = xk + beta * (xk - xo);
+    const double v = y - lr * grad;
+    double xn = zf_soft_threshold_nn(v, t * pj);
+    if (BOX) xn = zf_clip(xn, lo, hi);
+    const double dx = xn - y;
+    a.dot = __builtin_fma(grad, dx, a.dot);
+    a.ss = __builtin_fma(dx, dx, a.ss);
+    a.l1 = __builtin_fma(pj, fabs(xn), a.l1);
+    a.mx = zf_max_abs(a.mx, dx);
+    return xn;
+}
+
 // the same step with the variant chosen at run time (the operator problem's adjoint kernel runs it in its epilogue: one
 // kernel per blur size there, not per variant of the step)
 __device__ __forceinline__ double zf_elem_vec_rt(bool nesterov, bool box, double xk, double xo, double grad, double beta, double lr,
@@ -295,7 +316,7 @@ struct zf_step_args {
     const double* beta_ring;  // momentum ring: trial j > 0 of a chain uses beta_ring[(nit + j) % ZF_RING]
     double* xb[ZF_MAX_RING];  // x ring of ctl->ring_size buffers
     const double* p0;         // diag: d        vec: grad
-    const double* p1;         // diag: c        vec: unused
+    const double* p1;         // diag: c        vec: unused (zf_trial_pf_kernel: the penalty factors p, n doubles)
     double lam, lo, hi;
     int64_t n;
     int tiles_per_wg;         // interleaved tiles per workgroup (1 .. ZF_MAX_TILES_PER_WG)
@@ -903,13 +924,16 @@ __device__ __forceinline__ zf_pass_head zf_head_of(const zf_control* c) {
 // still running on another XCD has just stored (full chains through the DMA pipeline only; +0.7-1 % per pass, measured)
 // ENET: the elastic-net step (zf_elem_vec_enet; l2 is a kernel argument of its own - zf_step_args is as it was): single
 // trials on a gradient vector only.  Defaulted: every other instantiation is the one it was.
+// PF: the penalty-factor step (zf_elem_vec_pf): the factors are the stream A.p1, which the vector path does not use - one more
+// nontemporal 16-byte load per unit, issued with the others of its batch.  Single trials on a gradient vector; defaulted.
 template <bool GRAD_INLINE, bool NESTEROV, bool BOX, bool NT, int S, int MODE, bool HIST, int SP = S, bool COH = false, bool RES = false,
-          bool ENET = false>
+          bool ENET = false, bool PF = false>
 __device__ __forceinline__ double zf_trial_body(const zf_step_args& A, double* lds, const zf_pass_head& HD, const int lag,
                                                 const int nf, zf_d2* stage = nullptr, const double l2 = 0.0) {
     constexpr bool FULL = (MODE == 0);          // nothing replayed, S fresh trials
     static_assert(!RES || GRAD_INLINE, "resolved differences f(x+) - f(y): the separable problem");
     static_assert(!ENET || (!GRAD_INLINE && S == 1 && MODE == 0 && !COH), "elastic net: single trials on a gradient vector");
+    static_assert(!PF || (!GRAD_INLINE && S == 1 && MODE == 0 && !COH && !ENET && NT), "penalty factors: single trials on a gradient vector");
     static_assert(!COH || (FULL && !HIST && GRAD_INLINE && SP >= 16 && ZF_S16_GLDS != 0),
                   "coherent iterate traffic: branch-free chains of a 16-chain solver through the DMA pipeline");
     // (a run-ahead mid chain of <= ZF_MID_REG_MAX trials takes the DMA pipeline too: the coherent 16-byte load exists as DMA only)
@@ -988,6 +1012,9 @@ __device__ __forceinline__ double zf_trial_body(const zf_step_args& A, double* l
                 } else if constexpr (ENET) {
                     r.x = zf_elem_vec_enet<NESTEROV, BOX>(a.x, o.x, q.x, beta[j], lr, tau, shrink, A.lam, hl2, A.lo, A.hi, acc[j]);
                     r.y = zf_elem_vec_enet<NESTEROV, BOX>(a.y, o.y, q.y, beta[j], lr, tau, shrink, A.lam, hl2, A.lo, A.hi, acc[j]);
+                } else if constexpr (PF) {   // (cc: the factors of the unit)
+                    r.x = zf_elem_vec_pf<NESTEROV, BOX>(a.x, o.x, q.x, cc.x, beta[j], lr, tau, A.lo, A.hi, acc[j]);
+                    r.y = zf_elem_vec_pf<NESTEROV, BOX>(a.y, o.y, q.y, cc.y, beta[j], lr, tau, A.lo, A.hi, acc[j]);
                 } else {
                     r.x = zf_elem_vec<NESTEROV, BOX>(a.x, o.x, q.x, beta[j], lr, tau, A.lo, A.hi, acc[j]);
                     r.y = zf_elem_vec<NESTEROV, BOX>(a.y, o.y, q.y, beta[j], lr, tau, A.lo, A.hi, acc[j]);
@@ -1035,7 +1062,7 @@ __device__ __forceinline__ double zf_trial_body(const zf_step_args& A, double* l
             if (NESTEROV) o[u] = zf_ld2<NT && (ZF_X_NT != 0) && (S > 1)>(xo2 + i);
             q[u] = zf_ld2<NT>(p02 + i);
             cc[u] = q[u];
-            if (GRAD_INLINE) cc[u] = zf_ld2<NT>(p12 + i);
+            if (GRAD_INLINE || PF) cc[u] = zf_ld2<NT>(p12 + i);
         }
         // keep all loads of the batch in flight: without this fence the scheduler sinks the
         // last ones below the first arithmetic to save registers
@@ -1253,7 +1280,7 @@ __device__ __forceinline__ double zf_trial_body(const zf_step_args& A, double* l
                 a = xk[e];
                 o = NESTEROV ? xo[e] : a;
             }
-            const double q = p0[e], cc = GRAD_INLINE ? p1[e] : q;
+            const double q = p0[e], cc = (GRAD_INLINE || PF) ? p1[e] : q;
             if constexpr (!FULL && GRAD_INLINE) {
                 for (int i = 0; i < lag; ++i) {
                     double b_i, lr_i, tau_i;
@@ -1271,6 +1298,8 @@ __device__ __forceinline__ double zf_trial_body(const zf_step_args& A, double* l
                         r = zf_elem_diag<NESTEROV, BOX, RES>(a, o, q, cc, beta[j], lr, tau, A.lo, A.hi, acc[j]);
                     else if constexpr (ENET)
                         r = zf_elem_vec_enet<NESTEROV, BOX>(a, o, q, beta[j], lr, tau, shrink, A.lam, hl2, A.lo, A.hi, acc[j]);
+                    else if constexpr (PF)
+                        r = zf_elem_vec_pf<NESTEROV, BOX>(a, o, q, cc, beta[j], lr, tau, A.lo, A.hi, acc[j]);
                     else r = zf_elem_vec<NESTEROV, BOX>(a, o, q, beta[j], lr, tau, A.lo, A.hi, acc[j]);
                     o = a;
                     a = r;
@@ -1494,6 +1523,19 @@ __global__ __launch_bounds__(ZF_BLOCK) void zf_trial_enet_kernel(zf_step_args A,
     const zf_pass_head HD = zf_head_of(A.ctl);
     if (A.pass_log && blockIdx.x == 0 && threadIdx.x == 0) A.pass_log[A.pass_slot] = A.pass_tag | zf_log_shape(0, 1, 0);
     const double v = zf_trial_body<false, NESTEROV, BOX, true, 1, 0, HIST, 1, false, false, true>(A, lds, HD, 0, 1, nullptr, l2);
+    if (threadIdx.x < ZF_NPART) A.blk_part[(int64_t)threadIdx.x * gridDim.x + blockIdx.x] = v;   // (fin_mode 0: the vector path)
+}
+
+// The penalty-factor trial (zf_solver_set_penalty_factors): the single trial of zf_trial_kernel<false, ..., 1> with the step of
+// zf_elem_vec_pf; A.p1 holds the n factors.  The fourth partial is sum p_j |x+_j|: its pack scale stays lam.  Nontemporal
+// policy; HIST as there.
+template <bool NESTEROV, bool BOX, bool HIST>
+__global__ __launch_bounds__(ZF_BLOCK) void zf_trial_pf_kernel(zf_step_args A) {
+    __shared__ double lds[ZF_WAVES * ZF_NPART];
+    if (A.ctl->status != ZF_RUNNING) return;
+    const zf_pass_head HD = zf_head_of(A.ctl);
+    if (A.pass_log && blockIdx.x == 0 && threadIdx.x == 0) A.pass_log[A.pass_slot] = A.pass_tag | zf_log_shape(0, 1, 0);
+    const double v = zf_trial_body<false, NESTEROV, BOX, true, 1, 0, HIST, 1, false, false, false, true>(A, lds, HD, 0, 1);
     if (threadIdx.x < ZF_NPART) A.blk_part[(int64_t)threadIdx.x * gridDim.x + blockIdx.x] = v;   // (fin_mode 0: the vector path)
 }
 

@@ -146,6 +146,26 @@ __global__ __launch_bounds__(ZF_BLOCK) void zf_eval_enet_kernel(const double* __
     if (threadIdx.x < 3) partials[(int64_t)threadIdx.x * gridDim.x + blockIdx.x] = out;
 }
 
+// penalty factors: g(x0) / lam = sum p_j |x_j| in the same row, term by term as zf_elem_vec_pf forms it (p = 1: the sums of
+// zf_eval_kernel, bit for bit); zf_init_finalize_kernel takes it with lam as before
+template <bool BOX>
+__global__ __launch_bounds__(ZF_BLOCK) void zf_eval_pf_kernel(const double* __restrict__ x, const double* __restrict__ p, double lo, double hi,
+                                                              int64_t n, double* partials) {
+    __shared__ double lds[ZF_WAVES * 3];
+    double g = 0.0, viol = 0.0;
+    const int64_t stride = (int64_t)gridDim.x * ZF_BLOCK;
+    for (int64_t i = (int64_t)blockIdx.x * ZF_BLOCK + threadIdx.x; i < n; i += stride) {
+        const double xv = x[i];
+        g = __builtin_fma(p[i], fabs(xv), g);
+        if (BOX) viol += (xv < lo || xv > hi) ? 1.0 : 0.0;
+    }
+    const double sums[3] = {0.0, g, viol};
+    const double maxs[1] = {0.0};
+    double out = 0.0;
+    zf_block_reduce<3, 0, ZF_WAVES>(sums, maxs, lds, out);
+    if (threadIdx.x < 3) partials[(int64_t)threadIdx.x * gridDim.x + blockIdx.x] = out;
+}
+
 struct zf_init_args {
     const double* partials;
     int nblocks;
@@ -238,6 +258,8 @@ struct zf_solver {
     bool loss_part = false;       // the dense least-squares kind holds the 2 x ZF_SPMV_RESID_MAX_CHUNKS chunk sums of the loss kernels (zf_loss_part)
     const double* roww = nullptr; // per-row sample weights (zf_solver_set_row_weights; borrowed as b is): the loss sites take zf_kernels_wloss.h; NULL: what ran before
     double l2 = 0.0;              // elastic net (zf_solver_set_l2): g = lam |x|_1 + (l2 / 2) |x|^2; 0: every path is the l1 one
+    const double* pf = nullptr;   // per-column penalty factors (zf_solver_set_penalty_factors; borrowed as b is): g = lam sum p_j |x_j|; NULL: what ran before
+    double* gap_xp = nullptr;     // ... the certificate's scaled iterate p o x_k (n doubles, allocated by the first zf_solver_duality_gap)
     const zf_spmat* spmat = nullptr;   // sparse least squares: A and A^T with their plans (the caller's handle: zf_solver_create_sparse; never written through)
     double* sp_part_A = nullptr, *sp_part_At = nullptr;   // ... this solver's segment sums of the split rows of A / of A^T
     zf_op_plan op_plan = {};      // operator problem: which instantiation of the correlation kernels runs it (zf_op_make_plan)
@@ -381,7 +403,7 @@ static int zf_solver_free_all(zf_solver* s) {
     void* ptrs[] = {s->sp_part_A, s->sp_part_At, s->op_buf, s->row_part, s->ls_cnt, s->blk_part, s->slice_part, s->fin_cnt, s->grp_part, s->xbuf, s->partials, s->ctl_trace, s->beta_ring,
                     s->ra_word, s->ra_flags, s->blk_part2, s->grp_part2, s->fin_cnt2, s->pack2,
                     s->own_packs ? s->pack_local : nullptr, s->own_packs ? s->pack_all : nullptr,
-                    s->grad, s->sbuf, s->resid, s->slab, s->ls_scal, s->gap.rvec, s->gap.g, s->gap.part, s->gap.scal,
+                    s->grad, s->sbuf, s->resid, s->slab, s->ls_scal, s->gap.rvec, s->gap.g, s->gap.part, s->gap.scal, s->gap_xp,
                     s->own_svec ? s->s_part : nullptr, s->own_svec ? s->s_all : nullptr};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
@@ -796,7 +818,11 @@ static void zf_launch_trial_kernels(zf_solver* s, const zf_step_args& a, bool gr
     hipStream_t st = s->stream;
     if (!grad_inline) {   // least squares: one trial per pass
         if (s->l2 > 0.0) zf_launch_enet(v, s->hist != nullptr, grid, st, a, s->l2);
-        else if (s->hist) zf_launch_hist(v, false, 1, 0, grid, st, a);
+        else if (s->pf) {   // (the factors travel in the stream the vector path leaves unused)
+            zf_step_args f = a;
+            f.p1 = s->pf;
+            zf_launch_pf(v, s->hist != nullptr, grid, st, f);
+        } else if (s->hist) zf_launch_hist(v, false, 1, 0, grid, st, a);
         else zf_launch_vec(v, grid, st, a);
         return;
     }
@@ -1612,6 +1638,11 @@ static int zf_init_ls_tail(zf_solver* s) {
         else
             hipLaunchKernelGGL(zf_eval_enet_kernel<false>, dim3(g), dim3(ZF_BLOCK), 0, s->stream, s->xb[0], d.lam, 0.5 * s->l2, d.box_lo,
                                d.box_hi, n, s->partials);
+    } else if (s->pf) {
+        if (s->box)
+            hipLaunchKernelGGL(zf_eval_pf_kernel<true>, dim3(g), dim3(ZF_BLOCK), 0, s->stream, s->xb[0], s->pf, d.box_lo, d.box_hi, n, s->partials);
+        else
+            hipLaunchKernelGGL(zf_eval_pf_kernel<false>, dim3(g), dim3(ZF_BLOCK), 0, s->stream, s->xb[0], s->pf, d.box_lo, d.box_hi, n, s->partials);
     } else if (s->box)
         hipLaunchKernelGGL((zf_eval_kernel<false, true>), dim3(g), dim3(ZF_BLOCK), 0, s->stream, s->xb[0], nullptr,
                            nullptr, d.box_lo, d.box_hi, n, s->partials);
@@ -1884,8 +1915,26 @@ extern "C" int zf_solver_set_l2(zf_solver* s, double l2) {
                "ZF_PROBLEM_SPARSE_LOGISTIC_L1");
     ZF_REQUIRE(d.world == 1, "zf_solver_set_l2: not for a sharded solve (world > 1)");
     ZF_REQUIRE(l2 >= 0.0 && l2 <= DBL_MAX, "zf_solver_set_l2: l2 must be finite and >= 0");
+    ZF_REQUIRE(!(l2 > 0.0 && s->pf), "zf_solver_set_l2: not with penalty factors (zf_solver_set_penalty_factors: the ridge term would need them too)");
     s->l2 = l2;
     if (l2 > 0.0) s->ls_small = false;   // (the fused small-matrix kernels hold the l1 step: the general path, as the logistic kind)
+    return ZF_OK;
+}
+
+// Per-column penalty factors (include/zfista_hip.h): between create and init, on the four margins kinds.
+extern "C" int zf_solver_set_penalty_factors(zf_solver* s, const double* p_dev) {
+    ZF_REQUIRE(s && p_dev, "zf_solver_set_penalty_factors: null argument");
+    if (s->init_enqueued || s->initialised)
+        return zf_fail(ZF_ERR_STATE, "zf_solver_set_penalty_factors: call after zf_solver_create and before zf_solver_enqueue_init / zf_solver_restore%s%s");
+    const zf_problem_desc& d = s->desc;
+    ZF_REQUIRE(zf_is_dense_mat(d.kind) || zf_is_sparse_mat(d.kind),
+               "zf_solver_set_penalty_factors: only for ZF_PROBLEM_LEAST_SQUARES_L1, ZF_PROBLEM_SPARSE_LS_L1, ZF_PROBLEM_LOGISTIC_L1 and "
+               "ZF_PROBLEM_SPARSE_LOGISTIC_L1");
+    ZF_REQUIRE(d.world == 1, "zf_solver_set_penalty_factors: not for a sharded solve (world > 1)");
+    ZF_REQUIRE(!(s->l2 > 0.0), "zf_solver_set_penalty_factors: not with l2 > 0 (zf_solver_set_l2: the ridge term would need the factors too)");
+    ZF_REQUIRE(zf_aligned16(p_dev), "zf_solver_set_penalty_factors: the factors must be 16-byte aligned");
+    s->pf = p_dev;
+    s->ls_small = false;   // (the fused small-matrix kernels hold the unfactored l1 step: the general path, as the logistic kind)
     return ZF_OK;
 }
 
@@ -2801,8 +2850,9 @@ static void zf_gap_ws_free(zf_gap_ws* ws) {
 // (dense: MFMA when n % 32 == 0 and ZF_GEMV_MFMA is not 0), the n-passes and the composition; l2 > 0: the elastic-net evaluation.
 // scr != NULL (the *_screen_eval entries): the screen of zf_kernels_screen.h over the call's g behind the same sequence - its four
 // scalars follow the eight outputs; scr->cnt and scr->scal are allocated here
+// p_dev != NULL (the *_pf entries): penalty factors - g and the call's copy of x are scaled in place between step 2 and the tails
 static int zf_gap_eval_impl(const zf_matview& V, const double* b_dev, double scale, double lam, double l2, const zf_loss& L,
-                            const double* x_host, double* out, int64_t out_count, const zf_screen_req* scr) {
+                            const double* x_host, double* out, int64_t out_count, const zf_screen_req* scr, const double* p_dev = nullptr) {
     const int64_t m = V.m, n = V.n;
     zf_gap_ws ws = {nullptr, nullptr, nullptr, nullptr};
     zf_sweep_ws W = {nullptr, 1, m, nullptr, nullptr};
@@ -2822,6 +2872,7 @@ static int zf_gap_eval_impl(const zf_matview& V, const double* b_dev, double sca
         zf_launch_view_apply(V, nullptr, x, z, W);
         zf_launch_loss_gap_rows(nullptr, L, z, b_dev, m, scale, ws);
         zf_launch_view_adjoint(V, nullptr, ws.rvec, ws.g, zf_gfac(L, scale), mfma, W);
+        if (p_dev) zf_launch_gap_pf_scale(nullptr, ws.g, x, p_dev, x, n);
         const zf_gap_out res = zf_launch_loss_gap_tail(nullptr, L, z, b_dev, x, m, n, scale, lam, l2, ws, out_count);
         if (scr) {
             zf_screen_req rq = *scr;
@@ -2931,6 +2982,23 @@ extern "C" int zf_spmat_gap_eval_weighted(const zf_spmat* h, const double* b_dev
                         delta, x_host, out, count);
 }
 
+// with penalty factors p > 0 (include/zfista_hip.h): the l1 evaluation of this loss on g / p and p o x; w_dev: the row weights or NULL
+static int zf_gap_pf_entry(const char* who, zf_matview V, const double* b_dev, const double* w_dev, const double* p_dev, double scale,
+                           double lam, int32_t loss, double delta, const double* x_host, double* out, int64_t count) {
+    zf_loss L;
+    const int rc = zf_gap_args(who, &V, b_dev && p_dev && x_host && out, scale, lam, false, 0.0, count, loss, delta, w_dev, &L);
+    if (rc) return rc;
+    return zf_gap_eval_impl(V, b_dev, scale, lam, 0.0, L, x_host, out, count, nullptr, p_dev);
+}
+extern "C" int zf_gap_eval_pf(const double* A_dev, const double* b_dev, const double* w_dev, const double* p_dev, int64_t m_rows, int64_t n,
+                              double scale, double lam, int32_t loss, double delta, const double* x_host, double* out, int64_t count) {
+    return zf_gap_pf_entry("zf_gap_eval_pf", zf_dense_view(A_dev, m_rows, n), b_dev, w_dev, p_dev, scale, lam, loss, delta, x_host, out, count);
+}
+extern "C" int zf_spmat_gap_eval_pf(const zf_spmat* h, const double* b_dev, const double* w_dev, const double* p_dev, double scale, double lam,
+                                    int32_t loss, double delta, const double* x_host, double* out, int64_t count) {
+    return zf_gap_pf_entry("zf_spmat_gap_eval_pf", zf_csr_view(h), b_dev, w_dev, p_dev, scale, lam, loss, delta, x_host, out, count);
+}
+
 // the gap evaluation followed by the gap-safe screen of its g (zf_kernels_screen.h), l2 = 0 only: out[0 .. 8) as zf_gap_eval - the
 // same kernels in the same order, the same bits - then [r, E, r_eff, kept count].  Huber's loss: the rule, the guard and the four
 // screen launches are the least-squares kinds' - L = 2 scale, |c|_2 from sum c^2 where they read sum r^2 (the clip is exact and
@@ -3011,6 +3079,7 @@ extern "C" int zf_solver_duality_gap(zf_solver* s, double* out, int64_t count) {
             return rc;
         }
     }
+    if (s->pf && !s->gap_xp) ZF_HIP(hipMalloc(&s->gap_xp, sizeof(double) * n));
     zf_control c;
     ZF_HIP(hipMemcpyAsync(&c, s->ctl, sizeof(c), hipMemcpyDeviceToHost, s->stream));
     ZF_HIP(hipStreamSynchronize(s->stream));
@@ -3022,6 +3091,10 @@ extern "C" int zf_solver_duality_gap(zf_solver* s, double* out, int64_t count) {
     const zf_sweep_ws W = {s->slab, s->slices, s->rows_per_slice, s->sp_part_A, s->sp_part_At};
     zf_launch_loss_gap_rows(s->stream, loss, z, d.b, m, d.scale, ws);
     zf_launch_view_adjoint(V, s->stream, ws.rvec, ws.g, zf_gfac(loss, d.scale), s->gemv_mfma, W);
+    if (s->pf) {   // (penalty factors: the tails run on g / p and p o x_k)
+        zf_launch_gap_pf_scale(s->stream, ws.g, x, s->pf, s->gap_xp, n);
+        x = s->gap_xp;
+    }
     const zf_gap_out res = zf_launch_loss_gap_tail(s->stream, loss, z, d.b, x, m, n, d.scale, d.lam, s->l2, ws, count);
     ZF_HIP(hipGetLastError());
     ZF_HIP(hipMemcpyAsync(out, ws.scal + res.slot, sizeof(double) * res.count, hipMemcpyDeviceToHost, s->stream));

@@ -60,6 +60,8 @@ void zf_launch_hist(const zf_trial_sel& v, bool grad_inline, int S, int part, in
 void zf_launch_vec(const zf_trial_sel& v, int grid, hipStream_t st, const zf_step_args& a);
 // the same with the elastic-net step (zf_solver_set_l2, l2 > 0): zf_trial_enet_kernel, with (hist) or without the history ring
 void zf_launch_enet(const zf_trial_sel& v, bool hist, int grid, hipStream_t st, const zf_step_args& a, double l2);
+// the same with the penalty-factor step (zf_solver_set_penalty_factors): zf_trial_pf_kernel; a.p1 = the n factors
+void zf_launch_pf(const zf_trial_sel& v, bool hist, int grid, hipStream_t st, const zf_step_args& a);
 
 // CALL(NEST, BOX, NT) for the variant `v`, NT = true: the solver runs the nontemporal store policy only
 #define ZF_SEL_NBT(v, CALL)                                   \

@@ -526,6 +526,67 @@ extern "C" int zf_host_enet_g(const double* x_host, int64_t n, double lam, doubl
     return ZF_OK;
 }
 
+// ---- penalty factors at a host point: prox and g of lam sum p_j |x_j| (+ box) ---------------------------------------------------
+namespace {
+__global__ __launch_bounds__(ZF_BLOCK) void k_prox_pf_box(double* __restrict__ out, const double* __restrict__ x, const double* __restrict__ p,
+                                                          double t, double lo, double hi, int64_t n) {
+    const int64_t stride = (int64_t)gridDim.x * ZF_BLOCK;
+    // NumPy's expression, operation by operation - sign(u) * maximum(|u| - t * p, 0), clipped (k_prox_enet_box: why)
+    for (int64_t i = (int64_t)blockIdx.x * ZF_BLOCK + threadIdx.x; i < n; i += stride) {
+        const double u = x[i];
+        const double s = (u > 0.0) ? 1.0 : (u < 0.0) ? -1.0 : (u == 0.0) ? 0.0 : u;
+        double a = fabs(u) - t * p[i];
+        a = (a < 0.0) ? 0.0 : a;
+        out[i] = zf_clip(s * a, lo, hi);
+    }
+}
+__global__ __launch_bounds__(ZF_BLOCK) void k_pf_g(const double* __restrict__ x, const double* __restrict__ p, int64_t n, double* partials) {
+    __shared__ double lds[ZF_WAVES];
+    double g = 0.0;
+    const int64_t stride = (int64_t)gridDim.x * ZF_BLOCK;
+    for (int64_t i = (int64_t)blockIdx.x * ZF_BLOCK + threadIdx.x; i < n; i += stride) g = __builtin_fma(p[i], fabs(x[i]), g);
+    const double sums[1] = {g};
+    const double maxs[1] = {0.0};
+    double out = 0.0;
+    zf_block_reduce<1, 0, ZF_WAVES>(sums, maxs, lds, out);
+    if (threadIdx.x == 0) partials[blockIdx.x] = out;
+}
+}  // namespace
+
+extern "C" int zf_host_prox_pf_box(double* out_host, const double* x_host, const double* p_host, double t, double lo, double hi, int64_t n) {
+    ZF_REQUIRE(out_host && x_host && p_host && n >= 0, "zf_host_prox_pf_box: bad argument");
+    if (n == 0) return ZF_OK;
+    int rc = zf_ws_reserve(n);
+    if (rc) return rc;
+    const size_t bytes = sizeof(double) * n;
+    ZF_HIP(hipMemcpyAsync(g_ws.buf[0], x_host, bytes, hipMemcpyHostToDevice, nullptr));
+    ZF_HIP(hipMemcpyAsync(g_ws.buf[1], p_host, bytes, hipMemcpyHostToDevice, nullptr));
+    hipLaunchKernelGGL(k_prox_pf_box, dim3(zf_grid_for(n)), dim3(ZF_BLOCK), 0, nullptr, g_ws.buf[2], g_ws.buf[0], g_ws.buf[1], t, lo, hi, n);
+    ZF_HIP(hipGetLastError());
+    ZF_HIP(hipMemcpyAsync(out_host, g_ws.buf[2], bytes, hipMemcpyDeviceToHost, nullptr));
+    ZF_HIP(hipStreamSynchronize(nullptr));
+    return ZF_OK;
+}
+
+extern "C" int zf_host_pf_g(const double* x_host, const double* p_host, int64_t n, double lam, double* out) {
+    ZF_REQUIRE(x_host && p_host && out && n >= 0, "zf_host_pf_g: bad argument");
+    *out = 0.0;
+    if (n == 0) return ZF_OK;
+    int rc = zf_ws_reserve(n);
+    if (rc) return rc;
+    ZF_HIP(hipMemcpyAsync(g_ws.buf[0], x_host, sizeof(double) * n, hipMemcpyHostToDevice, nullptr));
+    ZF_HIP(hipMemcpyAsync(g_ws.buf[1], p_host, sizeof(double) * n, hipMemcpyHostToDevice, nullptr));
+    const int g = zf_grid_for(n);
+    hipLaunchKernelGGL(k_pf_g, dim3(g), dim3(ZF_BLOCK), 0, nullptr, g_ws.buf[0], g_ws.buf[1], n, g_ws.partials);
+    hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(256), 0, nullptr, g_ws.partials, g, 1, -1, g_ws.out);
+    ZF_HIP(hipGetLastError());
+    double sum = 0.0;
+    ZF_HIP(hipMemcpyAsync(&sum, g_ws.out, sizeof(double), hipMemcpyDeviceToHost, nullptr));
+    ZF_HIP(hipStreamSynchronize(nullptr));
+    *out = lam * sum;
+    return ZF_OK;
+}
+
 // Release the staging workspaces of the host-pointer entry points (all threads, all devices).  Call
 // when no zf_host_* / zf_dev_* call is in flight; later calls allocate again.
 extern "C" int zf_shutdown(void) {

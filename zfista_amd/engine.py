@@ -83,8 +83,9 @@ class DeviceSolver:
         huber = float(desc_fields.get("huber_delta", 0.0) or 0.0)   # Huber's loss on a least-squares kind: likewise (zf_solver_set_huber)
         poisson = bool(desc_fields.get("poisson", False))   # the Poisson loss on a least-squares kind: likewise (zf_solver_set_poisson)
         roww = desc_fields.get("row_weights")   # per-row sample weights (a device pointer): likewise (zf_solver_set_row_weights)
+        pf = desc_fields.get("penalty_factors")   # per-column penalty factors (a device pointer): likewise (zf_solver_set_penalty_factors)
         for k, v in desc_fields.items():
-            if k not in ("spmat", "l2", "huber_delta", "poisson", "row_weights"):
+            if k not in ("spmat", "l2", "huber_delta", "poisson", "row_weights", "penalty_factors"):
                 setattr(d, k, v)
         o = _lib.Options()
         for k, v in options.items():
@@ -107,6 +108,8 @@ class DeviceSolver:
             _lib.check(self.lib.zf_solver_set_poisson(h), "zf_solver_set_poisson")
         if roww:
             _lib.check(self.lib.zf_solver_set_row_weights(h, C.c_void_p(roww)), "zf_solver_set_row_weights")
+        if pf:
+            _lib.check(self.lib.zf_solver_set_penalty_factors(h, C.c_void_p(pf)), "zf_solver_set_penalty_factors")
         sub = C.c_int32(1)
         _lib.check(self.lib.zf_solver_sub_iters(h, C.byref(sub)), "zf_solver_sub_iters")
         self.sub_iters = int(sub.value)   # iterations one pass may accept (temporal blocking)

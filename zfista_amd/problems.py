@@ -214,6 +214,45 @@ def _check_weights(w, m, group=None):
     return host
 
 
+def _check_penalty_factor(p, n, group=None, l2=0.0):
+    """Per-column penalty factors as a host float64 vector: n of them, finite and >= 0.  ValueError otherwise - on the host,
+    before anything touches the device (a torch tensor is copied to the host for the check)."""
+    if group is not None:
+        raise ValueError("penalty_factor is not available with group=: the penalty-factor step, its certificate and "
+                         "zf_solver_set_penalty_factors are built for one GPU (world = 1)")
+    if l2 > 0:
+        raise ValueError("penalty_factor is not available with l2 > 0: the ridge term would need the factors too (glmnet scales "
+                         "both), and that step is not built")
+    host = p.detach().cpu().numpy() if hasattr(p, "detach") else np.asarray(p)
+    if np.dtype(host.dtype).kind not in "biuf":
+        raise ValueError(f"penalty_factor must be real numbers, got dtype {host.dtype}")
+    host = np.array(host, dtype=np.float64, order="C", copy=True)   # (the problem's own copy: never the caller's array)
+    if host.ndim != 1 or host.shape[0] != n:
+        raise ValueError(f"penalty_factor must be a vector of {n} factors (one per column of A), got shape {host.shape}")
+    if not np.all(np.isfinite(host)) or np.any(host < 0):
+        raise ValueError("penalty_factor must be finite and >= 0")
+    return host
+
+
+def add_intercept(A):
+    """``(A1, p)``: ``A`` with a leading column of ones - dense, or any ``scipy.sparse`` form (returned as CSR) - and the penalty
+    factors ``[0, 1, ..., 1]`` that leave that column unpenalised: ``cls(A1, b, lam, penalty_factor=p)`` is the model with an
+    intercept, x[0].  A host helper: no kernel."""
+    if hasattr(A, "tocsr") and not isinstance(A, np.ndarray):
+        import scipy.sparse as sp
+
+        A = sp.csr_matrix(A, dtype=np.float64)
+        A1 = sp.hstack([sp.csr_matrix(np.ones((A.shape[0], 1))), A], format="csr")
+    else:
+        A = A.detach().cpu().numpy() if hasattr(A, "detach") else np.asarray(A, dtype=np.float64)
+        if A.ndim != 2:
+            raise ValueError("A must be (m, n)")
+        A1 = np.ascontiguousarray(np.hstack([np.ones((A.shape[0], 1)), A]))
+    p = np.ones(A1.shape[1])
+    p[0] = 0.0
+    return A1, p
+
+
 class _classattr:
     """A read-only attribute computed from the class: it reads the same on the class and on an instance."""
 
@@ -227,7 +266,7 @@ class _classattr:
 class _GapMixin:
     """What the eight margins classes (LeastSquaresL1, SparseLeastSquaresL1, LogisticL1, SparseLogisticL1, HuberL1, SparseHuberL1,
     PoissonL1, SparsePoissonL1) share: f / jac_f at a host vector, the duality-gap certificate, lam_max, same-matrix siblings, gap-safe screening and column
-    restriction.  Which C entry point a call reaches is decided HERE, from the loss (``_loss``), the weights (``_w``) and ``l2``;
+    restriction.  Which C entry point a call reaches is decided HERE, from the loss (``_loss``), the weights (``_w``), the penalty factors (``_pf``) and ``l2``;
     the storage class below supplies the entry names (``_ENTRY``) and the matrix arguments they start with (``_lead``)."""
 
     has_duality_gap = True
@@ -236,6 +275,10 @@ class _GapMixin:
     # (csrc/zf_kernels_wloss.h).  _w: the device vector, shared by every sibling; None: the unweighted problem, every call as before
     _w = None
     _w_host = None
+    # per-column penalty factors: g(x) = lam sum_j p_j |x_j|, p_j >= 0 (0: an unpenalised column).  _pf: the device vector, shared
+    # by every sibling; None: the plain problem, every call as before
+    _pf = None
+    _pf_host = None
     _loss = _lib.ZF_LOSS_SQUARE   # the loss of the class: everything below that depends on it reads this one attribute
     _gap_logistic = _classattr(lambda cls: int(cls._loss == _lib.ZF_LOSS_LOGISTIC))
     _eval_name = _classattr(lambda cls: cls._ENTRY["eval"][cls._loss])   # f and jac_f of the unweighted problem
@@ -266,6 +309,11 @@ class _GapMixin:
         return self._ls(x, True)[1]
 
     def _gap_call(self, lib, x, out):
+        if self._pf is not None:   # (l2 = 0: refused together)
+            name = self._ENTRY["gap_pf"]
+            _lib.check(getattr(lib, name)(*self._lead_pf(), self.scale, self.lam, self._loss, self._w_delta(), C.c_void_p(_lib.ptr(x)),
+                                          C.c_void_p(_lib.ptr(out)), out.size), name)
+            return
         if self._loss == _lib.ZF_LOSS_POISSON:   # (its entries take the weights, or NULL)
             name, args = "gap_poisson", self._lead(_dp(self._w)) + (self.scale, self.lam, self.l2)
         elif self._w is not None:
@@ -288,7 +336,7 @@ class _GapMixin:
 
     def _finish_descriptor(self, fields, keep):
         """The descriptor of a storage class with what has no field of zf_problem_desc: the engine calls zf_solver_set_l2 /
-        zf_solver_set_row_weights / zf_solver_set_huber / zf_solver_set_poisson for these."""
+        zf_solver_set_row_weights / zf_solver_set_huber / zf_solver_set_poisson / zf_solver_set_penalty_factors for these."""
         if self.l2 > 0:
             fields["l2"] = self.l2
         if self._w is not None:
@@ -298,7 +346,40 @@ class _GapMixin:
             fields["huber_delta"] = self.delta
         if self._loss == _lib.ZF_LOSS_POISSON:
             fields["poisson"] = True
+        if self._pf is not None:
+            fields["penalty_factors"] = self._pf.data_ptr()
+            keep = keep + (self._pf,)
         return fields, keep
+
+    @property
+    def penalty_factor(self):
+        """The per-column penalty factors (a host copy), or None."""
+        return None if self._pf_host is None else self._pf_host.copy()
+
+    def with_penalty_factor(self, p):
+        """A sibling problem with g(x) = lam sum_j p_j |x_j| (``p``: n_features values, finite and >= 0; 0 leaves a column
+        unpenalised) that SHARES the device matrix, b, the matrix handle and the sample weights: only p is uploaded.  ``None``:
+        the plain sibling.  Not with l2 > 0.  ``with_lam`` and ``with_sample_weight`` keep the factors, so ``l1_path`` and
+        ``l1_cv`` work through the siblings.  With a zero in ``p`` there is no duality-gap certificate: solve with
+        ``gap_tol=None``."""
+        import copy
+
+        sib = copy.copy(self)
+        sib._set_penalty_factor(p)
+        return sib
+
+    def _set_penalty_factor(self, p):
+        if p is None:
+            self._pf = self._pf_host = None
+            return
+        host = _check_penalty_factor(p, self.n_features, getattr(self, "group", None), self.l2)
+        self._pf_host = host
+        self._pf = _to_device(host, "penalty_factor")
+
+    def _pf_refusal(self, what):
+        if self._pf is not None:
+            raise ValueError(f"{what} is not available with penalty_factor: the gap-safe rule compares against lam p_j, and its "
+                             "rounding guard has to be re-derived for g / p; neither is built yet")
 
     @property
     def sample_weight(self):
@@ -335,6 +416,15 @@ class _GapMixin:
 
     # -- g / prox with the ridge term (l2 = 0: the shared l1 forms, the same calls as before) --------------------
     def prox_wsum_g(self, weight, x):
+        if self._pf is not None:
+            x = _as_host(x)
+            if x.size != self.n_features:
+                raise ValueError(f"len(x) should be equal to n_features, got {x}.")
+            out = np.empty_like(x)
+            lib = _lib.require_gpu()
+            _lib.check(lib.zf_host_prox_pf_box(C.c_void_p(_lib.ptr(out)), C.c_void_p(_lib.ptr(x)), C.c_void_p(_lib.ptr(self._pf_host)),
+                                               float(self.lam * weight), self.box[0], self.box[1], x.size), "zf_host_prox_pf_box")
+            return out
         if not self.l2 > 0:
             return NativeProblem.prox_wsum_g(self, weight, x)
         x = _as_host(x)
@@ -348,6 +438,12 @@ class _GapMixin:
     def _eval_fg(self, x):
         lib = _lib.require_gpu()
         s = C.c_double(0.0)
+        if self._pf is not None:
+            if x.size != self.n_features:
+                raise ValueError(f"len(x) should be equal to n_features, got {x}.")
+            _lib.check(lib.zf_host_pf_g(C.c_void_p(_lib.ptr(x)), C.c_void_p(_lib.ptr(self._pf_host)), x.size, self.lam, C.byref(s)),
+                       "zf_host_pf_g")
+            return None, np.float64(s.value)
         if self.l2 > 0:
             _lib.check(lib.zf_host_enet_g(C.c_void_p(_lib.ptr(x)), x.size, self.lam, self.l2, C.byref(s)), "zf_host_enet_g")
             return None, np.float64(s.value)
@@ -356,6 +452,9 @@ class _GapMixin:
 
     def _screen_refusal(self):
         """Why this problem cannot be screened (None: it can)."""
+        if self._pf is not None:
+            return ("penalty_factor is set: the gap-safe rule compares against lam p_j, and its rounding guard has to be re-derived "
+                    "for g / p; neither is built yet")
         if self._w is not None:
             return ("sample_weight is set: the weighted rule needs sum_i w_i a_ij^2 for |a_j|^2 and a re-derived rounding guard, "
                     "which are not built yet")
@@ -368,6 +467,7 @@ class _GapMixin:
         """|a_j|_2 of every column of A: a float64 CUDA tensor of n_features, computed on the GPU once per matrix."""
         import torch
 
+        self._pf_refusal("column_norms")
         self._weights_refusal("column_norms")
         h = self._norms
         if h.norms is None:
@@ -433,6 +533,7 @@ class _GapMixin:
         the ``Screen`` of ``screen(x)``, a device mask, a host boolean mask, or a host array of column numbers (the columns
         keep their order).  With x_full[keep] = x and zeros elsewhere, f and jac_f of the restricted problem at x are the
         full problem's at x_full (jac_f: its kept entries).  Keeping no column is refused: that problem's solution is x = 0."""
+        self._pf_refusal("restrict")
         self._weights_refusal("restrict")
         why = self._gap_refusal()
         if why:
@@ -454,6 +555,9 @@ class _GapMixin:
             return "bounds are set: the dual of the boxed problem is a different one"
         if getattr(self, "group", None) is not None:
             return "the problem is sharded over a process group (group=): the dual point needs the whole A^T grad phi"
+        if self._pf_host is not None and not np.all(self._pf_host > 0):
+            return ("penalty_factor holds a zero (an unpenalised column): the dual candidate cannot be made feasible by scaling - it "
+                    "needs a_j^T theta = 0 exactly there; solve with gap_tol=None (the solver's own tol stops the solve)")
         return None
 
     def duality_gap(self, x):
@@ -470,9 +574,37 @@ class _GapMixin:
         self._gap_call(_lib.require_gpu(), x, out)
         return DualityGap(out)
 
-    def lam_max(self):
-        """|grad f(0)|_inf: the smallest lam for which x = 0 is optimal."""
-        return np.float64(np.max(np.abs(self.jac_f(np.zeros(self.n_features)))))
+    def lam_max(self, tol=1e-10, max_iter=5000, **solver_kwargs):
+        """|grad f(0)|_inf: the smallest lam for which x = 0 is optimal.  With penalty factors p > 0: max_j |grad f(0)_j| / p_j.
+        With unpenalised columns U (p_j = 0): max over p_j > 0 of |grad f(x_U)_j| / p_j, x_U the minimiser of f over the columns U
+        alone - the smallest lam at which every penalised coordinate is zero.  x_U is the solution of ``with_lam(L)`` for an L
+        large enough: L starts at twice the value at x = 0 and is accepted when every penalised entry of the solution is exactly
+        0 and the resulting value is <= L; otherwise it is doubled, at most 8 times (RuntimeError).  ``tol``, ``max_iter`` and
+        ``solver_kwargs`` go to those solves only."""
+        g0 = np.abs(self.jac_f(np.zeros(self.n_features)))
+        if self._pf_host is None:
+            return np.float64(np.max(g0))
+        p = self._pf_host
+        pen = p > 0
+        if not pen.any():
+            return np.float64(0.0)
+        if pen.all():
+            return np.float64(np.max(g0 / p))
+        L = 2.0 * float(np.max(g0[pen] / p[pen]))
+        if not L > 0:
+            L = 1.0
+        x = np.zeros(self.n_features)
+        for _ in range(8):
+            res = self.with_lam(L).minimize_proximal_gradient(x, tol=tol, max_iter=max_iter, **solver_kwargs)
+            x = np.asarray(res.x, dtype=np.float64)
+            if not np.any(x[pen] != 0):
+                val = float(np.max(np.abs(self.jac_f(x))[pen] / p[pen]))
+                if val <= L:
+                    return np.float64(val)
+            x = np.where(pen, 0.0, x)
+            L *= 2.0
+        raise RuntimeError("lam_max: no lam was found in 8 doublings at which every penalised coordinate is zero (raise max_iter, "
+                           "or loosen tol)")
 
     def with_lam(self, lam):
         """A sibling problem with another l1 weight that SHARES the device matrix, b and (sparse classes) the matrix
@@ -488,6 +620,9 @@ class _GapMixin:
         matrix, b and matrix handle; nothing is uploaded."""
         sib = self.with_lam(lam)
         sib.l2 = _check_l2(l2, getattr(self, "group", None))
+        if sib.l2 > 0 and self._pf is not None:
+            raise ValueError("l2 > 0 is not available with penalty_factor: the ridge term would need the factors too (glmnet scales "
+                             "both), and that step is not built")
         return sib
 
 
@@ -499,17 +634,23 @@ class _DenseMarginsL1(_GapMixin, NativeProblem):
     kind = None
     _ENTRY = dict(eval=("zf_ls_eval", "zf_logistic_eval", "zf_huber_eval", "zf_poisson_eval"), weval="zf_wloss_eval",   # (eval: by ZF_LOSS_* code)
                   gap="zf_gap_eval", gap_enet="zf_gap_eval_enet", gap_huber="zf_gap_eval_huber", gap_weighted="zf_gap_eval_weighted",
-                  gap_poisson="zf_gap_eval_poisson",
+                  gap_poisson="zf_gap_eval_poisson", gap_pf="zf_gap_eval_pf",
                   screen="zf_gap_screen_eval", screen_huber="zf_gap_screen_eval_huber")
 
     def _lead(self, *w):
         """What every dense entry point starts with: A, b, (the weights,) m, n."""
         return (_dp(self.A), _dp(self.b), *w, self.m_rows, self.n_features)
 
-    def _set(self, A, b, lam, scale, bounds, l2=0.0, sample_weight=None, group=None):
+    def _lead_pf(self):
+        return self._lead(_dp(self._w), _dp(self._pf))
+
+    def _set(self, A, b, lam, scale, bounds, l2=0.0, sample_weight=None, group=None, penalty_factor=None):
         self.l2 = _check_l2(l2)
         if sample_weight is not None:   # (every ValueError before anything touches the device)
             sample_weight = _check_weights(sample_weight, int(np.shape(b)[0]) if np.ndim(b) == 1 else -1, group)
+        if penalty_factor is not None:
+            shape = tuple(getattr(A, "shape", None) or np.shape(A))
+            penalty_factor = _check_penalty_factor(penalty_factor, int(shape[1]) if len(shape) == 2 else -1, group, self.l2)
         self.A = _to_device(A, "A")
         self.b = _to_device(b, "b")
         if self.A.ndim != 2 or self.b.ndim != 1 or self.A.shape[0] != self.b.shape[0]:
@@ -520,6 +661,7 @@ class _DenseMarginsL1(_GapMixin, NativeProblem):
         self.group = None
         self._norms = _ColumnNorms()
         self._set_weights(sample_weight)
+        self._set_penalty_factor(penalty_factor)
 
     def _norms_call(self, lib, norms, stats):
         _lib.check(lib.zf_dense_col_norms(_dp(self.A), self.m_rows, self.n_features, _dp(norms), _dp(stats)), "zf_dense_col_norms")
@@ -554,7 +696,7 @@ class LeastSquaresL1(_DenseMarginsL1):
     kind = _lib.ZF_PROBLEM_LEAST_SQUARES_L1
     taylor_remainder = True   # acceptance="remainder": R = scale |A (x+ - y)|^2 from the residual kernels at x+
 
-    def __init__(self, A, b, lam, scale=0.5, bounds=None, group=None, shard="columns", l2=0.0, *, sample_weight=None):
+    def __init__(self, A, b, lam, scale=0.5, bounds=None, group=None, shard="columns", l2=0.0, *, sample_weight=None, penalty_factor=None):
         """With ``group`` set and ``shard="columns"`` (default), ``A`` is this rank's column block A_p
         (m x n_p, row-major) of a matrix whose columns - and the decision vector - are partitioned
         over the ranks of that process group; ``b`` is replicated; the solve exchanges the m-vector
@@ -566,7 +708,7 @@ class LeastSquaresL1(_DenseMarginsL1):
             raise ValueError("shard must be 'columns' or 'rows'")
         self.shard = shard
         _check_l2(l2, group)
-        self._set(A, b, lam, scale, bounds, l2, sample_weight, group)
+        self._set(A, b, lam, scale, bounds, l2, sample_weight, group, penalty_factor)
         self.group = group
 
     def _descriptor(self):
@@ -619,7 +761,7 @@ class _SparseMarginsL1(_GapMixin, NativeProblem):
 
     kind = None
     _ENTRY = dict(eval=("zf_spmat_eval", "zf_spmat_logistic_eval", "zf_spmat_huber_eval", "zf_spmat_poisson_eval"),
-                  weval="zf_spmat_wloss_eval", gap_poisson="zf_spmat_gap_eval_poisson",
+                  weval="zf_spmat_wloss_eval", gap_poisson="zf_spmat_gap_eval_poisson", gap_pf="zf_spmat_gap_eval_pf",
                   gap="zf_spmat_gap_eval", gap_enet="zf_spmat_gap_eval_enet", gap_huber="zf_spmat_gap_eval_huber",
                   gap_weighted="zf_spmat_gap_eval_weighted", screen="zf_spmat_gap_screen_eval",
                   screen_huber="zf_spmat_gap_screen_eval_huber")
@@ -628,7 +770,10 @@ class _SparseMarginsL1(_GapMixin, NativeProblem):
         """What every sparse entry point starts with: the matrix handle, b (, the weights)."""
         return (self._spmat.value, _dp(self.b), *w)
 
-    def _set(self, A, b, lam, scale, bounds, l2=0.0, sample_weight=None):
+    def _lead_pf(self):
+        return self._lead(_dp(self._w), _dp(self._pf))
+
+    def _set(self, A, b, lam, scale, bounds, l2=0.0, sample_weight=None, penalty_factor=None):
         import torch
 
         from . import sparse
@@ -636,6 +781,8 @@ class _SparseMarginsL1(_GapMixin, NativeProblem):
         self.l2 = _check_l2(l2)
         if sample_weight is not None:   # (every ValueError before anything touches the device)
             sample_weight = _check_weights(sample_weight, int(A.shape[0]))
+        if penalty_factor is not None:
+            penalty_factor = _check_penalty_factor(penalty_factor, int(A.shape[1]), None, self.l2)
 
         b_host = b.detach().cpu().numpy() if isinstance(b, torch.Tensor) else b
         prep = sparse.prepare(A, b_host)   # (every ValueError comes from here, before anything touches the device)
@@ -649,6 +796,7 @@ class _SparseMarginsL1(_GapMixin, NativeProblem):
         self._norms = _ColumnNorms()
         self._longest = (int(np.diff(prep["indptr"]).max(initial=0)), int(np.diff(prep["t_indptr"]).max(initial=0)))
         self._set_weights(sample_weight)
+        self._set_penalty_factor(penalty_factor)
 
     def _norms_call(self, lib, norms, stats):
         _lib.check(lib.zf_spmat_col_norms(self._spmat.value, _dp(norms), _dp(stats)), "zf_spmat_col_norms")
@@ -708,8 +856,8 @@ class SparseLeastSquaresL1(_SparseMarginsL1):
     kind = _lib.ZF_PROBLEM_SPARSE_LS_L1
     taylor_remainder = True   # acceptance="remainder": R = scale |A (x+ - y)|^2 from the residual kernels at x+
 
-    def __init__(self, A, b, lam, scale=0.5, bounds=None, l2=0.0, *, sample_weight=None):
-        self._set(A, b, lam, scale, bounds, l2, sample_weight)
+    def __init__(self, A, b, lam, scale=0.5, bounds=None, l2=0.0, *, sample_weight=None, penalty_factor=None):
+        self._set(A, b, lam, scale, bounds, l2, sample_weight, penalty_factor=penalty_factor)
 
 
 def _check_labels(b, m=None):
@@ -787,10 +935,10 @@ class HuberL1(_HuberMixin, _DenseMarginsL1):
 
     kind = _lib.ZF_PROBLEM_LEAST_SQUARES_L1
 
-    def __init__(self, A, b, lam, delta, scale=0.5, bounds=None, l2=0.0, *, group=None, sample_weight=None):
+    def __init__(self, A, b, lam, delta, scale=0.5, bounds=None, l2=0.0, *, group=None, sample_weight=None, penalty_factor=None):
         self._refuse_group(group)
         self.delta = _check_delta(delta)
-        self._set(A, b, lam, scale, bounds, l2, sample_weight)
+        self._set(A, b, lam, scale, bounds, l2, sample_weight, penalty_factor=penalty_factor)
 
 
 class SparseHuberL1(_HuberMixin, _SparseMarginsL1):
@@ -800,10 +948,10 @@ class SparseHuberL1(_HuberMixin, _SparseMarginsL1):
 
     kind = _lib.ZF_PROBLEM_SPARSE_LS_L1
 
-    def __init__(self, A, b, lam, delta, scale=0.5, bounds=None, l2=0.0, *, group=None, sample_weight=None):
+    def __init__(self, A, b, lam, delta, scale=0.5, bounds=None, l2=0.0, *, group=None, sample_weight=None, penalty_factor=None):
         self._refuse_group(group)
         self.delta = _check_delta(delta)
-        self._set(A, b, lam, scale, bounds, l2, sample_weight)
+        self._set(A, b, lam, scale, bounds, l2, sample_weight, penalty_factor=penalty_factor)
 
 
 def _check_counts(b, m=None):
@@ -845,9 +993,10 @@ class _PoissonMixin:
     def restrict(self, keep):
         self._no_screening("restrict")
 
-    def lam_max(self):
-        """|grad f(0)|_inf = scale |A^T (w o (1 - b))|_inf: the smallest lam for which x = 0 is optimal."""
-        return super().lam_max()
+    def lam_max(self, *args, **kwargs):
+        """|grad f(0)|_inf = scale |A^T (w o (1 - b))|_inf: the smallest lam for which x = 0 is optimal (with penalty factors:
+        as the other margins classes)."""
+        return super().lam_max(*args, **kwargs)
 
 
 class PoissonL1(_PoissonMixin, _DenseMarginsL1):
@@ -864,13 +1013,13 @@ class PoissonL1(_PoissonMixin, _DenseMarginsL1):
 
     kind = _lib.ZF_PROBLEM_LEAST_SQUARES_L1
 
-    def __init__(self, A, b, lam, scale=1.0, bounds=None, l2=0.0, *, group=None, sample_weight=None):
+    def __init__(self, A, b, lam, scale=1.0, bounds=None, l2=0.0, *, group=None, sample_weight=None, penalty_factor=None):
         self._refuse_group(group)
         shape = tuple(getattr(A, "shape", np.shape(A)))
         if len(shape) != 2:
             raise ValueError("A must be (m, n) and b (m,)")
         _check_counts(b, shape[0])
-        self._set(A, b, lam, scale, bounds, l2, sample_weight)
+        self._set(A, b, lam, scale, bounds, l2, sample_weight, penalty_factor=penalty_factor)
 
 
 class SparsePoissonL1(_PoissonMixin, _SparseMarginsL1):
@@ -880,10 +1029,10 @@ class SparsePoissonL1(_PoissonMixin, _SparseMarginsL1):
 
     kind = _lib.ZF_PROBLEM_SPARSE_LS_L1
 
-    def __init__(self, A, b, lam, scale=1.0, bounds=None, l2=0.0, *, group=None, sample_weight=None):
+    def __init__(self, A, b, lam, scale=1.0, bounds=None, l2=0.0, *, group=None, sample_weight=None, penalty_factor=None):
         self._refuse_group(group)
         _check_counts(b)
-        self._set(A, b, lam, scale, bounds, l2, sample_weight)
+        self._set(A, b, lam, scale, bounds, l2, sample_weight, penalty_factor=penalty_factor)
 
 
 class BlurHaarL1(NativeProblem):
