@@ -90,16 +90,20 @@ def _check_trace(rows, exp):
     assert np.array_equal(rows[:, _lib.TR_TRIALS].astype(np.int64), np.asarray(exp.alltrials, np.int64))
 
 
-def _check_storage(case, storage, o, exp, solve):
-    """Both solves and the chunked run of one storage form against the oracle's result; returns the lr / trial columns."""
+def _check_storage(case, storage, o, exp, solve, cases=M, keep=None):
+    """Both solves and the chunked run of one storage form against the oracle's result; returns the lr / trial columns.
+    ``cases``: the table module the case comes from (its make_problem and dense_form); ``keep``: a dict that receives the
+    problem and what the two solves returned, for a caller with further checks on them."""
     from zfista_amd import _lib
     from zfista_amd.proximal_gradient import NativeRun
 
     spec, x0 = case.spec, case.x0
-    prob = M.make_problem(case, storage)
+    prob = cases.make_problem(case, storage)
     res, rows, plan = solve(prob, x0, return_all=True, **o)
     res1, rows1, plan1 = solve(prob, x0, return_all=False, **o)
-    assert plan == plan1 and plan[0] == (M.CSR if storage == "csr" else M.dense_form(spec)), (plan, plan1)
+    if keep is not None:
+        keep.update(prob=prob, res=res, rows=rows, res1=res1, rows1=rows1)
+    assert plan == plan1 and plan[0] == (M.CSR if storage == "csr" else cases.dense_form(spec)), (plan, plan1)
     ref_keys = set(exp.keys()) - {"alllrs", "alltrials"}       # (the oracle's two extra fields)
     for r, tr in ((res, rows), (res1, rows1)):
         assert r.success == exp.success and r.message == exp.message, (r.message, exp.message)
@@ -153,15 +157,19 @@ def test_fuzz_margins(spec, solve):
 def test_snapshot_resume_across_the_last_chunk(cls, kind, tmp_path):
     """The table's longest run of the class that ends by tol, and its longest that ends in the error path: a snapshot taken one
     chunk before the end, and the run resumed from it, end with the status, x and trace of the uninterrupted run."""
+    spec = {(sp.cls, k): sp for sp, k in M.resume_cases()}[(cls, kind)]
+    case, o, exp = M.oracle(spec)
+    _check_resume(case, o, exp, kind, tmp_path)
+
+
+def _check_resume(case, o, exp, kind, tmp_path, cases=M):
     from zfista_amd import _lib
     from zfista_amd.proximal_gradient import NativeRun
 
-    spec = {(sp.cls, k): sp for sp, k in M.resume_cases()}[(cls, kind)]
-    case, o, exp = M.oracle(spec)
     assert M.ending(exp) == kind
     want = {"tol": _lib.ZF_CONVERGED, "error": _lib.ZF_BACKTRACK_FAILED}[kind]
     for storage in M.FORMS:
-        prob = M.make_problem(case, storage)
+        prob = cases.make_problem(case, storage)
         whole = NativeRun(prob, case.x0, FULL | o)
         ref_rows, chunks = _drain(whole)
         ref_x, ref_status = whole.solver.get_x(), whole.status
