@@ -388,6 +388,9 @@ int zf_solver_launch_counts(zf_solver* s, int64_t* out, int64_t count /* >= 2 */
  * out[1] = 2 or 3 as ZF_PROBLEM_LEAST_SQUARES_L1 (never 1: the small-matrix kernels hold the squared loss), out[2], out[3]
  * the slices; ZF_PROBLEM_SPARSE_LOGISTIC_L1 out[0] = 5 and the lanes / split rows as ZF_PROBLEM_SPARSE_LS_L1.  (Both form
  * rho(y), f(y) and f(x+) with one workgroup up to 32768 rows and with up to 1024 beyond, chunk sums added in chunk order.)
+ * A dense matrix stored in fp32 (zf_solver_set_matrix_f32, either dense kind): out[0] = 6, 7 or 8 - the column sweep
+ * zf_gemvT_partial_f32_kernel<4> (16-byte loads of four floats, n % 4 == 0), <2> (8-byte loads, n % 4 == 2), <1> (odd n) -
+ * out[1] = 4, 5 or 6 - the row sweep zf_gemv_rows_f32_kernel<4>, <2>, <1> - out[2], out[3] the slices of the fp32 rule.
  * Other problems: zeros. */
 int zf_solver_ls_plan(zf_solver* s, int64_t* out, int64_t count /* >= 4 */);
 /* the same window split by the shape of the pass, which the kernel logs itself: out[0], out[1] = mean
@@ -759,6 +762,34 @@ int zf_spmat_gap_eval_pf(const zf_spmat* h, const double* b_dev, const double* w
 int zf_host_prox_pf_box(double* out_host, const double* x_host, const double* p_host, double t, double lo, double hi, int64_t n);
 /* out = lam * sum_i p_i |x_i|, each term one fused multiply-add into the running sum (as the step kernel forms it) */
 int zf_host_pf_g(const double* x_host, const double* p_host, int64_t n, double lam, double* out);
+
+/* ---- a dense matrix stored in fp32 on the two dense kinds 2, 5 -----------------------------------------------------------------
+ * Both sweeps of a trial stream A and nothing else of size, so storing A in fp32 halves their bytes and the footprint of A.
+ * Every other value stays double: x, r, the accumulators, the outputs; an element is widened in a register, exactly.  The solver
+ * therefore solves, in fp64 arithmetic, exactly the fp64 problem on float64(A32) - with sums in another order than the fp64 sweeps
+ * take (csrc/zf_kernels_gemv_f32.h).  Additive to ABI 6: no struct field, no version change.
+ * zf_solver_set_matrix_f32: after zf_solver_create, before zf_solver_enqueue_init / zf_solver_restore.  A32_dev: m_rows x n floats,
+ * row-major, device memory, 16-byte aligned, borrowed as desc->A is.  zf_solver_create still wants a non-NULL, 16-byte-aligned
+ * desc->A (the same address will do); after this call nothing reads it.  From then on every sweep of the solver - the trial's two,
+ * the initial evaluation, zf_solver_duality_gap - takes the fp32 kernels, the slices are those of the fp32 rule (panels of
+ * 256 * V columns, V = 4 / 2 / 1 for n % 4 == 0 / n % 4 == 2 / odd n; at most 64 slices of at least 8 rows), a matrix small enough
+ * for the two fused small-matrix launches takes the general path, ZF_GEMV_MFMA has no effect, and zf_solver_ls_plan says so.
+ * ZF_ERR_ARG: a null or misaligned pointer, a kind other than ZF_PROBLEM_LEAST_SQUARES_L1 / ZF_PROBLEM_LOGISTIC_L1, world > 1, a
+ * solver that is already initialised.  Composes with zf_solver_set_l2 / _huber / _poisson / _row_weights / _penalty_factors in
+ * any order.  A resumed solve sets the matrix again before zf_solver_restore (the snapshot carries nothing new).  A solver that
+ * was never asked launches and allocates what it did. */
+int zf_solver_set_matrix_f32(zf_solver* s, const float* A32_dev);
+/* f and (grad_out_host != NULL) grad at a host vector for such a matrix.  loss: any of the four ZF_LOSS_* codes; delta must be
+ * finite and > 0 for ZF_LOSS_HUBER and is ignored otherwise; w_dev: the row weights or NULL.  ZF_ERR_ARG as zf_wloss_eval. */
+int zf_f32_eval(const float* A32_dev, const double* b_dev, const double* w_dev, int64_t m_rows, int64_t n, double scale, int32_t loss,
+                double delta, const double* x_host, double* f_out, double* grad_out_host /* or NULL */);
+/* The certificate for such a matrix: out as zf_gap_eval_weighted (eight values; ten - ridge term and its gap - for l2 > 0 when the
+ * buffer holds them; l2 = 0 writes [8] = [9] = 0 into a buffer of ten).  p_dev: penalty factors or NULL; with them the values are
+ * those of zf_gap_eval_pf, and l2 > 0 is ZF_ERR_ARG.  zf_solver_duality_gap of a solver with zf_solver_set_matrix_f32 writes the same
+ * values, bit for bit. */
+int zf_f32_gap_eval(const float* A32_dev, const double* b_dev, const double* w_dev, const double* p_dev, int64_t m_rows, int64_t n,
+                    double scale, double lam, double l2, int32_t loss, double delta, const double* x_host, double* out,
+                    int64_t count /* >= 8; 10 for all */);
 
 /* ---- multi-objective trial (m >= 2), device side ---------------------------
  * The dual of the scalarised subproblem is minimised on the host by SciPy exactly

@@ -259,6 +259,10 @@ SIGNATURES = {
     "zf_spmat_gap_eval_pf": (C.c_int, [_P, _P, _P, _P, C.c_double, C.c_double, C.c_int32, C.c_double, _P, _P, C.c_int64]),
     "zf_host_prox_pf_box": (C.c_int, [_P, _P, _P, C.c_double, C.c_double, C.c_double, C.c_int64]),
     "zf_host_pf_g": (C.c_int, [_P, _P, C.c_int64, C.c_double, C.POINTER(C.c_double)]),
+    "zf_solver_set_matrix_f32": (C.c_int, [_P, _P]),
+    "zf_f32_eval": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_double, C.c_int32, C.c_double, _P, C.POINTER(C.c_double), _P]),
+    "zf_f32_gap_eval": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_double, _P, _P,
+                                  C.c_int64]),
 }
 
 _lib = None

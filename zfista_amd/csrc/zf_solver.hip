@@ -18,6 +18,7 @@
 #include "zf_decide.h"
 #include "zf_kernels_gemv.h"
 #include "zf_kernels_ls_small.h"
+#include "zf_kernels_gemv_f32.h"
 #include "zf_kernels_op.h"
 #include "zf_spmv.h"
 #include "zf_screen.h"
@@ -253,6 +254,7 @@ struct zf_solver {
     bool own_packs = true;
     bool gemv_mfma = false;       // A^T r on v_mfma_f64_16x16x4 (n % 32 == 0; ZF_GEMV_MFMA=0 disables)
     bool ls_small = false;        // cache-resident A: two fused launches per trial (zf_kernels_ls_small.h)
+    const float* A32 = nullptr;   // the matrix stored in fp32 (zf_solver_set_matrix_f32; borrowed as desc.A is): every sweep takes zf_kernels_gemv_f32.h and nothing reads desc.A; NULL: what ran before
     double huber = 0.0;           // Huber's loss (zf_solver_set_huber): delta > 0 swaps the residual kernels for zf_kernels_huber.h; 0: the squared loss
     bool poisson = false;         // the Poisson loss (zf_solver_set_poisson): the residual kernels swapped for zf_kernels_poisson.h
     bool loss_part = false;       // the dense least-squares kind holds the 2 x ZF_SPMV_RESID_MAX_CHUNKS chunk sums of the loss kernels (zf_loss_part)
@@ -456,6 +458,37 @@ static void zf_dense_slices(int64_t m, int64_t n, int* slices_out, int64_t* rows
     *rows_per_slice = (m + slices - 1) / slices;
     *slices_out = (int)((m + *rows_per_slice - 1) / *rows_per_slice);
 }
+// the same rule for a matrix stored in fp32 (zf_kernels_gemv_f32.h): panels of ZF_BLOCK * V columns with V up to 4, so a given n
+// has up to half the panels and takes up to twice the slices; the caps - 64 slices, at least 8 rows per slice - are the same
+static void zf_dense_slices_f32(int64_t m, int64_t n, int* slices_out, int64_t* rows_per_slice) {
+    const int V = zf_f32_width(n);
+    const int64_t panels = (n / V + ZF_BLOCK - 1) / ZF_BLOCK;
+    int64_t slices = (ZF_MAX_GRID + panels - 1) / panels;
+    if (slices > (m + 7) / 8) slices = (m + 7) / 8;
+    if (slices < 1) slices = 1;
+    if (slices > 64) slices = 64;
+    *rows_per_slice = (m + slices - 1) / slices;
+    *slices_out = (int)((m + *rows_per_slice - 1) / *rows_per_slice);
+}
+// the two sweeps over an fp32 matrix: sr = A xr (slot / ctl as zf_gemv_rows_kernel) ...
+static void zf_launch_rows_f32(hipStream_t st, const zf_control* ctl, const float* A32, zf_ring3 xr, zf_ring3 sr, int slot, int64_t m,
+                               int64_t n) {
+    int gr = (int)((m + GEMV_ROWS_F32 - 1) / GEMV_ROWS_F32);
+    if (gr > 8 * ZF_MAX_GRID) gr = 8 * ZF_MAX_GRID;
+    const int V = zf_f32_width(n);
+    if (V == 4) hipLaunchKernelGGL(zf_gemv_rows_f32_kernel<4>, dim3(gr), dim3(ZF_BLOCK), 0, st, ctl, A32, xr, sr, slot, m, n);
+    else if (V == 2) hipLaunchKernelGGL(zf_gemv_rows_f32_kernel<2>, dim3(gr), dim3(ZF_BLOCK), 0, st, ctl, A32, xr, sr, slot, m, n);
+    else hipLaunchKernelGGL(zf_gemv_rows_f32_kernel<1>, dim3(gr), dim3(ZF_BLOCK), 0, st, ctl, A32, xr, sr, slot, m, n);
+}
+// ... and the slice partials of A^T r (slices / rows_per_slice: zf_dense_slices_f32; zf_gemvT_combine_kernel follows)
+static void zf_launch_cols_f32(hipStream_t st, const zf_control* ctl, const float* A32, const double* r, double* slab, int64_t m,
+                               int64_t n, int slices, int64_t rows_per_slice) {
+    const int V = zf_f32_width(n);
+    const dim3 gT((unsigned)((n / V + ZF_BLOCK - 1) / ZF_BLOCK), (unsigned)slices);
+    if (V == 4) hipLaunchKernelGGL(zf_gemvT_partial_f32_kernel<4>, gT, dim3(ZF_BLOCK), 0, st, ctl, A32, r, slab, m, n, rows_per_slice);
+    else if (V == 2) hipLaunchKernelGGL(zf_gemvT_partial_f32_kernel<2>, gT, dim3(ZF_BLOCK), 0, st, ctl, A32, r, slab, m, n, rows_per_slice);
+    else hipLaunchKernelGGL(zf_gemvT_partial_f32_kernel<1>, gT, dim3(ZF_BLOCK), 0, st, ctl, A32, r, slab, m, n, rows_per_slice);
+}
 static zf_op_args zf_op_of(const zf_problem_desc& d, const zf_control* ctl, const zf_op_plan& pl, const double* taps, const double* sep) {
     zf_op_args P;
     P.ctl = ctl;
@@ -513,6 +546,10 @@ static void zf_launch_apply_A(zf_solver* s, const zf_control* ctl, zf_ring3 xr, 
     if (zf_is_sparse_mat(d.kind)) {
         const zf_spmv_io io = {{xr.p[0], xr.p[1], xr.p[2]}, {sout.p[0], sout.p[1], sout.p[2]}};
         zf_launch_spmv(s->spmat->A, s->stream, ctl, false, io, slot, 1.0, s->sp_part_A);
+        return;
+    }
+    if (s->A32) {
+        zf_launch_rows_f32(s->stream, ctl, s->A32, xr, sout, slot, m, n);
         return;
     }
     const int V = (n % 2 == 0) ? 2 : 1;
@@ -1512,7 +1549,9 @@ static int zf_launch_trial(zf_solver* s, bool decide_in_launch, bool dry = false
             ZF_HIP(hipGetLastError());
             return ZF_OK;
         }
-        if (s->gemv_mfma) {
+        if (s->A32) {
+            zf_launch_cols_f32(s->stream, s->ctl, s->A32, s->resid, s->slab, m, n, s->slices, s->rows_per_slice);
+        } else if (s->gemv_mfma) {
             dim3 gM((unsigned)((n + GEMVT_MFMA_COLS - 1) / GEMVT_MFMA_COLS), (unsigned)s->slices);
             hipLaunchKernelGGL(zf_gemvT_partial_mfma_kernel, gM, dim3(ZF_BLOCK), 0, s->stream, s->ctl, d.A,
                                s->resid, s->slab, m, n, s->rows_per_slice);
@@ -1553,7 +1592,9 @@ static int zf_launch_trial(zf_solver* s, bool decide_in_launch, bool dry = false
         if (d.world > 1) sout = {{s->s_part, s->s_part, s->s_part}};   // (column blocks; row blocks returned above)
         int gr = (int)((m + GEMV_ROWS - 1) / GEMV_ROWS);
         if (gr > 8 * ZF_MAX_GRID) gr = 8 * ZF_MAX_GRID;
-        if (V == 2)
+        if (s->A32)
+            zf_launch_rows_f32(s->stream, s->ctl, s->A32, xr, sout, 1, m, n);
+        else if (V == 2)
             hipLaunchKernelGGL(zf_gemv_rows_kernel<2>, dim3(gr), dim3(ZF_BLOCK), 0, s->stream, s->ctl, d.A,
                                xr, sout, 1, m, n);
         else
@@ -2008,6 +2049,32 @@ extern "C" int zf_solver_set_row_weights(zf_solver* s, const double* w_dev) {
     return ZF_OK;
 }
 
+// The matrix stored in fp32 (include/zfista_hip.h): between create and init, on the two dense kinds.
+extern "C" int zf_solver_set_matrix_f32(zf_solver* s, const float* A32_dev) {
+    ZF_REQUIRE(s && A32_dev, "zf_solver_set_matrix_f32: null argument");
+    ZF_REQUIRE(!(s->init_enqueued || s->initialised),
+               "zf_solver_set_matrix_f32: call after zf_solver_create and before zf_solver_enqueue_init / zf_solver_restore");
+    const zf_problem_desc& d = s->desc;
+    ZF_REQUIRE(zf_is_dense_mat(d.kind),"zf_solver_set_matrix_f32: only for ZF_PROBLEM_LEAST_SQUARES_L1 and ZF_PROBLEM_LOGISTIC_L1");
+    ZF_REQUIRE(d.world == 1, "zf_solver_set_matrix_f32: not for a sharded solve (world > 1)");
+    ZF_REQUIRE(zf_aligned16(A32_dev), "zf_solver_set_matrix_f32: the matrix must be 16-byte aligned");
+    int slices = 1;
+    int64_t rows_per_slice = d.m_rows;
+    zf_dense_slices_f32(d.m_rows, d.n, &slices, &rows_per_slice);
+    if (slices > s->slices) {   // (wider panels, so fewer of them: the fp32 rule may take more slices than the slab of zf_solver_create holds)
+        double* slab = nullptr;
+        ZF_HIP(hipMalloc(&slab, sizeof(double) * slices * d.n));
+        if (s->slab) (void)hipFree(s->slab);
+        s->slab = slab;
+    }
+    s->slices = slices;
+    s->rows_per_slice = rows_per_slice;
+    s->A32 = A32_dev;
+    s->gemv_mfma = false;  // (the MFMA column sweep reads fp64 A: ZF_GEMV_MFMA has no effect here)
+    s->ls_small = false;   // (the fused small-matrix kernels read fp64 A: the general path, as the logistic kind)
+    return ZF_OK;
+}
+
 extern "C" int zf_solver_launch_counts(zf_solver* s, int64_t* out, int64_t count) {
     ZF_REQUIRE(s && out, "zf_solver_launch_counts: null argument");
     ZF_REQUIRE(count >= 2, "zf_solver_launch_counts: the output holds fewer than 2 values");
@@ -2055,6 +2122,11 @@ extern "C" int zf_solver_ls_plan(zf_solver* s, int64_t* out, int64_t count) {
     const bool odd = s->desc.n % 2 != 0;
     out[0] = s->ls_small ? 1 : s->gemv_mfma ? 2 : odd ? 4 : 3;
     out[1] = s->ls_small ? 1 : odd ? 3 : 2;
+    if (s->A32) {   // zf_kernels_gemv_f32.h: 16-byte, 8-byte or scalar loads of floats
+        const int V = zf_f32_width(s->desc.n);
+        out[0] = V == 4 ? 6 : V == 2 ? 7 : 8;
+        out[1] = V == 4 ? 4 : V == 2 ? 5 : 6;
+    }
     out[2] = s->slices;
     out[3] = s->rows_per_slice;
     return ZF_OK;
@@ -2579,9 +2651,11 @@ struct zf_matview {
     int64_t m, n;        // (CSR: the handle's, filled in by zf_loss_args once the handle is known not to be NULL)
     const zf_spmat* h;   // CSR: A and A^T with their plans; NULL for dense
     bool csr;
+    const float* A32;    // dense, stored in fp32 (zf_kernels_gemv_f32.h): m x n row-major (device), 16-byte aligned - A is NULL then; NULL otherwise
 };
-static zf_matview zf_dense_view(const double* A, int64_t m, int64_t n) { return zf_matview{A, m, n, nullptr, false}; }
-static zf_matview zf_csr_view(const zf_spmat* h) { return zf_matview{nullptr, 0, 0, h, true}; }
+static zf_matview zf_dense_view(const double* A, int64_t m, int64_t n) { return zf_matview{A, m, n, nullptr, false, nullptr}; }
+static zf_matview zf_csr_view(const zf_spmat* h) { return zf_matview{nullptr, 0, 0, h, true, nullptr}; }
+static zf_matview zf_dense_view_f32(const float* A32, int64_t m, int64_t n) { return zf_matview{nullptr, m, n, nullptr, false, A32}; }
 
 // what the sweeps write between their launches: the slab of the dense column sweep and its slices, or the segment sums of the
 // split rows of A / A^T (a call's own, or a solver's: the handle is shared with live solvers on other streams)
@@ -2599,7 +2673,8 @@ static int zf_sweep_ws_alloc(const zf_matview& V, bool adjoint, zf_sweep_ws* W) 
         if (V.h->A.nseg > 0) ZF_KEEP_FIRST(hipMalloc(&W->part_A, sizeof(double) * V.h->A.nseg));
         if (adjoint && V.h->At.nseg > 0) ZF_KEEP_FIRST(hipMalloc(&W->part_At, sizeof(double) * V.h->At.nseg));
     } else if (adjoint) {
-        zf_dense_slices(V.m, V.n, &W->slices, &W->rows_per_slice);
+        if (V.A32) zf_dense_slices_f32(V.m, V.n, &W->slices, &W->rows_per_slice);
+        else zf_dense_slices(V.m, V.n, &W->slices, &W->rows_per_slice);
         ZF_KEEP_FIRST(hipMalloc(&W->slab, sizeof(double) * W->slices * V.n));
     }
     return rc;
@@ -2617,6 +2692,10 @@ static void zf_launch_view_apply(const zf_matview& V, hipStream_t st, double* x,
         return;
     }
     zf_ring3 xr = {{x, x, x}}, sr = {{z, z, z}};
+    if (V.A32) {
+        zf_launch_rows_f32(st, nullptr, V.A32, xr, sr, -1, V.m, V.n);
+        return;
+    }
     int gr = (int)((V.m + GEMV_ROWS - 1) / GEMV_ROWS);
     if (gr > 8 * ZF_MAX_GRID) gr = 8 * ZF_MAX_GRID;
     if (V.n % 2 == 0) hipLaunchKernelGGL(zf_gemv_rows_kernel<2>, dim3(gr), dim3(ZF_BLOCK), 0, st, nullptr, V.A, xr, sr, -1, V.m, V.n);
@@ -2634,7 +2713,9 @@ static void zf_launch_view_adjoint(const zf_matview& V, hipStream_t st, const do
     }
     const int64_t m = V.m, n = V.n;
     const int vw = (n % 2 == 0) ? 2 : 1;
-    if (mfma) {
+    if (V.A32) {   // (`mfma` does not apply: that sweep reads fp64 A)
+        zf_launch_cols_f32(st, nullptr, V.A32, r, W.slab, m, n, W.slices, W.rows_per_slice);
+    } else if (mfma) {
         dim3 gM((unsigned)((n + GEMVT_MFMA_COLS - 1) / GEMVT_MFMA_COLS), (unsigned)W.slices);
         hipLaunchKernelGGL(zf_gemvT_partial_mfma_kernel, gM, dim3(ZF_BLOCK), 0, st, nullptr, V.A, r, W.slab, m, n, W.rows_per_slice);
     } else {
@@ -2648,7 +2729,7 @@ static void zf_launch_view_adjoint(const zf_matview& V, hipStream_t st, const do
 // The checks every evaluation entry point shares (`who`: the entry's name).  First its pointers (`ok`) and its matrix ...
 static int zf_view_args(const char* who, const zf_matview& V, bool ok) {
     if (V.csr && !(ok && V.h)) return zf_fail(ZF_ERR_ARG, "%s: null argument%s", who);
-    if (!V.csr && !(ok && V.A && V.m >= 1 && V.n >= 1)) return zf_fail(ZF_ERR_ARG, "%s: bad argument%s", who);
+    if (!V.csr && !(ok && (V.A || V.A32) && V.m >= 1 && V.n >= 1)) return zf_fail(ZF_ERR_ARG, "%s: bad argument%s", who);
     return ZF_OK;
 }
 // ... then, behind zf_view_args, the loss code, Huber's delta and the alignment of a dense A; leaves the entry's loss in *L
@@ -2656,7 +2737,7 @@ static int zf_loss_args(const char* who, zf_matview* V, int32_t kind, double del
     if (kind != ZF_LOSS_SQUARE && kind != ZF_LOSS_LOGISTIC && kind != ZF_LOSS_HUBER && kind != ZF_LOSS_POISSON)
         return zf_fail(ZF_ERR_ARG, "%s: loss must be ZF_LOSS_SQUARE, ZF_LOSS_LOGISTIC, ZF_LOSS_HUBER or ZF_LOSS_POISSON%s", who);
     if (kind == ZF_LOSS_HUBER && !(delta > 0.0 && delta <= DBL_MAX)) return zf_fail(ZF_ERR_ARG, "%s: delta must be finite and > 0%s", who);
-    if (!V->csr && !zf_aligned16(V->A)) return zf_fail(ZF_ERR_ARG, "%s: A must be 16-byte aligned%s", who);
+    if (!V->csr && !zf_aligned16(V->A32 ? (const void*)V->A32 : (const void*)V->A)) return zf_fail(ZF_ERR_ARG, "%s: A must be 16-byte aligned%s", who);
     if (V->csr) V->m = V->h->m, V->n = V->h->n;
     *L = zf_loss{kind, kind == ZF_LOSS_HUBER ? delta : 0.0, w_dev};
     return ZF_OK;
@@ -2783,6 +2864,14 @@ extern "C" int zf_wloss_eval(const double* A_dev, const double* b_dev, const dou
 extern "C" int zf_spmat_wloss_eval(const zf_spmat* h, const double* b_dev, const double* w_dev, double scale, int32_t loss, double delta,
                                    const double* x_host, double* f_out, double* grad_out_host) {
     return zf_point_entry("zf_spmat_wloss_eval", zf_csr_view(h), b_dev, w_dev != nullptr, w_dev, scale, zf_wloss_code(loss), delta, x_host, f_out,
+                          grad_out_host);
+}
+
+// a dense matrix stored in fp32 (zf_kernels_gemv_f32.h) under any of the four losses, weighted or not: the rows kernels of the loss
+// dispatch on the fp32 sweeps.  (The unweighted squared loss goes through the residual kernels, as zf_ls_eval does.)
+extern "C" int zf_f32_eval(const float* A32_dev, const double* b_dev, const double* w_dev, int64_t m_rows, int64_t n, double scale,
+                           int32_t loss, double delta, const double* x_host, double* f_out, double* grad_out_host) {
+    return zf_point_entry("zf_f32_eval", zf_dense_view_f32(A32_dev, m_rows, n), b_dev, true, w_dev, scale, loss, delta, x_host, f_out,
                           grad_out_host);
 }
 
@@ -2999,6 +3088,17 @@ extern "C" int zf_spmat_gap_eval_pf(const zf_spmat* h, const double* b_dev, cons
     return zf_gap_pf_entry("zf_spmat_gap_eval_pf", zf_csr_view(h), b_dev, w_dev, p_dev, scale, lam, loss, delta, x_host, out, count);
 }
 
+// the certificate of a dense matrix stored in fp32: zf_gap_eval_pf with p_dev (l2 must be 0 then), else the elastic-net form of
+// this loss (l2 = 0: the l1 evaluation, [8] = [9] = 0 when the buffer holds ten)
+extern "C" int zf_f32_gap_eval(const float* A32_dev, const double* b_dev, const double* w_dev, const double* p_dev, int64_t m_rows,
+                               int64_t n, double scale, double lam, double l2, int32_t loss, double delta, const double* x_host,
+                               double* out, int64_t count) {
+    const zf_matview V = zf_dense_view_f32(A32_dev, m_rows, n);
+    if (!p_dev) return zf_gap_entry("zf_f32_gap_eval", V, b_dev, true, w_dev, scale, lam, true, l2, loss, delta, x_host, out, count);
+    ZF_REQUIRE(!(l2 > 0.0), "zf_f32_gap_eval: not with penalty factors and l2 > 0 together (the ridge term would need the factors too)");
+    return zf_gap_pf_entry("zf_f32_gap_eval", V, b_dev, w_dev, p_dev, scale, lam, loss, delta, x_host, out, count);
+}
+
 // the gap evaluation followed by the gap-safe screen of its g (zf_kernels_screen.h), l2 = 0 only: out[0 .. 8) as zf_gap_eval - the
 // same kernels in the same order, the same bits - then [r, E, r_eff, kept count].  Huber's loss: the rule, the guard and the four
 // screen launches are the least-squares kinds' - L = 2 scale, |c|_2 from sum c^2 where they read sum r^2 (the clip is exact and
@@ -3087,7 +3187,7 @@ extern "C" int zf_solver_duality_gap(zf_solver* s, double* out, int64_t count) {
     const double* x = s->xb[c.cur];
     const double* z = s->sring.p[c.cur];   // A x_k: every path of these kinds keeps it there (the fused small-matrix path too)
     const zf_gap_ws& ws = s->gap;
-    const zf_matview V = {d.A, m, n, s->spmat, zf_is_sparse_mat(d.kind)};
+    const zf_matview V = {s->A32 ? nullptr : d.A, m, n, s->spmat, zf_is_sparse_mat(d.kind), s->A32};
     const zf_sweep_ws W = {s->slab, s->slices, s->rows_per_slice, s->sp_part_A, s->sp_part_At};
     zf_launch_loss_gap_rows(s->stream, loss, z, d.b, m, d.scale, ws);
     zf_launch_view_adjoint(V, s->stream, ws.rvec, ws.g, zf_gfac(loss, d.scale), s->gemv_mfma, W);

@@ -84,8 +84,9 @@ class DeviceSolver:
         poisson = bool(desc_fields.get("poisson", False))   # the Poisson loss on a least-squares kind: likewise (zf_solver_set_poisson)
         roww = desc_fields.get("row_weights")   # per-row sample weights (a device pointer): likewise (zf_solver_set_row_weights)
         pf = desc_fields.get("penalty_factors")   # per-column penalty factors (a device pointer): likewise (zf_solver_set_penalty_factors)
+        a32 = desc_fields.get("matrix_f32")   # the matrix stored in fp32 (a device pointer): likewise (zf_solver_set_matrix_f32)
         for k, v in desc_fields.items():
-            if k not in ("spmat", "l2", "huber_delta", "poisson", "row_weights", "penalty_factors"):
+            if k not in ("spmat", "l2", "huber_delta", "poisson", "row_weights", "penalty_factors", "matrix_f32"):
                 setattr(d, k, v)
         o = _lib.Options()
         for k, v in options.items():
@@ -110,6 +111,8 @@ class DeviceSolver:
             _lib.check(self.lib.zf_solver_set_row_weights(h, C.c_void_p(roww)), "zf_solver_set_row_weights")
         if pf:
             _lib.check(self.lib.zf_solver_set_penalty_factors(h, C.c_void_p(pf)), "zf_solver_set_penalty_factors")
+        if a32:
+            _lib.check(self.lib.zf_solver_set_matrix_f32(h, C.c_void_p(a32)), "zf_solver_set_matrix_f32")
         sub = C.c_int32(1)
         _lib.check(self.lib.zf_solver_sub_iters(h, C.byref(sub)), "zf_solver_sub_iters")
         self.sub_iters = int(sub.value)   # iterations one pass may accept (temporal blocking)
@@ -305,7 +308,8 @@ class DeviceSolver:
     def ls_plan(self):
         """Least squares: (column-sweep form, row-sweep form, row slices, rows per slice) of the passes this solver
         runs (zf_solver_ls_plan).  Column sweep: 0 not least squares, 1 small matrix, 2 MFMA, 3 VALU 16-byte loads,
-        4 VALU scalar loads; row sweep: 1 the small-matrix rows kernel, 2 zf_gemv_rows_kernel<2>, 3 <1>.
+        4 VALU scalar loads; row sweep: 1 the small-matrix rows kernel, 2 zf_gemv_rows_kernel<2>, 3 <1>.  A matrix stored in
+        fp32 (``matrix_dtype="float32"``): column sweep 6, 7, 8 and row sweep 4, 5, 6 - four, two, one float per load.
         The operator problem (BlurHaarL1): (tile height - 8 or 32 rows, 1 separable correlation / 0 general,
         1 workgroups walk their tiles / 0 one workgroup per tile, 1 prox step fused into the adjoint kernel / 0 a
         launch of its own).  Sparse least squares (SparseLeastSquaresL1): (5, lanes per row of the sweep over A, lanes per

@@ -40,6 +40,44 @@ def _as_host(x):
     return np.ascontiguousarray(np.asarray(x, dtype=np.float64))
 
 
+def _matrix_dtype(v):
+    """``matrix_dtype`` as the string "float64" (None: the default) or "float32".  ValueError for anything else - on the host,
+    before anything touches the device."""
+    if v is None:
+        return "float64"
+    name = v if isinstance(v, str) else str(v).rsplit(".", 1)[-1] if type(v).__module__.split(".")[0] == "torch" else None
+    if name is None:
+        try:
+            name = np.dtype(v).name
+        except TypeError:
+            name = None
+    if name not in ("float64", "float32"):
+        raise ValueError(f"matrix_dtype must be None, 'float64' or 'float32' (or the NumPy / torch dtype of that name), got {v!r}")
+    return name
+
+
+def _to_device_f32(a, name):
+    """float32 contiguous CUDA tensor from a NumPy array or a torch tensor: a float32 CUDA tensor is taken as it is (no copy when it
+    is contiguous), anything else is rounded to nearest.  A value that is not finite after the rounding raises ValueError - found on
+    the host for a host matrix, by one ``isfinite().all()`` on the device for a device one."""
+    import torch
+
+    _lib.require_gpu()
+    bad = ValueError(f"{name} holds a value that is not finite as float32 (NaN, an infinity, or a magnitude beyond 3.4e38)")
+    if isinstance(a, torch.Tensor):
+        if a.dtype not in (torch.float32, torch.float64):
+            raise TypeError(f"{name} must be float32 or float64")
+        t = (a if a.is_cuda else a.cuda()).to(torch.float32).contiguous()
+        if not bool(torch.isfinite(t).all()):
+            raise bad
+        return t
+    with np.errstate(over="ignore"):
+        host = np.ascontiguousarray(np.asarray(a, dtype=np.float64).astype(np.float32))
+    if not np.all(np.isfinite(host)):
+        raise bad
+    return torch.from_numpy(host).cuda()
+
+
 class NativeProblem:
     """Marker base: a single-objective problem with a device descriptor."""
 
@@ -283,6 +321,7 @@ class _GapMixin:
     _gap_logistic = _classattr(lambda cls: int(cls._loss == _lib.ZF_LOSS_LOGISTIC))
     _eval_name = _classattr(lambda cls: cls._ENTRY["eval"][cls._loss])   # f and jac_f of the unweighted problem
     _longest = ()   # (sparse classes: the longest row and column, which their screen entries take)
+    _f32 = False    # (dense classes: A is stored in fp32 - f, jac_f and the certificate go to zf_f32_eval / zf_f32_gap_eval)
 
     def _ls(self, x, want_grad):
         """(f, jac_f or None) at a host vector."""
@@ -292,7 +331,9 @@ class _GapMixin:
         lib = _lib.require_gpu()
         fval = C.c_double(0.0)
         grad = np.empty_like(x) if want_grad else None
-        if self._loss == _lib.ZF_LOSS_POISSON:   # (its entries take the weights, or NULL)
+        if self._f32:   # (one entry for every loss, weighted or not)
+            name, args = "zf_f32_eval", self._lead(_dp(self._w)) + (self.scale, self._loss, self._w_delta())
+        elif self._loss == _lib.ZF_LOSS_POISSON:   # (its entries take the weights, or NULL)
             name, args = self._eval_name, self._lead(_dp(self._w)) + (self.scale,)
         elif self._w is not None:
             name, args = self._ENTRY["weval"], self._lead(_dp(self._w)) + (self.scale, self._loss, self._w_delta())
@@ -309,6 +350,10 @@ class _GapMixin:
         return self._ls(x, True)[1]
 
     def _gap_call(self, lib, x, out):
+        if self._f32:   # (one entry for every loss; penalty factors and l2 > 0 are refused together)
+            _lib.check(lib.zf_f32_gap_eval(*self._lead_pf(), self.scale, self.lam, self.l2, self._loss, self._w_delta(),
+                                           C.c_void_p(_lib.ptr(x)), C.c_void_p(_lib.ptr(out)), out.size), "zf_f32_gap_eval")
+            return
         if self._pf is not None:   # (l2 = 0: refused together)
             name = self._ENTRY["gap_pf"]
             _lib.check(getattr(lib, name)(*self._lead_pf(), self.scale, self.lam, self._loss, self._w_delta(), C.c_void_p(_lib.ptr(x)),
@@ -346,6 +391,8 @@ class _GapMixin:
             fields["huber_delta"] = self.delta
         if self._loss == _lib.ZF_LOSS_POISSON:
             fields["poisson"] = True
+        if self._f32:   # (zf_solver_create takes the same address as A; after zf_solver_set_matrix_f32 nothing reads it)
+            fields["matrix_f32"] = self.A.data_ptr()
         if self._pf is not None:
             fields["penalty_factors"] = self._pf.data_ptr()
             keep = keep + (self._pf,)
@@ -450,8 +497,17 @@ class _GapMixin:
         _lib.check(lib.zf_host_asum(C.c_void_p(_lib.ptr(x)), x.size, C.byref(s)), "zf_host_asum")
         return None, np.float64(self.lam * s.value)
 
+    _F32_NO_SCREEN = ("the matrix is stored in fp32 (matrix_dtype='float32'): the column-norm and restriction kernels "
+                      "(zf_dense_col_norms, zf_dense_restrict) and the screen's rounding guard read and assume an fp64 A")
+
+    def _f32_refusal(self, what):
+        if self._f32:
+            raise ValueError(f"{what} is not available: {self._F32_NO_SCREEN}")
+
     def _screen_refusal(self):
         """Why this problem cannot be screened (None: it can)."""
+        if self._f32:
+            return self._F32_NO_SCREEN
         if self._pf is not None:
             return ("penalty_factor is set: the gap-safe rule compares against lam p_j, and its rounding guard has to be re-derived "
                     "for g / p; neither is built yet")
@@ -467,6 +523,7 @@ class _GapMixin:
         """|a_j|_2 of every column of A: a float64 CUDA tensor of n_features, computed on the GPU once per matrix."""
         import torch
 
+        self._f32_refusal("column_norms")
         self._pf_refusal("column_norms")
         self._weights_refusal("column_norms")
         h = self._norms
@@ -533,6 +590,7 @@ class _GapMixin:
         the ``Screen`` of ``screen(x)``, a device mask, a host boolean mask, or a host array of column numbers (the columns
         keep their order).  With x_full[keep] = x and zeros elsewhere, f and jac_f of the restricted problem at x are the
         full problem's at x_full (jac_f: its kept entries).  Keeping no column is refused: that problem's solution is x = 0."""
+        self._f32_refusal("restrict")
         self._pf_refusal("restrict")
         self._weights_refusal("restrict")
         why = self._gap_refusal()
@@ -644,14 +702,48 @@ class _DenseMarginsL1(_GapMixin, NativeProblem):
     def _lead_pf(self):
         return self._lead(_dp(self._w), _dp(self._pf))
 
-    def _set(self, A, b, lam, scale, bounds, l2=0.0, sample_weight=None, group=None, penalty_factor=None):
+    @property
+    def matrix_dtype(self):
+        """How A is stored in HBM: "float64" or "float32"."""
+        return "float32" if self._f32 else "float64"
+
+    def with_matrix_dtype(self, dtype):
+        """A sibling problem whose matrix is stored as ``dtype`` ("float32" or "float64") that SHARES b, the sample weights and the
+        penalty factors.  Its matrix is a copy made on the device (``A.to(torch.float32)``: rounded to nearest; or widened, which
+        is exact) and it holds no reference to this problem's; a problem that already stores ``dtype`` returns a plain sibling
+        (nothing is copied).  An fp32 problem solves, in fp64 arithmetic, exactly the fp64 problem on ``A.to(torch.float64)``: both
+        sweeps of a trial read half the bytes, everything else is unchanged (csrc/zf_kernels_gemv_f32.h).  No screening on it."""
+        import copy
+
+        import torch
+
+        name = _matrix_dtype(dtype)
+        sib = copy.copy(self)
+        if name == self.matrix_dtype:
+            return sib
+        if name == "float32":
+            if getattr(self, "group", None) is not None:
+                raise ValueError("matrix_dtype='float32' is not available with group=: the fp32 sweeps are built for one GPU (world = 1)")
+            A32 = self.A.to(torch.float32)
+            if not bool(torch.isfinite(A32).all()):
+                raise ValueError("A holds a value that is not finite as float32 (NaN, an infinity, or a magnitude beyond 3.4e38)")
+            sib.A, sib._f32 = A32, True
+        else:
+            sib.A, sib._f32 = self.A.to(torch.float64), False
+        sib._norms = _ColumnNorms()
+        return sib
+
+    def _set(self, A, b, lam, scale, bounds, l2=0.0, sample_weight=None, group=None, penalty_factor=None, matrix_dtype=None):
+        self._f32 = _matrix_dtype(matrix_dtype) == "float32"   # (every ValueError before anything touches the device)
+        if self._f32 and group is not None:
+            raise ValueError("matrix_dtype='float32' is not available with group=: the fp32 sweeps are built for one GPU (world = 1)")
         self.l2 = _check_l2(l2)
         if sample_weight is not None:   # (every ValueError before anything touches the device)
             sample_weight = _check_weights(sample_weight, int(np.shape(b)[0]) if np.ndim(b) == 1 else -1, group)
         if penalty_factor is not None:
             shape = tuple(getattr(A, "shape", None) or np.shape(A))
             penalty_factor = _check_penalty_factor(penalty_factor, int(shape[1]) if len(shape) == 2 else -1, group, self.l2)
-        self.A = _to_device(A, "A")
+        self.A = _to_device_f32(A, "A") if self._f32 else _to_device(A, "A")
         self.b = _to_device(b, "b")
         if self.A.ndim != 2 or self.b.ndim != 1 or self.A.shape[0] != self.b.shape[0]:
             raise ValueError("A must be (m, n) and b (m,)")
@@ -696,19 +788,21 @@ class LeastSquaresL1(_DenseMarginsL1):
     kind = _lib.ZF_PROBLEM_LEAST_SQUARES_L1
     taylor_remainder = True   # acceptance="remainder": R = scale |A (x+ - y)|^2 from the residual kernels at x+
 
-    def __init__(self, A, b, lam, scale=0.5, bounds=None, group=None, shard="columns", l2=0.0, *, sample_weight=None, penalty_factor=None):
+    def __init__(self, A, b, lam, scale=0.5, bounds=None, group=None, shard="columns", l2=0.0, *, sample_weight=None, penalty_factor=None,
+                 matrix_dtype=None):
         """With ``group`` set and ``shard="columns"`` (default), ``A`` is this rank's column block A_p
         (m x n_p, row-major) of a matrix whose columns - and the decision vector - are partitioned
         over the ranks of that process group; ``b`` is replicated; the solve exchanges the m-vector
         A_p x_p once per trial.  ``shard="rows"``: ``A`` (m_p x n) and ``b`` (m_p) are this rank's ROW
         block, x is replicated on every rank (pass the whole x0) and the n-vector A_p^T r_p is
         exchanged instead - the layout for tall matrices.  ``f`` / ``jac_f`` as plain callables
-        refer to the local block only."""
+        refer to the local block only.  ``matrix_dtype="float32"`` stores A in single precision (``with_matrix_dtype``): a float32
+        CUDA tensor is adopted as it is, anything else is rounded to nearest; not with ``group``."""
         if shard not in ("columns", "rows"):
             raise ValueError("shard must be 'columns' or 'rows'")
         self.shard = shard
         _check_l2(l2, group)
-        self._set(A, b, lam, scale, bounds, l2, sample_weight, group, penalty_factor)
+        self._set(A, b, lam, scale, bounds, l2, sample_weight, group, penalty_factor, matrix_dtype)
         self.group = group
 
     def _descriptor(self):
@@ -935,10 +1029,11 @@ class HuberL1(_HuberMixin, _DenseMarginsL1):
 
     kind = _lib.ZF_PROBLEM_LEAST_SQUARES_L1
 
-    def __init__(self, A, b, lam, delta, scale=0.5, bounds=None, l2=0.0, *, group=None, sample_weight=None, penalty_factor=None):
+    def __init__(self, A, b, lam, delta, scale=0.5, bounds=None, l2=0.0, *, group=None, sample_weight=None, penalty_factor=None,
+                 matrix_dtype=None):
         self._refuse_group(group)
         self.delta = _check_delta(delta)
-        self._set(A, b, lam, scale, bounds, l2, sample_weight, penalty_factor=penalty_factor)
+        self._set(A, b, lam, scale, bounds, l2, sample_weight, penalty_factor=penalty_factor, matrix_dtype=matrix_dtype)
 
 
 class SparseHuberL1(_HuberMixin, _SparseMarginsL1):
@@ -1013,13 +1108,14 @@ class PoissonL1(_PoissonMixin, _DenseMarginsL1):
 
     kind = _lib.ZF_PROBLEM_LEAST_SQUARES_L1
 
-    def __init__(self, A, b, lam, scale=1.0, bounds=None, l2=0.0, *, group=None, sample_weight=None, penalty_factor=None):
+    def __init__(self, A, b, lam, scale=1.0, bounds=None, l2=0.0, *, group=None, sample_weight=None, penalty_factor=None,
+                 matrix_dtype=None):
         self._refuse_group(group)
         shape = tuple(getattr(A, "shape", np.shape(A)))
         if len(shape) != 2:
             raise ValueError("A must be (m, n) and b (m,)")
         _check_counts(b, shape[0])
-        self._set(A, b, lam, scale, bounds, l2, sample_weight, penalty_factor=penalty_factor)
+        self._set(A, b, lam, scale, bounds, l2, sample_weight, penalty_factor=penalty_factor, matrix_dtype=matrix_dtype)
 
 
 class SparsePoissonL1(_PoissonMixin, _SparseMarginsL1):
