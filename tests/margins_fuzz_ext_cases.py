@@ -41,6 +41,7 @@ iterations of a step beyond 2 / L: there Poisson's lr comes from 10^(-4.5 .. -3.
 import contextlib
 import functools
 import io
+import sys
 import warnings
 from collections import namedtuple
 
@@ -205,12 +206,13 @@ class ExtRef:
     """The four closures of a case on either storage form (module docstring).  ``nonfinite_f`` counts the returns of f that
     were not finite - for Poisson the trials whose margins overflow exp."""
 
-    def __init__(self, case, storage="csr", second=False):
+    def __init__(self, case, storage="csr", second=False, cases=None):
+        T = _table(cases)
         sp_ = case.spec
-        A = case.A if storage == "csr" else dense(sp_.loss, sp_.shape)
+        A = case.A if storage == "csr" else T.dense(sp_.loss, sp_.shape)
         b, w = case.b, case.w
         if second:
-            A, b, w = dense_reversed(sp_.loss, sp_.shape), b[::-1].copy(), None if w is None else w[::-1].copy()
+            A, b, w = T.dense_reversed(sp_.loss, sp_.shape), b[::-1].copy(), None if w is None else w[::-1].copy()
         p = np.ones(sp_.shape[1]) if case.p is None else case.p
         self.rows = PF.PenaltyRef(A, b, case.lam, p, sp_.loss, case.delta, sp_.scale, sp_.bounds, w)
         self.library = second and sp_.loss == "logistic"
@@ -264,8 +266,8 @@ class ExtRef:
         return self.f, self.g, self.jac_f, self.prox_wsum_g
 
 
-def make_ref(case, storage="csr", second=False):
-    return ExtRef(case, storage, second)
+def make_ref(case, storage="csr", second=False, cases=None):
+    return ExtRef(case, storage, second, cases)
 
 
 def _cls(loss, storage):
@@ -306,34 +308,41 @@ _ORACLE = {}
 Oracle = namedtuple("Oracle", "case options exp nonfinite_f")
 
 
-def oracle(spec):
+def _table(cases):
+    """The table module a call is about: this one, or one built on it (``cases``: its own SHAPES, TABLE, draw, build, dense,
+    dense_reversed and _ORACLE - tests/f32_fuzz_cases.py)."""
+    return sys.modules[__name__] if cases is None else cases
+
+
+def oracle(spec, cases=None):
     """(case, options after the stagnation cut, the oracle's result on the closures over the CSR matrix, how many returns of f
     were not finite in that run): one run per case, shared by both storage forms and both test files; read-only."""
+    T = _table(cases)
     key = (spec.loss, spec.seed)
-    if key not in _ORACLE:
-        case = build(spec)
+    if key not in T._ORACLE:
+        case = T.build(spec)
         o = dict(spec.options)
-        ref = make_ref(case)
+        ref = make_ref(case, cases=cases)
         exp = run_ref(ref, case.x0, o)
         cut = stagnation_cut(exp)
         if cut is not None:
             o["max_iter"] = cut
-            ref = make_ref(case)
+            ref = make_ref(case, cases=cases)
             exp = run_ref(ref, case.x0, o) if cut >= 1 else None
-        _ORACLE[key] = Oracle(case, o, exp, ref.nonfinite_f)
-    return _ORACLE[key]
+        T._ORACLE[key] = Oracle(case, o, exp, ref.nonfinite_f)
+    return T._ORACLE[key]
 
 
-def other_form(spec):
+def other_form(spec, cases=None):
     """The second CPU evaluation of a case, under the cut options."""
-    orc = oracle(spec)
-    return run_ref(make_ref(orc.case, second=True), orc.case.x0, orc.options)
+    orc = oracle(spec, cases)
+    return run_ref(make_ref(orc.case, second=True, cases=cases), orc.case.x0, orc.options)
 
 
-def accepted(spec):
+def accepted(spec, cases=None):
     """None if the case meets what tests/test_margins_fuzz_ext_cases.py asks of every case (decision-stable between the two
     evaluations, every accepted F finite, F(x0) = inf only outside the box, a run left after the stagnation cut); else why not."""
-    case, o, exp, _ = oracle(spec)
+    case, o, exp, _ = oracle(spec, cases)
     if exp is None:
         return "no run left"
     if ending(exp) != "error" and exp.nit < 1:
@@ -342,15 +351,16 @@ def accepted(spec):
         return "an accepted F is not finite"
     if not (np.isfinite(exp.allfuns[0]) or outside_box(case)):
         return "F(x0) is not finite inside the box"
-    other = other_form(spec)
+    other = other_form(spec, cases)
     return disagreement(exp, other) or disagreement(other, exp)
 
 
-def resume_cases():
+def resume_cases(cases=None):
     """[(spec, kind)]: per loss the table's longest run that ends by tol and its longest that ends in the error path."""
+    T = _table(cases)
     out = []
     for loss in LOSSES:
-        runs = [(draw(c, s), oracle(draw(c, s)).exp) for c, s in TABLE if c == loss]
+        runs = [(T.draw(c, s), oracle(T.draw(c, s), cases).exp) for c, s in T.TABLE if c == loss]
         for kind in ("tol", "error"):
             nit, spec = max(((exp.nit, sp) for sp, exp in runs if ending(exp) == kind), key=lambda t: (t[0], -t[1].seed))
             out.append((spec, kind))
@@ -368,7 +378,9 @@ def ones_cases():
     return out
 
 
-def extra_block(k):
+def extra_block(k, cases=None):
     """Block k >= 1 of further seeds (ZF_FUZZ_SCALE): outside the CPU-checked table, so a case that ``accepted`` turns down is
     dropped here - before any GPU work."""
-    return [(loss, seed) for loss in LOSSES for seed in range(1000 * k, 1000 * k + BLOCK) if accepted(draw(loss, seed)) is None]
+    T = _table(cases)
+    return [(loss, seed) for loss in LOSSES for seed in range(1000 * k, 1000 * k + BLOCK)
+            if accepted(T.draw(loss, seed), cases) is None]

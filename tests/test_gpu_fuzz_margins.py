@@ -93,7 +93,7 @@ def _check_trace(rows, exp):
 def _check_storage(case, storage, o, exp, solve, cases=M, keep=None):
     """Both solves and the chunked run of one storage form against the oracle's result; returns the lr / trial columns.
     ``cases``: the table module the case comes from (its make_problem and dense_form); ``keep``: a dict that receives the
-    problem and what the two solves returned, for a caller with further checks on them."""
+    problem, what the two solves returned and the solver's ls_plan, for a caller with further checks on them."""
     from zfista_amd import _lib
     from zfista_amd.proximal_gradient import NativeRun
 
@@ -102,7 +102,7 @@ def _check_storage(case, storage, o, exp, solve, cases=M, keep=None):
     res, rows, plan = solve(prob, x0, return_all=True, **o)
     res1, rows1, plan1 = solve(prob, x0, return_all=False, **o)
     if keep is not None:
-        keep.update(prob=prob, res=res, rows=rows, res1=res1, rows1=rows1)
+        keep.update(prob=prob, res=res, rows=rows, res1=res1, rows1=rows1, plan=plan)
     assert plan == plan1 and plan[0] == (M.CSR if storage == "csr" else cases.dense_form(spec)), (plan, plan1)
     ref_keys = set(exp.keys()) - {"alllrs", "alltrials"}       # (the oracle's two extra fields)
     for r, tr in ((res, rows), (res1, rows1)):
@@ -168,7 +168,7 @@ def _check_resume(case, o, exp, kind, tmp_path, cases=M):
 
     assert M.ending(exp) == kind
     want = {"tol": _lib.ZF_CONVERGED, "error": _lib.ZF_BACKTRACK_FAILED}[kind]
-    for storage in M.FORMS:
+    for storage in cases.FORMS:   # (every table module has M.FORMS but the fp32 one, which has no CSR form)
         prob = cases.make_problem(case, storage)
         whole = NativeRun(prob, case.x0, FULL | o)
         ref_rows, chunks = _drain(whole)
