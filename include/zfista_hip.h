@@ -391,6 +391,11 @@ int zf_solver_launch_counts(zf_solver* s, int64_t* out, int64_t count /* >= 2 */
  * A dense matrix stored in fp32 (zf_solver_set_matrix_f32, either dense kind): out[0] = 6, 7 or 8 - the column sweep
  * zf_gemvT_partial_f32_kernel<4> (16-byte loads of four floats, n % 4 == 0), <2> (8-byte loads, n % 4 == 2), <1> (odd n) -
  * out[1] = 4, 5 or 6 - the row sweep zf_gemv_rows_f32_kernel<4>, <2>, <1> - out[2], out[3] the slices of the fp32 rule.
+ * K responses (zf_solver_set_responses, either dense kind): out[0] = 9 or 10 - the column sweep zf_mr_cols_partial_kernel<K, 2>
+ * (16-byte loads, even n) or <K, 1> (odd n; n the matrix's own column count) - out[1] = 7 or 8 - the row sweep
+ * zf_mr_rows_kernel<K, 2>, <K, 1> - out[2], out[3] the slices of that rule on the matrix's own shape.
+ * count >= 6 (dense kinds; what the first four slots hold does not depend on count): out[4] = K (1 without the setter), out[5] = the
+ * rows a workgroup of the K-response row sweep owns (0 without the setter).
  * Other problems: zeros. */
 int zf_solver_ls_plan(zf_solver* s, int64_t* out, int64_t count /* >= 4 */);
 /* the same window split by the shape of the pass, which the kernel logs itself: out[0], out[1] = mean
@@ -790,6 +795,33 @@ int zf_f32_eval(const float* A32_dev, const double* b_dev, const double* w_dev, 
 int zf_f32_gap_eval(const float* A32_dev, const double* b_dev, const double* w_dev, const double* p_dev, int64_t m_rows, int64_t n,
                     double scale, double lam, double l2, int32_t loss, double delta, const double* x_host, double* out,
                     int64_t count /* >= 8; 10 for all */);
+
+/* ---- K responses on one dense matrix, on the two dense kinds 2, 5 ---------------------------------------------------------------
+ * X in R^{n x K}, B in R^{m x K}: f(X) = scale sum_k sum_i W_ik phi((A x_k)_i ; B_ik), g(X) = lam sum_jk P_jk |X_jk| (+ the ridge term,
+ * + a box) is the margins problem of the matrix A (x) I_K on vectors flattened in C order: x[j K + k] = X[j][k], b[i K + k] = B[i][k].
+ * Everything element-wise around the two sweeps runs unchanged on m K and n K entries; the sweeps (csrc/zf_kernels_mr.h) multiply A
+ * into K columns and read A once, so K solves cost one solve's bytes.  Additive to ABI 6: no struct field, no version change.
+ * zf_solver_set_responses: after zf_solver_create, before zf_solver_enqueue_init / zf_solver_restore.  The solver was created with
+ * desc->m_rows = m K, desc->n = n K, desc->A the m x n matrix, desc->b the m K targets (labels +-1 for the logistic kind).  From then
+ * on every sweep of the solver - the trial's two, the initial evaluation and zf_solver_restore, zf_solver_duality_gap - takes the
+ * K-response kernels, the slices are those of the rule on m x n, the unweighted squared loss forms its residuals with up to 1024
+ * workgroups beyond 32768 rows of m K (as the sparse kind does), a matrix small enough for the two fused small-matrix launches takes
+ * the general path, ZF_GEMV_MFMA has no effect, and zf_solver_ls_plan says so.
+ * ZF_ERR_ARG: K outside 2 .. 16, m_rows or n not a multiple of K, a kind other than ZF_PROBLEM_LEAST_SQUARES_L1 /
+ * ZF_PROBLEM_LOGISTIC_L1, world > 1, ZF_ACCEPT_REMAINDER / ZF_ACCEPT_RESOLVED, a solver with zf_solver_set_huber / _poisson /
+ * _matrix_f32 (and those three after this one), a second call.  ZF_ERR_STATE: a solver that is already initialised.  Composes with
+ * zf_solver_set_l2 / _row_weights (m K weights) / _penalty_factors (n K factors) in any order.  A resumed solve sets the responses
+ * again before zf_solver_restore.  A solver that was never asked launches and allocates what it did. */
+int zf_solver_set_responses(zf_solver* s, int32_t K);
+/* f and (grad_out_host != NULL) grad at a host vector of n K doubles for such a problem.  A_dev: m_rows x n; b_dev, w_dev (or NULL):
+ * m_rows K doubles; loss: ZF_LOSS_SQUARE or ZF_LOSS_LOGISTIC.  ZF_ERR_ARG: K outside 2 .. 16, another loss, and as zf_wloss_eval. */
+int zf_mr_eval(const double* A_dev, const double* b_dev, const double* w_dev, int64_t m_rows, int64_t n, int32_t K, double scale,
+               int32_t loss, const double* x_host, double* f_out, double* grad_out_host /* or NULL */);
+/* The certificate of such a problem: out, l2 and p_dev (n K positive factors or NULL) as zf_f32_gap_eval.  One alpha scales the dual
+ * candidate of all K responses, so it is feasible for each of them and the gap is a sum of K non-negative gaps.
+ * zf_solver_duality_gap of a solver with zf_solver_set_responses writes the same values, bit for bit. */
+int zf_mr_gap_eval(const double* A_dev, const double* b_dev, const double* w_dev, const double* p_dev, int64_t m_rows, int64_t n, int32_t K,
+                   double scale, double lam, double l2, int32_t loss, const double* x_host, double* out, int64_t count /* >= 8; 10 for all */);
 
 /* ---- multi-objective trial (m >= 2), device side ---------------------------
  * The dual of the scalarised subproblem is minimised on the host by SciPy exactly

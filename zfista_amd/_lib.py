@@ -263,6 +263,10 @@ SIGNATURES = {
     "zf_f32_eval": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_double, C.c_int32, C.c_double, _P, C.POINTER(C.c_double), _P]),
     "zf_f32_gap_eval": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_double, _P, _P,
                                   C.c_int64]),
+    "zf_solver_set_responses": (C.c_int, [_P, C.c_int32]),
+    "zf_mr_eval": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_int32, C.c_double, C.c_int32, _P, C.POINTER(C.c_double), _P]),
+    "zf_mr_gap_eval": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int64, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_int32, _P, _P,
+                                 C.c_int64]),
 }
 
 _lib = None

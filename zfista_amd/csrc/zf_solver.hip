@@ -19,6 +19,7 @@
 #include "zf_kernels_gemv.h"
 #include "zf_kernels_ls_small.h"
 #include "zf_kernels_gemv_f32.h"
+#include "zf_kernels_mr.h"
 #include "zf_kernels_op.h"
 #include "zf_spmv.h"
 #include "zf_screen.h"
@@ -255,6 +256,7 @@ struct zf_solver {
     bool gemv_mfma = false;       // A^T r on v_mfma_f64_16x16x4 (n % 32 == 0; ZF_GEMV_MFMA=0 disables)
     bool ls_small = false;        // cache-resident A: two fused launches per trial (zf_kernels_ls_small.h)
     const float* A32 = nullptr;   // the matrix stored in fp32 (zf_solver_set_matrix_f32; borrowed as desc.A is): every sweep takes zf_kernels_gemv_f32.h and nothing reads desc.A; NULL: what ran before
+    int K = 1;                    // responses (zf_solver_set_responses): desc.A is (m_rows / K) x (n / K), the vectors are response-interleaved and every sweep takes zf_kernels_mr.h; 1: what ran before
     double huber = 0.0;           // Huber's loss (zf_solver_set_huber): delta > 0 swaps the residual kernels for zf_kernels_huber.h; 0: the squared loss
     bool poisson = false;         // the Poisson loss (zf_solver_set_poisson): the residual kernels swapped for zf_kernels_poisson.h
     bool loss_part = false;       // the dense least-squares kind holds the 2 x ZF_SPMV_RESID_MAX_CHUNKS chunk sums of the loss kernels (zf_loss_part)
@@ -550,6 +552,10 @@ static void zf_launch_apply_A(zf_solver* s, const zf_control* ctl, zf_ring3 xr, 
     }
     if (s->A32) {
         zf_launch_rows_f32(s->stream, ctl, s->A32, xr, sout, slot, m, n);
+        return;
+    }
+    if (s->K > 1) {
+        zf_launch_mr_rows(s->stream, ctl, d.A, xr, sout, slot, m / s->K, n / s->K, s->K);
         return;
     }
     const int V = (n % 2 == 0) ? 2 : 1;
@@ -1446,7 +1452,10 @@ static int zf_launch_trial(zf_solver* s, bool decide_in_launch, bool dry = false
         if (time_whole && e0) ZF_HIP(hipEventRecord(e0, s->stream));
         // (1) r = A y - b by linearity, f(y); grad = 2 scale A^T r   [only when y changed]
         // (sparse matrices have 1e5 .. 1e7 rows: beyond what one workgroup should walk, the residuals take many - zf_kernels_spmv.h)
-        const bool wide_resid = d.kind == ZF_PROBLEM_SPARSE_LS_L1 && m > ZF_SPMV_WIDE_RESID_MIN_ROWS;
+        // (K responses: m is m K rows of the interleaved margins - the same threshold on the same count, so the order of f is a
+        //  function of the row count alone)
+        const bool wide_resid = (d.kind == ZF_PROBLEM_SPARSE_LS_L1 || (s->K > 1 && d.kind == ZF_PROBLEM_LEAST_SQUARES_L1)) &&
+                                m > ZF_SPMV_WIDE_RESID_MIN_ROWS;
         if (!zf_launch_loss_y(s->stream, s->ctl, s->sring.p[0], s->sring.p[1], s->sring.p[2], d.b, loss, s->resid, d.scale, m,
                               (int)s->opt.nesterov, s->row_part, s->ls_scal + 0)) {
             if (wide_resid)
@@ -1551,6 +1560,8 @@ static int zf_launch_trial(zf_solver* s, bool decide_in_launch, bool dry = false
         }
         if (s->A32) {
             zf_launch_cols_f32(s->stream, s->ctl, s->A32, s->resid, s->slab, m, n, s->slices, s->rows_per_slice);
+        } else if (s->K > 1) {
+            zf_launch_mr_cols(s->stream, s->ctl, d.A, s->resid, s->slab, m / s->K, n / s->K, s->K, s->slices, s->rows_per_slice);
         } else if (s->gemv_mfma) {
             dim3 gM((unsigned)((n + GEMVT_MFMA_COLS - 1) / GEMVT_MFMA_COLS), (unsigned)s->slices);
             hipLaunchKernelGGL(zf_gemvT_partial_mfma_kernel, gM, dim3(ZF_BLOCK), 0, s->stream, s->ctl, d.A,
@@ -1594,6 +1605,8 @@ static int zf_launch_trial(zf_solver* s, bool decide_in_launch, bool dry = false
         if (gr > 8 * ZF_MAX_GRID) gr = 8 * ZF_MAX_GRID;
         if (s->A32)
             zf_launch_rows_f32(s->stream, s->ctl, s->A32, xr, sout, 1, m, n);
+        else if (s->K > 1)
+            zf_launch_mr_rows(s->stream, s->ctl, d.A, xr, sout, 1, m / s->K, n / s->K, s->K);
         else if (V == 2)
             hipLaunchKernelGGL(zf_gemv_rows_kernel<2>, dim3(gr), dim3(ZF_BLOCK), 0, s->stream, s->ctl, d.A,
                                xr, sout, 1, m, n);
@@ -1602,8 +1615,13 @@ static int zf_launch_trial(zf_solver* s, bool decide_in_launch, bool dry = false
                                xr, sout, 1, m, n);
         if (d.world == 1) {
             if (!zf_launch_loss_x(s->stream, s->ctl, s->sring.p[0], s->sring.p[1], s->sring.p[2], 1, d.b, loss, d.scale, m,
-                                  s->row_part + ZF_SPMV_RESID_MAX_CHUNKS, s->ls_scal + 1))
-                zf_launch_resid_x(s);
+                                  s->row_part + ZF_SPMV_RESID_MAX_CHUNKS, s->ls_scal + 1)) {
+                if (wide_resid)   // (K responses beyond the threshold; the sparse kind returned above)
+                    zf_launch_spmv_resid_x(s->stream, s->ctl, s->sring.p[0], s->sring.p[1], s->sring.p[2], 1, d.b, d.scale, m,
+                                           s->row_part + ZF_SPMV_RESID_MAX_CHUNKS, s->ls_scal + 1);
+                else
+                    zf_launch_resid_x(s);
+            }
             zf_launch_finalize(s, decide_in_launch);
         }
     }
@@ -2004,6 +2022,7 @@ extern "C" int zf_solver_set_huber(zf_solver* s, double delta) {
     ZF_REQUIRE(delta > 0.0 && delta <= DBL_MAX, "zf_solver_set_huber: delta must be finite and > 0");
     ZF_REQUIRE(!s->rem, "zf_solver_set_huber: not with ZF_ACCEPT_REMAINDER (scale |A (x+ - y)|^2 is not the Taylor remainder of this loss)");
     ZF_REQUIRE(!s->poisson, "zf_solver_set_huber: the solver already has the Poisson loss (zf_solver_set_poisson)");
+    ZF_REQUIRE(s->K == 1, "zf_solver_set_huber: not with several responses (zf_solver_set_responses)");
     const int rc = zf_loss_part(s);
     if (rc) return rc;
     s->huber = delta;
@@ -2023,6 +2042,7 @@ extern "C" int zf_solver_set_poisson(zf_solver* s) {
     ZF_REQUIRE(!s->rem, "zf_solver_set_poisson: not with ZF_ACCEPT_REMAINDER (scale |A (x+ - y)|^2 is not the Taylor remainder of this loss)");
     ZF_REQUIRE(!s->res, "zf_solver_set_poisson: not with ZF_ACCEPT_RESOLVED");
     ZF_REQUIRE(!(s->huber > 0.0), "zf_solver_set_poisson: the solver already has Huber's loss (zf_solver_set_huber)");
+    ZF_REQUIRE(s->K == 1, "zf_solver_set_poisson: not with several responses (zf_solver_set_responses)");
     const int rc = zf_loss_part(s);
     if (rc) return rc;
     s->poisson = true;
@@ -2058,6 +2078,7 @@ extern "C" int zf_solver_set_matrix_f32(zf_solver* s, const float* A32_dev) {
     ZF_REQUIRE(zf_is_dense_mat(d.kind),"zf_solver_set_matrix_f32: only for ZF_PROBLEM_LEAST_SQUARES_L1 and ZF_PROBLEM_LOGISTIC_L1");
     ZF_REQUIRE(d.world == 1, "zf_solver_set_matrix_f32: not for a sharded solve (world > 1)");
     ZF_REQUIRE(zf_aligned16(A32_dev), "zf_solver_set_matrix_f32: the matrix must be 16-byte aligned");
+    ZF_REQUIRE(s->K == 1, "zf_solver_set_matrix_f32: not with several responses (zf_solver_set_responses)");
     int slices = 1;
     int64_t rows_per_slice = d.m_rows;
     zf_dense_slices_f32(d.m_rows, d.n, &slices, &rows_per_slice);
@@ -2072,6 +2093,39 @@ extern "C" int zf_solver_set_matrix_f32(zf_solver* s, const float* A32_dev) {
     s->A32 = A32_dev;
     s->gemv_mfma = false;  // (the MFMA column sweep reads fp64 A: ZF_GEMV_MFMA has no effect here)
     s->ls_small = false;   // (the fused small-matrix kernels read fp64 A: the general path, as the logistic kind)
+    return ZF_OK;
+}
+
+// K responses on one matrix (include/zfista_hip.h): between create and init, on the two dense kinds.
+extern "C" int zf_solver_set_responses(zf_solver* s, int32_t K) {
+    ZF_REQUIRE(s, "zf_solver_set_responses: null argument");
+    if (s->init_enqueued || s->initialised)
+        return zf_fail(ZF_ERR_STATE, "zf_solver_set_responses: call after zf_solver_create and before zf_solver_enqueue_init / zf_solver_restore%s%s");
+    const zf_problem_desc& d = s->desc;
+    ZF_REQUIRE(zf_is_dense_mat(d.kind), "zf_solver_set_responses: only for ZF_PROBLEM_LEAST_SQUARES_L1 and ZF_PROBLEM_LOGISTIC_L1");
+    ZF_REQUIRE(d.world == 1, "zf_solver_set_responses: not for a sharded solve (world > 1)");
+    ZF_REQUIRE(K >= 2 && K <= ZF_MR_MAX_K, "zf_solver_set_responses: K must be 2 .. 16");
+    ZF_REQUIRE(s->K == 1, "zf_solver_set_responses: the solver already has its responses");
+    ZF_REQUIRE(d.m_rows % K == 0 && d.n % K == 0, "zf_solver_set_responses: m_rows and n of the solver must be multiples of K (they are m K and n K)");
+    ZF_REQUIRE(!s->rem && !s->res, "zf_solver_set_responses: not with ZF_ACCEPT_REMAINDER or ZF_ACCEPT_RESOLVED");
+    ZF_REQUIRE(!(s->huber > 0.0) && !s->poisson, "zf_solver_set_responses: not with Huber's or the Poisson loss (zf_solver_set_huber, zf_solver_set_poisson)");
+    ZF_REQUIRE(!s->A32, "zf_solver_set_responses: not with a matrix stored in fp32 (zf_solver_set_matrix_f32)");
+    const int rc = zf_loss_part(s);   // (the wide residual kernels beyond ZF_SPMV_WIDE_RESID_MIN_ROWS rows write chunk sums)
+    if (rc) return rc;
+    int slices = 1;
+    int64_t rows_per_slice = d.m_rows / K;
+    zf_mr_slices(d.m_rows / K, d.n / K, &slices, &rows_per_slice);
+    if (slices > s->slices) {   // (the rule runs on A's own shape: it may take more slices than the slab of zf_solver_create holds)
+        double* slab = nullptr;
+        ZF_HIP(hipMalloc(&slab, sizeof(double) * slices * d.n));
+        if (s->slab) (void)hipFree(s->slab);
+        s->slab = slab;
+    }
+    s->slices = slices;
+    s->rows_per_slice = rows_per_slice;
+    s->K = K;
+    s->gemv_mfma = false;  // (no MFMA form of the K-response sweeps)
+    s->ls_small = false;   // (the fused small-matrix kernels hold one response: the general path, as the logistic kind)
     return ZF_OK;
 }
 
@@ -2119,7 +2173,7 @@ extern "C" int zf_solver_ls_plan(zf_solver* s, int64_t* out, int64_t count) {
         return ZF_OK;
     }
     if (!zf_is_dense_mat(s->desc.kind)) return ZF_OK;
-    const bool odd = s->desc.n % 2 != 0;
+    const bool odd = (s->desc.n / s->K) % 2 != 0;   // (K responses: the parity of the matrix's own column count)
     out[0] = s->ls_small ? 1 : s->gemv_mfma ? 2 : odd ? 4 : 3;
     out[1] = s->ls_small ? 1 : odd ? 3 : 2;
     if (s->A32) {   // zf_kernels_gemv_f32.h: 16-byte, 8-byte or scalar loads of floats
@@ -2127,8 +2181,16 @@ extern "C" int zf_solver_ls_plan(zf_solver* s, int64_t* out, int64_t count) {
         out[0] = V == 4 ? 6 : V == 2 ? 7 : 8;
         out[1] = V == 4 ? 4 : V == 2 ? 5 : 6;
     }
+    if (s->K > 1) {   // zf_kernels_mr.h: 16-byte or scalar loads of A, K right-hand sides
+        out[0] = odd ? 10 : 9;
+        out[1] = odd ? 8 : 7;
+    }
     out[2] = s->slices;
     out[3] = s->rows_per_slice;
+    if (count >= 6) {   // responses, and the rows a workgroup of the row sweep owns (0: the plain sweeps' own constant)
+        out[4] = s->K;
+        out[5] = s->K > 1 ? zf_mr_rows_per_wg(s->K) : 0;
+    }
     return ZF_OK;
 }
 
@@ -2652,10 +2714,14 @@ struct zf_matview {
     const zf_spmat* h;   // CSR: A and A^T with their plans; NULL for dense
     bool csr;
     const float* A32;    // dense, stored in fp32 (zf_kernels_gemv_f32.h): m x n row-major (device), 16-byte aligned - A is NULL then; NULL otherwise
+    int k = 1;           // responses (zf_kernels_mr.h; dense fp64 only): m and n stay the matrix's, the vectors hold m k and n k doubles
 };
+static int64_t zf_view_rows(const zf_matview& V) { return V.m * V.k; }   // length of a margins vector
+static int64_t zf_view_cols(const zf_matview& V) { return V.n * V.k; }   // length of a decision vector
 static zf_matview zf_dense_view(const double* A, int64_t m, int64_t n) { return zf_matview{A, m, n, nullptr, false, nullptr}; }
 static zf_matview zf_csr_view(const zf_spmat* h) { return zf_matview{nullptr, 0, 0, h, true, nullptr}; }
 static zf_matview zf_dense_view_f32(const float* A32, int64_t m, int64_t n) { return zf_matview{nullptr, m, n, nullptr, false, A32}; }
+static zf_matview zf_dense_view_mr(const double* A, int64_t m, int64_t n, int k) { return zf_matview{A, m, n, nullptr, false, nullptr, k}; }
 
 // what the sweeps write between their launches: the slab of the dense column sweep and its slices, or the segment sums of the
 // split rows of A / A^T (a call's own, or a solver's: the handle is shared with live solvers on other streams)
@@ -2674,8 +2740,9 @@ static int zf_sweep_ws_alloc(const zf_matview& V, bool adjoint, zf_sweep_ws* W) 
         if (adjoint && V.h->At.nseg > 0) ZF_KEEP_FIRST(hipMalloc(&W->part_At, sizeof(double) * V.h->At.nseg));
     } else if (adjoint) {
         if (V.A32) zf_dense_slices_f32(V.m, V.n, &W->slices, &W->rows_per_slice);
+        else if (V.k > 1) zf_mr_slices(V.m, V.n, &W->slices, &W->rows_per_slice);
         else zf_dense_slices(V.m, V.n, &W->slices, &W->rows_per_slice);
-        ZF_KEEP_FIRST(hipMalloc(&W->slab, sizeof(double) * W->slices * V.n));
+        ZF_KEEP_FIRST(hipMalloc(&W->slab, sizeof(double) * W->slices * zf_view_cols(V)));
     }
     return rc;
 }
@@ -2694,6 +2761,10 @@ static void zf_launch_view_apply(const zf_matview& V, hipStream_t st, double* x,
     zf_ring3 xr = {{x, x, x}}, sr = {{z, z, z}};
     if (V.A32) {
         zf_launch_rows_f32(st, nullptr, V.A32, xr, sr, -1, V.m, V.n);
+        return;
+    }
+    if (V.k > 1) {
+        zf_launch_mr_rows(st, nullptr, V.A, xr, sr, -1, V.m, V.n, V.k);
         return;
     }
     int gr = (int)((V.m + GEMV_ROWS - 1) / GEMV_ROWS);
@@ -2715,6 +2786,8 @@ static void zf_launch_view_adjoint(const zf_matview& V, hipStream_t st, const do
     const int vw = (n % 2 == 0) ? 2 : 1;
     if (V.A32) {   // (`mfma` does not apply: that sweep reads fp64 A)
         zf_launch_cols_f32(st, nullptr, V.A32, r, W.slab, m, n, W.slices, W.rows_per_slice);
+    } else if (V.k > 1) {   // (nor here: the K-response sweep has no MFMA form)
+        zf_launch_mr_cols(st, nullptr, V.A, r, W.slab, m, n, V.k, W.slices, W.rows_per_slice);
     } else if (mfma) {
         dim3 gM((unsigned)((n + GEMVT_MFMA_COLS - 1) / GEMVT_MFMA_COLS), (unsigned)W.slices);
         hipLaunchKernelGGL(zf_gemvT_partial_mfma_kernel, gM, dim3(ZF_BLOCK), 0, st, nullptr, V.A, r, W.slab, m, n, W.rows_per_slice);
@@ -2723,7 +2796,8 @@ static void zf_launch_view_adjoint(const zf_matview& V, hipStream_t st, const do
         if (vw == 2) hipLaunchKernelGGL(zf_gemvT_partial_kernel<2>, gT, dim3(ZF_BLOCK), 0, st, nullptr, V.A, r, W.slab, m, n, W.rows_per_slice);
         else hipLaunchKernelGGL(zf_gemvT_partial_kernel<1>, gT, dim3(ZF_BLOCK), 0, st, nullptr, V.A, r, W.slab, m, n, W.rows_per_slice);
     }
-    hipLaunchKernelGGL(zf_gemvT_combine_kernel, dim3(zf_grid_for(n)), dim3(ZF_BLOCK), 0, st, nullptr, W.slab, g, factor, n, W.slices);
+    const int64_t nk = zf_view_cols(V);
+    hipLaunchKernelGGL(zf_gemvT_combine_kernel, dim3(zf_grid_for(nk)), dim3(ZF_BLOCK), 0, st, nullptr, W.slab, g, factor, nk, W.slices);
 }
 
 // The checks every evaluation entry point shares (`who`: the entry's name).  First its pointers (`ok`) and its matrix ...
@@ -2750,7 +2824,7 @@ static int zf_loss_args(const char* who, zf_matview* V, int32_t kind, double del
 // of this loss runs.  The column sweep of a dense A is always the VALU one: jac_f has the same bits whatever n % 32 is.
 static int zf_point_eval(const zf_matview& V, const double* b_dev, double scale, const zf_loss& L, const double* x_host, double* f_out,
                          double* grad_out_host) {
-    const int64_t m = V.m, n = V.n;
+    const int64_t m = zf_view_rows(V), n = zf_view_cols(V);
     const bool own_rows = L.w || L.kind != ZF_LOSS_SQUARE;   // (zf_launch_loss_y / _x return true)
     double *x = nullptr, *z = nullptr, *grad = nullptr, *fdev = nullptr, *rho = nullptr, *part = nullptr;
     zf_sweep_ws W;
@@ -2875,6 +2949,21 @@ extern "C" int zf_f32_eval(const float* A32_dev, const double* b_dev, const doub
                           grad_out_host);
 }
 
+// K responses on one dense fp64 matrix (zf_kernels_mr.h), squared or logistic loss, weighted or not: A_dev is m_rows x n, b_dev /
+// w_dev hold m_rows K and x_host / grad_out_host n K doubles, response-interleaved.  The loss kernels see m_rows K rows.
+static int zf_mr_args(const char* who, int32_t K, int32_t loss) {
+    if (!(K >= 2 && K <= ZF_MR_MAX_K)) return zf_fail(ZF_ERR_ARG, "%s: K must be 2 .. 16%s", who);
+    if (loss != ZF_LOSS_SQUARE && loss != ZF_LOSS_LOGISTIC) return zf_fail(ZF_ERR_ARG, "%s: loss must be ZF_LOSS_SQUARE or ZF_LOSS_LOGISTIC%s", who);
+    return ZF_OK;
+}
+extern "C" int zf_mr_eval(const double* A_dev, const double* b_dev, const double* w_dev, int64_t m_rows, int64_t n, int32_t K, double scale,
+                          int32_t loss, const double* x_host, double* f_out, double* grad_out_host) {
+    const int rc = zf_mr_args("zf_mr_eval", K, loss);
+    if (rc) return rc;
+    return zf_point_entry("zf_mr_eval", zf_dense_view_mr(A_dev, m_rows, n, K), b_dev, true, w_dev, scale, loss, 0.0, x_host, f_out,
+                          grad_out_host);
+}
+
 // f(x) = scale |B W^-1 x - b|^2 and (optionally) jac_f(x) = 2 scale W B (B W^-1 x - b) of the operator problem
 // (zf_kernels_op.h; reference: examples/cameraman.ipynb cell 8) for a host vector: the callbacks of
 // zfista_amd.problems.BlurHaarL1 outside the device-resident loop.  taps_dev: K x K, b_dev: H x W (device).
@@ -2942,7 +3031,7 @@ static void zf_gap_ws_free(zf_gap_ws* ws) {
 // p_dev != NULL (the *_pf entries): penalty factors - g and the call's copy of x are scaled in place between step 2 and the tails
 static int zf_gap_eval_impl(const zf_matview& V, const double* b_dev, double scale, double lam, double l2, const zf_loss& L,
                             const double* x_host, double* out, int64_t out_count, const zf_screen_req* scr, const double* p_dev = nullptr) {
-    const int64_t m = V.m, n = V.n;
+    const int64_t m = zf_view_rows(V), n = zf_view_cols(V);
     zf_gap_ws ws = {nullptr, nullptr, nullptr, nullptr};
     zf_sweep_ws W = {nullptr, 1, m, nullptr, nullptr};
     double *x = nullptr, *z = nullptr, *scr_scal = nullptr;
@@ -2956,7 +3045,7 @@ static int zf_gap_eval_impl(const zf_matview& V, const double* b_dev, double sca
     ZF_KEEP_FIRST(hipMalloc(&x, sizeof(double) * (n + 2)));
     ZF_KEEP_FIRST(hipMalloc(&z, sizeof(double) * (m + 2)));
     if (rc == ZF_OK) {
-        const bool mfma = !V.csr && n % 32 == 0 && zf_env_read().gemv_mfma;
+        const bool mfma = !V.csr && V.k == 1 && n % 32 == 0 && zf_env_read().gemv_mfma;
         ZF_KEEP_FIRST(hipMemcpyAsync(x, x_host, sizeof(double) * n, hipMemcpyHostToDevice, nullptr));
         zf_launch_view_apply(V, nullptr, x, z, W);
         zf_launch_loss_gap_rows(nullptr, L, z, b_dev, m, scale, ws);
@@ -3099,6 +3188,18 @@ extern "C" int zf_f32_gap_eval(const float* A32_dev, const double* b_dev, const 
     return zf_gap_pf_entry("zf_f32_gap_eval", V, b_dev, w_dev, p_dev, scale, lam, loss, delta, x_host, out, count);
 }
 
+// the certificate of K responses on one dense fp64 matrix (zf_mr_eval's arguments; p_dev: n K positive factors or NULL): the
+// evaluation of the m_rows K x n K problem - the joint alpha is feasible for every response - with zf_f32_gap_eval's rules for l2 / p_dev
+extern "C" int zf_mr_gap_eval(const double* A_dev, const double* b_dev, const double* w_dev, const double* p_dev, int64_t m_rows, int64_t n,
+                              int32_t K, double scale, double lam, double l2, int32_t loss, const double* x_host, double* out, int64_t count) {
+    const int rc = zf_mr_args("zf_mr_gap_eval", K, loss);
+    if (rc) return rc;
+    const zf_matview V = zf_dense_view_mr(A_dev, m_rows, n, K);
+    if (!p_dev) return zf_gap_entry("zf_mr_gap_eval", V, b_dev, true, w_dev, scale, lam, true, l2, loss, 0.0, x_host, out, count);
+    ZF_REQUIRE(!(l2 > 0.0), "zf_mr_gap_eval: not with penalty factors and l2 > 0 together (the ridge term would need the factors too)");
+    return zf_gap_pf_entry("zf_mr_gap_eval", V, b_dev, w_dev, p_dev, scale, lam, loss, 0.0, x_host, out, count);
+}
+
 // the gap evaluation followed by the gap-safe screen of its g (zf_kernels_screen.h), l2 = 0 only: out[0 .. 8) as zf_gap_eval - the
 // same kernels in the same order, the same bits - then [r, E, r_eff, kept count].  Huber's loss: the rule, the guard and the four
 // screen launches are the least-squares kinds' - L = 2 scale, |c|_2 from sum c^2 where they read sum r^2 (the clip is exact and
@@ -3187,7 +3288,7 @@ extern "C" int zf_solver_duality_gap(zf_solver* s, double* out, int64_t count) {
     const double* x = s->xb[c.cur];
     const double* z = s->sring.p[c.cur];   // A x_k: every path of these kinds keeps it there (the fused small-matrix path too)
     const zf_gap_ws& ws = s->gap;
-    const zf_matview V = {s->A32 ? nullptr : d.A, m, n, s->spmat, zf_is_sparse_mat(d.kind), s->A32};
+    const zf_matview V = {s->A32 ? nullptr : d.A, m / s->K, n / s->K, s->spmat, zf_is_sparse_mat(d.kind), s->A32, s->K};
     const zf_sweep_ws W = {s->slab, s->slices, s->rows_per_slice, s->sp_part_A, s->sp_part_At};
     zf_launch_loss_gap_rows(s->stream, loss, z, d.b, m, d.scale, ws);
     zf_launch_view_adjoint(V, s->stream, ws.rvec, ws.g, zf_gfac(loss, d.scale), s->gemv_mfma, W);

@@ -85,8 +85,9 @@ class DeviceSolver:
         roww = desc_fields.get("row_weights")   # per-row sample weights (a device pointer): likewise (zf_solver_set_row_weights)
         pf = desc_fields.get("penalty_factors")   # per-column penalty factors (a device pointer): likewise (zf_solver_set_penalty_factors)
         a32 = desc_fields.get("matrix_f32")   # the matrix stored in fp32 (a device pointer): likewise (zf_solver_set_matrix_f32)
+        responses = int(desc_fields.get("responses", 1) or 1)   # K responses on one dense matrix: likewise (zf_solver_set_responses)
         for k, v in desc_fields.items():
-            if k not in ("spmat", "l2", "huber_delta", "poisson", "row_weights", "penalty_factors", "matrix_f32"):
+            if k not in ("spmat", "l2", "huber_delta", "poisson", "row_weights", "penalty_factors", "matrix_f32", "responses"):
                 setattr(d, k, v)
         o = _lib.Options()
         for k, v in options.items():
@@ -113,6 +114,8 @@ class DeviceSolver:
             _lib.check(self.lib.zf_solver_set_penalty_factors(h, C.c_void_p(pf)), "zf_solver_set_penalty_factors")
         if a32:
             _lib.check(self.lib.zf_solver_set_matrix_f32(h, C.c_void_p(a32)), "zf_solver_set_matrix_f32")
+        if responses > 1:   # (K = 1 is the plain problem: the setter is not called)
+            _lib.check(self.lib.zf_solver_set_responses(h, responses), "zf_solver_set_responses")
         sub = C.c_int32(1)
         _lib.check(self.lib.zf_solver_sub_iters(h, C.byref(sub)), "zf_solver_sub_iters")
         self.sub_iters = int(sub.value)   # iterations one pass may accept (temporal blocking)
@@ -318,6 +321,14 @@ class DeviceSolver:
         out = np.zeros(4, dtype=np.int64)
         _lib.check(self.lib.zf_solver_ls_plan(self.handle, C.c_void_p(_lib.ptr(out)), out.size))
         return tuple(int(v) for v in out)
+
+    def responses_plan(self):
+        """(K, rows a workgroup of the K-response row sweep owns) of a dense solver (zf_solver_ls_plan, slots 4 and 5): (1, 0)
+        without ``zf_solver_set_responses``.  With it ``ls_plan()`` reports column sweep 9 / 10 and row sweep 7 / 8 - 16-byte /
+        scalar loads of A (csrc/zf_kernels_mr.h)."""
+        out = np.zeros(6, dtype=np.int64)
+        _lib.check(self.lib.zf_solver_ls_plan(self.handle, C.c_void_p(_lib.ptr(out)), out.size))
+        return int(out[4]), int(out[5])
 
     def runahead_counts(self):
         """(run-ahead passes launched, those of them launched while their predecessor was still in flight) since the

@@ -160,3 +160,76 @@ def l1_cv(problem, lams, folds=5, seed=0, x0=None, gap_tol=1e-6, refit=True, ret
     out.paths = paths if return_paths else None
     out.problems = sibs + [problem] if return_paths else None
     return out
+
+
+def l1_cv_lockstep(problem, lams, folds=5, seed=0, x0=None, gap_tol=1e-6, refit=True, **solver_kwargs):
+    """``l1_cv`` with all folds solved TOGETHER: the K folds of a dense ``LeastSquaresL1`` or ``LogisticL1`` are the K responses
+    of one ``problem.with_responses(B, W)`` - B holds b in every column, ``W[:, k] = w_base * (ids != k)`` - and one ``l1_path``
+    over ``lams`` solves them in lockstep, every sweep reading the matrix once for all folds (K <= 16 folds).
+
+    Fold numbers (``cv_fold_ids``), scores (the held-out loss per unit of held-out weight, taken with the plain class's
+    ``with_sample_weight(w_base * (ids == k)).f``) and the summary (``cv_summary``) are ``l1_cv``'s; so is the returned ``L1CV``
+    (``paths`` holds the one joint path, ``problems`` the joint problem and ``problem``; ``path`` is the plain refit on all rows
+    when ``refit``).
+
+    Stopping: the joint problem is stopped on ITS duality gap.  Its dual point scales the candidates of all folds by one alpha -
+    the smallest any fold needs - so it is feasible for every fold, and the joint gap is the sum of the K non-negative gaps of
+    the folds at that point: ``gap_tol`` on the joint gap certifies every fold to ``gap_tol``.  (A fold's own certificate, with
+    its own alpha, is at most that.)  The folds share one step size and one stopping time, so a fold is solved at least as far
+    as ``l1_cv`` would solve it, not to the same iterate.  ``gap_tol=None`` is refused: without the certificate nothing says when
+    the slowest fold is done."""
+    from .problems import MAX_RESPONSES, LeastSquaresL1, LogisticL1
+
+    if not isinstance(problem, (LeastSquaresL1, LogisticL1)):
+        raise ValueError("l1_cv_lockstep needs a dense LeastSquaresL1 or LogisticL1 (the K-response sweeps read a dense fp64 matrix)")
+    if gap_tol is None:
+        raise ValueError("l1_cv_lockstep needs gap_tol: the joint duality gap is what certifies every fold (use l1_cv for gap_tol=None)")
+    if solver_kwargs.get("screen"):
+        raise ValueError("l1_cv_lockstep(screen=True) is not available: the K-response problem has no screening")
+    lams = [float(v) for v in lams]
+    if not lams:
+        raise ValueError("lams must hold at least one value")
+    m, n = problem.m_rows, problem.n_features
+    ids = cv_fold_ids(m, folds, seed)
+    base = problem.sample_weight
+    w_base = np.ones(m) if base is None else base
+    labels = [int(k) for k in np.unique(ids)]
+    K = len(labels)
+    if K < 2:
+        raise ValueError("l1_cv_lockstep needs at least two folds")
+    if K > MAX_RESPONSES:
+        raise ValueError(f"l1_cv_lockstep runs at most {MAX_RESPONSES} folds at once (one response each), got {K}")
+    for k in labels:   # (before anything is uploaded)
+        if not np.any(w_base * (ids != k) > 0):
+            raise ValueError(f"fold {k} leaves no training weight: every row with a positive weight lies in it")
+    for k in labels:
+        if not np.any(w_base * (ids == k) > 0):
+            raise ValueError(f"fold {k} holds no weight: no held-out row to score on")
+    W = np.stack([w_base * (ids != k) for k in labels], axis=1)
+    b = problem.b.detach().cpu().numpy()
+    joint = problem.with_responses(np.repeat(b.reshape(m, 1), K, axis=1), sample_weight=W)
+    if x0 is None:
+        start = np.zeros(n * K)
+    else:
+        start = np.asarray(x0, dtype=np.float64)
+        start = np.repeat(start.reshape(n, 1), K, axis=1).reshape(-1) if start.shape == (n,) else start.reshape(-1)
+    path = l1_path(joint, lams, x0=start, gap_tol=gap_tol, **solver_kwargs)
+    scores = np.empty((K, len(lams)))
+    nnz = np.zeros((K, len(lams)), dtype=np.int64)
+    for r, k in enumerate(labels):
+        w_test = w_base * (ids == k)
+        test = problem.with_sample_weight(w_test)
+        wsum = w_test.sum()
+        for l, res in enumerate(path):
+            xk = np.ascontiguousarray(joint.coef(res.x)[:, r])
+            scores[r, l] = test.f(xk) / wsum
+            nnz[r, l] = int(np.count_nonzero(xk))
+    out = L1CV()
+    out.lams = np.asarray(lams, dtype=np.float64)
+    out.fold_ids, out.folds = ids, labels
+    out.scores, out.nnz = scores, nnz
+    out.mean, out.se, out.best, out.lam_best, out.lam_1se = cv_summary(lams, scores)
+    out.path = l1_path(problem, lams, x0=x0, gap_tol=gap_tol, **solver_kwargs) if refit else None
+    out.paths = [path]   # (the one joint path: res.x holds the K fold solutions as the columns of joint.coef(res.x))
+    out.problems = [joint, problem]
+    return out

@@ -1131,6 +1131,216 @@ class SparsePoissonL1(_PoissonMixin, _SparseMarginsL1):
         self._set(A, b, lam, scale, bounds, l2, sample_weight, penalty_factor=penalty_factor)
 
 
+# ---------------------------------------------------------------------------
+# K responses on one dense matrix (csrc/zf_kernels_mr.h)
+# ---------------------------------------------------------------------------
+MAX_RESPONSES = 16
+
+
+def _broadcast_columns(v, rows, K, what, per):
+    """``v`` - (rows,) or (rows, K), host or torch - as a host (rows, K) array (a 1-D form is repeated for every response)."""
+    host = v.detach().cpu().numpy() if hasattr(v, "detach") else np.asarray(v)
+    if np.dtype(host.dtype).kind not in "biuf":
+        raise ValueError(f"{what} must be real numbers, got dtype {host.dtype}")
+    if host.shape == (rows,):
+        host = np.repeat(host.reshape(rows, 1), K, axis=1)
+    if host.shape != (rows, K):
+        raise ValueError(f"{what} must have shape ({rows},) or ({rows}, {K}) (one value per {per}, or per {per} and response), "
+                         f"got shape {host.shape}")
+    return np.ascontiguousarray(host, dtype=np.float64)
+
+
+class _MultiResponseMixin:
+    r"""K right-hand sides on one resident matrix: X in R^{n x K}, B in R^{m x K},
+
+        f(X) = scale sum_k sum_i W_ik phi((A x_k)_i ; B_ik),   g(X) = lam sum_jk P_jk |X_jk| (+ (l2 / 2) |X|^2) (+ box).
+
+    This is the plain problem of the class on the matrix A (x) I_K (``np.kron(A, np.eye(K))``) with every array flattened in C
+    order - ``x[j K + k] = X[j, k]`` - so everything the plain class offers carries over on vectors of n K and m K entries;
+    only the two sweeps over A differ: they multiply A into K columns and read A once per sweep (csrc/zf_kernels_mr.h), so K
+    solves cost one solve's HBM traffic.  One step size serves all responses (the Lipschitz constant of A (x) I_K is A's).
+    ``n_features`` = n K, ``n_responses`` = K, ``coef(x)`` -> (n, K); ``x0`` may be (n, K) or flat, results are flat.
+    The duality gap uses one alpha for all responses: the dual point is feasible for each of them, and the gap is the sum of
+    the K per-response gaps at that point.  K = 1 is the plain class, bit for bit.  K <= 16.  No screening, no fp32 matrix,
+    no process group, no acceptance="remainder" / "resolved"."""
+
+    taylor_remainder = False
+    n_responses = 1
+
+    _MR_WHY = ("the problem has several responses: the column-norm, screening and restriction kernels see one column of x per "
+               "column of A, and the K-response forms are not built")
+
+    def _set_mr(self, A, B, lam, scale, bounds, l2, sample_weight, penalty_factor, share=None):
+        """Everything that can be refused is refused on the host, before anything touches the device.  ``share``: a plain problem
+        whose device matrix is adopted (``with_responses``)."""
+        Bh = B.detach().cpu().numpy() if hasattr(B, "detach") else np.asarray(B)
+        shape = tuple(share.A.shape) if share is not None else tuple(getattr(A, "shape", None) or np.shape(A))
+        if len(shape) != 2 or Bh.ndim != 2 or Bh.shape[0] != shape[0] or Bh.shape[1] < 1:
+            raise ValueError(f"A must be (m, n) and B (m, K) with K >= 1, got A {shape} and B {Bh.shape}")
+        m, n, K = int(shape[0]), int(shape[1]), int(Bh.shape[1])
+        if K > MAX_RESPONSES:
+            raise ValueError(f"at most {MAX_RESPONSES} responses per problem (the register tiles of the K-response sweeps are built "
+                             f"for K <= {MAX_RESPONSES}), got K = {K}: split B into groups of columns")
+        if self._loss == _lib.ZF_LOSS_LOGISTIC:
+            _check_labels(Bh.reshape(-1))
+        self.l2 = _check_l2(l2)
+        w = p = None
+        if sample_weight is not None:
+            w = _check_weights(_broadcast_columns(sample_weight, m, K, "sample_weight", "row").reshape(-1), m * K)
+        if penalty_factor is not None:
+            p = _check_penalty_factor(_broadcast_columns(penalty_factor, n, K, "penalty_factor", "column").reshape(-1), n * K, None, self.l2)
+        self._f32 = False
+        self.A = share.A if share is not None else _to_device(A, "A")
+        self.b = _to_device(np.ascontiguousarray(Bh, dtype=np.float64).reshape(-1), "B")
+        self.lam, self.scale = float(lam), float(scale)
+        self.box = (-np.inf, np.inf) if bounds is None else (float(bounds[0]), float(bounds[1]))
+        self.n_responses, self._m, self._n = K, m, n
+        self.m_rows, self.n_features = m * K, n * K   # (the lengths of the flattened margins and decision vectors)
+        self.group = None
+        self._norms = _ColumnNorms()
+        self._set_weights(w)
+        self._set_penalty_factor(p)
+
+    # -- shapes --------------------------------------------------------------------------------
+    def coef(self, x):
+        """The flat vector ``x`` as the (n, K) matrix of coefficients, one column per response."""
+        return np.asarray(x, dtype=np.float64).reshape(self._n, self.n_responses)
+
+    def _flat(self, x):
+        if type(x).__module__.split(".")[0] == "torch":
+            return x.reshape(-1) if x.ndim == 2 and tuple(x.shape) == (self._n, self.n_responses) else x
+        a = np.asarray(x)
+        return a.reshape(-1) if a.ndim == 2 and a.shape == (self._n, self.n_responses) else x
+
+    def minimize_proximal_gradient(self, x0, **kwargs):
+        return NativeProblem.minimize_proximal_gradient(self, self._flat(x0), **kwargs)
+
+    # -- entry points ---------------------------------------------------------------------------
+    def _lead(self, *w):
+        return (_dp(self.A), _dp(self.b), *w, self._m, self._n)
+
+    def _ls(self, x, want_grad):
+        if self.n_responses == 1:
+            return super()._ls(self._flat(x), want_grad)
+        x = _as_host(self._flat(x))
+        if x.size != self.n_features:
+            raise ValueError(f"len(x) should be equal to n_features, got {x}.")
+        lib = _lib.require_gpu()
+        fval = C.c_double(0.0)
+        grad = np.empty_like(x) if want_grad else None
+        _lib.check(lib.zf_mr_eval(*self._lead(_dp(self._w)), self.n_responses, self.scale, self._loss, C.c_void_p(_lib.ptr(x)),
+                                  C.byref(fval), C.c_void_p(_lib.ptr(grad)) if want_grad else None), "zf_mr_eval")
+        return np.float64(fval.value), grad
+
+    def f(self, x):
+        return self._ls(x, False)[0]
+
+    def jac_f(self, x):
+        return self._ls(x, True)[1]
+
+    def _gap_call(self, lib, x, out):
+        if self.n_responses == 1:
+            return super()._gap_call(lib, x, out)
+        _lib.check(lib.zf_mr_gap_eval(*self._lead_pf(), self.n_responses, self.scale, self.lam, self.l2, self._loss,
+                                      C.c_void_p(_lib.ptr(x)), C.c_void_p(_lib.ptr(out)), out.size), "zf_mr_gap_eval")
+
+    def duality_gap(self, x):
+        return super().duality_gap(self._flat(x))
+
+    def _descriptor(self):
+        fields, keep = super()._descriptor()   # (m_rows and n_features are the flattened lengths already)
+        if self.n_responses > 1:
+            fields["responses"] = self.n_responses
+        return fields, keep
+
+    # -- siblings ------------------------------------------------------------------------------
+    def with_sample_weight(self, w):
+        """A sibling with the weights ``w`` - (m,), repeated for every response, or (m, K) - on the same device matrix and B."""
+        if w is not None:
+            w = _broadcast_columns(w, self._m, self.n_responses, "sample_weight", "row").reshape(-1)
+        return super().with_sample_weight(w)
+
+    def with_penalty_factor(self, p):
+        """A sibling with the penalty factors ``p`` - (n,), repeated for every response, or (n, K) - on the same device matrix."""
+        if p is not None:
+            p = _broadcast_columns(p, self._n, self.n_responses, "penalty_factor", "column").reshape(-1)
+        return super().with_penalty_factor(p)
+
+    def with_matrix_dtype(self, dtype):
+        if _matrix_dtype(dtype) == "float32":
+            raise ValueError("matrix_dtype='float32' is not available with several responses: the K-response sweeps read an fp64 A")
+        return super().with_matrix_dtype(dtype)
+
+    # -- what has no K-response form ---------------------------------------------------------------
+    def _mr_refusal(self, what):
+        if self.n_responses > 1:
+            raise ValueError(f"{what} is not available: {self._MR_WHY}")
+
+    def _screen_refusal(self):
+        return self._MR_WHY if self.n_responses > 1 else super()._screen_refusal()
+
+    def column_norms(self):
+        self._mr_refusal("column_norms")
+        return super().column_norms()
+
+    def screen(self, x):
+        self._mr_refusal("screen")
+        return super().screen(x)
+
+    def restrict(self, keep):
+        self._mr_refusal("restrict")
+        return super().restrict(keep)
+
+
+class MultiResponseLeastSquaresL1(_MultiResponseMixin, _DenseMarginsL1):
+    r"""``LeastSquaresL1`` for K right-hand sides at once: f(X) = scale \|A X - B\|_F^2 (weighted: scale sum W o (A X - B)^2),
+    B (m, K); sklearn's ``Lasso.fit(X, Y)`` with 2-D ``Y``.  See ``_MultiResponseMixin``."""
+
+    kind = _lib.ZF_PROBLEM_LEAST_SQUARES_L1
+
+    def __init__(self, A, B, lam, scale=0.5, bounds=None, l2=0.0, *, sample_weight=None, penalty_factor=None, _share=None):
+        self._set_mr(A, B, lam, scale, bounds, l2, sample_weight, penalty_factor, _share)
+
+
+class MultiResponseLogisticL1(_MultiResponseMixin, _DenseMarginsL1):
+    r"""``LogisticL1`` for K label vectors at once (one-vs-rest classification): B (m, K) holds exactly -1 / +1.
+    See ``_MultiResponseMixin``."""
+
+    kind = _lib.ZF_PROBLEM_LOGISTIC_L1
+    _loss = _lib.ZF_LOSS_LOGISTIC
+
+    def __init__(self, A, B, lam, scale=1.0, bounds=None, l2=0.0, *, sample_weight=None, penalty_factor=None, _share=None):
+        self._set_mr(A, B, lam, scale, bounds, l2, sample_weight, penalty_factor, _share)
+
+
+def _with_responses(problem, cls, B, sample_weight):
+    if problem._f32:
+        raise ValueError("with_responses is not available with matrix_dtype='float32': the K-response sweeps read an fp64 A")
+    if getattr(problem, "group", None) is not None:
+        raise ValueError("with_responses is not available with group=: the K-response sweeps are built for one GPU (world = 1)")
+    bounds = problem.box if problem._has_box() else None
+    return cls(None, B, problem.lam, problem.scale, bounds, problem.l2, sample_weight=sample_weight,
+               penalty_factor=problem.penalty_factor, _share=problem)
+
+
+def _ls_with_responses(self, B, sample_weight=None):
+    """A ``MultiResponseLeastSquaresL1`` on this problem's device matrix (shared, nothing but B is uploaded) with its lam, scale,
+    bounds, l2 and penalty factors (repeated for every response).  ``B``: (m, K); ``sample_weight``: (m,) or (m, K) or None.
+    Not for an fp32 matrix or a process group."""
+    return _with_responses(self, MultiResponseLeastSquaresL1, B, sample_weight)
+
+
+def _logistic_with_responses(self, B, sample_weight=None):
+    """A ``MultiResponseLogisticL1`` on this problem's device matrix (shared, nothing but B is uploaded) with its lam, scale,
+    bounds, l2 and penalty factors (repeated for every response).  ``B``: (m, K) of -1 / +1; ``sample_weight``: (m,) or (m, K) or
+    None."""
+    return _with_responses(self, MultiResponseLogisticL1, B, sample_weight)
+
+
+LeastSquaresL1.with_responses = _ls_with_responses
+LogisticL1.with_responses = _logistic_with_responses
+
+
 class BlurHaarL1(NativeProblem):
     r"""Operator-form LASSO: f(x) = scale \|B W^{-1} x - b\|^2,  g(x) = lam \|x\|_1 (+ optional box), with B the
     correlation with ``kernel`` (odd size <= 15, symmetric boundary - ``scipy.signal.correlate2d(..., mode="same",

@@ -180,6 +180,14 @@ def minimize_proximal_gradient(
     if native is not None and not (lr > 0 and decay_rate > 0 and native.lam >= 0):
         native = None   # the fused kernels assume a threshold lam * lr >= 0; the callback path does not
     native_multi = match_native_multi(f, g, jac_f, prox_wsum_g)
+    if native is not None and getattr(native, "n_responses", 1) > 1:   # (zfista_amd.problems.MultiResponse*: x0 may be (n, K))
+        x0 = native._flat(x0)
+        if acceptance in ("resolved", "remainder"):
+            if accept_from_env:
+                opts["acceptance"] = acceptance = "reference"   # (the environment asks for what this problem has not: the reference's test runs)
+            else:
+                raise ValueError(f"acceptance={acceptance!r} is not available with several responses: zf_solver_set_responses takes "
+                                 "the reference's acceptance test only (the kernels that form the Taylor remainder walk one response)")
     if acceptance in ("resolved", "remainder") and native is not None and getattr(native, "sample_weight", None) is not None:
         if accept_from_env:
             opts["acceptance"] = acceptance = "reference"   # (the environment asks for what this problem has not: the reference's test runs)
