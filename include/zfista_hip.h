@@ -395,7 +395,9 @@ int zf_solver_launch_counts(zf_solver* s, int64_t* out, int64_t count /* >= 2 */
  * (16-byte loads, even n) or <K, 1> (odd n; n the matrix's own column count) - out[1] = 7 or 8 - the row sweep
  * zf_mr_rows_kernel<K, 2>, <K, 1> - out[2], out[3] the slices of that rule on the matrix's own shape.
  * count >= 6 (dense kinds; what the first four slots hold does not depend on count): out[4] = K (1 without the setter), out[5] = the
- * rows a workgroup of the K-response row sweep owns (0 without the setter).
+ * rows a workgroup of the K-response row sweep owns (0 without the setter).  The sparse kinds keep 5, L(A), L(A^T), split rows in the
+ * first four slots whatever K is (the handle's plan serves every K); count >= 6: out[4] = K (zf_solver_create_sparse_responses; 1
+ * otherwise), out[5] = 0.
  * Other problems: zeros. */
 int zf_solver_ls_plan(zf_solver* s, int64_t* out, int64_t count /* >= 4 */);
 /* the same window split by the shape of the pass, which the kernel logs itself: out[0], out[1] = mean
@@ -521,6 +523,37 @@ int zf_spmat_logistic_eval(const zf_spmat* h, const double* b_dev, double scale,
  * scale, lam and the box as for the dense kind, world = 1.  The handle must outlive the solver.  Everything else - init,
  * steps, poll, restore, history - is the solver's as for every kind. */
 int zf_solver_create_sparse(zf_solver** out, const zf_problem_desc* desc, const zf_spmat* h, const zf_options* opt, void* stream);
+
+/* ---- K responses on one CSR matrix, on the two sparse kinds 4, 6 (csrc/zf_kernels_spmm.h) -------------------------------------------
+ * The problem of zf_solver_set_responses - X in R^{n x K}, B in R^{m x K}, the margins problem of A (x) I_K on vectors flattened in C
+ * order, x[j K + k] = X[j][k] - with A behind a zf_spmat handle.  Row i K + k of A (x) I_K holds the elements of row i of A, in the same
+ * order, at columns j K + k: the K values a stored element needs are K 8 contiguous bytes, so one index, one value and one gathered
+ * line serve K responses.  The two sweeps sum response k exactly as the plain sweeps sum a vector (the same lanes per row, the same
+ * element order per lane, two roundings per element, one shuffle tree, the handle's segments for long rows): every value a solve or
+ * an evaluation produces is bit-equal to the plain sparse kind on the stored Kronecker matrix.  The handle is used as it is - no new
+ * plan, no upload - and stays immutable; a solver's or an evaluation's own segment sums hold nseg K doubles.  No LDS, no atomics:
+ * equal columns of the input give bit-equal columns of the output; a non-finite value in one column leaves the bits of the others.
+ * Everything element-wise around the sweeps runs unchanged on m K and n K entries (beyond 32768 rows of m K the unweighted squared
+ * loss forms its residuals with up to 1024 workgroups, as the sparse kind does by its row count).  Additive to ABI 6.
+ * zf_solver_create_sparse_responses: zf_solver_create_sparse with desc->m_rows = K h->m, desc->n = K h->n, desc->b of m K values.
+ * ZF_ERR_ARG: K outside 2 .. 16, dimensions that are not K times the handle's, a kind other than 4 / 6, world > 1,
+ * ZF_ACCEPT_REMAINDER / ZF_ACCEPT_RESOLVED.  zf_solver_set_huber / _poisson / _matrix_f32 refuse such a solver; it composes with
+ * zf_solver_set_l2 / _row_weights (m K weights) / _penalty_factors (n K factors).  zf_solver_create_sparse keeps its dimension check
+ * and zf_solver_set_responses keeps refusing the sparse kinds: K is set at creation or never.  A solver not created here launches and
+ * allocates what it did.  Vectors of n K >= 2^31 entries are indexed in 64 bits (n < 2^31, n K is not). */
+int zf_solver_create_sparse_responses(zf_solver** out, const zf_problem_desc* desc, const zf_spmat* h, int32_t K, const zf_options* opt,
+                                      void* stream);
+/* zf_mr_eval over the handle: b_dev, w_dev (or NULL) hold h->m K doubles, x_host / grad_out_host h->n K. */
+int zf_spmat_mr_eval(const zf_spmat* h, const double* b_dev, const double* w_dev, int32_t K, double scale, int32_t loss,
+                     const double* x_host, double* f_out, double* grad_out_host /* or NULL */);
+/* zf_mr_gap_eval over the handle (p_dev: n K positive factors or NULL; not with l2 > 0).  zf_solver_duality_gap of a solver of
+ * zf_solver_create_sparse_responses writes the same values, bit for bit. */
+int zf_spmat_mr_gap_eval(const zf_spmat* h, const double* b_dev, const double* w_dev, const double* p_dev, int32_t K, double scale,
+                         double lam, double l2, int32_t loss, const double* x_host, double* out, int64_t count /* >= 8; 10 for all */);
+/* One sweep alone, for element-wise tests of those kernels, outside any solve: out_host = out_scale * A in_host (transpose == 0: in
+ * n K, out m K doubles) or out_scale * A^T in_host (in m K, out n K), response-interleaved.  K = 1 runs the plain sweep
+ * (zf_launch_spmv), K = 2 .. 16 the K-response one (zf_launch_spmm).  ZF_ERR_ARG: a NULL argument, K outside 1 .. 16. */
+int zf_spmat_mr_apply(const zf_spmat* h, int32_t transpose, int32_t K, double out_scale, const double* in_host, double* out_host);
 
 /* ---- duality gap of the margins kinds (csrc/zf_kernels_gap.h) -----------------------------------------------------------
  * P(x) = sum_i phi_i((A x)_i) + lam |x|_1 with phi_i(z) = scale (z - b_i)^2 (logistic = 0) or scale softplus(-b_i z)

@@ -267,6 +267,10 @@ SIGNATURES = {
     "zf_mr_eval": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_int32, C.c_double, C.c_int32, _P, C.POINTER(C.c_double), _P]),
     "zf_mr_gap_eval": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int64, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_int32, _P, _P,
                                  C.c_int64]),
+    "zf_solver_create_sparse_responses": (C.c_int, [C.POINTER(_P), C.POINTER(ProblemDesc), _P, C.c_int32, C.POINTER(Options), _P]),
+    "zf_spmat_mr_eval": (C.c_int, [_P, _P, _P, C.c_int32, C.c_double, C.c_int32, _P, C.POINTER(C.c_double), _P]),
+    "zf_spmat_mr_gap_eval": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_int32, _P, _P, C.c_int64]),
+    "zf_spmat_mr_apply": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_double, _P, _P]),
 }
 
 _lib = None

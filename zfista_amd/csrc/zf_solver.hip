@@ -547,7 +547,8 @@ static void zf_launch_apply_A(zf_solver* s, const zf_control* ctl, zf_ring3 xr, 
     }
     if (zf_is_sparse_mat(d.kind)) {
         const zf_spmv_io io = {{xr.p[0], xr.p[1], xr.p[2]}, {sout.p[0], sout.p[1], sout.p[2]}};
-        zf_launch_spmv(s->spmat->A, s->stream, ctl, false, io, slot, 1.0, s->sp_part_A);
+        if (s->K > 1) zf_launch_spmm(s->spmat->A, s->stream, ctl, false, io, slot, 1.0, s->K, s->sp_part_A);
+        else zf_launch_spmv(s->spmat->A, s->stream, ctl, false, io, slot, 1.0, s->sp_part_A);
         return;
     }
     if (s->A32) {
@@ -603,8 +604,10 @@ static hipError_t zf_second_stream(zf_solver* s) {
     return hipSuccess;
 }
 
-// sp: the matrix handle of ZF_PROBLEM_SPARSE_LS_L1 (zf_solver_create_sparse), NULL for every other kind
-static int zf_solver_create_impl(zf_solver** out, const zf_problem_desc* desc, const zf_options* opt, void* stream, const zf_spmat* sp) {
+// sp: the matrix handle of ZF_PROBLEM_SPARSE_LS_L1 (zf_solver_create_sparse), NULL for every other kind; K > 1: the responses of
+// zf_solver_create_sparse_responses (desc holds the flattened lengths sp->m K and sp->n K)
+static int zf_solver_create_impl(zf_solver** out, const zf_problem_desc* desc, const zf_options* opt, void* stream, const zf_spmat* sp,
+                                 int K = 1) {
     ZF_REQUIRE(out && desc && opt, "zf_solver_create: null argument");
     ZF_REQUIRE(desc->n >= 1, "zf_solver_create: n must be >= 1");
     ZF_REQUIRE(desc->world >= 1 && desc->rank >= 0 && desc->rank < desc->world,
@@ -634,7 +637,11 @@ static int zf_solver_create_impl(zf_solver** out, const zf_problem_desc* desc, c
     } else if (zf_is_sparse_mat(desc->kind)) {
         ZF_REQUIRE(sp, "zf_solver_create: ZF_PROBLEM_SPARSE_LS_L1 and ZF_PROBLEM_SPARSE_LOGISTIC_L1 take their matrix through zf_solver_create_sparse");
         ZF_REQUIRE(desc->b && !desc->A, "zf_solver_create_sparse: b is required and A must be NULL (the matrix is the handle's)");
-        ZF_REQUIRE(desc->m_rows == sp->m && desc->n == sp->n, "zf_solver_create_sparse: m_rows and n differ from the matrix handle's");
+        if (K > 1)
+            ZF_REQUIRE(desc->m_rows == sp->m * K && desc->n == sp->n * K,
+                       "zf_solver_create_sparse_responses: m_rows and n must be K times the matrix handle's");
+        else
+            ZF_REQUIRE(desc->m_rows == sp->m && desc->n == sp->n, "zf_solver_create_sparse: m_rows and n differ from the matrix handle's");
         ZF_REQUIRE(desc->world == 1, "zf_solver_create_sparse: sparse problems are not sharded");
     } else {
         return zf_fail(ZF_ERR_ARG, "zf_solver_create: unknown problem kind");
@@ -644,6 +651,7 @@ static int zf_solver_create_impl(zf_solver** out, const zf_problem_desc* desc, c
     s->desc = *desc;
     s->opt = *opt;
     s->spmat = sp;
+    s->K = K;
     s->env = zf_env_read();
     s->pass_seq = s->env.pass_seq_start;
     s->stream = reinterpret_cast<hipStream_t>(stream);
@@ -779,8 +787,9 @@ static int zf_solver_create_impl(zf_solver** out, const zf_problem_desc* desc, c
     }
     if (zf_is_sparse_mat(desc->kind)) {   // what the dense kind takes, minus the slab, plus the segment sums of split rows
         // (per solver: solves that share a matrix handle may run at the same time on other streams)
-        if (sp->A.nseg > 0) ZF_TRY(hipMalloc(&s->sp_part_A, sizeof(double) * sp->A.nseg));
-        if (sp->At.nseg > 0) ZF_TRY(hipMalloc(&s->sp_part_At, sizeof(double) * sp->At.nseg));
+        // (K responses: a segment holds K sums)
+        if (sp->A.nseg > 0) ZF_TRY(hipMalloc(&s->sp_part_A, sizeof(double) * sp->A.nseg * K));
+        if (sp->At.nseg > 0) ZF_TRY(hipMalloc(&s->sp_part_At, sizeof(double) * sp->At.nseg * K));
         const int64_t m_pad = (desc->m_rows + 63) & ~int64_t(63);
         ZF_TRY(hipMalloc(&s->grad, sizeof(double) * n_pad));
         ZF_TRY(hipMalloc(&s->sbuf, sizeof(double) * 3 * m_pad));
@@ -832,6 +841,19 @@ extern "C" int zf_solver_create_sparse(zf_solver** out, const zf_problem_desc* d
     ZF_REQUIRE(out && desc && h && opt, "zf_solver_create_sparse: null argument");
     ZF_REQUIRE(zf_is_sparse_mat(desc->kind), "zf_solver_create_sparse: desc->kind must be ZF_PROBLEM_SPARSE_LS_L1 or ZF_PROBLEM_SPARSE_LOGISTIC_L1");
     return zf_solver_create_impl(out, desc, opt, stream, h);
+}
+
+// K responses on one CSR matrix (include/zfista_hip.h): the sparse solver of the flattened problem whose two sweeps take
+// zf_launch_spmm on the handle as it is
+extern "C" int zf_solver_create_sparse_responses(zf_solver** out, const zf_problem_desc* desc, const zf_spmat* h, int32_t K,
+                                                 const zf_options* opt, void* stream) {
+    ZF_REQUIRE(out && desc && h && opt, "zf_solver_create_sparse_responses: null argument");
+    ZF_REQUIRE(zf_is_sparse_mat(desc->kind),
+               "zf_solver_create_sparse_responses: desc->kind must be ZF_PROBLEM_SPARSE_LS_L1 or ZF_PROBLEM_SPARSE_LOGISTIC_L1");
+    ZF_REQUIRE(K >= 2 && K <= ZF_SPMM_MAX_K, "zf_solver_create_sparse_responses: K must be 2 .. 16");
+    ZF_REQUIRE(desc->world == 1, "zf_solver_create_sparse_responses: not for a sharded solve (world > 1)");
+    ZF_REQUIRE(opt->accept_mode == ZF_ACCEPT_REFERENCE, "zf_solver_create_sparse_responses: not with ZF_ACCEPT_REMAINDER or ZF_ACCEPT_RESOLVED");
+    return zf_solver_create_impl(out, desc, opt, stream, h, K);
 }
 
 extern "C" int zf_solver_destroy(zf_solver* s) {
@@ -1535,7 +1557,8 @@ static int zf_launch_trial(zf_solver* s, bool decide_in_launch, bool dry = false
             // the trial of a dense matrix with its two sweeps swapped for the CSR row sums: grad = 2 scale A^T r over the
             // stored A^T (only when y changed), the prox step, s+ = A x+, f(x+), finalize
             const zf_spmv_io gio = {{s->resid, s->resid, s->resid}, {s->grad, s->grad, s->grad}};
-            zf_launch_spmv(s->spmat->At, s->stream, s->ctl, true, gio, -1, gfac, s->sp_part_At);
+            if (s->K > 1) zf_launch_spmm(s->spmat->At, s->stream, s->ctl, true, gio, -1, gfac, s->K, s->sp_part_At);
+            else zf_launch_spmv(s->spmat->At, s->stream, s->ctl, true, gio, -1, gfac, s->sp_part_At);
             a.p0 = s->grad;
             a.p1 = nullptr;
             zf_launch_trial_kernels(s, a, false);
@@ -2170,6 +2193,10 @@ extern "C" int zf_solver_ls_plan(zf_solver* s, int64_t* out, int64_t count) {
         out[1] = s->spmat->A.lanes;
         out[2] = s->spmat->At.lanes;
         out[3] = s->spmat->A.nsplit + s->spmat->At.nsplit;
+        if (count >= 6) {   // responses (zf_solver_create_sparse_responses; 1 otherwise)
+            out[4] = s->K;
+            out[5] = 0;
+        }
         return ZF_OK;
     }
     if (!zf_is_dense_mat(s->desc.kind)) return ZF_OK;
@@ -2714,13 +2741,14 @@ struct zf_matview {
     const zf_spmat* h;   // CSR: A and A^T with their plans; NULL for dense
     bool csr;
     const float* A32;    // dense, stored in fp32 (zf_kernels_gemv_f32.h): m x n row-major (device), 16-byte aligned - A is NULL then; NULL otherwise
-    int k = 1;           // responses (zf_kernels_mr.h; dense fp64 only): m and n stay the matrix's, the vectors hold m k and n k doubles
+    int k = 1;           // responses (zf_kernels_mr.h for dense fp64, zf_kernels_spmm.h for CSR): m and n stay the matrix's, the vectors hold m k and n k doubles
 };
 static int64_t zf_view_rows(const zf_matview& V) { return V.m * V.k; }   // length of a margins vector
 static int64_t zf_view_cols(const zf_matview& V) { return V.n * V.k; }   // length of a decision vector
 static zf_matview zf_dense_view(const double* A, int64_t m, int64_t n) { return zf_matview{A, m, n, nullptr, false, nullptr}; }
 static zf_matview zf_csr_view(const zf_spmat* h) { return zf_matview{nullptr, 0, 0, h, true, nullptr}; }
 static zf_matview zf_dense_view_f32(const float* A32, int64_t m, int64_t n) { return zf_matview{nullptr, m, n, nullptr, false, A32}; }
+static zf_matview zf_csr_view_mr(const zf_spmat* h, int k) { return zf_matview{nullptr, 0, 0, h, true, nullptr, k}; }
 static zf_matview zf_dense_view_mr(const double* A, int64_t m, int64_t n, int k) { return zf_matview{A, m, n, nullptr, false, nullptr, k}; }
 
 // what the sweeps write between their launches: the slab of the dense column sweep and its slices, or the segment sums of the
@@ -2736,8 +2764,8 @@ static int zf_sweep_ws_alloc(const zf_matview& V, bool adjoint, zf_sweep_ws* W) 
     int rc = ZF_OK;
     *W = zf_sweep_ws{nullptr, 1, V.m, nullptr, nullptr};
     if (V.csr) {
-        if (V.h->A.nseg > 0) ZF_KEEP_FIRST(hipMalloc(&W->part_A, sizeof(double) * V.h->A.nseg));
-        if (adjoint && V.h->At.nseg > 0) ZF_KEEP_FIRST(hipMalloc(&W->part_At, sizeof(double) * V.h->At.nseg));
+        if (V.h->A.nseg > 0) ZF_KEEP_FIRST(hipMalloc(&W->part_A, sizeof(double) * V.h->A.nseg * V.k));
+        if (adjoint && V.h->At.nseg > 0) ZF_KEEP_FIRST(hipMalloc(&W->part_At, sizeof(double) * V.h->At.nseg * V.k));
     } else if (adjoint) {
         if (V.A32) zf_dense_slices_f32(V.m, V.n, &W->slices, &W->rows_per_slice);
         else if (V.k > 1) zf_mr_slices(V.m, V.n, &W->slices, &W->rows_per_slice);
@@ -2755,7 +2783,8 @@ static void zf_sweep_ws_free(zf_sweep_ws* W) {
 static void zf_launch_view_apply(const zf_matview& V, hipStream_t st, double* x, double* z, const zf_sweep_ws& W) {
     if (V.csr) {
         const zf_spmv_io aio = {{x, x, x}, {z, z, z}};
-        zf_launch_spmv(V.h->A, st, nullptr, false, aio, -1, 1.0, W.part_A);
+        if (V.k > 1) zf_launch_spmm(V.h->A, st, nullptr, false, aio, -1, 1.0, V.k, W.part_A);
+        else zf_launch_spmv(V.h->A, st, nullptr, false, aio, -1, 1.0, W.part_A);
         return;
     }
     zf_ring3 xr = {{x, x, x}}, sr = {{z, z, z}};
@@ -2779,7 +2808,8 @@ static void zf_launch_view_adjoint(const zf_matview& V, hipStream_t st, const do
                                    const zf_sweep_ws& W) {
     if (V.csr) {
         const zf_spmv_io gio = {{r, r, r}, {g, g, g}};
-        zf_launch_spmv(V.h->At, st, nullptr, false, gio, -1, factor, W.part_At);
+        if (V.k > 1) zf_launch_spmm(V.h->At, st, nullptr, false, gio, -1, factor, V.k, W.part_At);
+        else zf_launch_spmv(V.h->At, st, nullptr, false, gio, -1, factor, W.part_At);
         return;
     }
     const int64_t m = V.m, n = V.n;
@@ -2962,6 +2992,40 @@ extern "C" int zf_mr_eval(const double* A_dev, const double* b_dev, const double
     if (rc) return rc;
     return zf_point_entry("zf_mr_eval", zf_dense_view_mr(A_dev, m_rows, n, K), b_dev, true, w_dev, scale, loss, 0.0, x_host, f_out,
                           grad_out_host);
+}
+
+// K responses on one CSR matrix behind a handle (zf_kernels_spmm.h): zf_mr_eval with the handle for A_dev, m_rows, n
+extern "C" int zf_spmat_mr_eval(const zf_spmat* h, const double* b_dev, const double* w_dev, int32_t K, double scale, int32_t loss,
+                                const double* x_host, double* f_out, double* grad_out_host) {
+    const int rc = zf_mr_args("zf_spmat_mr_eval", K, loss);
+    if (rc) return rc;
+    return zf_point_entry("zf_spmat_mr_eval", zf_csr_view_mr(h, K), b_dev, true, w_dev, scale, loss, 0.0, x_host, f_out, grad_out_host);
+}
+
+// out = out_scale * A in (transpose == 0: in holds n K, out m K doubles) or out_scale * A^T in (in m K, out n K), host vectors,
+// response-interleaved: one sweep alone, outside any solve, for element-wise tests.  K = 1: zf_launch_spmv; 2 .. 16: zf_launch_spmm.
+extern "C" int zf_spmat_mr_apply(const zf_spmat* h, int32_t transpose, int32_t K, double out_scale, const double* in_host, double* out_host) {
+    ZF_REQUIRE(h && in_host && out_host, "zf_spmat_mr_apply: null argument");
+    ZF_REQUIRE(K >= 1 && K <= ZF_SPMM_MAX_K, "zf_spmat_mr_apply: K must be 1 .. 16");
+    const zf_spmv_mat& M = transpose ? h->At : h->A;
+    const int64_t n_in = M.cols * K, n_out = M.rows * K;
+    double *in = nullptr, *out = nullptr, *part = nullptr;
+    int rc = ZF_OK;
+    ZF_KEEP_FIRST(hipMalloc(&in, sizeof(double) * n_in));
+    ZF_KEEP_FIRST(hipMalloc(&out, sizeof(double) * n_out));
+    if (M.nseg > 0) ZF_KEEP_FIRST(hipMalloc(&part, sizeof(double) * M.nseg * K));
+    if (rc == ZF_OK) {
+        ZF_KEEP_FIRST(hipMemcpyAsync(in, in_host, sizeof(double) * n_in, hipMemcpyHostToDevice, nullptr));
+        const zf_spmv_io io = {{in, in, in}, {out, out, out}};
+        if (K == 1) zf_launch_spmv(M, nullptr, nullptr, false, io, -1, out_scale, part);
+        else zf_launch_spmm(M, nullptr, nullptr, false, io, -1, out_scale, K, part);
+        ZF_KEEP_FIRST(hipGetLastError());
+        ZF_KEEP_FIRST(hipMemcpyAsync(out_host, out, sizeof(double) * n_out, hipMemcpyDeviceToHost, nullptr));
+        ZF_KEEP_FIRST(hipStreamSynchronize(nullptr));
+    }
+    for (void* p : {(void*)in, (void*)out, (void*)part})
+        if (p) (void)hipFree(p);
+    return rc;
 }
 
 // f(x) = scale |B W^-1 x - b|^2 and (optionally) jac_f(x) = 2 scale W B (B W^-1 x - b) of the operator problem
@@ -3198,6 +3262,18 @@ extern "C" int zf_mr_gap_eval(const double* A_dev, const double* b_dev, const do
     if (!p_dev) return zf_gap_entry("zf_mr_gap_eval", V, b_dev, true, w_dev, scale, lam, true, l2, loss, 0.0, x_host, out, count);
     ZF_REQUIRE(!(l2 > 0.0), "zf_mr_gap_eval: not with penalty factors and l2 > 0 together (the ridge term would need the factors too)");
     return zf_gap_pf_entry("zf_mr_gap_eval", V, b_dev, w_dev, p_dev, scale, lam, loss, 0.0, x_host, out, count);
+}
+
+// the same certificate for K responses on one CSR matrix (zf_spmat_mr_eval's arguments): zf_solver_duality_gap of a solver of
+// zf_solver_create_sparse_responses writes the same values, bit for bit
+extern "C" int zf_spmat_mr_gap_eval(const zf_spmat* h, const double* b_dev, const double* w_dev, const double* p_dev, int32_t K, double scale,
+                                    double lam, double l2, int32_t loss, const double* x_host, double* out, int64_t count) {
+    const int rc = zf_mr_args("zf_spmat_mr_gap_eval", K, loss);
+    if (rc) return rc;
+    const zf_matview V = zf_csr_view_mr(h, K);
+    if (!p_dev) return zf_gap_entry("zf_spmat_mr_gap_eval", V, b_dev, true, w_dev, scale, lam, true, l2, loss, 0.0, x_host, out, count);
+    ZF_REQUIRE(!(l2 > 0.0), "zf_spmat_mr_gap_eval: not with penalty factors and l2 > 0 together (the ridge term would need the factors too)");
+    return zf_gap_pf_entry("zf_spmat_mr_gap_eval", V, b_dev, w_dev, p_dev, scale, lam, loss, 0.0, x_host, out, count);
 }
 
 // the gap evaluation followed by the gap-safe screen of its g (zf_kernels_screen.h), l2 = 0 only: out[0 .. 8) as zf_gap_eval - the

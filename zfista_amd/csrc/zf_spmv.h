@@ -45,6 +45,14 @@ struct zf_spmv_io {
 void zf_launch_spmv(const zf_spmv_mat& M, hipStream_t st, const zf_control* ctl, bool grad_guard, const zf_spmv_io& io, int slot,
                     double out_scale, double* partial);
 
+// The same sweep against K response-interleaved columns (zf_kernels_spmm.h, zf_spmm.hip): in holds M.cols K doubles, out M.rows K,
+// out[i K + k] = out_scale * sum_e values[e] * in[indices[e] K + k].  Response k is summed exactly as zf_launch_spmv sums a vector:
+// column k of out is bit-equal to that sweep on column k of in.  2 <= K <= ZF_SPMM_MAX_K (the caller checks); the same plan, the
+// same grid and launch count; partial: M.nseg K doubles of the caller (NULL when M has no split row).
+constexpr int ZF_SPMM_MAX_K = 16;
+void zf_launch_spmm(const zf_spmv_mat& M, hipStream_t st, const zf_control* ctl, bool grad_guard, const zf_spmv_io& io, int slot,
+                    double out_scale, int K, double* partial);
+
 // ---- residuals of LONG vectors --------------------------------------------------------------------------------------
 // r = A y - b by linearity with f(y), and f(x+) from s+ = A x+, as zf_resid_y_kernel / zf_resid_x_kernel compute them - but
 // those walk the m rows with ONE workgroup (dense matrices have at most a few 10^4 rows), and a sparse problem has 10^5 ..

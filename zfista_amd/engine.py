@@ -85,7 +85,7 @@ class DeviceSolver:
         roww = desc_fields.get("row_weights")   # per-row sample weights (a device pointer): likewise (zf_solver_set_row_weights)
         pf = desc_fields.get("penalty_factors")   # per-column penalty factors (a device pointer): likewise (zf_solver_set_penalty_factors)
         a32 = desc_fields.get("matrix_f32")   # the matrix stored in fp32 (a device pointer): likewise (zf_solver_set_matrix_f32)
-        responses = int(desc_fields.get("responses", 1) or 1)   # K responses on one dense matrix: likewise (zf_solver_set_responses)
+        responses = int(desc_fields.get("responses", 1) or 1)   # K responses on one matrix: likewise (dense: zf_solver_set_responses; with spmat: zf_solver_create_sparse_responses)
         for k, v in desc_fields.items():
             if k not in ("spmat", "l2", "huber_delta", "poisson", "row_weights", "penalty_factors", "matrix_f32", "responses"):
                 setattr(d, k, v)
@@ -94,7 +94,10 @@ class DeviceSolver:
             setattr(o, k, v)
         self.nesterov = bool(options.get("nesterov", 0))
         h = C.c_void_p()
-        if spmat is not None:
+        if spmat is not None and responses > 1:   # (K responses on one CSR matrix: a creator of its own; K = 1 takes the plain one)
+            _lib.check(self.lib.zf_solver_create_sparse_responses(C.byref(h), C.byref(d), C.c_void_p(spmat), responses, C.byref(o),
+                                                                  C.c_void_p(stream)), "zf_solver_create_sparse_responses")
+        elif spmat is not None:
             _lib.check(self.lib.zf_solver_create_sparse(C.byref(h), C.byref(d), C.c_void_p(spmat), C.byref(o), C.c_void_p(stream)),
                        "zf_solver_create_sparse")
         else:
@@ -114,7 +117,7 @@ class DeviceSolver:
             _lib.check(self.lib.zf_solver_set_penalty_factors(h, C.c_void_p(pf)), "zf_solver_set_penalty_factors")
         if a32:
             _lib.check(self.lib.zf_solver_set_matrix_f32(h, C.c_void_p(a32)), "zf_solver_set_matrix_f32")
-        if responses > 1:   # (K = 1 is the plain problem: the setter is not called)
+        if responses > 1 and spmat is None:   # (K = 1 is the plain problem: the setter is not called)
             _lib.check(self.lib.zf_solver_set_responses(h, responses), "zf_solver_set_responses")
         sub = C.c_int32(1)
         _lib.check(self.lib.zf_solver_sub_iters(h, C.byref(sub)), "zf_solver_sub_iters")
@@ -324,7 +327,8 @@ class DeviceSolver:
 
     def responses_plan(self):
         """(K, rows a workgroup of the K-response row sweep owns) of a dense solver (zf_solver_ls_plan, slots 4 and 5): (1, 0)
-        without ``zf_solver_set_responses``.  With it ``ls_plan()`` reports column sweep 9 / 10 and row sweep 7 / 8 - 16-byte /
+        without ``zf_solver_set_responses``.  A sparse solver: (K, 0) - K > 1 through ``zf_solver_create_sparse_responses``; its
+        ``ls_plan()`` is the plain sparse solver's (the handle's plan serves every K: csrc/zf_kernels_spmm.h).  With it ``ls_plan()`` reports column sweep 9 / 10 and row sweep 7 / 8 - 16-byte /
         scalar loads of A (csrc/zf_kernels_mr.h)."""
         out = np.zeros(6, dtype=np.int64)
         _lib.check(self.lib.zf_solver_ls_plan(self.handle, C.c_void_p(_lib.ptr(out)), out.size))

@@ -163,7 +163,8 @@ def l1_cv(problem, lams, folds=5, seed=0, x0=None, gap_tol=1e-6, refit=True, ret
 
 
 def l1_cv_lockstep(problem, lams, folds=5, seed=0, x0=None, gap_tol=1e-6, refit=True, **solver_kwargs):
-    """``l1_cv`` with all folds solved TOGETHER: the K folds of a dense ``LeastSquaresL1`` or ``LogisticL1`` are the K responses
+    """``l1_cv`` with all folds solved TOGETHER: the K folds of a ``LeastSquaresL1`` / ``LogisticL1`` (dense) or a
+    ``SparseLeastSquaresL1`` / ``SparseLogisticL1`` are the K responses
     of one ``problem.with_responses(B, W)`` - B holds b in every column, ``W[:, k] = w_base * (ids != k)`` - and one ``l1_path``
     over ``lams`` solves them in lockstep, every sweep reading the matrix once for all folds (K <= 16 folds).
 
@@ -178,10 +179,11 @@ def l1_cv_lockstep(problem, lams, folds=5, seed=0, x0=None, gap_tol=1e-6, refit=
     its own alpha, is at most that.)  The folds share one step size and one stopping time, so a fold is solved at least as far
     as ``l1_cv`` would solve it, not to the same iterate.  ``gap_tol=None`` is refused: without the certificate nothing says when
     the slowest fold is done."""
-    from .problems import MAX_RESPONSES, LeastSquaresL1, LogisticL1
+    from .problems import MAX_RESPONSES, LeastSquaresL1, LogisticL1, SparseLeastSquaresL1, SparseLogisticL1
 
-    if not isinstance(problem, (LeastSquaresL1, LogisticL1)):
-        raise ValueError("l1_cv_lockstep needs a dense LeastSquaresL1 or LogisticL1 (the K-response sweeps read a dense fp64 matrix)")
+    if not isinstance(problem, (LeastSquaresL1, LogisticL1, SparseLeastSquaresL1, SparseLogisticL1)):
+        raise ValueError("l1_cv_lockstep needs a dense LeastSquaresL1 or LogisticL1, or a SparseLeastSquaresL1 or SparseLogisticL1 (the "
+                         "K-response sweeps read a dense fp64 matrix or a CSR matrix, under the squared or the logistic loss)")
     if gap_tol is None:
         raise ValueError("l1_cv_lockstep needs gap_tol: the joint duality gap is what certifies every fold (use l1_cv for gap_tol=None)")
     if solver_kwargs.get("screen"):

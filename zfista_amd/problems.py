@@ -1170,11 +1170,10 @@ class _MultiResponseMixin:
     _MR_WHY = ("the problem has several responses: the column-norm, screening and restriction kernels see one column of x per "
                "column of A, and the K-response forms are not built")
 
-    def _set_mr(self, A, B, lam, scale, bounds, l2, sample_weight, penalty_factor, share=None):
-        """Everything that can be refused is refused on the host, before anything touches the device.  ``share``: a plain problem
-        whose device matrix is adopted (``with_responses``)."""
+    def _check_mr(self, shape, B, l2, sample_weight, penalty_factor):
+        """Everything that can be refused is refused on the host, before anything touches the device: (B as a host array, m, n,
+        K, the flat weights or None, the flat factors or None) for a matrix of ``shape``; sets ``l2``."""
         Bh = B.detach().cpu().numpy() if hasattr(B, "detach") else np.asarray(B)
-        shape = tuple(share.A.shape) if share is not None else tuple(getattr(A, "shape", None) or np.shape(A))
         if len(shape) != 2 or Bh.ndim != 2 or Bh.shape[0] != shape[0] or Bh.shape[1] < 1:
             raise ValueError(f"A must be (m, n) and B (m, K) with K >= 1, got A {shape} and B {Bh.shape}")
         m, n, K = int(shape[0]), int(shape[1]), int(Bh.shape[1])
@@ -1189,8 +1188,10 @@ class _MultiResponseMixin:
             w = _check_weights(_broadcast_columns(sample_weight, m, K, "sample_weight", "row").reshape(-1), m * K)
         if penalty_factor is not None:
             p = _check_penalty_factor(_broadcast_columns(penalty_factor, n, K, "penalty_factor", "column").reshape(-1), n * K, None, self.l2)
-        self._f32 = False
-        self.A = share.A if share is not None else _to_device(A, "A")
+        return Bh, m, n, K, w, p
+
+    def _finish_mr(self, Bh, lam, scale, bounds, m, n, K, w, p):
+        """B, the scalars, the flattened lengths, the weights and the factors - whatever the storage of the matrix is."""
         self.b = _to_device(np.ascontiguousarray(Bh, dtype=np.float64).reshape(-1), "B")
         self.lam, self.scale = float(lam), float(scale)
         self.box = (-np.inf, np.inf) if bounds is None else (float(bounds[0]), float(bounds[1]))
@@ -1200,6 +1201,14 @@ class _MultiResponseMixin:
         self._norms = _ColumnNorms()
         self._set_weights(w)
         self._set_penalty_factor(p)
+
+    def _set_mr(self, A, B, lam, scale, bounds, l2, sample_weight, penalty_factor, share=None):
+        """``share``: a plain problem whose device matrix is adopted (``with_responses``)."""
+        shape = tuple(share.A.shape) if share is not None else tuple(getattr(A, "shape", None) or np.shape(A))
+        checked = self._check_mr(shape, B, l2, sample_weight, penalty_factor)
+        self._f32 = False
+        self.A = share.A if share is not None else _to_device(A, "A")
+        self._finish_mr(checked[0], lam, scale, bounds, *checked[1:])
 
     # -- shapes --------------------------------------------------------------------------------
     def coef(self, x):
@@ -1216,6 +1225,8 @@ class _MultiResponseMixin:
         return NativeProblem.minimize_proximal_gradient(self, self._flat(x0), **kwargs)
 
     # -- entry points ---------------------------------------------------------------------------
+    _MR_ENTRY = ("zf_mr_eval", "zf_mr_gap_eval")   # (f / jac_f and the certificate at K > 1; the sparse classes name their own)
+
     def _lead(self, *w):
         return (_dp(self.A), _dp(self.b), *w, self._m, self._n)
 
@@ -1228,8 +1239,9 @@ class _MultiResponseMixin:
         lib = _lib.require_gpu()
         fval = C.c_double(0.0)
         grad = np.empty_like(x) if want_grad else None
-        _lib.check(lib.zf_mr_eval(*self._lead(_dp(self._w)), self.n_responses, self.scale, self._loss, C.c_void_p(_lib.ptr(x)),
-                                  C.byref(fval), C.c_void_p(_lib.ptr(grad)) if want_grad else None), "zf_mr_eval")
+        name = self._MR_ENTRY[0]
+        _lib.check(getattr(lib, name)(*self._lead(_dp(self._w)), self.n_responses, self.scale, self._loss, C.c_void_p(_lib.ptr(x)),
+                                      C.byref(fval), C.c_void_p(_lib.ptr(grad)) if want_grad else None), name)
         return np.float64(fval.value), grad
 
     def f(self, x):
@@ -1241,8 +1253,9 @@ class _MultiResponseMixin:
     def _gap_call(self, lib, x, out):
         if self.n_responses == 1:
             return super()._gap_call(lib, x, out)
-        _lib.check(lib.zf_mr_gap_eval(*self._lead_pf(), self.n_responses, self.scale, self.lam, self.l2, self._loss,
-                                      C.c_void_p(_lib.ptr(x)), C.c_void_p(_lib.ptr(out)), out.size), "zf_mr_gap_eval")
+        name = self._MR_ENTRY[1]
+        _lib.check(getattr(lib, name)(*self._lead_pf(), self.n_responses, self.scale, self.lam, self.l2, self._loss,
+                                      C.c_void_p(_lib.ptr(x)), C.c_void_p(_lib.ptr(out)), out.size), name)
 
     def duality_gap(self, x):
         return super().duality_gap(self._flat(x))
@@ -1339,6 +1352,88 @@ def _logistic_with_responses(self, B, sample_weight=None):
 
 LeastSquaresL1.with_responses = _ls_with_responses
 LogisticL1.with_responses = _logistic_with_responses
+
+
+# ---------------------------------------------------------------------------
+# K responses on one CSR matrix (csrc/zf_kernels_spmm.h)
+# ---------------------------------------------------------------------------
+class _SparseMultiResponseMixin(_MultiResponseMixin):
+    r"""``_MultiResponseMixin`` on the storage of ``_SparseMarginsL1``: the plain sparse problem on ``sp.kron(A, sp.identity(K))``
+    with every array flattened in C order, solved on the handle of A as it is - same CSR arrays, same plans, nothing stored K
+    times.  The two sweeps gather the K values of a stored element as K 8 contiguous bytes (csrc/zf_kernels_spmm.h): one index,
+    one value and one gathered line serve K responses, and response k is summed exactly as the plain sweep sums a vector, so
+    every output is bit-equal to the plain sparse class on the Kronecker matrix.  K = 1 is the plain sparse class, bit for bit
+    (the plain creator, the plain entries).  K <= 16.  No screening, no acceptance="remainder" / "resolved"."""
+
+    _MR_ENTRY = ("zf_spmat_mr_eval", "zf_spmat_mr_gap_eval")
+
+    def _lead(self, *w):
+        return (self._spmat.value, _dp(self.b), *w)
+
+    def _set_mr(self, A, B, lam, scale, bounds, l2, sample_weight, penalty_factor, share=None):
+        """``share``: a plain sparse problem whose matrix handle - the object itself - is adopted (``with_responses``)."""
+        from . import sparse
+
+        shape = (share.m_rows, share.n_features) if share is not None else tuple(getattr(A, "shape", None) or ())
+        checked = self._check_mr(shape, B, l2, sample_weight, penalty_factor)
+        if not np.isfinite(checked[0]).all():
+            raise ValueError("B holds non-finite values")
+        if share is not None:
+            self._spmat, self.nnz, self.plan, self._longest = share._spmat, share.nnz, share.plan, share._longest
+        else:
+            prep = sparse.prepare(A)   # (every ValueError comes from here, before anything touches the device)
+            self.nnz, self.plan = prep["nnz"], (prep["plan"], prep["t_plan"])
+            self._longest = (int(np.diff(prep["indptr"]).max(initial=0)), int(np.diff(prep["t_indptr"]).max(initial=0)))
+            self._spmat = _SpmatHandle(prep)
+        self._finish_mr(checked[0], lam, scale, bounds, *checked[1:])
+
+    def with_matrix_dtype(self, dtype):
+        raise ValueError("with_matrix_dtype is not available: a sparse matrix is stored as fp64 values")
+
+
+class SparseMultiResponseLeastSquaresL1(_SparseMultiResponseMixin, _SparseMarginsL1):
+    r"""``SparseLeastSquaresL1`` for K right-hand sides at once: f(X) = scale \|A X - B\|_F^2 (weighted: scale sum W o (A X - B)^2),
+    B (m, K), A any scipy.sparse matrix.  See ``_SparseMultiResponseMixin``."""
+
+    kind = _lib.ZF_PROBLEM_SPARSE_LS_L1
+
+    def __init__(self, A, B, lam, scale=0.5, bounds=None, l2=0.0, *, sample_weight=None, penalty_factor=None, _share=None):
+        self._set_mr(A, B, lam, scale, bounds, l2, sample_weight, penalty_factor, _share)
+
+
+class SparseMultiResponseLogisticL1(_SparseMultiResponseMixin, _SparseMarginsL1):
+    r"""``SparseLogisticL1`` for K label vectors at once (one-vs-rest classification): B (m, K) holds exactly -1 / +1.
+    See ``_SparseMultiResponseMixin``."""
+
+    kind = _lib.ZF_PROBLEM_SPARSE_LOGISTIC_L1
+    _loss = _lib.ZF_LOSS_LOGISTIC
+
+    def __init__(self, A, B, lam, scale=1.0, bounds=None, l2=0.0, *, sample_weight=None, penalty_factor=None, _share=None):
+        self._set_mr(A, B, lam, scale, bounds, l2, sample_weight, penalty_factor, _share)
+
+
+def _sparse_with_responses(problem, cls, B, sample_weight):
+    bounds = problem.box if problem._has_box() else None
+    return cls(None, B, problem.lam, problem.scale, bounds, problem.l2, sample_weight=sample_weight,
+               penalty_factor=problem.penalty_factor, _share=problem)
+
+
+def _sparse_ls_with_responses(self, B, sample_weight=None):
+    """A ``SparseMultiResponseLeastSquaresL1`` on this problem's matrix handle (the same object: no upload, no new plan; only B is
+    uploaded) with its lam, scale, bounds, l2 and penalty factors (repeated for every response).  ``B``: (m, K);
+    ``sample_weight``: (m,) or (m, K) or None."""
+    return _sparse_with_responses(self, SparseMultiResponseLeastSquaresL1, B, sample_weight)
+
+
+def _sparse_logistic_with_responses(self, B, sample_weight=None):
+    """A ``SparseMultiResponseLogisticL1`` on this problem's matrix handle (the same object; only B is uploaded) with its lam,
+    scale, bounds, l2 and penalty factors (repeated for every response).  ``B``: (m, K) of -1 / +1; ``sample_weight``: (m,) or
+    (m, K) or None."""
+    return _sparse_with_responses(self, SparseMultiResponseLogisticL1, B, sample_weight)
+
+
+SparseLeastSquaresL1.with_responses = _sparse_ls_with_responses
+SparseLogisticL1.with_responses = _sparse_logistic_with_responses
 
 
 class BlurHaarL1(NativeProblem):
