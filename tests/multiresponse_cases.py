@@ -25,9 +25,9 @@ import weight_cases as W
 from oracle import problems_ref as P
 
 SCALE = {"square": 0.5, "logistic": 1.0}
-KS = (2, 3, 5, 8, 12, 16)   # (12: the three-row register tile of K = 9 .. 12, 24 rows per workgroup)
+KS = tuple(range(2, 17))    # every K is a kernel instantiation of its own (ZF_MR_EACH_K): the element-wise tests run them all
 REPLACED = 11  # seeds replaced when the table was drawn: nine of the box endings (iterates of at most 0.3: a few ulps there are 1e-15 of the
-               # largest entry), two of the boxed K = 16 cases of the main table
+               # largest entry), two of the boxed K = 16 cases of the main table; none of ALL_K
 ITER_TOL = 3e-15
 
 
@@ -260,8 +260,24 @@ def _endings():
     return out
 
 
+def _all_k():
+    """One short solve per loss and per K = 2 .. 16 through the solver's ring-indexed launches: m one row into the second workgroup
+    of the row sweep; n = 67 (scalar loads, V = 1) under one loss and 130 (16-byte loads, V = 2) under the other, swapped with
+    K // 2, so every K meets both widths; none / weights / factors by K % 3."""
+    out = []
+    for loss, s0 in (("square", 600), ("logistic", 700)):
+        for K in range(2, 17):
+            n = (67, 130)[((K // 2) + (loss == "logistic")) % 2]
+            extra = (dict(), dict(weights="real"), dict(factors="pos"))[K % 3]
+            c = Case(loss, K, rows_per_wg(K) + 1, n, s0 + K, opts=dict(max_iter=30), **extra)
+            c.tag = "allk"
+            out.append(c)
+    return out
+
+
 CASES = _table()
 ENDINGS = _endings()
+ALL_K = _all_k()
 # m K > 32768 rows of margins, unweighted squared loss: the solver forms r(y), f(y) and f(x+) with many workgroups there (the wide
 # residual kernels of the sparse kind), which no case above reaches.  Tall and narrow, so the reference closures stay cheap; eight
 # iterations: the columns are scaled over 1.5 decades, yet the few active coefficients are found within ten iterations, after

@@ -25,11 +25,12 @@ import sparse_cases as S
 import weight_cases as W
 
 SCALE = M.SCALE
-KS = (2, 3, 5, 8, 12, 16)          # the sweeps, element-wise
-SOLVE_KS = (2, 5, 9, 12, 16)       # the solves
+KS = tuple(range(2, 17))           # the sweeps, element-wise: every K is a kernel instantiation of its own (ZF_SPMM_CASE)
+MANY_SPLIT_KS = (2, 4, 7, 16)      # ... on `many-split` (1.2e6 elements per sweep): both gather forms at both pipeline depths
+SOLVE_KS = (2, 5, 9, 12, 16)       # the solves of CASES (ALL_K: every K)
 THRESHOLD = 4096                   # zfista_amd.sparse.SPLIT_THRESHOLD (asserted on the CPU)
 LANES = (4, 8, 16, 32, 64)
-REPLACED = 0   # seeds replaced when the tables were drawn
+REPLACED = 0   # seeds replaced when the tables were drawn (ALL_K included)
 BOX = M.BOX
 # (m, n, density): lanes per row of A / of A^T = 8 / 8, 64 / 8, 4 / 16, 32 / 16
 SHAPES = {"a": (60, 90, 0.15), "b": (40, 300, 0.25), "c": (200, 50, 0.1), "d": (33, 67, 0.6)}
@@ -170,8 +171,22 @@ def _endings():
     return out
 
 
+def _all_k():
+    """One short solve per loss and per K = 2 .. 16 through the solver's own launches: the shape, hence the two lane widths, by
+    K % 4; none / weights / factors by K % 3 (multiresponse_cases.ALL_K's seeds and options)."""
+    out = []
+    for loss, s0 in (("square", 600), ("logistic", 700)):
+        for K in range(2, 17):
+            extra = (dict(), dict(weights="real"), dict(factors="pos"))[K % 3]
+            c = Case(loss, K, "abcd"[K % 4], s0 + K, opts=dict(max_iter=30), **extra)
+            c.tag = "allk"
+            out.append(c)
+    return out
+
+
 CASES = _table()
 ENDINGS = _endings()
+ALL_K = _all_k()
 SNAPSHOT_CASES = [0, 5, 13]   # indices into CASES
 TALL_K = 8                    # sparse_cases.TALL with K = 8: 320 000 rows of margins (the wide residual kernels), a split row of A^T
 

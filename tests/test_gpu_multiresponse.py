@@ -2,15 +2,16 @@
 MultiResponseLogisticL1, l1_cv_lockstep).
 
 (1) The two sweeps element-wise: f and every element of jac_f against oracle.problems_ref.ls_longdouble per response, inside its
-    a-priori bound, for K in {2, 3, 5, 8, 12, 16} on every load width and remainder path (multiresponse_cases.sweep_shapes), the
-    kernel forms asserted through zf_solver_ls_plan.  ZF_MR_BOUNDS_RECORD=1 appends the worst error / bound ratios to
+    a-priori bound, for EVERY K = 2 .. 16 (each is a kernel instantiation of its own) on every load width and remainder path
+    (multiresponse_cases.sweep_shapes), the kernel forms asserted through zf_solver_ls_plan.  ZF_MR_BOUNDS_RECORD=1 appends the worst error / bound ratios to
     profiles/multiresponse_bounds.jsonl (any other value: to that path).
 (2) Response symmetry: equal columns of B give bit-equal columns of jac_f and of every iterate of a 30-iteration FISTA solve.
-(3) Response independence: another column k of B changes no bit of the other columns; inf in X[:, k] leaves the others finite.
+(3) Response independence, every K: another column k of B changes no bit of the other columns; inf in X[:, k] leaves the others finite.
 (4) Solves against the CPU oracle on the Kronecker matrix at 1e-10, the lr and trial sequences exactly (multiresponse_cases.CASES and
     ENDINGS; TALL: m K > 32768, the wide residual kernels), against the existing
     device class on the same Kronecker matrix, with and without return_all, advanced three passes at a time, and resumed from a
-    snapshot.
+    snapshot.  multiresponse_cases.ALL_K: one 30-iteration solve per loss and per K = 2 .. 16 through the solver's ring-indexed
+    launches, each K under both load widths - oracle, sequences, sub_iters, the Kronecker class and the certificate.
 (5) The certificate against the existing class's on the Kronecker matrix; the live solver's; gap_tol; every response's own gap.
 (6) l1_cv_lockstep: fold ids and every fold's certificate for both losses; the score bound and lam_best against l1_cv for the squared
     loss only (the bound needs strong convexity in x).  (7) K = 1, with_responses, streams.  (8) Refusals at the C level in both call orders."""
@@ -155,7 +156,7 @@ def test_equal_columns_give_bit_equal_columns(K, loss):
 
 
 # ---- (3) response independence -----------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("K", [2, 5, 16])
+@pytest.mark.parametrize("K", M.KS)
 def test_a_response_touches_no_other(K):
     m, n = 65, 130
     rng = np.random.default_rng(K)
@@ -471,6 +472,50 @@ def test_gap_tol_stops_where_a_hand_run_probe_predicts(loss):
     res = _quiet(minimize_proximal_gradient, *prob.callbacks(), case.x0(), lr=1.0, tol=0.0, nesterov=True, max_iter=4000, gap_tol=gap_tol, gap_every=16)
     assert res.success and res.message == "Duality gap reached gap_tol" and res.dual_gap_checks == checks and res.nit == nit_probe
     assert np.array_equal(_bits(res.x), _bits(x_probe)) and 0 <= res.dual_gap <= gap_tol
+
+
+@pytest.mark.parametrize("idx", range(len(M.ALL_K)), ids=[c.id for c in M.ALL_K])
+def test_every_k_solves_through_the_solvers_own_launches(idx):
+    """multiresponse_cases.ALL_K: every K = 2 .. 16 under both losses, m one row into the second workgroup of the row sweep, n = 67
+    (V = 1) under one loss and 130 (V = 2) under the other.  The comparisons are those of the tests above, unchanged: the oracle on
+    the Kronecker closures at TOL (iterates, F, err), the lr and trial sequences exactly, sub_iters 1 / 16 three passes at a time
+    bit-equal to the plain solve, the existing class on np.kron(A, I_K) at TOL, the certificate at the final iterate inside the
+    long-double bounds of _gap_reference, the live solver's certificate bit-equal to the standalone one."""
+    import weight_cases as W
+    from zfista_amd import _lib, minimize_proximal_gradient
+    from zfista_amd.proximal_gradient import NativeRun
+
+    case = M.ALL_K[idx]
+    exp = _oracle(idx, "ALL_K")
+    prob, kron = _problem(case), _kron_problem(case)
+    kw = dict(case.opts, gap_tol=None)
+    res = _quiet(minimize_proximal_gradient, *prob.callbacks(), case.x0(), return_all=True, **kw)
+    _compare(res, exp, case)
+    assert res.nit == 30 and np.abs(prob.coef(res.x)).max() > 0
+    for sub in (1, 16):
+        rows, x = _drain(prob, case, 3, sub_iters=sub)
+        assert np.array_equal(_bits(x), _bits(res.x)) and len(rows) == res.nit, sub
+        assert np.array_equal(rows[:, _lib.TR_F], np.asarray(res.allfuns[1:], float).reshape(-1))
+        _check_sequences(rows, exp)
+        assert int(rows[:, _lib.TR_TRIALS].sum()) > res.nit, "the case must reject trials"
+    kr = _quiet(minimize_proximal_gradient, *kron.callbacks(), case.x0(), return_all=True, **kw)
+    assert kr.nit == res.nit and rel_err(res.x, kr.x) <= TOL and abs(res.fun - kr.fun) <= TOL * abs(kr.fun)
+    # the certificate at the final iterate: inside the long-double bounds, as the existing class's
+    a, b = prob.duality_gap(res.x), kron.duality_gap(res.x)
+    vals, bounds = _gap_reference(case, res.x)
+    ra, rb = W.worst_ratio(a, vals, bounds), W.worst_ratio(b, vals, bounds)
+    print(f"{case.id}: worst certificate error / bound {max(ra.values()):.3g}")
+    assert max(ra.values()) <= 1.0 and max(rb.values()) <= 1.0, (ra, rb)
+    assert a.gap >= 0
+    _record(dict(test="certificate", case=case.id, ratio=max(ra.values())))
+    # the live solver's certificate is the standalone one, bit for bit
+    run = NativeRun(prob, case.x0(), dict(_OPTS, max_iter=100000))
+    for _ in range(20):
+        run.advance(1)
+    live, alone = run.duality_gap(), prob.duality_gap(run.solver.get_x())
+    assert run.solver.responses_plan() == (case.K, M.rows_per_wg(case.K))
+    run.solver.close()
+    assert all(np.array_equal(_bits(getattr(live, k)), _bits(getattr(alone, k))) for k in GC.KEYS), (live, alone)
 
 
 # ---- (6) l1_cv_lockstep ---------------------------------------------------------------------------------------------------------

@@ -7,13 +7,14 @@ sum a vector - so the existing sparse classes on the Kronecker matrix perform th
 order, and every comparison against them below is bit for bit.  The CPU oracle on the SciPy closures of the Kronecker matrix is
 the independent reference, at the project's parity tolerance 1e-10.
 
-(1) Both sweeps element-wise: zf_spmat_mr_apply(K)[:, k] == zf_spmat_mr_apply(K = 1) on column k, K in {2, 3, 5, 8, 12, 16}, on the
-    SMALL and TALL matrices and on hand-built ones: every remainder of a lane per lane width, nnz = 0, one row, one column, the
-    split threshold from both sides, 300 split rows.
+(1) Both sweeps element-wise: zf_spmat_mr_apply(K)[:, k] == zf_spmat_mr_apply(K = 1) on column k, for EVERY K = 2 .. 16 (each is a
+    kernel instantiation of its own, per lane width), on the SMALL and TALL matrices and on hand-built ones: every remainder of a
+    lane per lane width, nnz = 0, one row, one column, the split threshold from both sides, 300 split rows (K in {2, 4, 7, 16}).
 (2) Equal columns give bit-equal columns (jac_f, 30 FISTA iterates); inf in one column leaves the others' bits.
 (3) f, jac_f, duality_gap: the Kronecker class's bits, inside the long-double bounds on the Kronecker CSR.
 (4) Solves: the Kronecker class bit for bit (nit, status, message, iterates, F, err, lr and trial columns; sub_iters 1 / 16; three
-    passes at a time), the oracle at 1e-10; every ending.  (5) TALL with K = 8: FISTA and ISTA, a resume across a snapshot.
+    passes at a time), the oracle at 1e-10; every ending; sparse_multiresponse_cases.ALL_K: one solve per loss and per K = 2 .. 16
+    through the solver's own launches.  (5) TALL with K = 8: FISTA and ISTA, a resume across a snapshot.
 (6) gap_tol, the live certificate, l1_cv_lockstep on sparse problems.  (7) K = 1, with_responses, streams, the creator's
     refusals, the plain sparse solver's launch count."""
 import contextlib
@@ -128,6 +129,8 @@ SWEEP_NAMES = [f"small{i}" for i in range(len(S.SMALL))] + ["tall"] + [n for n, 
 
 @pytest.mark.parametrize("name", SWEEP_NAMES)
 def test_every_column_of_a_sweep_is_the_plain_sweep_on_that_column(name):
+    """Every K = 2 .. 16 on every matrix but `many-split` (1.2e6 elements per sweep), which takes K in (2, 4, 7, 16): the 16-byte and
+    the scalar gather, each at four and at two elements in flight."""
     from zfista_amd import _lib
 
     lib = _lib.require_gpu()
@@ -135,7 +138,8 @@ def test_every_column_of_a_sweep_is_the_plain_sweep_on_that_column(name):
     A = sp.csr_matrix(dict(_sweep_inputs())[name])
     absA = abs(A)
     scale = 0.3
-    ks = (2, 16) if name == "many-split" else SM.KS   # (1.2e6 elements per sweep: the two gather forms' extremes)
+    ks = SM.MANY_SPLIT_KS if name == "many-split" else SM.KS
+    assert tuple(SM.KS) == tuple(range(2, 17))
     for transpose in (0, 1):
         Mx, absM = (A.T, absA.T) if transpose else (A, absA)
         cols = Mx.shape[1]
@@ -176,7 +180,7 @@ def test_equal_columns_give_bit_equal_columns(K, loss):
     assert np.abs(prob.coef(res.x)).max() > 0
 
 
-@pytest.mark.parametrize("K", [2, 5, 16])
+@pytest.mark.parametrize("K", SM.KS)
 def test_a_response_touches_no_other(K):
     A, B, lam = SM.make("square", "d", K, 78)
     m, n = A.shape
@@ -339,6 +343,44 @@ def test_every_ending_is_the_kronecker_class_and_the_oracle(idx):
     assert status == status_k and _same(rows, rows_k) and _same(x, x_k) and _same(x, res.x)
     assert np.array_equal(rows[:, _lib.TR_TRIALS].astype(np.int64), np.asarray(exp.alltrials, np.int64))
     assert np.array_equal(rows[:, _lib.TR_LR], np.asarray(exp.alllrs, float))
+
+
+@pytest.mark.parametrize("idx", range(len(SM.ALL_K)), ids=[c.id for c in SM.ALL_K])
+def test_every_k_solves_through_the_solvers_own_launches(idx):
+    """sparse_multiresponse_cases.ALL_K: every K = 2 .. 16 under both losses, the shape (hence the lane widths of both sweeps) by K % 4.
+    The Kronecker class bit for bit - nit, status, message, every iterate, F, err (return_all) and every trace column, lr and trials
+    among them; the oracle at 1e-10 and its lr / trial sequences exactly; f, jac_f and the certificate at x = 0 and at the final
+    iterate bit for bit."""
+    from zfista_amd import _lib
+
+    case = SM.ALL_K[idx]
+    exp = _oracle(idx, "ALL_K")
+    new, kr, res = _solve_both_ways(case, exp)
+    assert res.nit == 30 and np.abs(new.coef(res.x)).max() > 0
+    opts = dict(_OPTS, **case.opts)
+    rows, x, status = _drain(new, case.x0(), opts, 3)
+    rows_k, x_k, status_k = _drain(kr, case.x0(), opts, 3)
+    assert len(rows) == res.nit and status == status_k and _same(rows, rows_k) and _same(x, x_k) and _same(x, res.x)
+    assert np.array_equal(rows[:, _lib.TR_TRIALS].astype(np.int64), np.asarray(exp.alltrials, np.int64))
+    assert np.array_equal(rows[:, _lib.TR_LR], np.asarray(exp.alllrs, float))
+    assert int(rows[:, _lib.TR_TRIALS].sum()) > res.nit, "the case must reject trials"
+    assert _responses_plan(new, case) == (case.K, 0)
+    for xp in (np.zeros(case.n * case.K), np.asarray(res.x)):
+        assert _same(new.f(xp), kr.f(xp)), (new.f(xp), kr.f(xp))
+        assert _same(new.jac_f(xp), kr.jac_f(xp))
+        a, b = new.duality_gap(xp), kr.duality_gap(xp)
+        assert all(_same(getattr(a, k), getattr(b, k)) for k in GC.KEYS), (a, b)
+        assert a.gap >= 0
+
+
+def _responses_plan(prob, case):
+    """responses_plan() of a solver of the problem: (K, 0) for the sparse kind."""
+    from zfista_amd.proximal_gradient import NativeRun
+
+    run = NativeRun(prob, case.x0(), dict(_OPTS, **case.opts))
+    plan = run.solver.responses_plan()
+    run.solver.close()
+    return plan
 
 
 @pytest.mark.parametrize("idx", SM.SNAPSHOT_CASES, ids=[SM.CASES[i].id for i in SM.SNAPSHOT_CASES])

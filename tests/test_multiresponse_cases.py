@@ -3,7 +3,8 @@
 Every case is solved by the reference solver twice - on the closures of the existing case modules over np.kron(A, I_K), and on the
 per-response closures (A @ X, A.T @ R) - and both must decide every trial alike (the same nit, message, step and trial sequences)
 and keep every iterate within 3e-15 of each other: the table then says nothing about summation orders, and a device that departs
-from the oracle on it departs for a reason of its own.  The endings table holds every way a run ends three times per loss."""
+from the oracle on it departs for a reason of its own.  The endings table holds every way a run ends three times per loss; ALL_K
+holds one solve per loss and per K = 2 .. 16 (every K is a kernel instantiation of its own), each under both load widths."""
 import contextlib
 import io
 import warnings
@@ -36,7 +37,7 @@ def _both(case):
     return _RES[case.id]
 
 
-@pytest.mark.parametrize("case", M.CASES + M.ENDINGS + M.TALL, ids=lambda c: c.id)
+@pytest.mark.parametrize("case", M.CASES + M.ENDINGS + M.TALL + M.ALL_K, ids=lambda c: c.id)
 def test_the_two_evaluations_decide_alike_and_stay_together(case):
     a, b = _both(case)
     assert a.nit == b.nit and a.message == b.message and a.success == b.success
@@ -51,14 +52,34 @@ def test_the_two_evaluations_decide_alike_and_stay_together(case):
 
 
 def test_ids_are_unique_and_the_kronecker_matrices_stay_small():
-    ids = [c.id for c in M.CASES + M.ENDINGS]
+    ids = [c.id for c in M.CASES + M.ENDINGS + M.ALL_K]
     assert len(set(ids)) == len(ids)
     assert all(c.m * c.K > 32768 and c.m * c.K * c.n * c.K * 8 <= 64 << 20 and c.weights is None and c.loss == "square" for c in M.TALL)
-    for c in M.CASES + M.ENDINGS:
+    for c in M.CASES + M.ENDINGS + M.ALL_K:
         assert c.m * c.K <= 1200 and c.n * c.K <= 2100 and 2 <= c.K <= 16, c.id
     assert {c.K for c in M.CASES} == {2, 5, 9, 12, 16} and {c.loss for c in M.CASES} == {"square", "logistic"}
     assert all(0 <= i < len(M.CASES) for i in M.SNAPSHOT_CASES) and len(M.SNAPSHOT_CASES) == 4
     assert M.REPLACED >= 0
+
+
+def test_all_k_holds_every_k_under_both_losses_and_both_load_widths():
+    """ALL_K as the issue of this table fixes it: 30 cases, K = 2 .. 16 under both losses; one row into the second workgroup of the row
+    sweep; each K with an odd n (V = 1) under one loss and an even n (V = 2) under the other; none / weights / factors by K % 3; every
+    case rejects trials (the acceptance test is exercised); at most one seed in four replaced (by seed + 100, counted in REPLACED)."""
+    assert len(M.ALL_K) == 30 and M.KS == tuple(range(2, 17))
+    for loss, s0 in (("square", 600), ("logistic", 700)):
+        mine = [c for c in M.ALL_K if c.loss == loss]
+        assert [c.K for c in mine] == list(range(2, 17))
+        assert {c.seed - s0 - c.K for c in mine} <= {0, 100} and sum(c.seed != s0 + c.K for c in mine) <= len(mine) // 4
+        assert {c.n % 2 for c in mine} == {0, 1}
+    for K in range(2, 17):
+        sq, lg = (next(c for c in M.ALL_K if c.K == K and c.loss == loss) for loss in ("square", "logistic"))
+        assert sq.m == lg.m == M.rows_per_wg(K) + 1 and sq.n == (67, 130)[(K // 2) % 2] and {sq.n, lg.n} == {67, 130}, "both column parities"
+        for c in (sq, lg):
+            assert (c.weights, c.factors) == ((None, None), ("real", None), (None, "pos"))[K % 3] and c.opts["max_iter"] == 30
+            assert c.box is None and not c.l2fac, "a certificate exists for every case"
+            a, _ = _both(c)
+            assert a.nit == 30 and int(np.sum(a.alltrials)) > a.nit, (c.id, "the case must reject trials")
 
 
 @pytest.mark.parametrize("loss", ["square", "logistic"])
@@ -83,7 +104,8 @@ def test_every_ending_occurs_three_times(loss):
 
 
 def test_the_restated_launch_rules():
-    assert [M.rows_per_wg(K) for K in (2, 8, 9, 12, 13, 16)] == [16, 16, 24, 24, 32, 32] and 12 in M.KS
+    assert [M.rows_per_wg(K) for K in (2, 8, 9, 12, 13, 16)] == [16, 16, 24, 24, 32, 32] and M.KS == tuple(range(2, 17))
+    assert [M.rows_per_wg(K) for K in M.KS] == [16] * 7 + [24] * 4 + [32] * 4
     assert M.slices_of(100, 518) == (13, 8) and M.slices_of(17, 64) == (3, 6) and M.slices_of(1, 7) == (1, 1)
     for K in M.KS:
         shapes = M.sweep_shapes(K)

@@ -1,7 +1,7 @@
 """CPU: the tables of tests/sparse_multiresponse_cases.py are what they claim.  The plan and the row contents of
 sp.kron(A, I_K) are those of A per response, for A and for A^T, on every matrix the GPU file uses (the claim the exact comparisons
 rest on); the shapes reach all five lane widths in both sweeps and split rows in both; every case decides every trial alike under
-two CPU evaluations; the endings end as their tags say."""
+two CPU evaluations; the endings end as their tags say; ALL_K holds one solve per loss and per K = 2 .. 16."""
 import contextlib
 import io
 import warnings
@@ -34,12 +34,14 @@ def test_the_constants_restate_the_library():
         assert SM.lanes_of(A) == sparse.lanes_for(lengths)
 
 
-@pytest.mark.parametrize("K", [2, 3, 5, 8, 16])
+@pytest.mark.parametrize("K", SM.KS)
 def test_the_kronecker_matrix_has_the_plan_and_the_rows_of_a_per_response(K):
+    """Every K = 2 .. 16 on every matrix the GPU file uses - SMALL, TALL, the hand-built sweep matrices and SHAPES (the whole
+    parametrisation takes ten seconds); `many-split` (1.2e6 elements) at the K the GPU file sweeps it with."""
     seen, split_A, split_At = set(), 0, 0
     mats = [(f"small{i}", S.make_sparse(*c)[0]) for i, c in enumerate(S.SMALL)]
     mats.append(("tall", S.make_sparse(*S.TALL)[0]))
-    mats += [(n, A) for n, A in SM.sweep_matrices() if n != "many-split" or K == 2]   # (1.2e6 elements: once)
+    mats += [(n, A) for n, A in SM.sweep_matrices() if n != "many-split" or K in SM.MANY_SPLIT_KS]
     mats += [(s, SM.make("square", s, K, 1)[0]) for s in SM.SHAPES]
     for name, A in mats:
         (la, sa), (lt, st) = SM.plan_claim(A, K)
@@ -70,7 +72,18 @@ def test_the_edge_rows_hit_every_remainder_of_a_lane():
 
 def test_the_tables_cover_what_they_name():
     ks = {c.K for c in SM.CASES}
-    assert ks == set(SM.SOLVE_KS)
+    assert ks == set(SM.SOLVE_KS) and SM.KS == tuple(range(2, 17)) and set(SM.MANY_SPLIT_KS) == {2, 4, 7, 16}
+    # ALL_K: 30 cases, K = 2 .. 16 under both losses, the shape by K % 4 and the extras by K % 3, seeds 600 + K / 700 + K (a replaced one:
+    # + 100, at most one in four, counted in REPLACED)
+    assert len(SM.ALL_K) == 30
+    for loss, s0 in (("square", 600), ("logistic", 700)):
+        mine = [c for c in SM.ALL_K if c.loss == loss]
+        assert [c.K for c in mine] == list(range(2, 17))
+        assert {c.seed - s0 - c.K for c in mine} <= {0, 100} and sum(c.seed != s0 + c.K for c in mine) <= len(mine) // 4
+        for c in mine:
+            assert c.shape == "abcd"[c.K % 4] and c.opts["max_iter"] == 30 and c.box is None and not c.l2fac
+            assert (c.weights, c.factors) == ((None, None), ("real", None), (None, "pos"))[c.K % 3]
+    assert sum(c.seed not in (600 + c.K, 700 + c.K) for c in SM.ALL_K) <= SM.REPLACED
     for loss in ("square", "logistic"):
         mine = [c for c in SM.CASES if c.loss == loss]
         assert {c.weights for c in mine} == {None, "real", "mask"} and {c.factors for c in mine} == {None, "pos", "zero"}
@@ -78,13 +91,13 @@ def test_the_tables_cover_what_they_name():
         assert {c.shape for c in mine} == set(SM.SHAPES)
         tags = [c.tag for c in SM.ENDINGS if c.loss == loss]
         assert sorted(tags) == sorted(["tol", "fail0", "one", "failk"] * 2)
-    assert len({c.id for c in SM.CASES + SM.ENDINGS}) == len(SM.CASES) + len(SM.ENDINGS)
+    assert len({c.id for c in SM.CASES + SM.ENDINGS + SM.ALL_K}) == len(SM.CASES) + len(SM.ENDINGS) + len(SM.ALL_K)
     assert all(SM.CASES[i].K in (2, 9, 16) for i in SM.SNAPSHOT_CASES)
     A, B, lam = SM.make_tall()
     assert A.shape[0] * SM.TALL_K > 32768 and B.shape == (A.shape[0], SM.TALL_K) and lam > 0
 
 
-@pytest.mark.parametrize("table", ["CASES", "ENDINGS"])
+@pytest.mark.parametrize("table", ["CASES", "ENDINGS", "ALL_K"])
 def test_two_cpu_evaluations_decide_every_trial_alike(table):
     worst = 0.0
     for case in getattr(SM, table):
@@ -93,7 +106,10 @@ def test_two_cpu_evaluations_decide_every_trial_alike(table):
         assert a.nit == b.nit and a.message == b.message, case.id
         assert list(a.alltrials) == list(b.alltrials) and list(a.alllrs) == list(b.alllrs), case.id
         size = max(1.0, max(float(np.max(np.abs(v))) for v in a.allvecs))
-        worst = max(worst, max(float(np.max(np.abs(np.asarray(u) - np.asarray(v)))) for u, v in zip(a.allvecs, b.allvecs)) / size)
+        dev = max(float(np.max(np.abs(np.asarray(u) - np.asarray(v)))) for u, v in zip(a.allvecs, b.allvecs)) / size
+        worst = max(worst, dev)
+        if table == "ALL_K":
+            print(f"{case.id}: nit {a.nit}, trials {int(np.sum(a.alltrials))}, deviation {dev:.2e}")
         if case.tag == "tol":
             assert a.success and 1 < a.nit < case.opts["max_iter"]
         elif case.tag == "fail0":
@@ -102,6 +118,8 @@ def test_two_cpu_evaluations_decide_every_trial_alike(table):
             assert "Backtracking failed" in a.message and a.nit >= 2 and int(np.sum(a.alltrials)) == a.nit
         elif case.tag == "one":
             assert a.nit == 1
+        elif case.tag == "allk":
+            assert a.nit == 30 and int(np.sum(a.alltrials)) > a.nit, (case.id, "the case must reject trials")
         else:
             assert a.nit == 60 and int(np.sum(a.alltrials)) > a.nit, "the case must reject trials"
     print(f"{table}: the two evaluations part by at most {worst:.2e} of the iterates' size")
