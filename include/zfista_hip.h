@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define ZF_ABI_VERSION 6
+#define ZF_ABI_VERSION 7
 
 /* ---- status codes ------------------------------------------------------ */
 #define ZF_OK 0
@@ -464,15 +464,6 @@ int zf_host_asum(const double* x_host, int64_t n, double* out);
 /* out = d * (x - c) */
 int zf_host_diag_grad(double* out_host, const double* x_host, const double* d_dev,
                       const double* c_dev, int64_t n);
-/* f = scale |A x - b|^2 and (grad_out_host != NULL) grad = 2 scale A^T (A x - b)
- * (tests/test_proximal_gradient.py:49-57) */
-int zf_ls_eval(const double* A_dev, const double* b_dev, int64_t m_rows, int64_t n, double scale,
-               const double* x_host, double* f_out, double* grad_out_host);
-/* the same for ZF_PROBLEM_LOGISTIC_L1: f = scale sum_i softplus(-b_i (A x)_i) and (grad_out_host != NULL) grad = scale A^T rho,
- * rho_i = -b_i sigma(-b_i (A x)_i); b_dev: the labels, +-1 (m_rows doubles).  Finite for every finite margin: one
- * exp(-|t|) per row feeds softplus(t) = max(t, 0) + log1p(e) and sigma(t) = t >= 0 ? 1 / (1 + e) : e / (1 + e) */
-int zf_logistic_eval(const double* A_dev, const double* b_dev, int64_t m_rows, int64_t n, double scale,
-                     const double* x_host, double* f_out, double* grad_out_host);
 /* The Taylor remainder of the squared loss as a ZF_ACCEPT_REMAINDER solver forms it, for caller-supplied margins (host
  * arrays of m doubles): R = scale sum_i (s+_i - s_y,i)^2, s_y = s_k + beta (s_k - s_{k-1}) (nesterov != 0) or s_k.
  * wide = 0: the one-workgroup kernel (dense problems; sparse ones up to 32768 rows); wide = 1: the chunked pair of kernels
@@ -495,7 +486,7 @@ int zf_ls_remainder_eval(const double* s_plus_host, const double* s_k_host, cons
  * pointers to the host once and checks the plan against them - split_row must list exactly the rows longer than
  * `threshold`, the segments of a row must start with the row, lie `threshold` apart and cover it - returns ZF_ERR_ARG for
  * a plan that does not fit, and keeps device copies.  plan_bytes = sizeof(zf_spmv_plan).
- * The handle is immutable once created: any number of solvers and zf_spmat_eval calls may use it at the same time, on any
+ * The handle is immutable once created: any number of solvers and zf_margins_* calls may use it at the same time, on any
  * streams (the segment sums of split rows belong to each solver / each call). */
 typedef struct zf_spmv_plan {
     int32_t lanes;
@@ -512,13 +503,6 @@ int zf_spmat_create(zf_spmat** out, int64_t m, int64_t n, int64_t nnz, const int
                     const double* values_dev, const zf_spmv_plan* plan, const int64_t* t_indptr_dev, const int32_t* t_indices_dev,
                     const double* t_values_dev, const zf_spmv_plan* t_plan, int64_t plan_bytes);
 int zf_spmat_destroy(zf_spmat* h);
-/* f = scale |A x - b|^2 and (grad_out_host != NULL) grad = 2 scale A^T (A x - b) for a host vector x (n doubles; b_dev: m):
- * the callback bodies of zfista_amd.problems.SparseLeastSquaresL1, on the kernels the solver runs */
-int zf_spmat_eval(const zf_spmat* h, const double* b_dev, double scale, const double* x_host, double* f_out,
-                  double* grad_out_host);
-/* zf_logistic_eval over the handle: f and grad of ZF_PROBLEM_SPARSE_LOGISTIC_L1 (b_dev: the labels, +-1) */
-int zf_spmat_logistic_eval(const zf_spmat* h, const double* b_dev, double scale, const double* x_host, double* f_out,
-                           double* grad_out_host);
 /* zf_solver_create for ZF_PROBLEM_SPARSE_LS_L1 and ZF_PROBLEM_SPARSE_LOGISTIC_L1: desc->kind = 4 or 6, A = NULL, b (dev, m), m_rows = m and n as the handle's,
  * scale, lam and the box as for the dense kind, world = 1.  The handle must outlive the solver.  Everything else - init,
  * steps, poll, restore, history - is the solver's as for every kind. */
@@ -543,36 +527,14 @@ int zf_solver_create_sparse(zf_solver** out, const zf_problem_desc* desc, const 
  * allocates what it did.  Vectors of n K >= 2^31 entries are indexed in 64 bits (n < 2^31, n K is not). */
 int zf_solver_create_sparse_responses(zf_solver** out, const zf_problem_desc* desc, const zf_spmat* h, int32_t K, const zf_options* opt,
                                       void* stream);
-/* zf_mr_eval over the handle: b_dev, w_dev (or NULL) hold h->m K doubles, x_host / grad_out_host h->n K. */
-int zf_spmat_mr_eval(const zf_spmat* h, const double* b_dev, const double* w_dev, int32_t K, double scale, int32_t loss,
-                     const double* x_host, double* f_out, double* grad_out_host /* or NULL */);
-/* zf_mr_gap_eval over the handle (p_dev: n K positive factors or NULL; not with l2 > 0).  zf_solver_duality_gap of a solver of
- * zf_solver_create_sparse_responses writes the same values, bit for bit. */
-int zf_spmat_mr_gap_eval(const zf_spmat* h, const double* b_dev, const double* w_dev, const double* p_dev, int32_t K, double scale,
-                         double lam, double l2, int32_t loss, const double* x_host, double* out, int64_t count /* >= 8; 10 for all */);
 /* One sweep alone, for element-wise tests of those kernels, outside any solve: out_host = out_scale * A in_host (transpose == 0: in
  * n K, out m K doubles) or out_scale * A^T in_host (in m K, out n K), response-interleaved.  K = 1 runs the plain sweep
  * (zf_launch_spmv), K = 2 .. 16 the K-response one (zf_launch_spmm).  ZF_ERR_ARG: a NULL argument, K outside 1 .. 16. */
 int zf_spmat_mr_apply(const zf_spmat* h, int32_t transpose, int32_t K, double out_scale, const double* in_host, double* out_host);
 
-/* ---- duality gap of the margins kinds (csrc/zf_kernels_gap.h) -----------------------------------------------------------
- * P(x) = sum_i phi_i((A x)_i) + lam |x|_1 with phi_i(z) = scale (z - b_i)^2 (logistic = 0) or scale softplus(-b_i z)
- * (logistic != 0; b_i = +-1).  Dual point nu = alpha grad phi(A x), alpha = min(1, lam / |g|_inf) (1 when g = 0), g = grad f(x)
- * = A^T grad phi(A x): |A^T nu|_inf <= lam, D = -sum_i phi_i^*(nu_i) <= min P.  The reference has no such certificate; its
- * stopping test |x+ - y|_inf < tol measures the step.
- * out (count >= 8 doubles) = [P, D, gap, alpha, |g|_inf, f(x), lam |x|_1, rows gap].  `gap` is NOT P - D (a difference of two
- * numbers of the size of F) but the sum of the two Fenchel-Young gaps, every term >= 0:
- *   rows     least squares scale (1 - alpha)^2 |A x - b|^2;  logistic scale sum_i KL(alpha q_i || q_i), q_i = sigma(-b_i (A x)_i)
- *   columns  sum_j (lam |x_j| + alpha g_j x_j), term by term
- * with 1 - alpha = max(0, (|g|_inf - lam) / |g|_inf).  Finite for every finite margin; alpha = 1 gives a rows gap of exactly 0;
- * a NaN or +-inf in x or g gives a NaN gap.  No atomics, every sum in an order fixed by m or n alone.  scale > 0, lam >= 0.
- * zf_gap_eval: dense row-major A (dev, 16-byte aligned) at a host vector x, on the sweeps a solver of that shape runs;
- * zf_spmat_gap_eval: the same over a matrix handle. */
-int zf_gap_eval(const double* A_dev, const double* b_dev, int64_t m_rows, int64_t n, double scale, double lam, int32_t logistic,
-                const double* x_host, double* out, int64_t count /* >= 8 */);
-int zf_spmat_gap_eval(const zf_spmat* h, const double* b_dev, double scale, double lam, int32_t logistic, const double* x_host,
-                      double* out, int64_t count /* >= 8 */);
-/* The same eight values at the current x_k of a live solver of kind 2, 4, 5 or 6, on the solver's stream (synchronises it).
+/* ---- duality gap at x_k of a live solver (csrc/zf_kernels_gap.h) ---------------------------------------------------------------
+ * The values of zf_margins_gap (below: the certificate, loss by loss) at the current x_k of a live solver of kind 2, 4, 5 or 6, on
+ * the solver's stream (synchronises it).
  * The margins A x_k are the solver's own (its margin ring: no sweep over A); one sweep over A^T forms g.  The workspace (one
  * m-vector, one n-vector, chunk results) is allocated by the first call: a solve that never asks launches and allocates
  * nothing more than before.  r, the gradient, the trial's scalars and the control block are not touched - the call may come
@@ -589,23 +551,9 @@ int zf_solver_duality_gap(zf_solver* s, double* out, int64_t count /* >= 8 */);
  * ZF_ERR_ARG: another problem kind, world > 1, l2 < 0 or not finite.  With l2 > 0 every trial runs the elastic-net step kernel
  * (zf_trial_enet_kernel: the general vector path; a matrix small enough for the two fused small-matrix launches takes the
  * general path too, and zf_solver_ls_plan says so), F(x0) includes the ridge term, and zf_solver_duality_gap evaluates the
- * certificate below.  l2 = 0 changes nothing: the launches, allocations and bits of a solver that was never asked.  A resumed
+ * ridge form of the certificate (zf_margins_gap).  l2 = 0 changes nothing: the launches, allocations and bits of a solver that was never asked.  A resumed
  * solve sets l2 again before zf_solver_restore (the snapshot carries nothing new). */
 int zf_solver_set_l2(zf_solver* s, double l2);
-/* The certificate: the ridge term is n more rows phi(t) = (l2 / 2) t^2 at z = x.  gt = grad f(x) + l2 x, alpha = min(1, lam /
- * |gt|_inf) (1 when gt = 0), 1 - alpha and alpha log alpha as above;
- *   P = f + lam |x|_1 + (l2 / 2) sum x^2          D = D_loss(alpha) - (l2 / 2) alpha^2 sum x^2
- *   ridge = (l2 / 2) (1 - alpha)^2 sum x^2        columns = sum_j (lam |x_j| + alpha gt_j x_j), term by term, clamped at 0
- *   gap = rows + ridge + columns                  (rows: the loss part, as above)
- * out = the eight values above with |gt|_inf in [4]; count >= 10: [8] = (l2 / 2) sum x^2, [9] = the ridge part of the gap.
- * The |.|_inf pass forms gt on the fly from g and x (16 n bytes).  No atomics; every sum in an order fixed by m or n alone.
- * l2 = 0 runs the evaluation above (the same kernels, the same eight values) and writes [8] = [9] = 0.  zf_solver_duality_gap
- * of a solver with l2 > 0 writes the same ten values (count >= 10; the first eight otherwise); of any other solver the eight
- * it wrote before, whatever count. */
-int zf_gap_eval_enet(const double* A_dev, const double* b_dev, int64_t m_rows, int64_t n, double scale, double lam, double l2,
-                     int32_t logistic, const double* x_host, double* out, int64_t count /* >= 8; 10 for all */);
-int zf_spmat_gap_eval_enet(const zf_spmat* h, const double* b_dev, double scale, double lam, double l2, int32_t logistic,
-                           const double* x_host, double* out, int64_t count /* >= 8; 10 for all */);
 /* out = clip(soft_threshold(x, tau) * shrink, lo, hi) at a host vector: the elastic-net prox with tau = lam w and the caller's
  * scalar shrink = 1 / (1 + l2 w) */
 int zf_host_prox_enet_box(double* out_host, const double* x_host, double tau, double shrink, double lo, double hi, int64_t n);
@@ -621,17 +569,6 @@ int zf_host_enet_g(const double* x_host, int64_t n, double lam, double l2, doubl
  * over the stored A^T with its plan; dense: row-major A (m_rows x n).  An empty column has norm 0 exactly. */
 int zf_spmat_col_norms(const zf_spmat* h, double* norms_dev, double* stats_dev);
 int zf_dense_col_norms(const double* A_dev, int64_t m_rows, int64_t n, double* norms_dev, double* stats_dev);
-/* zf_gap_eval / zf_spmat_gap_eval - the same kernels in the same order, out[0 .. 8) the same bits - followed by the screen of
- * the call's g: keep_dev (n bytes) = !(alpha |g_j| + r_eff |a_j| < lam), index_dev (n int32) = the exclusive scan of keep (the
- * new column number of a kept column), out[8 .. 12) = [r, E, r_eff, kept count].  A non-finite gap, alpha or g_j keeps
- * everything.  count >= 12; norms_dev / stats_dev as the norms calls left them; max_row / max_col: the stored elements of the
- * longest row / column of A (dense: n and m_rows, taken from the sizes). */
-int zf_gap_screen_eval(const double* A_dev, const double* b_dev, int64_t m_rows, int64_t n, double scale, double lam, int32_t logistic,
-                       const double* x_host, double* out, int64_t count /* >= 12 */, const double* norms_dev, const double* stats_dev,
-                       uint8_t* keep_dev, int32_t* index_dev);
-int zf_spmat_gap_screen_eval(const zf_spmat* h, const double* b_dev, double scale, double lam, int32_t logistic, const double* x_host,
-                             double* out, int64_t count /* >= 12 */, const double* norms_dev, const double* stats_dev, int64_t max_row,
-                             int64_t max_col, uint8_t* keep_dev, int32_t* index_dev);
 /* index_dev (n int32) = the exclusive scan of a caller's mask keep_dev (n bytes, non-zero = kept), *count_out = the kept count:
  * one workgroup up to 4096 elements, contiguous chunks combined in chunk order beyond. */
 int zf_screen_scan(const uint8_t* keep_dev, int64_t n, int32_t* index_dev, int64_t* count_out);
@@ -665,34 +602,6 @@ int zf_dense_restrict(const double* A_dev, int64_t m_rows, int64_t n, const uint
  * path, and zf_solver_ls_plan says so.  A solver that was never asked launches and allocates what it did.  A resumed solve
  * sets delta again before zf_solver_restore. */
 int zf_solver_set_huber(zf_solver* s, double delta);
-/* f and (grad_out_host != NULL) grad at a host vector: zf_ls_eval / zf_spmat_eval with the loss kernels the solver runs.
- * ZF_ERR_ARG before anything else: a null pointer, m_rows or n < 1, delta not finite or <= 0, a misaligned A. */
-int zf_huber_eval(const double* A_dev, const double* b_dev, int64_t m_rows, int64_t n, double scale, double delta,
-                  const double* x_host, double* f_out, double* grad_out_host);
-int zf_spmat_huber_eval(const zf_spmat* h, const double* b_dev, double scale, double delta, const double* x_host, double* f_out,
-                        double* grad_out_host);
-/* The certificate.  phi_i^*(nu) = nu b_i + nu^2 / (4 scale) on |nu| <= 2 scale delta, and nu = alpha 2 scale c never leaves that
- * interval.  One rows pass stores c and returns sum H, sum c^2, sum b c and T = sum |c| (|r| - |c|) (every term >= 0, exactly 0
- * on an unclipped row); none depends on alpha:
- *   P = scale sum H + lam |x|_1                    D = -scale (alpha^2 sum c^2 + 2 alpha sum b c)
- *   rows = scale (1 - alpha) ((1 - alpha) sum c^2 + 2 T)         columns, alpha, 1 - alpha: as zf_gap_eval
- *   gap = rows + columns   (+ the ridge part, gt = fma(l2, x, g) and the two further outputs of zf_gap_eval_enet when l2 > 0)
- * out: the eight slots of zf_gap_eval; count >= 10 and l2 > 0: the ten of zf_gap_eval_enet (l2 = 0: [8] = [9] = 0).
- * zf_solver_duality_gap of a solver with zf_solver_set_huber writes the same values, bit for bit.  delta >= max |r| gives the
- * least-squares rows gap scale (1 - alpha)^2 |r|^2.  ZF_ERR_ARG as zf_gap_eval_enet, and for delta not finite or <= 0. */
-int zf_gap_eval_huber(const double* A_dev, const double* b_dev, int64_t m_rows, int64_t n, double scale, double lam, double l2,
-                      double delta, const double* x_host, double* out, int64_t count /* >= 8; 10 for all */);
-int zf_spmat_gap_eval_huber(const zf_spmat* h, const double* b_dev, double scale, double lam, double l2, double delta,
-                            const double* x_host, double* out, int64_t count /* >= 8; 10 for all */);
-/* The screen (l2 = 0): zf_gap_screen_eval's rule with L = 2 scale and its guard with c for r, |c|_2 = sqrt(sum c^2) - the clip
- * is exact and 1-Lipschitz.  The radius, mask, scan and restriction kernels are the same.  Arguments and outputs as
- * zf_gap_screen_eval / zf_spmat_gap_screen_eval, with delta where they take `logistic`. */
-int zf_gap_screen_eval_huber(const double* A_dev, const double* b_dev, int64_t m_rows, int64_t n, double scale, double lam, double delta,
-                             const double* x_host, double* out, int64_t count /* >= 12 */, const double* norms_dev,
-                             const double* stats_dev, uint8_t* keep_dev, int32_t* index_dev);
-int zf_spmat_gap_screen_eval_huber(const zf_spmat* h, const double* b_dev, double scale, double lam, double delta, const double* x_host,
-                                   double* out, int64_t count /* >= 12 */, const double* norms_dev, const double* stats_dev,
-                                   int64_t max_row, int64_t max_col, uint8_t* keep_dev, int32_t* index_dev);
 
 /* ---- per-row sample weights on the four margins kinds 2, 4, 5, 6 (csrc/zf_kernels_wloss.h) -----------------------------------
  * f(x) = scale sum_i w_i phi_i(z_i) - a weighted SUM, not a mean; the weights are used as given - and
@@ -711,25 +620,6 @@ enum { ZF_LOSS_SQUARE = 0, ZF_LOSS_LOGISTIC = 1, ZF_LOSS_HUBER = 2 };
  * enough for the two fused small-matrix launches takes the general path, and zf_solver_ls_plan says so.  A solver that was
  * never asked launches and allocates what it did.  A resumed solve sets the weights again before zf_solver_restore. */
 int zf_solver_set_row_weights(zf_solver* s, const double* w_dev);
-/* f and (grad_out_host != NULL) grad at a host vector with the weighted loss kernels the solver runs.  loss: ZF_LOSS_*; delta
- * must be finite and > 0 for ZF_LOSS_HUBER and is ignored otherwise.  The three codes above only: the Poisson loss takes its
- * weights through its own entry points (below), and ZF_LOSS_POISSON is refused here as every other code is.  ZF_ERR_ARG before
- * anything else: a null pointer, m_rows or
- * n < 1, an unknown loss, a bad delta, a misaligned A. */
-int zf_wloss_eval(const double* A_dev, const double* b_dev, const double* w_dev, int64_t m_rows, int64_t n, double scale, int32_t loss,
-                  double delta, const double* x_host, double* f_out, double* grad_out_host);
-int zf_spmat_wloss_eval(const zf_spmat* h, const double* b_dev, const double* w_dev, double scale, int32_t loss, double delta,
-                        const double* x_host, double* f_out, double* grad_out_host);
-/* The certificate with every row term times w_i ((w phi)^*(w u) = w phi^*(u); the dual point is nu = alpha grad phi(z) as
- * before): square sum w r^2, sum w b r; Huber sum w H, sum w c^2, sum w b c, sum w |c| (|r| - |c|); logistic sum w KL,
- * sum w [p log p + (1 - p) log(1 - p)].  The n-passes and the compositions are those of zf_gap_eval / zf_gap_eval_enet /
- * zf_gap_eval_huber.  out: the eight slots of zf_gap_eval; count >= 10 and l2 > 0: the ten of zf_gap_eval_enet (l2 = 0:
- * [8] = [9] = 0).  zf_solver_duality_gap of a solver with zf_solver_set_row_weights writes the same values, bit for bit. */
-int zf_gap_eval_weighted(const double* A_dev, const double* b_dev, const double* w_dev, int64_t m_rows, int64_t n, double scale,
-                         double lam, double l2, int32_t loss, double delta, const double* x_host, double* out,
-                         int64_t count /* >= 8; 10 for all */);
-int zf_spmat_gap_eval_weighted(const zf_spmat* h, const double* b_dev, const double* w_dev, double scale, double lam, double l2,
-                               int32_t loss, double delta, const double* x_host, double* out, int64_t count /* >= 8; 10 for all */);
 
 /* ---- the Poisson loss with a log link on the least-squares kinds 2 and 4 (csrc/zf_kernels_poisson.h) ------------------------
  * f(x) = scale sum_i w_i (exp(z_i) - b_i z_i), z = A x, with counts b_i >= 0, finite, not necessarily integers (a rate
@@ -748,28 +638,6 @@ int zf_spmat_gap_eval_weighted(const zf_spmat* h, const double* b_dev, const dou
  * asked launches and allocates what it did.  A resumed solve calls it again before zf_solver_restore. */
 enum { ZF_LOSS_POISSON = 3 };   /* the fourth ZF_LOSS_* code (struct zf_loss of csrc/zf_loss_dispatch.h) */
 int zf_solver_set_poisson(zf_solver* s);
-/* f and (grad_out_host != NULL) grad at a host vector: zf_ls_eval / zf_spmat_eval with the loss kernels the solver runs.
- * w_dev: the row weights (m_rows doubles in device memory, as zf_solver_set_row_weights takes them) or NULL for the unweighted
- * loss - the weighted form of this loss is reached here, not through zf_wloss_eval.  ZF_ERR_ARG before anything else: a null
- * pointer (but w_dev), m_rows or n < 1, a misaligned A. */
-int zf_poisson_eval(const double* A_dev, const double* b_dev, const double* w_dev, int64_t m_rows, int64_t n, double scale,
-                    const double* x_host, double* f_out, double* grad_out_host);
-int zf_spmat_poisson_eval(const zf_spmat* h, const double* b_dev, const double* w_dev, double scale, const double* x_host, double* f_out,
-                          double* grad_out_host);
-/* The certificate.  h(z) = e^z - b z has h^*(u) = v log v - v, v = u + b >= 0 (0 log 0 = 0); with nu = alpha grad phi(z),
- * v = alpha e^z + (1 - alpha) b >= 0 always.
- *   P = f + lam |x|_1                                D = -scale sum w (v log v - v)
- *   rows = scale sum w [e^z - v + v (log v - z)]     every term >= 0, exactly 0 at alpha = 1; columns, alpha: as zf_gap_eval
- *   gap = rows + columns   (+ the ridge part, gt = fma(l2, x, g) and the two further outputs of zf_gap_eval_enet when l2 > 0)
- * The row terms depend on alpha: a second rows pass follows the n-passes, as for the logistic loss.  out: the eight slots of
- * zf_gap_eval; count >= 10 and l2 > 0: the ten of zf_gap_eval_enet (l2 = 0: [8] = [9] = 0).  w_dev: the row weights or NULL, as
- * above.  zf_solver_duality_gap of a solver with zf_solver_set_poisson (and zf_solver_set_row_weights) writes the same values,
- * bit for bit.  ZF_ERR_ARG as zf_gap_eval_enet.  There is no screen entry: exp is not globally Lipschitz, so the
- * gap-safe radius of zf_gap_screen_eval does not apply. */
-int zf_gap_eval_poisson(const double* A_dev, const double* b_dev, const double* w_dev, int64_t m_rows, int64_t n, double scale, double lam,
-                        double l2, const double* x_host, double* out, int64_t count /* >= 8; 10 for all */);
-int zf_spmat_gap_eval_poisson(const zf_spmat* h, const double* b_dev, const double* w_dev, double scale, double lam, double l2,
-                              const double* x_host, double* out, int64_t count /* >= 8; 10 for all */);
 
 /* ---- per-column penalty factors on the four margins kinds 2, 4, 5, 6 --------------------------------------------------------
  * g(x) = lam sum_j p_j |x_j| (+ box), p_j >= 0: p_j = 0 leaves column j unpenalised (an intercept: a column of ones with p = 0).
@@ -785,17 +653,6 @@ int zf_spmat_gap_eval_poisson(const zf_spmat* h, const double* b_dev, const doub
  * zf_solver_set_huber / _poisson / _row_weights in any order, and with ZF_ACCEPT_REMAINDER, which touches f only.  A resumed
  * solve sets the factors again before zf_solver_restore (the snapshot carries nothing new). */
 int zf_solver_set_penalty_factors(zf_solver* s, const double* p_dev);
-/* The certificate with p > 0: the dual constraint is |a_j^T theta| <= lam p_j.  With g'_j = g_j / p_j and x'_j = x_j p_j every
- * quantity is that of the unfactored evaluation of this loss at (g', x'): one n-pass writes g' and x' (an IEEE division and a
- * multiplication per element) between g = grad f(x) and the tails, which run unchanged.  out: the eight slots of zf_gap_eval with
- * [4] = max_j |g_j| / p_j and [6] = lam sum p_j |x_j| = g(x).  loss: ZF_LOSS_SQUARE / _LOGISTIC / _HUBER (delta) / _POISSON;
- * w_dev: the row weights or NULL.  A p_j = 0 divides by zero: the dual candidate cannot be made feasible by scaling (it needs
- * a_j^T theta = 0 exactly), and the callers above this level refuse.  zf_solver_duality_gap of a solver with
- * zf_solver_set_penalty_factors writes the same values, bit for bit.  ZF_ERR_ARG as zf_gap_eval_weighted. */
-int zf_gap_eval_pf(const double* A_dev, const double* b_dev, const double* w_dev, const double* p_dev, int64_t m_rows, int64_t n,
-                   double scale, double lam, int32_t loss, double delta, const double* x_host, double* out, int64_t count /* >= 8 */);
-int zf_spmat_gap_eval_pf(const zf_spmat* h, const double* b_dev, const double* w_dev, const double* p_dev, double scale, double lam,
-                         int32_t loss, double delta, const double* x_host, double* out, int64_t count /* >= 8 */);
 /* out = clip(sign(x) * max(|x| - t * p, 0), lo, hi) at host vectors, NumPy's expression operation by operation */
 int zf_host_prox_pf_box(double* out_host, const double* x_host, const double* p_host, double t, double lo, double hi, int64_t n);
 /* out = lam * sum_i p_i |x_i|, each term one fused multiply-add into the running sum (as the step kernel forms it) */
@@ -817,17 +674,6 @@ int zf_host_pf_g(const double* x_host, const double* p_host, int64_t n, double l
  * any order.  A resumed solve sets the matrix again before zf_solver_restore (the snapshot carries nothing new).  A solver that
  * was never asked launches and allocates what it did. */
 int zf_solver_set_matrix_f32(zf_solver* s, const float* A32_dev);
-/* f and (grad_out_host != NULL) grad at a host vector for such a matrix.  loss: any of the four ZF_LOSS_* codes; delta must be
- * finite and > 0 for ZF_LOSS_HUBER and is ignored otherwise; w_dev: the row weights or NULL.  ZF_ERR_ARG as zf_wloss_eval. */
-int zf_f32_eval(const float* A32_dev, const double* b_dev, const double* w_dev, int64_t m_rows, int64_t n, double scale, int32_t loss,
-                double delta, const double* x_host, double* f_out, double* grad_out_host /* or NULL */);
-/* The certificate for such a matrix: out as zf_gap_eval_weighted (eight values; ten - ridge term and its gap - for l2 > 0 when the
- * buffer holds them; l2 = 0 writes [8] = [9] = 0 into a buffer of ten).  p_dev: penalty factors or NULL; with them the values are
- * those of zf_gap_eval_pf, and l2 > 0 is ZF_ERR_ARG.  zf_solver_duality_gap of a solver with zf_solver_set_matrix_f32 writes the same
- * values, bit for bit. */
-int zf_f32_gap_eval(const float* A32_dev, const double* b_dev, const double* w_dev, const double* p_dev, int64_t m_rows, int64_t n,
-                    double scale, double lam, double l2, int32_t loss, double delta, const double* x_host, double* out,
-                    int64_t count /* >= 8; 10 for all */);
 
 /* ---- K responses on one dense matrix, on the two dense kinds 2, 5 ---------------------------------------------------------------
  * X in R^{n x K}, B in R^{m x K}: f(X) = scale sum_k sum_i W_ik phi((A x_k)_i ; B_ik), g(X) = lam sum_jk P_jk |X_jk| (+ the ridge term,
@@ -846,15 +692,108 @@ int zf_f32_gap_eval(const float* A32_dev, const double* b_dev, const double* w_d
  * zf_solver_set_l2 / _row_weights (m K weights) / _penalty_factors (n K factors) in any order.  A resumed solve sets the responses
  * again before zf_solver_restore.  A solver that was never asked launches and allocates what it did. */
 int zf_solver_set_responses(zf_solver* s, int32_t K);
-/* f and (grad_out_host != NULL) grad at a host vector of n K doubles for such a problem.  A_dev: m_rows x n; b_dev, w_dev (or NULL):
- * m_rows K doubles; loss: ZF_LOSS_SQUARE or ZF_LOSS_LOGISTIC.  ZF_ERR_ARG: K outside 2 .. 16, another loss, and as zf_wloss_eval. */
-int zf_mr_eval(const double* A_dev, const double* b_dev, const double* w_dev, int64_t m_rows, int64_t n, int32_t K, double scale,
-               int32_t loss, const double* x_host, double* f_out, double* grad_out_host /* or NULL */);
-/* The certificate of such a problem: out, l2 and p_dev (n K positive factors or NULL) as zf_f32_gap_eval.  One alpha scales the dual
- * candidate of all K responses, so it is feasible for each of them and the gap is a sum of K non-negative gaps.
- * zf_solver_duality_gap of a solver with zf_solver_set_responses writes the same values, bit for bit. */
-int zf_mr_gap_eval(const double* A_dev, const double* b_dev, const double* w_dev, const double* p_dev, int64_t m_rows, int64_t n, int32_t K,
-                   double scale, double lam, double l2, int32_t loss, const double* x_host, double* out, int64_t count /* >= 8; 10 for all */);
+
+/* ---- the margins problems at a host point: f / grad, the certificate, the screen (ABI 7) --------------------------------------------
+ * One descriptor names the storage of A, the loss and the options of the problem
+ *     f(x) = scale sum_i w_i phi((A x)_i ; b_i),   g(x) = lam sum_j p_j |x_j| + (l2 / 2) |x|^2
+ * and three entries evaluate it at a point given in host memory (problem data stays in HBM), on the rows kernels and the sweeps a
+ * solver of that storage and loss runs.  These back f, jac_f, duality_gap and screen of zfista_amd.problems.*.  A new loss or a new
+ * storage is a new value of a field: no entry is added.  (They replace the 32 per-loss entries of ABI 6: INTEGRATION.md lists them.)
+ * Exactly one of A / A32 / spmat is set.  Dense: m_rows x n row-major in device memory, 16-byte aligned; a handle knows its own
+ * sizes and m_rows, n are ignored.  K responses (1 .. 16; K > 1: ZF_LOSS_SQUARE / ZF_LOSS_LOGISTIC on A or spmat only): m_rows and n
+ * stay the MATRIX's, b / w hold m_rows K, p / x_host / grad_out_host n K doubles, response-interleaved (x[j K + k] = X[j][k]); K = 1
+ * is the plain problem.  w (row weights, finite and >= 0) and p (penalty factors, > 0) may each be NULL: the unweighted / unfactored
+ * problem - other kernels, other bits than w = 1.  delta: Huber's, finite and > 0; ignored for the other losses. */
+typedef struct zf_eval_desc {
+    const double* A;          /* dev: dense fp64 matrix, or NULL                                       */
+    const float* A32;         /* dev: dense matrix stored in fp32 (zf_solver_set_matrix_f32), or NULL  */
+    const zf_spmat* spmat;    /* CSR handle (zf_spmat_create), or NULL                                 */
+    int64_t m_rows, n;        /* dense: the matrix's sizes                                             */
+    const double* b;          /* dev, m_rows K: targets / labels +-1 / counts                          */
+    const double* w;          /* dev, m_rows K, or NULL                                                */
+    const double* p;          /* dev, n K, or NULL (the certificate only)                              */
+    double scale, lam, l2, delta;
+    int32_t loss;             /* ZF_LOSS_SQUARE / _LOGISTIC / _HUBER / _POISSON                        */
+    int32_t K;
+} zf_eval_desc;
+int64_t zf_sizeof_eval_desc(void);
+/* ZF_ERR_ARG from all three, before anything touches a device or is written: d NULL or desc_bytes != zf_sizeof_eval_desc(); not exactly
+ * one matrix; b, x_host or the output pointer NULL; dense m_rows or n < 1, a misaligned matrix; an unknown loss; a bad delta with
+ * ZF_LOSS_HUBER; K outside 1 .. 16, K > 1 with another loss than square / logistic or with A32.
+ *
+ * zf_margins_eval: *f_out = f(x) and (grad_out_host != NULL) grad f(x) = gfac A^T (w o psi(A x)), gfac = 2 scale (square, Huber) |
+ * scale (logistic, Poisson).  Reads neither lam, l2 nor p.  The column sweep of a dense fp64 A is always the VALU one: jac_f has the
+ * same bits whatever n % 32 is.  Per loss (z = A x):
+ *   square    phi = (z - b)^2 (tests/test_proximal_gradient.py:49-57); unweighted: f from the residual kernels, sqrt(sum)^2
+ *   logistic  phi = softplus(-b z), psi = -b sigma(-b z), b = +-1.  Finite for every finite margin: one exp(-|t|) per row feeds
+ *             softplus(t) = max(t, 0) + log1p(e) and sigma(t) = t >= 0 ? 1 / (1 + e) : e / (1 + e)
+ *   Huber     phi = H(r), psi = c = clip(r, -delta, delta), r = z - b (the section of zf_solver_set_huber)
+ *   Poisson   phi = exp(z) - b z, psi = exp(z) - b (the section of zf_solver_set_poisson)
+ * weighted: rho_i = w_i psi_i, acc += w_i phi_i (the section of zf_solver_set_row_weights). */
+int zf_margins_eval(const zf_eval_desc* d, int64_t desc_bytes, const double* x_host, double* f_out, double* grad_out_host /* or NULL */);
+
+/* zf_margins_gap: the duality-gap certificate (csrc/zf_kernels_gap.h).
+ * P(x) = sum_i phi_i((A x)_i) + lam |x|_1.  Dual point nu = alpha grad phi(A x), alpha = min(1, lam / |g|_inf) (1 when g = 0),
+ * g = grad f(x) = A^T grad phi(A x): |A^T nu|_inf <= lam, D = -sum_i phi_i^*(nu_i) <= min P.  The reference has no such certificate;
+ * its stopping test |x+ - y|_inf < tol measures the step.
+ * out (count >= 8 doubles) = [P, D, gap, alpha, |g|_inf, f(x), lam |x|_1, rows gap].  `gap` is NOT P - D (a difference of two
+ * numbers of the size of F) but the sum of the two Fenchel-Young gaps, every term >= 0:
+ *   rows     per loss, below
+ *   columns  sum_j (lam |x_j| + alpha g_j x_j), term by term
+ * with 1 - alpha = max(0, (|g|_inf - lam) / |g|_inf).  Finite for every finite margin; alpha = 1 gives a rows gap of exactly 0;
+ * a NaN or +-inf in x or g gives a NaN gap.  No atomics, every sum in an order fixed by m or n alone.  g by the column sweep a solver
+ * of this shape runs (dense fp64, K = 1: MFMA when n % 32 == 0 and ZF_GEMV_MFMA is not 0).  zf_solver_duality_gap of a solver with
+ * the same storage, loss and options writes the same values, bit for bit.
+ * ZF_ERR_ARG also: count < 8; scale not > 0, lam < 0, l2 negative or not finite; p together with l2 > 0.
+ *
+ * Square.  rows = scale (1 - alpha)^2 |A x - b|^2.
+ * Logistic.  rows = scale sum_i KL(alpha q_i || q_i), q_i = sigma(-b_i (A x)_i); the row terms depend on alpha: a second rows pass
+ * follows the n-passes.
+ * Huber.  phi_i^*(nu) = nu b_i + nu^2 / (4 scale) on |nu| <= 2 scale delta, and nu = alpha 2 scale c never leaves that interval.  One
+ * rows pass stores c and returns sum H, sum c^2, sum b c and T = sum |c| (|r| - |c|) (every term >= 0, exactly 0 on an unclipped
+ * row); none depends on alpha:
+ *   P = scale sum H + lam |x|_1                    D = -scale (alpha^2 sum c^2 + 2 alpha sum b c)
+ *   rows = scale (1 - alpha) ((1 - alpha) sum c^2 + 2 T)
+ * delta >= max |r| gives the least-squares rows gap scale (1 - alpha)^2 |r|^2.
+ * Poisson.  h(z) = e^z - b z has h^*(u) = v log v - v, v = u + b >= 0 (0 log 0 = 0); with nu = alpha grad phi(z),
+ * v = alpha e^z + (1 - alpha) b >= 0 always.
+ *   P = f + lam |x|_1                                D = -scale sum w (v log v - v)
+ *   rows = scale sum w [e^z - v + v (log v - z)]     every term >= 0, exactly 0 at alpha = 1
+ * The row terms depend on alpha: a second rows pass follows the n-passes, as for the logistic loss.
+ * Row weights (w).  Every row term times w_i ((w phi)^*(w u) = w phi^*(u); the dual point is nu = alpha grad phi(z) as before):
+ * square sum w r^2, sum w b r; Huber sum w H, sum w c^2, sum w b c, sum w |c| (|r| - |c|); logistic sum w KL,
+ * sum w [p log p + (1 - p) log(1 - p)].  The n-passes and the compositions are unchanged.
+ * Ridge (l2 > 0).  The ridge term is n more rows phi(t) = (l2 / 2) t^2 at z = x.  gt = grad f(x) + l2 x = fma(l2, x, g),
+ * alpha = min(1, lam / |gt|_inf) (1 when gt = 0), 1 - alpha and alpha log alpha as above;
+ *   P = f + lam |x|_1 + (l2 / 2) sum x^2          D = D_loss(alpha) - (l2 / 2) alpha^2 sum x^2
+ *   ridge = (l2 / 2) (1 - alpha)^2 sum x^2        columns = sum_j (lam |x_j| + alpha gt_j x_j), term by term, clamped at 0
+ *   gap = rows + ridge + columns                  (rows: the loss part, as above)
+ * out = the eight values above with |gt|_inf in [4]; count >= 10: [8] = (l2 / 2) sum x^2, [9] = the ridge part of the gap.
+ * The |.|_inf pass forms gt on the fly from g and x (16 n bytes).  l2 = 0 runs the l1 evaluation (the same kernels, the same eight
+ * values) and writes [8] = [9] = 0 into a buffer of ten.  zf_solver_duality_gap of a solver with l2 > 0 writes the same ten values
+ * (count >= 10; the first eight otherwise); of any other solver the eight it wrote before, whatever count.
+ * Penalty factors (p > 0, l2 = 0).  The dual constraint is |a_j^T theta| <= lam p_j.  With g'_j = g_j / p_j and x'_j = x_j p_j every
+ * quantity is that of the unfactored evaluation of this loss at (g', x'): one n-pass writes g' and x' (an IEEE division and a
+ * multiplication per element) between g = grad f(x) and the tails, which run unchanged.  out: the eight slots with
+ * [4] = max_j |g_j| / p_j and [6] = lam sum p_j |x_j| = g(x).  A p_j = 0 divides by zero: the dual candidate cannot be made feasible
+ * by scaling (it needs a_j^T theta = 0 exactly), and the callers above this level refuse.
+ * K responses.  The evaluation of the m_rows K x n K problem: one alpha scales the dual candidate of all K responses, so it is
+ * feasible for each of them and the gap is a sum of K non-negative gaps. */
+int zf_margins_gap(const zf_eval_desc* d, int64_t desc_bytes, const double* x_host, double* out, int64_t count /* >= 8; 10 for all */);
+
+/* zf_margins_screen: zf_margins_gap - the same kernels in the same order, out[0 .. 8) the same bits - followed by the gap-safe screen
+ * of the call's g (the section "gap-safe screening" above): keep_dev (n bytes) = !(alpha |g_j| + r_eff |a_j| < lam), index_dev (n
+ * int32) = the exclusive scan of keep (the new column number of a kept column), out[8 .. 12) = [r, E, r_eff, kept count].  A
+ * non-finite gap, alpha or g_j keeps everything.  norms_dev / stats_dev as the norms calls left them; max_row / max_col: the stored
+ * elements of the longest row / column of A, read for a handle only (dense: n and m_rows, taken from the sizes).
+ * Huber's loss: the rule with L = 2 scale and the guard with c for r, |c|_2 = sqrt(sum c^2) - the clip is exact and 1-Lipschitz.  The
+ * radius, mask, scan and restriction kernels are the same.
+ * ZF_ERR_ARG also, each with a message of its own: count < 12; ZF_LOSS_POISSON (exp is not globally Lipschitz, so the gap-safe radius
+ * does not apply); w, p, l2 > 0, A32 or K > 1 (the rule and its rounding guard are not built for them); dense n > 2^31 - 1; norms_dev,
+ * stats_dev, keep_dev or index_dev NULL; a handle with max_row or max_col < 0. */
+int zf_margins_screen(const zf_eval_desc* d, int64_t desc_bytes, const double* x_host, double* out, int64_t count /* >= 12 */,
+                      const double* norms_dev, const double* stats_dev, int64_t max_row, int64_t max_col, uint8_t* keep_dev,
+                      int32_t* index_dev);
 
 /* ---- multi-objective trial (m >= 2), device side ---------------------------
  * The dual of the scalarised subproblem is minimised on the host by SciPy exactly

@@ -8,6 +8,7 @@ import re
 import numpy as np
 import pytest
 
+import evaldesc as E
 from conftest import ROOT
 from zfista_amd import _lib
 
@@ -25,7 +26,7 @@ def test_library_loads_and_exports_every_declared_symbol():
     for n in names:
         assert hasattr(lib, n), f"{n} declared in zfista_hip.h but not exported"
     assert sorted(_lib.SIGNATURES) == names, "ctypes table and header disagree"
-    assert lib.zf_abi_version() == 6
+    assert lib.zf_abi_version() == 7
 
 
 def test_struct_mirrors():
@@ -34,6 +35,7 @@ def test_struct_mirrors():
     assert C.sizeof(_lib.ProblemDesc) == 128
     assert C.sizeof(_lib.Options) == 64
     assert C.sizeof(_lib.CommDesc) == 296
+    assert lib.zf_sizeof_eval_desc() == C.sizeof(_lib.EvalDesc) == 104
 
 
 def test_error_reporting_is_c_style():
@@ -114,6 +116,16 @@ def test_short_output_buffers_are_refused():
         wide[:] = -7
         rc = raw(lib.zf_solver_launch_counts, [P, P, I], C.addressof(dummy), _lib.ptr(wide), count)
         assert rc == 0 and (wide[:written] != -7).all() and (wide[written:] == -7).all(), (count, wide)
+    # the evaluation descriptor is sized: another size - a host built against another layout - is refused before anything is read
+    f = C.c_double(-7.0)
+    gout = np.full(12, -7.0)
+    G = C.c_void_p(_lib.ptr(gout))
+    for wrong in (0, C.sizeof(_lib.EvalDesc) - 8, C.sizeof(_lib.EvalDesc) + 8):
+        assert E.point(E.dense(G), G, C.byref(f), desc_bytes=wrong) == -2 and b"desc_bytes" in lib.zf_last_error()
+        assert E.gap(E.dense(G), G, G, 10, desc_bytes=wrong) == -2 and b"desc_bytes" in lib.zf_last_error()
+        assert E.screen(E.dense(G), G, G, 12, G, G, 0, 0, G, G, desc_bytes=wrong) == -2 and b"desc_bytes" in lib.zf_last_error()
+    assert lib.zf_margins_eval(None, C.sizeof(_lib.EvalDesc), G, C.byref(f), None) == -2
+    assert f.value == -7.0 and (gout == -7.0).all()
     # the least-squares plan query takes four values
     rc = raw(lib.zf_solver_ls_plan, [P, P, I], C.addressof(dummy), _lib.ptr(iout), 3)
     assert rc == -2 and b"fewer than 4" in lib.zf_last_error() and not iout.any()

@@ -1,5 +1,4 @@
-"""CPU: the interface of the elastic-net feature without a GPU - header and ctypes table (additive: ABI 6 and the struct sizes
-as they were), the argument checks of the new entry points, the ValueErrors of the host classes, and the siblings."""
+"""CPU: the interface of the elastic-net feature without a GPU - header and ctypes table (the struct sizes as they were), the argument checks of the new entry points, the ValueErrors of the host classes, and the siblings."""
 import ctypes as C
 import inspect
 import os
@@ -8,10 +7,11 @@ import re
 import numpy as np
 import pytest
 
+import evaldesc as E
 from conftest import ROOT
 from zfista_amd import _lib, path, problems, screening
 
-NEW = ("zf_solver_set_l2", "zf_gap_eval_enet", "zf_spmat_gap_eval_enet", "zf_host_prox_enet_box", "zf_host_enet_g")
+NEW = ("zf_solver_set_l2", "zf_margins_gap", "zf_host_prox_enet_box", "zf_host_enet_g")
 
 
 def test_header_and_ctypes_table_declare_the_new_entry_points_and_nothing_else_moved():
@@ -22,10 +22,9 @@ def test_header_and_ctypes_table_declare_the_new_entry_points_and_nothing_else_m
         assert re.search(r"\bint\s+" + name + r"\s*\(", src), name
         assert name in _lib.SIGNATURES and hasattr(lib, name)
     assert sorted(_lib.SIGNATURES) == sorted(set(re.findall(r"\b(zf_[A-Za-z0-9_]+)\s*\(", src))), "header = ctypes table"
-    assert lib.zf_abi_version() == 6 and lib.zf_sizeof_control() == 424 == C.sizeof(_lib.Control)
+    assert lib.zf_abi_version() == 7 and lib.zf_sizeof_control() == 424 == C.sizeof(_lib.Control)
     assert C.sizeof(_lib.ProblemDesc) == 128 and C.sizeof(_lib.Options) == 64, "additive exports only: no struct field"
-    assert "l2" not in [f[0] for f in _lib.ProblemDesc._fields_]
-    assert len(_lib.SIGNATURES["zf_gap_eval_enet"][1]) == 11 and len(_lib.SIGNATURES["zf_spmat_gap_eval_enet"][1]) == 9
+    assert "l2" not in [f[0] for f in _lib.ProblemDesc._fields_] and "l2" in [f[0] for f in _lib.EvalDesc._fields_]
 
 
 def test_new_entry_points_refuse_bad_arguments_before_touching_a_device():
@@ -33,14 +32,14 @@ def test_new_entry_points_refuse_bad_arguments_before_touching_a_device():
     out = np.full(10, -7.0)
     P = C.c_void_p(_lib.ptr(out))
     assert lib.zf_solver_set_l2(None, 0.1) == -2 and b"zf_solver_set_l2" in lib.zf_last_error()
-    assert lib.zf_gap_eval_enet(None, P, 3, 2, 1.0, 0.1, 0.1, 0, P, P, 10) == -2 and b"zf_gap_eval_enet" in lib.zf_last_error()
-    assert lib.zf_gap_eval_enet(P, P, 3, 2, 1.0, 0.1, 0.1, 0, P, P, 7) == -2 and b"fewer than 8" in lib.zf_last_error()
+    assert E.gap(E.dense(None, l2=0.1), P, P, 10) == -2 and b"zf_margins_gap" in lib.zf_last_error()
+    assert E.gap(E.dense(P, l2=0.1), P, P, 7) == -2 and b"fewer than 8" in lib.zf_last_error()
     for bad in (-1e-9, float("inf"), float("nan")):
-        assert lib.zf_gap_eval_enet(P, P, 3, 2, 1.0, 0.1, bad, 0, P, P, 10) == -2 and b"l2" in lib.zf_last_error()
-        assert lib.zf_spmat_gap_eval_enet(P, P, 1.0, 0.1, bad, 0, P, P, 10) == -2 and b"l2" in lib.zf_last_error()
-    assert lib.zf_gap_eval_enet(P, P, 3, 2, 1.0, -0.1, 0.1, 1, P, P, 10) == -2 and b"lam >= 0" in lib.zf_last_error()
-    assert lib.zf_spmat_gap_eval_enet(None, P, 1.0, 0.1, 0.1, 0, P, P, 10) == -2
-    assert lib.zf_spmat_gap_eval_enet(P, P, 1.0, 0.1, 0.1, 0, P, P, 3) == -2 and b"fewer than 8" in lib.zf_last_error()
+        assert E.gap(E.dense(P, l2=bad), P, P, 10) == -2 and b"l2" in lib.zf_last_error()
+        assert E.gap(E.sparse(P, l2=bad), P, P, 10) == -2 and b"l2" in lib.zf_last_error()
+    assert E.gap(E.dense(P, lam=-0.1, l2=0.1, loss=1), P, P, 10) == -2 and b"lam >= 0" in lib.zf_last_error()
+    assert E.gap(E.sparse(None, l2=0.1), P, P, 10) == -2
+    assert E.gap(E.sparse(P, l2=0.1), P, P, 3) == -2 and b"fewer than 8" in lib.zf_last_error()
     assert lib.zf_host_prox_enet_box(None, P, 0.1, 1.0, -1.0, 1.0, 4) == -2 and lib.zf_host_enet_g(None, 4, 0.1, 0.1, None) == -2
     assert (out == -7.0).all()
 

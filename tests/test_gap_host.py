@@ -7,10 +7,11 @@ import re
 import numpy as np
 import pytest
 
+import evaldesc as E
 from conftest import ROOT
 from zfista_amd import _lib, minimize_proximal_gradient
 
-NEW = ("zf_gap_eval", "zf_spmat_gap_eval", "zf_solver_duality_gap")
+NEW = ("zf_margins_gap", "zf_solver_duality_gap")
 
 
 def test_header_and_ctypes_table_declare_the_new_entry_points():
@@ -20,8 +21,8 @@ def test_header_and_ctypes_table_declare_the_new_entry_points():
     for name in NEW:
         assert re.search(r"\bint\s+" + name + r"\s*\(", src), name
         assert name in _lib.SIGNATURES and hasattr(lib, name)
-    assert lib.zf_abi_version() == 6 and lib.zf_sizeof_control() == 424, "additive: no version bump, no struct change"
-    assert len(_lib.SIGNATURES["zf_gap_eval"][1]) == 10 and len(_lib.SIGNATURES["zf_spmat_gap_eval"][1]) == 8
+    assert lib.zf_abi_version() == 7 and lib.zf_sizeof_control() == 424, "no struct change"
+    assert len(_lib.SIGNATURES["zf_margins_gap"][1]) == 5
     assert _lib.ACCEPT_MODES == {"reference": 0, "resolved": 1, "remainder": 2}
 
 
@@ -29,14 +30,14 @@ def test_new_entry_points_refuse_null_and_short_arguments():
     lib = _lib.load()
     out = np.full(8, -7.0)
     P = C.c_void_p(_lib.ptr(out))
-    assert lib.zf_gap_eval(None, P, 3, 2, 1.0, 0.1, 0, P, P, 8) == -2 and b"zf_gap_eval" in lib.zf_last_error()
-    assert lib.zf_gap_eval(P, P, 0, 2, 1.0, 0.1, 0, P, P, 8) == -2
-    assert lib.zf_gap_eval(P, P, 3, 2, 1.0, 0.1, 0, P, P, 7) == -2 and b"fewer than 8" in lib.zf_last_error()
-    assert lib.zf_gap_eval(P, P, 3, 2, 0.0, 0.1, 0, P, P, 8) == -2 and b"scale > 0" in lib.zf_last_error()
-    assert lib.zf_gap_eval(P, P, 3, 2, 1.0, -0.1, 1, P, P, 8) == -2 and b"lam >= 0" in lib.zf_last_error()
-    assert lib.zf_gap_eval(C.c_void_p(_lib.ptr(out) + 8), P, 3, 2, 1.0, 0.1, 0, P, P, 8) == -2 and b"aligned" in lib.zf_last_error()
-    assert lib.zf_spmat_gap_eval(None, P, 1.0, 0.1, 0, P, P, 8) == -2 and b"zf_spmat_gap_eval" in lib.zf_last_error()
-    assert lib.zf_spmat_gap_eval(P, P, 1.0, 0.1, 0, P, P, 3) == -2 and b"fewer than 8" in lib.zf_last_error()
+    assert E.gap(E.dense(None), P, P, 8) == -2 and b"zf_margins_gap" in lib.zf_last_error()
+    assert E.gap(E.dense(P, m_rows=0), P, P, 8) == -2
+    assert E.gap(E.dense(P), P, P, 7) == -2 and b"fewer than 8" in lib.zf_last_error()
+    assert E.gap(E.dense(P, scale=0.0), P, P, 8) == -2 and b"scale > 0" in lib.zf_last_error()
+    assert E.gap(E.dense(P, lam=-0.1, loss=1), P, P, 8) == -2 and b"lam >= 0" in lib.zf_last_error()
+    assert E.gap(E.dense(_lib.ptr(out) + 8), P, P, 8) == -2 and b"aligned" in lib.zf_last_error()
+    assert E.gap(E.sparse(None), P, P, 8) == -2 and b"zf_margins_gap" in lib.zf_last_error()
+    assert E.gap(E.sparse(P), P, P, 3) == -2 and b"fewer than 8" in lib.zf_last_error()
     assert lib.zf_solver_duality_gap(None, P, 8) == -2 and b"zf_solver_duality_gap" in lib.zf_last_error()
     # a short buffer is refused before the handle is read or written through: a patterned region stands in for it
     dummy = (C.c_ubyte * (1 << 20))()

@@ -426,16 +426,16 @@ def test_refusals(cases):
     lib = _lib.require_gpu()
     import ctypes as Ct
 
+    import evaldesc as E
+
     out, xz = np.zeros(10), np.zeros(C.n)
-    rc = lib.zf_f32_gap_eval(Ct.c_void_p(p32.A.data_ptr()), Ct.c_void_p(C.b_dev.data_ptr()), None, Ct.c_void_p(C.b_dev.data_ptr()), C.m, C.n,
-                             0.5, 0.1, 0.5, 0, 0.0, Ct.c_void_p(_lib.ptr(xz)), Ct.c_void_p(_lib.ptr(out)), 10)
-    assert rc == -2 and b"zf_f32_gap_eval" in lib.zf_last_error()
+    fields = dict(A32=p32.A.data_ptr(), b=C.b_dev.data_ptr(), m_rows=C.m, n=C.n, scale=0.5, lam=0.1)
+    rc = E.gap(E.desc(**fields, p=C.b_dev.data_ptr(), l2=0.5), Ct.c_void_p(_lib.ptr(xz)), Ct.c_void_p(_lib.ptr(out)), 10)
+    assert rc == -2 and b"zf_margins_gap" in lib.zf_last_error() and b"penalty factors and l2" in lib.zf_last_error()
     f = Ct.c_double(0.0)
-    rc = lib.zf_f32_eval(Ct.c_void_p(p32.A.data_ptr() + 4), Ct.c_void_p(C.b_dev.data_ptr()), None, C.m, C.n, 0.5, 0, 0.0,
-                         Ct.c_void_p(_lib.ptr(xz)), Ct.byref(f), None)
+    rc = E.point(E.desc(**{**fields, "A32": p32.A.data_ptr() + 4}), Ct.c_void_p(_lib.ptr(xz)), Ct.byref(f))
     assert rc == -2 and b"aligned" in lib.zf_last_error()
-    rc = lib.zf_f32_eval(Ct.c_void_p(p32.A.data_ptr()), Ct.c_void_p(C.b_dev.data_ptr()), None, C.m, C.n, 0.5, 7, 0.0,
-                         Ct.c_void_p(_lib.ptr(xz)), Ct.byref(f), None)
+    rc = E.point(E.desc(**fields, loss=7), Ct.c_void_p(_lib.ptr(xz)), Ct.byref(f))
     assert rc == -2 and b"ZF_LOSS" in lib.zf_last_error()
 
 

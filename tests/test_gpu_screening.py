@@ -425,14 +425,22 @@ def test_interface():
     dense = LeastSquaresL1(A.toarray(), b, 0.2 * lmax)
     assert lib.zf_spmat_col_norms(None, dp(norms), dp(stats)) == -2 and lib.zf_spmat_col_norms(h, None, dp(stats)) == -2
     assert lib.zf_dense_col_norms(None, 3, 3, dp(norms), dp(stats)) == -2 and lib.zf_dense_col_norms(dp(dense.A), 0, n, dp(norms), dp(stats)) == -2
-    args = [h, dp(prob.b), 0.5, 0.1, 0, P(_lib.ptr(x)), P(_lib.ptr(out)), 12, dp(norms), dp(stats), 10, 10, dp(keep), dp(index)]
-    assert lib.zf_spmat_gap_screen_eval(*args) == 0
-    for pos, bad in ((0, None), (7, 11), (8, None), (9, None), (10, -1), (12, None), (13, None), (2, 0.0)):
-        assert lib.zf_spmat_gap_screen_eval(*(args[:pos] + [bad] + args[pos + 1:])) == -2, pos
-    dargs = [dp(dense.A), dp(dense.b), prob.m_rows, n, 0.5, 0.1, 0, P(_lib.ptr(x)), P(_lib.ptr(out)), 12, dp(norms), dp(stats), dp(keep), dp(index)]
-    assert lib.zf_gap_screen_eval(*dargs) == 0
-    for pos, bad in ((0, None), (9, 8), (10, None), (12, None), (13, None), (3, 0)):
-        assert lib.zf_gap_screen_eval(*(dargs[:pos] + [bad] + dargs[pos + 1:])) == -2, pos
+    import evaldesc as E
+
+    fields = dict(spmat=h, b=dp(prob.b), scale=0.5, lam=0.1)   # (the squared loss, K = 1)
+    args = [P(_lib.ptr(x)), P(_lib.ptr(out)), 12, dp(norms), dp(stats), 10, 10, dp(keep), dp(index)]
+    assert E.screen(E.desc(**fields), *args) == 0
+    for pos, bad in ((2, 11), (3, None), (4, None), (5, -1), (7, None), (8, None)):   # count, norms, stats, max_row, keep, index
+        assert E.screen(E.desc(**fields), *(args[:pos] + [bad] + args[pos + 1:])) == -2, pos
+    for name, bad in (("spmat", None), ("scale", 0.0)):
+        assert E.screen(E.desc(**{**fields, name: bad}), *args) == -2, name
+    fields = dict(A=dp(dense.A), b=dp(dense.b), m_rows=prob.m_rows, n=n, scale=0.5, lam=0.1)
+    dargs = [P(_lib.ptr(x)), P(_lib.ptr(out)), 12, dp(norms), dp(stats), 0, 0, dp(keep), dp(index)]   # (max_row / max_col: a handle's)
+    assert E.screen(E.desc(**fields), *dargs) == 0
+    for pos, bad in ((2, 8), (3, None), (7, None), (8, None)):   # count, norms, keep, index
+        assert E.screen(E.desc(**fields), *(dargs[:pos] + [bad] + dargs[pos + 1:])) == -2, pos
+    for name, bad in (("A", None), ("n", 0)):
+        assert E.screen(E.desc(**{**fields, name: bad}), *dargs) == -2, name
     assert lib.zf_screen_scan(None, n, dp(index), C.byref(k)) == -2 and lib.zf_screen_scan(dp(keep), 0, dp(index), C.byref(k)) == -2
     keep.fill_(1)   # (the screen calls above wrote their mask here)
     torch.cuda.synchronize()

@@ -636,12 +636,15 @@ def test_the_creator_refuses_and_the_setter_still_refuses_the_sparse_kinds():
     # the standalone entries' argument checks
     P = C.c_void_p(_lib.ptr(np.zeros(4)))
     f = C.c_double(0.0)
-    for bad in (1, 17):
-        assert lib.zf_spmat_mr_eval(new._spmat.value, P, None, bad, 0.5, 0, P, C.byref(f), None) == -2 and b"2 .. 16" in lib.zf_last_error()
-        assert lib.zf_spmat_mr_gap_eval(new._spmat.value, P, None, None, bad, 0.5, 0.1, 0.0, 0, P, P, 10) == -2
-    assert lib.zf_spmat_mr_eval(new._spmat.value, P, None, 2, 0.5, 2, P, C.byref(f), None) == -2 and b"ZF_LOSS_SQUARE or ZF_LOSS_LOGISTIC" in lib.zf_last_error()
-    assert lib.zf_spmat_mr_eval(None, P, None, 2, 0.5, 0, P, C.byref(f), None) == -2
-    assert lib.zf_spmat_mr_gap_eval(new._spmat.value, P, None, P, 2, 0.5, 0.1, 0.25, 0, P, P, 10) == -2 and b"penalty factors and l2" in lib.zf_last_error()
+    import evaldesc as E
+
+    H = new._spmat.value
+    for bad in (17,):
+        assert E.point(E.sparse(P, spmat=H, K=bad), P, C.byref(f)) == -2 and b"K must be 1 .. 16" in lib.zf_last_error()
+        assert E.gap(E.sparse(P, spmat=H, K=bad), P, P, 10) == -2
+    assert E.point(E.sparse(P, spmat=H, K=2, loss=2, delta=1.0), P, C.byref(f)) == -2 and b"ZF_LOSS_SQUARE or ZF_LOSS_LOGISTIC" in lib.zf_last_error()
+    assert E.point(E.sparse(P, spmat=None, K=2), P, C.byref(f)) == -2
+    assert E.gap(E.sparse(P, spmat=H, K=2, p=P, l2=0.25), P, P, 10) == -2 and b"penalty factors and l2" in lib.zf_last_error()
     assert lib.zf_spmat_mr_apply(new._spmat.value, 0, 17, 1.0, P, P) == -2 and lib.zf_spmat_mr_apply(None, 0, 2, 1.0, P, P) == -2
 
 

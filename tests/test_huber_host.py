@@ -1,4 +1,4 @@
-"""CPU: the interface of the Huber classes without a GPU - header and ctypes table (additive: ABI 6 and the struct sizes as they
+"""CPU: the interface of the Huber classes without a GPU - header and ctypes table (the struct sizes as they
 were, no problem kind), the argument checks of the new entry points before any device is touched, the ValueErrors of the host
 classes, the siblings, and that the product does not import the oracle."""
 import ctypes as C
@@ -11,12 +11,13 @@ import sys
 import numpy as np
 import pytest
 
+import evaldesc as E
 from conftest import ROOT
 from zfista_amd import _lib, path, problems, screening
 from zfista_amd.proximal_gradient import minimize_proximal_gradient
 
-NEW = ("zf_solver_set_huber", "zf_huber_eval", "zf_spmat_huber_eval", "zf_gap_eval_huber", "zf_spmat_gap_eval_huber",
-       "zf_gap_screen_eval_huber", "zf_spmat_gap_screen_eval_huber")
+NEW = ("zf_solver_set_huber", "zf_margins_eval", "zf_margins_gap", "zf_margins_screen")
+HUBER_LOSS = dict(loss=_lib.ZF_LOSS_HUBER, delta=1.0)
 BAD_DELTAS = (0.0, -1.0, float("inf"), float("-inf"), float("nan"))
 
 
@@ -28,18 +29,13 @@ def test_header_and_ctypes_table_declare_the_new_entry_points_and_nothing_else_m
         assert re.search(r"\bint\s+" + name + r"\s*\(", src), name
         assert name in _lib.SIGNATURES and hasattr(lib, name)
     assert sorted(_lib.SIGNATURES) == sorted(set(re.findall(r"\b(zf_[A-Za-z0-9_]+)\s*\(", src))), "header = ctypes table"
-    assert lib.zf_abi_version() == 6 and lib.zf_sizeof_control() == 424 == C.sizeof(_lib.Control)
+    assert lib.zf_abi_version() == 7 and lib.zf_sizeof_control() == 424 == C.sizeof(_lib.Control)
     assert C.sizeof(_lib.ProblemDesc) == 128 and C.sizeof(_lib.Options) == 64, "additive exports only: no struct field"
     fields = [f[0] for f in _lib.ProblemDesc._fields_]
     assert "huber_delta" not in fields and "delta" not in fields
     kinds = sorted(v for k, v in vars(_lib).items() if k.startswith("ZF_PROBLEM_"))
     assert max(kinds) == 6, "no new problem kind"
-    # the siblings' signatures with a delta argument
-    assert len(_lib.SIGNATURES["zf_huber_eval"][1]) == len(_lib.SIGNATURES["zf_ls_eval"][1]) + 1
-    assert len(_lib.SIGNATURES["zf_spmat_huber_eval"][1]) == len(_lib.SIGNATURES["zf_spmat_eval"][1]) + 1
-    assert len(_lib.SIGNATURES["zf_gap_eval_huber"][1]) == len(_lib.SIGNATURES["zf_gap_eval_enet"][1])
-    assert len(_lib.SIGNATURES["zf_gap_screen_eval_huber"][1]) == len(_lib.SIGNATURES["zf_gap_screen_eval"][1])
-    assert len(_lib.SIGNATURES["zf_spmat_gap_screen_eval_huber"][1]) == len(_lib.SIGNATURES["zf_spmat_gap_screen_eval"][1])
+    assert "delta" in [f[0] for f in _lib.EvalDesc._fields_], "delta is a field of the evaluation descriptor"
 
 
 def test_new_entry_points_refuse_bad_arguments_before_touching_a_device():
@@ -49,32 +45,34 @@ def test_new_entry_points_refuse_bad_arguments_before_touching_a_device():
     f = C.c_double(-7.0)
     assert lib.zf_solver_set_huber(None, 1.0) == -2 and b"zf_solver_set_huber" in lib.zf_last_error()
     # f / grad
-    assert lib.zf_huber_eval(None, P, 3, 2, 0.5, 1.0, P, C.byref(f), None) == -2 and b"zf_huber_eval" in lib.zf_last_error()
-    assert lib.zf_huber_eval(P, P, 0, 2, 0.5, 1.0, P, C.byref(f), None) == -2
-    assert lib.zf_spmat_huber_eval(None, P, 0.5, 1.0, P, C.byref(f), None) == -2 and b"zf_spmat_huber_eval" in lib.zf_last_error()
+    H = HUBER_LOSS
+    assert E.point(E.dense(None, **H), P, C.byref(f)) == -2 and b"zf_margins_eval" in lib.zf_last_error()
+    assert E.point(E.dense(P, m_rows=0, **H), P, C.byref(f)) == -2
+    assert E.point(E.sparse(None, **H), P, C.byref(f)) == -2 and b"zf_margins_eval" in lib.zf_last_error()
     for bad in BAD_DELTAS:
-        assert lib.zf_huber_eval(P, P, 3, 2, 0.5, bad, P, C.byref(f), None) == -2 and b"delta" in lib.zf_last_error()
-        assert lib.zf_spmat_huber_eval(P, P, 0.5, bad, P, C.byref(f), None) == -2 and b"delta" in lib.zf_last_error()
-        assert lib.zf_gap_eval_huber(P, P, 3, 2, 0.5, 0.1, 0.0, bad, P, P, 10) == -2 and b"delta" in lib.zf_last_error()
-        assert lib.zf_spmat_gap_eval_huber(P, P, 0.5, 0.1, 0.0, bad, P, P, 10) == -2 and b"delta" in lib.zf_last_error()
-        assert lib.zf_gap_screen_eval_huber(P, P, 3, 2, 0.5, 0.1, bad, P, P, 12, P, P, P, P) == -2 and b"delta" in lib.zf_last_error()
-        assert lib.zf_spmat_gap_screen_eval_huber(P, P, 0.5, 0.1, bad, P, P, 12, P, P, 2, 3, P, P) == -2 and b"delta" in lib.zf_last_error()
+        B = dict(loss=_lib.ZF_LOSS_HUBER, delta=bad)
+        assert E.point(E.dense(P, **B), P, C.byref(f)) == -2 and b"delta" in lib.zf_last_error()
+        assert E.point(E.sparse(P, **B), P, C.byref(f)) == -2 and b"delta" in lib.zf_last_error()
+        assert E.gap(E.dense(P, **B), P, P, 10) == -2 and b"delta" in lib.zf_last_error()
+        assert E.gap(E.sparse(P, **B), P, P, 10) == -2 and b"delta" in lib.zf_last_error()
+        assert E.screen(E.dense(P, **B), P, P, 12, P, P, 0, 0, P, P) == -2 and b"delta" in lib.zf_last_error()
+        assert E.screen(E.sparse(P, **B), P, P, 12, P, P, 2, 3, P, P) == -2 and b"delta" in lib.zf_last_error()
     # the certificate
-    assert lib.zf_gap_eval_huber(None, P, 3, 2, 0.5, 0.1, 0.0, 1.0, P, P, 10) == -2 and b"zf_gap_eval_huber" in lib.zf_last_error()
-    assert lib.zf_gap_eval_huber(P, P, 3, 2, 0.5, 0.1, 0.0, 1.0, P, P, 7) == -2 and b"fewer than 8" in lib.zf_last_error()
-    assert lib.zf_spmat_gap_eval_huber(None, P, 0.5, 0.1, 0.0, 1.0, P, P, 10) == -2
-    assert lib.zf_spmat_gap_eval_huber(P, P, 0.5, 0.1, 0.0, 1.0, P, P, 3) == -2 and b"fewer than 8" in lib.zf_last_error()
+    assert E.gap(E.dense(None, **H), P, P, 10) == -2 and b"zf_margins_gap" in lib.zf_last_error()
+    assert E.gap(E.dense(P, **H), P, P, 7) == -2 and b"fewer than 8" in lib.zf_last_error()
+    assert E.gap(E.sparse(None, **H), P, P, 10) == -2
+    assert E.gap(E.sparse(P, **H), P, P, 3) == -2 and b"fewer than 8" in lib.zf_last_error()
     for bad in (-1e-9, float("inf"), float("nan")):
-        assert lib.zf_gap_eval_huber(P, P, 3, 2, 0.5, 0.1, bad, 1.0, P, P, 10) == -2 and b"l2" in lib.zf_last_error()
-        assert lib.zf_spmat_gap_eval_huber(P, P, 0.5, 0.1, bad, 1.0, P, P, 10) == -2 and b"l2" in lib.zf_last_error()
-    assert lib.zf_gap_eval_huber(P, P, 3, 2, 0.5, -0.1, 0.0, 1.0, P, P, 10) == -2 and b"lam >= 0" in lib.zf_last_error()
-    assert lib.zf_gap_eval_huber(P, P, 3, 2, 0.0, 0.1, 0.0, 1.0, P, P, 10) == -2 and b"scale > 0" in lib.zf_last_error()
+        assert E.gap(E.dense(P, l2=bad, **H), P, P, 10) == -2 and b"l2" in lib.zf_last_error()
+        assert E.gap(E.sparse(P, l2=bad, **H), P, P, 10) == -2 and b"l2" in lib.zf_last_error()
+    assert E.gap(E.dense(P, lam=-0.1, **H), P, P, 10) == -2 and b"lam >= 0" in lib.zf_last_error()
+    assert E.gap(E.dense(P, scale=0.0, **H), P, P, 10) == -2 and b"scale > 0" in lib.zf_last_error()
     # the screen
-    assert lib.zf_gap_screen_eval_huber(None, P, 3, 2, 0.5, 0.1, 1.0, P, P, 12, P, P, P, P) == -2
-    assert lib.zf_gap_screen_eval_huber(P, P, 3, 2, 0.5, 0.1, 1.0, P, P, 11, P, P, P, P) == -2 and b"fewer than 12" in lib.zf_last_error()
-    assert lib.zf_gap_screen_eval_huber(P, P, 3, 2, 0.5, 0.1, 1.0, P, P, 12, None, P, P, P) == -2 and b"null" in lib.zf_last_error()
-    assert lib.zf_spmat_gap_screen_eval_huber(None, P, 0.5, 0.1, 1.0, P, P, 12, P, P, 2, 3, P, P) == -2
-    assert lib.zf_spmat_gap_screen_eval_huber(P, P, 0.5, 0.1, 1.0, P, P, 12, P, P, -1, 3, P, P) == -2 and b">= 0" in lib.zf_last_error()
+    assert E.screen(E.dense(None, **H), P, P, 12, P, P, 0, 0, P, P) == -2
+    assert E.screen(E.dense(P, **H), P, P, 11, P, P, 0, 0, P, P) == -2 and b"fewer than 12" in lib.zf_last_error()
+    assert E.screen(E.dense(P, **H), P, P, 12, None, P, 0, 0, P, P) == -2 and b"null" in lib.zf_last_error()
+    assert E.screen(E.sparse(None, **H), P, P, 12, P, P, 2, 3, P, P) == -2
+    assert E.screen(E.sparse(P, **H), P, P, 12, P, P, -1, 3, P, P) == -2 and b">= 0" in lib.zf_last_error()
     assert (out == -7.0).all() and f.value == -7.0
 
 
@@ -131,7 +129,8 @@ def test_the_classes_are_least_squares_kinds_with_huber_delta_in_the_descriptor(
     sib.shard = "columns"
     assert "huber_delta" not in sib._descriptor()[0], "a least-squares problem hands the engine what it handed it before"
     assert not hasattr(_lib.ProblemDesc(), "huber_delta")
-    assert p.has_duality_gap and p._gap_logistic == 0
+    d = p._eval_desc()
+    assert p.has_duality_gap and (d.loss, d.delta) == (_lib.ZF_LOSS_HUBER, 0.75)
 
 
 @pytest.mark.parametrize("cls", HUBER)

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import scipy.sparse as sp
 
+import evaldesc as E
 from conftest import ROOT
 from zfista_amd import _lib
 
@@ -97,7 +98,7 @@ def test_descriptor_fields_and_class_layout():
     # a logistic problem is no least-squares problem (the shared plumbing is a base without a loss) and cannot be sharded
     assert not issubclass(problems.LogisticL1, problems.LeastSquaresL1) and not hasattr(problems.LogisticL1, "shard")
     assert not issubclass(problems.SparseLogisticL1, problems.SparseLeastSquaresL1)
-    assert problems.LogisticL1._eval_name == "zf_logistic_eval" and problems.SparseLogisticL1._eval_name == "zf_spmat_logistic_eval"
+    assert problems.LogisticL1._loss == problems.SparseLogisticL1._loss == _lib.ZF_LOSS_LOGISTIC
 
     class _T:   # what _descriptor reads of a device tensor
         def data_ptr(self):
@@ -111,10 +112,14 @@ def test_descriptor_fields_and_class_layout():
     fields, _ = p._descriptor()
     assert fields["kind"] == 5 and fields["world"] == 1 and fields["rank"] == 0 and fields["row_sharded"] == 0
     assert (fields["n"], fields["m_rows"], fields["A"], fields["b"], fields["scale"], fields["lam"]) == (8, 5, 4096, 4096, 1.0, 0.25)
+    e = p._eval_desc()
+    assert (e.A, e.A32, e.spmat, e.m_rows, e.n, e.b, e.loss, e.K) == (4096, None, None, 5, 8, 4096, _lib.ZF_LOSS_LOGISTIC, 1)
     q = object.__new__(problems.SparseLogisticL1)
     q.b, q.lam, q.scale, q.box, q.m_rows, q.n_features, q._spmat = _T(), 0.25, 1.0, (-1.0, 2.0), 5, 8, _H()
     fields, _ = q._descriptor()
     assert fields["kind"] == 6 and fields["A"] is None and fields["spmat"] == 8192 and (fields["box_lo"], fields["box_hi"]) == (-1.0, 2.0)
+    e = q._eval_desc()
+    assert (e.A, e.A32, e.spmat, e.b, e.loss, e.K) == (None, None, 8192, 4096, _lib.ZF_LOSS_LOGISTIC, 1)
     d = _lib.ProblemDesc()
     for k, v in fields.items():
         if k != "spmat":
@@ -125,22 +130,20 @@ def test_descriptor_fields_and_class_layout():
 def test_abi_additions():
     src = open(os.path.join(ROOT, "include", "zfista_hip.h")).read()
     assert re.search(r"#define\s+ZF_PROBLEM_LOGISTIC_L1\s+5\b", src) and re.search(r"#define\s+ZF_PROBLEM_SPARSE_LOGISTIC_L1\s+6\b", src)
-    assert re.search(r"#define\s+ZF_ABI_VERSION\s+6\b", src)
-    for name in ("zf_logistic_eval", "zf_spmat_logistic_eval"):
-        assert name in _lib.SIGNATURES and re.search(r"\b" + name + r"\s*\(", src), name
-    assert _lib.SIGNATURES["zf_logistic_eval"] == _lib.SIGNATURES["zf_ls_eval"]
-    assert _lib.SIGNATURES["zf_spmat_logistic_eval"] == _lib.SIGNATURES["zf_spmat_eval"]
+    assert re.search(r"#define\s+ZF_ABI_VERSION\s+7\b", src)
+    assert "zf_margins_eval" in _lib.SIGNATURES and re.search(r"\bzf_margins_eval\s*\(", src)
+    assert re.search(r"ZF_LOSS_LOGISTIC\s*=\s*1\b", src) and _lib.ZF_LOSS_LOGISTIC == 1
     assert C.sizeof(_lib.ProblemDesc) == 128 and C.sizeof(_lib.Options) == 64
     lib = _lib.load()
-    assert lib.zf_abi_version() == 6 and lib.zf_sizeof_control() == 424
+    assert lib.zf_abi_version() == 7 and lib.zf_sizeof_control() == 424
     # argument checks come before anything is dereferenced or any device is touched
     dummy = (C.c_ubyte * 4096)()
     P = C.addressof(dummy)
     fval = C.c_double(0.0)
-    assert lib.zf_logistic_eval(None, P, 3, 2, 1.0, P, C.byref(fval), None) == -2 and b"zf_logistic_eval" in lib.zf_last_error()
-    assert lib.zf_logistic_eval(P, P, 0, 2, 1.0, P, C.byref(fval), None) == -2
-    assert lib.zf_logistic_eval(P + 8, P, 3, 2, 1.0, P, C.byref(fval), None) == -2 and b"aligned" in lib.zf_last_error()
-    assert lib.zf_spmat_logistic_eval(None, P, 1.0, P, C.byref(fval), None) == -2 and b"zf_spmat_logistic_eval" in lib.zf_last_error()
+    assert E.point(E.dense(None, loss=1), P, C.byref(fval)) == -2 and b"zf_margins_eval" in lib.zf_last_error()
+    assert E.point(E.dense(P, loss=1, m_rows=0), P, C.byref(fval)) == -2
+    assert E.point(E.dense(P + 8, loss=1), P, C.byref(fval)) == -2 and b"aligned" in lib.zf_last_error()
+    assert E.point(E.sparse(None, loss=1), P, C.byref(fval)) == -2 and b"zf_margins_eval" in lib.zf_last_error()
     # kind / creator mismatches
     o, s = _lib.Options(lr=1.0, decay_rate=0.5, max_iter=1), C.c_void_p()
     d = _lib.ProblemDesc(kind=6, world=1, n=2, m_rows=3)

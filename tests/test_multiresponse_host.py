@@ -1,4 +1,4 @@
-"""CPU: the interface of the multi-response classes without a GPU - header and ctypes table (additive: ABI 6 and the struct sizes
+"""CPU: the interface of the multi-response classes without a GPU - header and ctypes table (the struct sizes
 as they were, no problem kind), the argument checks of the new entry points before any device is touched, the ValueErrors of the
 host classes (each with its message, each before anything is uploaded), the descriptor, the siblings."""
 import ctypes as C
@@ -9,11 +9,12 @@ import re
 import numpy as np
 import pytest
 
+import evaldesc as E
 from conftest import ROOT
 from zfista_amd import _lib, path, problems, screening
 from zfista_amd.proximal_gradient import minimize_proximal_gradient
 
-NEW = ("zf_solver_set_responses", "zf_mr_eval", "zf_mr_gap_eval")
+NEW = ("zf_solver_set_responses", "zf_margins_eval", "zf_margins_gap")
 MR = [problems.MultiResponseLeastSquaresL1, problems.MultiResponseLogisticL1]
 
 
@@ -25,13 +26,11 @@ def test_header_and_ctypes_table_declare_the_new_entry_points_and_nothing_else_m
         assert re.search(r"\bint\s+" + name + r"\s*\(", src), name
         assert name in _lib.SIGNATURES and hasattr(lib, name)
     assert sorted(_lib.SIGNATURES) == sorted(set(re.findall(r"\b(zf_[A-Za-z0-9_]+)\s*\(", src))), "header = ctypes table"
-    assert lib.zf_abi_version() == 6 and lib.zf_sizeof_control() == 424 == C.sizeof(_lib.Control)
+    assert lib.zf_abi_version() == 7 and lib.zf_sizeof_control() == 424 == C.sizeof(_lib.Control)
     assert C.sizeof(_lib.ProblemDesc) == 128 and C.sizeof(_lib.Options) == 64, "additive exports only: no struct field"
     assert "responses" not in [f[0] for f in _lib.ProblemDesc._fields_]
     assert max(v for k, v in vars(_lib).items() if k.startswith("ZF_PROBLEM_")) == 6, "no new problem kind"
-    # zf_f32_eval's / zf_f32_gap_eval's argument lists with K for delta
-    assert len(_lib.SIGNATURES["zf_mr_eval"][1]) == len(_lib.SIGNATURES["zf_f32_eval"][1])
-    assert len(_lib.SIGNATURES["zf_mr_gap_eval"][1]) == len(_lib.SIGNATURES["zf_f32_gap_eval"][1])
+    assert "K" in [f[0] for f in _lib.EvalDesc._fields_], "K is a field of the evaluation descriptor"
 
 
 def test_new_entry_points_refuse_bad_arguments_before_touching_a_device():
@@ -40,23 +39,23 @@ def test_new_entry_points_refuse_bad_arguments_before_touching_a_device():
     P = C.c_void_p(_lib.ptr(out))
     f = C.c_double(-7.0)
     assert lib.zf_solver_set_responses(None, 2) == -2 and b"zf_solver_set_responses" in lib.zf_last_error()
-    for bad in (1, 0, -3, 17):
-        assert lib.zf_mr_eval(P, P, None, 3, 2, bad, 0.5, 0, P, C.byref(f), None) == -2 and b"2 .. 16" in lib.zf_last_error()
-        assert lib.zf_mr_gap_eval(P, P, None, None, 3, 2, bad, 0.5, 0.1, 0.0, 0, P, P, 10) == -2 and b"2 .. 16" in lib.zf_last_error()
+    for bad in (0, -3, 17):
+        assert E.point(E.dense(P, K=bad), P, C.byref(f)) == -2 and b"K must be 1 .. 16" in lib.zf_last_error()
+        assert E.gap(E.dense(P, K=bad), P, P, 10) == -2 and b"K must be 1 .. 16" in lib.zf_last_error()
     for bad in (2, 3, -1, 7):   # Huber, Poisson, unknown
-        assert lib.zf_mr_eval(P, P, None, 3, 2, 2, 0.5, bad, P, C.byref(f), None) == -2 and b"ZF_LOSS_SQUARE or ZF_LOSS_LOGISTIC" in lib.zf_last_error()
-        assert lib.zf_mr_gap_eval(P, P, None, None, 3, 2, 2, 0.5, 0.1, 0.0, bad, P, P, 10) == -2
-    assert lib.zf_mr_eval(None, P, None, 3, 2, 2, 0.5, 0, P, C.byref(f), None) == -2 and b"zf_mr_eval" in lib.zf_last_error()
-    assert lib.zf_mr_eval(P, None, None, 3, 2, 2, 0.5, 0, P, C.byref(f), None) == -2
-    assert lib.zf_mr_eval(P, P, None, 0, 2, 2, 0.5, 0, P, C.byref(f), None) == -2
-    assert lib.zf_mr_eval(P, P, None, 3, 2, 2, 0.5, 0, None, C.byref(f), None) == -2
-    assert lib.zf_mr_gap_eval(None, P, None, None, 3, 2, 2, 0.5, 0.1, 0.0, 0, P, P, 10) == -2 and b"zf_mr_gap_eval" in lib.zf_last_error()
-    assert lib.zf_mr_gap_eval(P, P, None, None, 3, 2, 2, 0.5, 0.1, 0.0, 0, P, P, 7) == -2 and b"fewer than 8" in lib.zf_last_error()
-    assert lib.zf_mr_gap_eval(P, P, None, None, 3, 2, 2, 0.0, 0.1, 0.0, 0, P, P, 10) == -2 and b"scale > 0" in lib.zf_last_error()
-    assert lib.zf_mr_gap_eval(P, P, None, None, 3, 2, 2, 0.5, -0.1, 0.0, 0, P, P, 10) == -2 and b"lam >= 0" in lib.zf_last_error()
+        assert E.point(E.dense(P, K=2, loss=bad, delta=1.0), P, C.byref(f)) == -2 and b"ZF_LOSS_SQUARE or ZF_LOSS_LOGISTIC" in lib.zf_last_error()
+        assert E.gap(E.dense(P, K=2, loss=bad, delta=1.0), P, P, 10) == -2
+    assert E.point(E.dense(None, K=2), P, C.byref(f)) == -2 and b"zf_margins_eval" in lib.zf_last_error()
+    assert E.point(E.dense(P, K=2, b=None), P, C.byref(f)) == -2
+    assert E.point(E.dense(P, K=2, m_rows=0), P, C.byref(f)) == -2
+    assert E.point(E.dense(P, K=2), None, C.byref(f)) == -2
+    assert E.gap(E.dense(None, K=2), P, P, 10) == -2 and b"zf_margins_gap" in lib.zf_last_error()
+    assert E.gap(E.dense(P, K=2), P, P, 7) == -2 and b"fewer than 8" in lib.zf_last_error()
+    assert E.gap(E.dense(P, K=2, scale=0.0), P, P, 10) == -2 and b"scale > 0" in lib.zf_last_error()
+    assert E.gap(E.dense(P, K=2, lam=-0.1), P, P, 10) == -2 and b"lam >= 0" in lib.zf_last_error()
     for bad in (-1e-9, float("inf"), float("nan")):
-        assert lib.zf_mr_gap_eval(P, P, None, None, 3, 2, 2, 0.5, 0.1, bad, 0, P, P, 10) == -2 and b"l2" in lib.zf_last_error()
-    assert lib.zf_mr_gap_eval(P, P, None, P, 3, 2, 2, 0.5, 0.1, 0.25, 0, P, P, 10) == -2 and b"penalty factors and l2" in lib.zf_last_error()
+        assert E.gap(E.dense(P, K=2, l2=bad), P, P, 10) == -2 and b"l2" in lib.zf_last_error()
+    assert E.gap(E.dense(P, K=2, p=P, l2=0.25), P, P, 10) == -2 and b"penalty factors and l2" in lib.zf_last_error()
     assert (out == -7.0).all() and f.value == -7.0
 
 

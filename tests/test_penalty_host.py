@@ -1,4 +1,4 @@
-"""CPU: the interface of per-column penalty factors without a GPU - header and ctypes table (additive: ABI 6 and the struct sizes
+"""CPU: the interface of per-column penalty factors without a GPU - header and ctypes table (the struct sizes
 as they were), the argument checks of the new entry points and of the two host functions before any device is touched, every
 ValueError of the host classes, the siblings, and add_intercept."""
 import ctypes as C
@@ -11,10 +11,11 @@ import pytest
 import scipy.sparse as sp
 
 from conftest import ROOT
+import evaldesc as E
 from zfista_amd import _lib, path, problems, screening
 from zfista_amd.proximal_gradient import minimize_proximal_gradient
 
-NEW = ("zf_solver_set_penalty_factors", "zf_gap_eval_pf", "zf_spmat_gap_eval_pf", "zf_host_prox_pf_box", "zf_host_pf_g")
+NEW = ("zf_solver_set_penalty_factors", "zf_margins_gap", "zf_host_prox_pf_box", "zf_host_pf_g")
 EIGHT = [problems.LeastSquaresL1, problems.SparseLeastSquaresL1, problems.LogisticL1, problems.SparseLogisticL1, problems.HuberL1,
          problems.SparseHuberL1, problems.PoissonL1, problems.SparsePoissonL1]
 WITH_KEYWORD = [c for c in EIGHT if "Logistic" not in c.__name__]
@@ -28,12 +29,10 @@ def test_header_and_ctypes_table_declare_the_new_entry_points_and_nothing_else_m
         assert re.search(r"\bint\s+" + name + r"\s*\(", src), name
         assert name in _lib.SIGNATURES and hasattr(lib, name)
     assert sorted(_lib.SIGNATURES) == sorted(set(re.findall(r"\b(zf_[A-Za-z0-9_]+)\s*\(", src))), "header = ctypes table"
-    assert lib.zf_abi_version() == 6 and lib.zf_sizeof_control() == 424 == C.sizeof(_lib.Control)
+    assert lib.zf_abi_version() == 7 and lib.zf_sizeof_control() == 424 == C.sizeof(_lib.Control)
     assert C.sizeof(_lib.ProblemDesc) == 128 and C.sizeof(_lib.Options) == 64, "additive exports only: no struct field"
     assert "penalty_factors" not in [f[0] for f in _lib.ProblemDesc._fields_]
-    # the weighted certificate's signature with p in place of l2
-    assert len(_lib.SIGNATURES["zf_gap_eval_pf"][1]) == len(_lib.SIGNATURES["zf_gap_eval_weighted"][1]) == 13
-    assert len(_lib.SIGNATURES["zf_spmat_gap_eval_pf"][1]) == len(_lib.SIGNATURES["zf_spmat_gap_eval_weighted"][1]) == 11
+    assert "p" in [f[0] for f in _lib.EvalDesc._fields_], "the factors are a field of the evaluation descriptor"
     assert len(_lib.SIGNATURES["zf_host_prox_pf_box"][1]) == len(_lib.SIGNATURES["zf_host_prox_l1_box"][1]) + 1
 
 
@@ -44,29 +43,30 @@ def test_new_entry_points_refuse_bad_arguments_before_touching_a_device():
     s = C.c_double(-7.0)
     assert lib.zf_solver_set_penalty_factors(None, P) == -2 and b"zf_solver_set_penalty_factors" in lib.zf_last_error()
     # the certificate: a null pointer in every place but the weights (NULL: unweighted), short buffers, scale, lam, the loss, delta
-    for k in (0, 1, 3, 10, 11):
-        args = [P, P, P, P, 3, 2, 0.5, 0.1, 0, 0.0, P, P, 8]
-        args[k] = None
-        assert lib.zf_gap_eval_pf(*args) == -2 and b"zf_gap_eval_pf" in lib.zf_last_error(), k
-    for k in (0, 1, 3, 8, 9):
-        args = [P, P, P, P, 0.5, 0.1, 0, 0.0, P, P, 8]
-        args[k] = None
-        assert lib.zf_spmat_gap_eval_pf(*args) == -2 and b"zf_spmat_gap_eval_pf" in lib.zf_last_error(), k
-    assert lib.zf_gap_eval_pf(P, P, None, P, 0, 2, 0.5, 0.1, 0, 0.0, P, P, 8) == -2
-    assert lib.zf_gap_eval_pf(P, P, None, P, 3, 0, 0.5, 0.1, 0, 0.0, P, P, 8) == -2
+    for field in ("A", "b"):
+        assert E.gap(E.dense(P, w=P, p=P, **{field: None}), P, P, 8) == -2 and b"zf_margins_gap" in lib.zf_last_error(), field
+    for field in ("spmat", "b"):
+        assert E.gap(E.sparse(P, w=P, p=P, **{field: None}), P, P, 8) == -2 and b"zf_margins_gap" in lib.zf_last_error(), field
+    for d in (E.dense(P, w=P, p=P), E.sparse(P, w=P, p=P)):
+        assert E.gap(d, None, P, 8) == -2 and b"zf_margins_gap" in lib.zf_last_error()
+        assert E.gap(d, P, None, 8) == -2 and b"zf_margins_gap" in lib.zf_last_error()
+    assert E.gap(E.dense(P, p=P, m_rows=0), P, P, 8) == -2
+    assert E.gap(E.dense(P, p=P, n=0), P, P, 8) == -2
     for short in (0, 3, 7):
-        assert lib.zf_gap_eval_pf(P, P, None, P, 3, 2, 0.5, 0.1, 0, 0.0, P, P, short) == -2 and b"fewer than 8" in lib.zf_last_error()
-        assert lib.zf_spmat_gap_eval_pf(P, P, None, P, 0.5, 0.1, 1, 0.0, P, P, short) == -2 and b"fewer than 8" in lib.zf_last_error()
+        assert E.gap(E.dense(P, p=P), P, P, short) == -2 and b"fewer than 8" in lib.zf_last_error()
+        assert E.gap(E.sparse(P, p=P, loss=1), P, P, short) == -2 and b"fewer than 8" in lib.zf_last_error()
     for bad_loss in (-1, 4, 7):
-        assert lib.zf_gap_eval_pf(P, P, None, P, 3, 2, 0.5, 0.1, bad_loss, 1.0, P, P, 8) == -2 and b"ZF_LOSS_" in lib.zf_last_error()
-        assert lib.zf_spmat_gap_eval_pf(P, P, None, P, 0.5, 0.1, bad_loss, 1.0, P, P, 8) == -2 and b"ZF_LOSS_" in lib.zf_last_error()
+        assert E.gap(E.dense(P, p=P, loss=bad_loss, delta=1.0), P, P, 8) == -2 and b"ZF_LOSS_" in lib.zf_last_error()
+        assert E.gap(E.sparse(P, p=P, loss=bad_loss, delta=1.0), P, P, 8) == -2 and b"ZF_LOSS_" in lib.zf_last_error()
     for bad in (0.0, -1.0, float("inf"), float("nan")):   # delta: checked for Huber's loss only
-        assert lib.zf_gap_eval_pf(P, P, None, P, 3, 2, 0.5, 0.1, 2, bad, P, P, 8) == -2 and b"delta" in lib.zf_last_error()
-        assert lib.zf_spmat_gap_eval_pf(P, P, None, P, 0.5, 0.1, 2, bad, P, P, 8) == -2 and b"delta" in lib.zf_last_error()
-    assert lib.zf_gap_eval_pf(P, P, None, P, 3, 2, 0.5, -0.1, 0, 0.0, P, P, 8) == -2 and b"lam >= 0" in lib.zf_last_error()
-    assert lib.zf_gap_eval_pf(P, P, None, P, 3, 2, 0.0, 0.1, 0, 0.0, P, P, 8) == -2 and b"scale > 0" in lib.zf_last_error()
+        assert E.gap(E.dense(P, p=P, loss=2, delta=bad), P, P, 8) == -2 and b"delta" in lib.zf_last_error()
+        assert E.gap(E.sparse(P, p=P, loss=2, delta=bad), P, P, 8) == -2 and b"delta" in lib.zf_last_error()
+    assert E.gap(E.dense(P, p=P, lam=-0.1), P, P, 8) == -2 and b"lam >= 0" in lib.zf_last_error()
+    assert E.gap(E.dense(P, p=P, scale=0.0), P, P, 8) == -2 and b"scale > 0" in lib.zf_last_error()
     odd = C.c_void_p(_lib.ptr(out) + 8)
-    assert lib.zf_gap_eval_pf(odd, P, None, P, 3, 2, 0.5, 0.1, 0, 0.0, P, P, 8) == -2 and b"16-byte" in lib.zf_last_error()
+    assert E.gap(E.dense(odd, p=P), P, P, 8) == -2 and b"16-byte" in lib.zf_last_error()
+    for d in (E.dense(P, p=P, l2=0.25), E.sparse(P, p=P, l2=0.25)):   # the ridge term would need the factors too
+        assert E.gap(d, P, P, 10) == -2 and b"penalty factors and l2" in lib.zf_last_error()
     # the two host functions: null pointers, a negative length; n = 0 is legal and touches nothing
     for k in (0, 1, 2):
         args = [P, P, P, 0.1, -1.0, 1.0, 4]

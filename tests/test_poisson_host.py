@@ -1,4 +1,4 @@
-"""CPU: the interface of the Poisson classes without a GPU - header and ctypes table (additive: ABI 6 and the struct sizes as they
+"""CPU: the interface of the Poisson classes without a GPU - header and ctypes table (the struct sizes as they
 were, no problem kind), the argument checks of the new entry points before any device is touched, the ValueErrors of the host
 classes, the siblings, and the refusals of screening."""
 import ctypes as C
@@ -9,11 +9,12 @@ import re
 import numpy as np
 import pytest
 
+import evaldesc as E
 from conftest import ROOT
 from zfista_amd import _lib, path, problems, screening
 from zfista_amd.proximal_gradient import minimize_proximal_gradient
 
-NEW = ("zf_solver_set_poisson", "zf_poisson_eval", "zf_spmat_poisson_eval", "zf_gap_eval_poisson", "zf_spmat_gap_eval_poisson")
+NEW = ("zf_solver_set_poisson", "zf_margins_eval", "zf_margins_gap")
 
 
 def test_header_and_ctypes_table_declare_the_new_entry_points_and_nothing_else_moved():
@@ -25,16 +26,11 @@ def test_header_and_ctypes_table_declare_the_new_entry_points_and_nothing_else_m
         assert name in _lib.SIGNATURES and hasattr(lib, name)
     assert sorted(_lib.SIGNATURES) == sorted(set(re.findall(r"\b(zf_[A-Za-z0-9_]+)\s*\(", src))), "header = ctypes table"
     assert re.search(r"ZF_LOSS_POISSON\s*=\s*3\b", src) and _lib.ZF_LOSS_POISSON == 3
-    assert lib.zf_abi_version() == 6 and lib.zf_sizeof_control() == 424 == C.sizeof(_lib.Control)
+    assert lib.zf_abi_version() == 7 and lib.zf_sizeof_control() == 424 == C.sizeof(_lib.Control)
     assert C.sizeof(_lib.ProblemDesc) == 128 and C.sizeof(_lib.Options) == 64, "additive exports only: no struct field"
     assert "poisson" not in [f[0] for f in _lib.ProblemDesc._fields_]
     kinds = sorted(v for k, v in vars(_lib).items() if k.startswith("ZF_PROBLEM_"))
     assert max(kinds) == 6, "no new problem kind"
-    # the siblings' signatures with the weights for Huber's delta
-    assert len(_lib.SIGNATURES["zf_poisson_eval"][1]) == len(_lib.SIGNATURES["zf_huber_eval"][1])
-    assert len(_lib.SIGNATURES["zf_spmat_poisson_eval"][1]) == len(_lib.SIGNATURES["zf_spmat_huber_eval"][1])
-    assert len(_lib.SIGNATURES["zf_gap_eval_poisson"][1]) == len(_lib.SIGNATURES["zf_gap_eval_huber"][1])
-    assert len(_lib.SIGNATURES["zf_spmat_gap_eval_poisson"][1]) == len(_lib.SIGNATURES["zf_spmat_gap_eval_huber"][1])
     assert _lib.SIGNATURES["zf_solver_set_poisson"][1] == [C.c_void_p]
 
 
@@ -47,36 +43,38 @@ def test_new_entry_points_refuse_bad_arguments_before_touching_a_device():
     f = C.c_double(-7.0)
     assert lib.zf_solver_set_poisson(None) == -2 and b"zf_solver_set_poisson" in lib.zf_last_error()
     # f / grad: null pointers, bad sizes, a misaligned A - with and without the weights
+    PO = _lib.ZF_LOSS_POISSON
     for w in (None, P):
-        assert lib.zf_poisson_eval(None, P, w, 3, 2, 1.0, P, C.byref(f), None) == -2 and b"zf_poisson_eval" in lib.zf_last_error()
-        assert lib.zf_poisson_eval(P, None, w, 3, 2, 1.0, P, C.byref(f), None) == -2
-        assert lib.zf_poisson_eval(P, P, w, 3, 2, 1.0, None, C.byref(f), None) == -2
-        assert lib.zf_poisson_eval(P, P, w, 3, 2, 1.0, P, None, None) == -2
-        assert lib.zf_poisson_eval(P, P, w, 0, 2, 1.0, P, C.byref(f), None) == -2
-        assert lib.zf_poisson_eval(P, P, w, 3, 0, 1.0, P, C.byref(f), None) == -2
-        assert lib.zf_poisson_eval(odd, P, w, 3, 2, 1.0, P, C.byref(f), None) == -2 and b"aligned" in lib.zf_last_error()
-        assert lib.zf_spmat_poisson_eval(None, P, w, 1.0, P, C.byref(f), None) == -2 and b"zf_spmat_poisson_eval" in lib.zf_last_error()
+        D = lambda **kw: E.dense(P, **{**dict(loss=PO, w=w, scale=1.0), **kw})    # noqa: E731
+        S = lambda **kw: E.sparse(P, **{**dict(loss=PO, w=w, scale=1.0), **kw})   # noqa: E731
+        assert E.point(D(A=None), P, C.byref(f)) == -2 and b"zf_margins_eval" in lib.zf_last_error()
+        assert E.point(D(b=None), P, C.byref(f)) == -2
+        assert E.point(D(), None, C.byref(f)) == -2
+        assert E.point(D(), P, None) == -2
+        assert E.point(D(m_rows=0), P, C.byref(f)) == -2
+        assert E.point(D(n=0), P, C.byref(f)) == -2
+        assert E.point(D(A=odd), P, C.byref(f)) == -2 and b"aligned" in lib.zf_last_error()
+        assert E.point(S(spmat=None), P, C.byref(f)) == -2 and b"zf_margins_eval" in lib.zf_last_error()
         # the certificate
-        assert lib.zf_gap_eval_poisson(None, P, w, 3, 2, 1.0, 0.1, 0.0, P, P, 10) == -2 and b"zf_gap_eval_poisson" in lib.zf_last_error()
-        assert lib.zf_gap_eval_poisson(P, P, w, 3, 2, 1.0, 0.1, 0.0, None, P, 10) == -2
-        assert lib.zf_gap_eval_poisson(P, P, w, 3, 2, 1.0, 0.1, 0.0, P, None, 10) == -2
-        assert lib.zf_gap_eval_poisson(P, P, w, -3, 2, 1.0, 0.1, 0.0, P, P, 10) == -2
-        assert lib.zf_gap_eval_poisson(odd, P, w, 3, 2, 1.0, 0.1, 0.0, P, P, 10) == -2 and b"aligned" in lib.zf_last_error()
-        assert lib.zf_spmat_gap_eval_poisson(None, P, w, 1.0, 0.1, 0.0, P, P, 10) == -2 and b"zf_spmat_gap_eval_poisson" in lib.zf_last_error()
+        assert E.gap(D(A=None), P, P, 10) == -2 and b"zf_margins_gap" in lib.zf_last_error()
+        assert E.gap(D(), None, P, 10) == -2
+        assert E.gap(D(), P, None, 10) == -2
+        assert E.gap(D(m_rows=-3), P, P, 10) == -2
+        assert E.gap(D(A=odd), P, P, 10) == -2 and b"aligned" in lib.zf_last_error()
+        assert E.gap(S(spmat=None), P, P, 10) == -2 and b"zf_margins_gap" in lib.zf_last_error()
         for short in (0, 3, 7):
-            assert lib.zf_gap_eval_poisson(P, P, w, 3, 2, 1.0, 0.1, 0.0, P, P, short) == -2 and b"fewer than 8" in lib.zf_last_error()
-            assert lib.zf_spmat_gap_eval_poisson(P, P, w, 1.0, 0.1, 0.0, P, P, short) == -2 and b"fewer than 8" in lib.zf_last_error()
+            assert E.gap(D(), P, P, short) == -2 and b"fewer than 8" in lib.zf_last_error()
+            assert E.gap(S(), P, P, short) == -2 and b"fewer than 8" in lib.zf_last_error()
         for bad in (-1e-9, float("inf"), float("nan")):
-            assert lib.zf_gap_eval_poisson(P, P, w, 3, 2, 1.0, 0.1, bad, P, P, 10) == -2 and b"l2" in lib.zf_last_error()
-            assert lib.zf_spmat_gap_eval_poisson(P, P, w, 1.0, 0.1, bad, P, P, 10) == -2 and b"l2" in lib.zf_last_error()
-        assert lib.zf_gap_eval_poisson(P, P, w, 3, 2, 1.0, -0.1, 0.0, P, P, 10) == -2 and b"lam >= 0" in lib.zf_last_error()
-        assert lib.zf_gap_eval_poisson(P, P, w, 3, 2, 0.0, 0.1, 0.0, P, P, 10) == -2 and b"scale > 0" in lib.zf_last_error()
-    # the loss codes of the generic weighted entries are the three they were built for: the Poisson code and every unknown one
-    for bad_loss in (-1, _lib.ZF_LOSS_POISSON, 4, 7):
-        assert lib.zf_wloss_eval(P, P, P, 3, 2, 0.5, bad_loss, 1.0, P, C.byref(f), None) == -2 and b"ZF_LOSS_" in lib.zf_last_error()
-        assert lib.zf_spmat_wloss_eval(P, P, P, 0.5, bad_loss, 1.0, P, C.byref(f), None) == -2 and b"ZF_LOSS_" in lib.zf_last_error()
-        assert lib.zf_gap_eval_weighted(P, P, P, 3, 2, 0.5, 0.1, 0.0, bad_loss, 1.0, P, P, 10) == -2 and b"ZF_LOSS_" in lib.zf_last_error()
-        assert lib.zf_spmat_gap_eval_weighted(P, P, P, 0.5, 0.1, 0.0, bad_loss, 1.0, P, P, 10) == -2 and b"ZF_LOSS_" in lib.zf_last_error()
+            assert E.gap(D(l2=bad), P, P, 10) == -2 and b"l2" in lib.zf_last_error()
+            assert E.gap(S(l2=bad), P, P, 10) == -2 and b"l2" in lib.zf_last_error()
+        assert E.gap(D(lam=-0.1), P, P, 10) == -2 and b"lam >= 0" in lib.zf_last_error()
+        assert E.gap(D(scale=0.0), P, P, 10) == -2 and b"scale > 0" in lib.zf_last_error()
+    # every unknown loss code is refused, with weights too (the message names the four codes)
+    for bad_loss in (-1, 4, 7):
+        for d in (E.dense(P, w=P, loss=bad_loss, delta=1.0), E.sparse(P, w=P, loss=bad_loss, delta=1.0)):
+            assert E.point(d, P, C.byref(f)) == -2 and b"ZF_LOSS_POISSON" in lib.zf_last_error()
+            assert E.gap(d, P, P, 10) == -2 and b"ZF_LOSS_POISSON" in lib.zf_last_error()
     assert (out == -7.0).all() and f.value == -7.0
 
 
@@ -138,9 +136,9 @@ def test_the_classes_are_least_squares_kinds_with_poisson_in_the_descriptor(cls)
     sib = _standin(base)
     sib.shard = "columns"
     assert "poisson" not in sib._descriptor()[0], "a least-squares problem hands the engine what it handed it before"
-    assert p.has_duality_gap and p._gap_logistic == 0
-    assert cls._eval_name == ("zf_poisson_eval" if cls.kind == 2 else "zf_spmat_poisson_eval")
-    assert cls._ENTRY["gap_poisson"] == ("zf_gap_eval_poisson" if cls.kind == 2 else "zf_spmat_gap_eval_poisson")
+    d = p._eval_desc()
+    assert p.has_duality_gap and (d.loss, d.delta, d.w, d.p) == (_lib.ZF_LOSS_POISSON, 0.0, None, None)
+    assert (bool(d.A), bool(d.spmat)) == (cls.kind == 2, cls.kind == 4) and not d.A32
 
 
 @pytest.mark.parametrize("cls", POISSON)

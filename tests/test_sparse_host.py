@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import scipy.sparse as sp
 
+import evaldesc as E
 from conftest import ROOT
 from zfista_amd import _lib, sparse
 
@@ -199,12 +200,12 @@ def test_plan_summation_order_reproduces_the_row_sums():
 def test_abi_additions():
     src = open(os.path.join(ROOT, "include", "zfista_hip.h")).read()
     assert re.search(r"#define\s+ZF_PROBLEM_SPARSE_LS_L1\s+4\b", src) and _lib.ZF_PROBLEM_SPARSE_LS_L1 == 4
-    assert re.search(r"#define\s+ZF_ABI_VERSION\s+6\b", src)
-    for name in ("zf_spmat_create", "zf_spmat_destroy", "zf_spmat_eval", "zf_solver_create_sparse"):
+    assert re.search(r"#define\s+ZF_ABI_VERSION\s+7\b", src)
+    for name in ("zf_spmat_create", "zf_spmat_destroy", "zf_margins_eval", "zf_solver_create_sparse"):
         assert name in _lib.SIGNATURES and re.search(r"\b" + name + r"\s*\(", src), name
     assert C.sizeof(_lib.SpmvPlan) == 56 and C.sizeof(_lib.ProblemDesc) == 128 and C.sizeof(_lib.Options) == 64
     lib = _lib.load()
-    assert lib.zf_abi_version() == 6 and lib.zf_sizeof_control() == 424
+    assert lib.zf_abi_version() == 7 and lib.zf_sizeof_control() == 424
     # size and null checks come before anything is dereferenced or any device is touched
     h = C.c_void_p()
     plan = _lib.SpmvPlan(lanes=4, threshold=4096)
@@ -218,7 +219,7 @@ def test_abi_additions():
     assert h.value is None
     assert lib.zf_spmat_destroy(None) == 0
     fval = C.c_double(0.0)
-    assert lib.zf_spmat_eval(None, P, 0.5, P, C.byref(fval), None) == -2 and b"zf_spmat_eval" in lib.zf_last_error()
+    assert E.point(E.sparse(None), P, C.byref(fval)) == -2 and b"zf_margins_eval" in lib.zf_last_error()
     d, o, s = _lib.ProblemDesc(kind=4, world=1, n=2, m_rows=3), _lib.Options(lr=1.0, decay_rate=0.5, max_iter=1), C.c_void_p()
     assert lib.zf_solver_create_sparse(C.byref(s), C.byref(d), None, C.byref(o), None) == -2
     d.kind = 2

@@ -1,5 +1,5 @@
-"""CPU: the interface of the sparse multi-response classes without a GPU - header, ctypes table and the built library (additive:
-ABI 6 and the struct sizes as they were, no problem kind), the argument checks of the new entry points before any device is
+"""CPU: the interface of the sparse multi-response classes without a GPU - header, ctypes table and the built library (the
+struct sizes as they were, no problem kind), the argument checks of the new entry points before any device is
 touched, the ValueErrors of the host classes (each before anything is uploaded), shape broadcasting, the descriptor, the siblings."""
 import ctypes as C
 import inspect
@@ -10,11 +10,12 @@ import numpy as np
 import pytest
 import scipy.sparse as sp
 
+import evaldesc as E
 from conftest import ROOT
 from zfista_amd import _lib, path, problems, screening
 from zfista_amd.proximal_gradient import minimize_proximal_gradient
 
-NEW = ("zf_solver_create_sparse_responses", "zf_spmat_mr_eval", "zf_spmat_mr_gap_eval", "zf_spmat_mr_apply")
+NEW = ("zf_solver_create_sparse_responses", "zf_margins_eval", "zf_margins_gap", "zf_spmat_mr_apply")
 MR = [problems.SparseMultiResponseLeastSquaresL1, problems.SparseMultiResponseLogisticL1]
 
 
@@ -26,12 +27,9 @@ def test_header_ctypes_table_and_library_hold_the_new_entry_points_and_nothing_e
         assert re.search(r"\bint\s+" + name + r"\s*\(", src), name
         assert name in _lib.SIGNATURES and hasattr(lib, name)
     assert sorted(_lib.SIGNATURES) == sorted(set(re.findall(r"\b(zf_[A-Za-z0-9_]+)\s*\(", src))), "header = ctypes table"
-    assert lib.zf_abi_version() == 6 and lib.zf_sizeof_control() == 424 == C.sizeof(_lib.Control)
+    assert lib.zf_abi_version() == 7 and lib.zf_sizeof_control() == 424 == C.sizeof(_lib.Control)
     assert C.sizeof(_lib.ProblemDesc) == 128 and C.sizeof(_lib.Options) == 64, "additive exports only: no struct field"
     assert max(v for k, v in vars(_lib).items() if k.startswith("ZF_PROBLEM_")) == 6, "no new problem kind"
-    # zf_mr_eval's / zf_mr_gap_eval's argument lists with the handle for A_dev, m_rows, n
-    assert len(_lib.SIGNATURES["zf_spmat_mr_eval"][1]) == len(_lib.SIGNATURES["zf_mr_eval"][1]) - 2
-    assert len(_lib.SIGNATURES["zf_spmat_mr_gap_eval"][1]) == len(_lib.SIGNATURES["zf_mr_gap_eval"][1]) - 2
     assert len(_lib.SIGNATURES["zf_solver_create_sparse_responses"][1]) == len(_lib.SIGNATURES["zf_solver_create_sparse"][1]) + 1
     mk = open(os.path.join(ROOT, "zfista_amd", "csrc", "Makefile")).read()
     assert "zf_spmm.hip" in mk and "zf_kernels_spmm.h" in mk, "a translation unit of its own, a header the objects depend on"
@@ -48,22 +46,23 @@ def test_new_entry_points_refuse_bad_arguments_before_touching_a_device():
     assert b"zf_solver_create_sparse_responses" in lib.zf_last_error()
     for bad in (1, 0, -3, 17):   # (K is checked before the handle is read: P is no handle)
         assert lib.zf_solver_create_sparse_responses(C.byref(h), C.byref(d), P, bad, C.byref(o), None) == -2 and b"2 .. 16" in lib.zf_last_error()
-        assert lib.zf_spmat_mr_eval(P, P, None, bad, 0.5, 0, P, C.byref(f), None) == -2 and b"2 .. 16" in lib.zf_last_error()
-        assert lib.zf_spmat_mr_gap_eval(P, P, None, None, bad, 0.5, 0.1, 0.0, 0, P, P, 10) == -2 and b"2 .. 16" in lib.zf_last_error()
+    for bad in (0, -3, 17):   # (K = 1 is the plain problem; K is checked before the handle is read)
+        assert E.point(E.sparse(P, K=bad), P, C.byref(f)) == -2 and b"K must be 1 .. 16" in lib.zf_last_error()
+        assert E.gap(E.sparse(P, K=bad), P, P, 10) == -2 and b"K must be 1 .. 16" in lib.zf_last_error()
     d.kind = _lib.ZF_PROBLEM_LEAST_SQUARES_L1
     assert lib.zf_solver_create_sparse_responses(C.byref(h), C.byref(d), P, 2, C.byref(o), None) == -2
     assert b"ZF_PROBLEM_SPARSE_LS_L1 or ZF_PROBLEM_SPARSE_LOGISTIC_L1" in lib.zf_last_error()
     for bad in (2, 3, -1, 7):   # Huber, Poisson, unknown
-        assert lib.zf_spmat_mr_eval(P, P, None, 2, 0.5, bad, P, C.byref(f), None) == -2 and b"ZF_LOSS_SQUARE or ZF_LOSS_LOGISTIC" in lib.zf_last_error()
-        assert lib.zf_spmat_mr_gap_eval(P, P, None, None, 2, 0.5, 0.1, 0.0, bad, P, P, 10) == -2
-    assert lib.zf_spmat_mr_eval(None, P, None, 2, 0.5, 0, P, C.byref(f), None) == -2 and b"zf_spmat_mr_eval" in lib.zf_last_error()
-    assert lib.zf_spmat_mr_eval(P, None, None, 2, 0.5, 0, P, C.byref(f), None) == -2
-    assert lib.zf_spmat_mr_eval(P, P, None, 2, 0.5, 0, None, C.byref(f), None) == -2
-    assert lib.zf_spmat_mr_gap_eval(None, P, None, None, 2, 0.5, 0.1, 0.0, 0, P, P, 10) == -2 and b"zf_spmat_mr_gap_eval" in lib.zf_last_error()
-    assert lib.zf_spmat_mr_gap_eval(P, P, None, None, 2, 0.5, 0.1, 0.0, 0, P, P, 7) == -2 and b"fewer than 8" in lib.zf_last_error()
-    assert lib.zf_spmat_mr_gap_eval(P, P, None, None, 2, 0.0, 0.1, 0.0, 0, P, P, 10) == -2 and b"scale > 0" in lib.zf_last_error()
+        assert E.point(E.sparse(P, K=2, loss=bad, delta=1.0), P, C.byref(f)) == -2 and b"ZF_LOSS_SQUARE or ZF_LOSS_LOGISTIC" in lib.zf_last_error()
+        assert E.gap(E.sparse(P, K=2, loss=bad, delta=1.0), P, P, 10) == -2
+    assert E.point(E.sparse(None, K=2), P, C.byref(f)) == -2 and b"zf_margins_eval" in lib.zf_last_error()
+    assert E.point(E.sparse(P, K=2, b=None), P, C.byref(f)) == -2
+    assert E.point(E.sparse(P, K=2), None, C.byref(f)) == -2
+    assert E.gap(E.sparse(None, K=2), P, P, 10) == -2 and b"zf_margins_gap" in lib.zf_last_error()
+    assert E.gap(E.sparse(P, K=2), P, P, 7) == -2 and b"fewer than 8" in lib.zf_last_error()
+    assert E.gap(E.sparse(P, K=2, scale=0.0), P, P, 10) == -2 and b"scale > 0" in lib.zf_last_error()
     for bad in (-1e-9, float("inf"), float("nan")):
-        assert lib.zf_spmat_mr_gap_eval(P, P, None, None, 2, 0.5, 0.1, bad, 0, P, P, 10) == -2 and b"l2" in lib.zf_last_error()
+        assert E.gap(E.sparse(P, K=2, l2=bad), P, P, 10) == -2 and b"l2" in lib.zf_last_error()
     for bad in (0, -1, 17):
         assert lib.zf_spmat_mr_apply(P, 0, bad, 1.0, P, P) == -2 and b"1 .. 16" in lib.zf_last_error()
     assert lib.zf_spmat_mr_apply(None, 0, 2, 1.0, P, P) == -2 and lib.zf_spmat_mr_apply(P, 0, 2, 1.0, None, P) == -2
@@ -143,8 +142,6 @@ def test_the_descriptor_carries_the_handle_the_responses_and_no_new_kind(cls):
     base = problems.SparseLogisticL1 if cls is problems.SparseMultiResponseLogisticL1 else problems.SparseLeastSquaresL1
     assert cls.kind == base.kind and cls._loss == base._loss and issubclass(cls, problems._SparseMarginsL1)
     assert issubclass(cls, problems._MultiResponseMixin) and not issubclass(cls, problems._DenseMarginsL1)
-    assert cls._MR_ENTRY == ("zf_spmat_mr_eval", "zf_spmat_mr_gap_eval")
-    assert problems.MultiResponseLeastSquaresL1._MR_ENTRY == ("zf_mr_eval", "zf_mr_gap_eval")
     p = _standin(cls)
     fields, keep = p._descriptor()
     assert fields["responses"] == 3 and fields["m_rows"] == 15 and fields["n"] == 21 and fields["kind"] == cls.kind
@@ -155,7 +152,8 @@ def test_the_descriptor_carries_the_handle_the_responses_and_no_new_kind(cls):
     q = p.with_lam(0.2)
     assert type(q) is cls and q._spmat is p._spmat and q.b is p.b and q.n_responses == 3 and p.lam == 0.3
     assert problems.match_native(*q.callbacks()) is q
-    assert len(p._lead("w")) == 3 and p._lead("w")[0] is p._spmat.value and p._lead("w")[2] == "w", "handle, b, weights"
+    e = p._eval_desc()
+    assert (e.spmat, e.A, e.A32, e.b, e.w, e.p, e.K, e.loss) == (8192, None, None, 4096, None, None, 3, cls._loss), "the handle, b, K; no weights"
     assert p.coef(np.arange(21.0)).shape == (7, 3) and p.coef(np.arange(21.0))[2, 1] == 7.0
     assert p._flat(np.zeros((7, 3))).shape == (21,) and p._flat(np.zeros(21)).shape == (21,)
     assert p.has_duality_gap and p._gap_refusal() is None

@@ -1,4 +1,4 @@
-"""CPU: the interface of per-row sample weights without a GPU - header and ctypes table (additive: ABI 6 and the struct sizes as
+"""CPU: the interface of per-row sample weights without a GPU - header and ctypes table (the struct sizes as
 they were), the argument checks of the new entry points before any device is touched, the ValueErrors of the host classes, the
 siblings, the fold numbers of l1_cv and its refusals."""
 import ctypes as C
@@ -9,12 +9,13 @@ import re
 import numpy as np
 import pytest
 
+import evaldesc as E
 import weight_cases as W
 from conftest import ROOT
 from zfista_amd import _lib, path, problems, screening
 from zfista_amd.proximal_gradient import minimize_proximal_gradient
 
-NEW = ("zf_solver_set_row_weights", "zf_wloss_eval", "zf_spmat_wloss_eval", "zf_gap_eval_weighted", "zf_spmat_gap_eval_weighted")
+NEW = ("zf_solver_set_row_weights", "zf_margins_eval", "zf_margins_gap")
 SIX = [problems.LeastSquaresL1, problems.SparseLeastSquaresL1, problems.LogisticL1, problems.SparseLogisticL1, problems.HuberL1,
        problems.SparseHuberL1]
 
@@ -27,16 +28,12 @@ def test_header_and_ctypes_table_declare_the_new_entry_points_and_nothing_else_m
         assert re.search(r"\bint\s+" + name + r"\s*\(", src), name
         assert name in _lib.SIGNATURES and hasattr(lib, name)
     assert sorted(_lib.SIGNATURES) == sorted(set(re.findall(r"\b(zf_[A-Za-z0-9_]+)\s*\(", src))), "header = ctypes table"
-    assert lib.zf_abi_version() == 6 and lib.zf_sizeof_control() == 424 == C.sizeof(_lib.Control)
+    assert lib.zf_abi_version() == 7 and lib.zf_sizeof_control() == 424 == C.sizeof(_lib.Control)
     assert C.sizeof(_lib.ProblemDesc) == 128 and C.sizeof(_lib.Options) == 64, "additive exports only: no struct field"
     assert re.search(r"enum\s*\{\s*ZF_LOSS_SQUARE\s*=\s*0,\s*ZF_LOSS_LOGISTIC\s*=\s*1,\s*ZF_LOSS_HUBER\s*=\s*2\s*\}", src)
     assert (_lib.ZF_LOSS_SQUARE, _lib.ZF_LOSS_LOGISTIC, _lib.ZF_LOSS_HUBER) == (0, 1, 2) == tuple(W.LOSS_CODE[k] for k in ("square", "logistic", "huber"))
     assert "row_weights" not in [f[0] for f in _lib.ProblemDesc._fields_]
-    # the Huber entry points' signatures plus w and loss
-    assert len(_lib.SIGNATURES["zf_wloss_eval"][1]) == len(_lib.SIGNATURES["zf_huber_eval"][1]) + 2
-    assert len(_lib.SIGNATURES["zf_spmat_wloss_eval"][1]) == len(_lib.SIGNATURES["zf_spmat_huber_eval"][1]) + 2
-    assert len(_lib.SIGNATURES["zf_gap_eval_weighted"][1]) == len(_lib.SIGNATURES["zf_gap_eval_huber"][1]) + 2
-    assert len(_lib.SIGNATURES["zf_spmat_gap_eval_weighted"][1]) == len(_lib.SIGNATURES["zf_spmat_gap_eval_huber"][1]) + 2
+    assert {"w", "loss"} <= {f[0] for f in _lib.EvalDesc._fields_}, "w and loss are fields of the evaluation descriptor"
 
 
 def test_new_entry_points_refuse_bad_arguments_before_touching_a_device():
@@ -45,44 +42,40 @@ def test_new_entry_points_refuse_bad_arguments_before_touching_a_device():
     P = C.c_void_p(_lib.ptr(out))
     f = C.c_double(-7.0)
     assert lib.zf_solver_set_row_weights(None, P) == -2 and b"zf_solver_set_row_weights" in lib.zf_last_error()
-    # f / grad: a null pointer in every place, sizes, the loss, delta
-    for k in (0, 1, 2, 8, 9):
-        args = [P, P, P, 3, 2, 0.5, 0, 0.0, P, C.byref(f), None]
-        args[k] = None
-        assert lib.zf_wloss_eval(*args) == -2 and b"zf_wloss_eval" in lib.zf_last_error(), k
-    assert lib.zf_wloss_eval(P, P, P, 0, 2, 0.5, 0, 0.0, P, C.byref(f), None) == -2
-    assert lib.zf_wloss_eval(P, P, P, 3, 0, 0.5, 0, 0.0, P, C.byref(f), None) == -2
-    for k in (0, 1, 2, 6, 7):
-        args = [P, P, P, 0.5, 0, 0.0, P, C.byref(f), None]
-        args[k] = None
-        assert lib.zf_spmat_wloss_eval(*args) == -2 and b"zf_spmat_wloss_eval" in lib.zf_last_error(), k
-    for bad_loss in (-1, 3, 7):
-        assert lib.zf_wloss_eval(P, P, P, 3, 2, 0.5, bad_loss, 1.0, P, C.byref(f), None) == -2 and b"ZF_LOSS_" in lib.zf_last_error()
-        assert lib.zf_spmat_wloss_eval(P, P, P, 0.5, bad_loss, 1.0, P, C.byref(f), None) == -2 and b"ZF_LOSS_" in lib.zf_last_error()
-        assert lib.zf_gap_eval_weighted(P, P, P, 3, 2, 0.5, 0.1, 0.0, bad_loss, 1.0, P, P, 10) == -2 and b"ZF_LOSS_" in lib.zf_last_error()
-        assert lib.zf_spmat_gap_eval_weighted(P, P, P, 0.5, 0.1, 0.0, bad_loss, 1.0, P, P, 10) == -2 and b"ZF_LOSS_" in lib.zf_last_error()
+    # f / grad: a null pointer in every place (but w: NULL weights are the unweighted problem), sizes, the loss, delta
+    for field in ("A", "b"):
+        assert E.point(E.dense(P, w=P, **{field: None}), P, C.byref(f)) == -2 and b"zf_margins_eval" in lib.zf_last_error(), field
+    for field in ("spmat", "b"):
+        assert E.point(E.sparse(P, w=P, **{field: None}), P, C.byref(f)) == -2 and b"zf_margins_eval" in lib.zf_last_error(), field
+    for d in (E.dense(P, w=P), E.sparse(P, w=P)):
+        assert E.point(d, None, C.byref(f)) == -2 and b"zf_margins_eval" in lib.zf_last_error()
+        assert E.point(d, P, None) == -2 and b"zf_margins_eval" in lib.zf_last_error()
+    assert E.point(E.dense(P, w=P, m_rows=0), P, C.byref(f)) == -2
+    assert E.point(E.dense(P, w=P, n=0), P, C.byref(f)) == -2
+    for bad_loss in (-1, 4, 7):
+        for d in (E.dense(P, w=P, loss=bad_loss, delta=1.0), E.sparse(P, w=P, loss=bad_loss, delta=1.0)):
+            assert E.point(d, P, C.byref(f)) == -2 and b"ZF_LOSS_" in lib.zf_last_error()
+            assert E.gap(d, P, P, 10) == -2 and b"ZF_LOSS_" in lib.zf_last_error()
     for bad in (0.0, -1.0, float("inf"), float("-inf"), float("nan")):   # delta: checked for Huber's loss only
-        assert lib.zf_wloss_eval(P, P, P, 3, 2, 0.5, 2, bad, P, C.byref(f), None) == -2 and b"delta" in lib.zf_last_error()
-        assert lib.zf_spmat_wloss_eval(P, P, P, 0.5, 2, bad, P, C.byref(f), None) == -2 and b"delta" in lib.zf_last_error()
-        assert lib.zf_gap_eval_weighted(P, P, P, 3, 2, 0.5, 0.1, 0.0, 2, bad, P, P, 10) == -2 and b"delta" in lib.zf_last_error()
-        assert lib.zf_spmat_gap_eval_weighted(P, P, P, 0.5, 0.1, 0.0, 2, bad, P, P, 10) == -2 and b"delta" in lib.zf_last_error()
+        for d in (E.dense(P, w=P, loss=2, delta=bad), E.sparse(P, w=P, loss=2, delta=bad)):
+            assert E.point(d, P, C.byref(f)) == -2 and b"delta" in lib.zf_last_error()
+            assert E.gap(d, P, P, 10) == -2 and b"delta" in lib.zf_last_error()
+            assert E.point(E.dense(P, w=P, loss=0, delta=bad, m_rows=0), P, C.byref(f)) == -2 and b"delta" not in lib.zf_last_error()
     # the certificate: null pointers, short buffers, scale, lam, l2
-    for k in (0, 1, 2, 10, 11):
-        args = [P, P, P, 3, 2, 0.5, 0.1, 0.0, 0, 0.0, P, P, 10]
-        args[k] = None
-        assert lib.zf_gap_eval_weighted(*args) == -2 and b"zf_gap_eval_weighted" in lib.zf_last_error(), k
-    for k in (0, 1, 2, 8, 9):
-        args = [P, P, P, 0.5, 0.1, 0.0, 0, 0.0, P, P, 10]
-        args[k] = None
-        assert lib.zf_spmat_gap_eval_weighted(*args) == -2 and b"zf_spmat_gap_eval_weighted" in lib.zf_last_error(), k
-    for short in (0, 3, 7):
-        assert lib.zf_gap_eval_weighted(P, P, P, 3, 2, 0.5, 0.1, 0.0, 0, 0.0, P, P, short) == -2 and b"fewer than 8" in lib.zf_last_error()
-        assert lib.zf_spmat_gap_eval_weighted(P, P, P, 0.5, 0.1, 0.0, 1, 0.0, P, P, short) == -2 and b"fewer than 8" in lib.zf_last_error()
+    for field in ("A", "b"):
+        assert E.gap(E.dense(P, w=P, **{field: None}), P, P, 10) == -2 and b"zf_margins_gap" in lib.zf_last_error(), field
+    for field in ("spmat", "b"):
+        assert E.gap(E.sparse(P, w=P, **{field: None}), P, P, 10) == -2 and b"zf_margins_gap" in lib.zf_last_error(), field
+    for d in (E.dense(P, w=P), E.sparse(P, w=P, loss=1)):
+        assert E.gap(d, None, P, 10) == -2 and b"zf_margins_gap" in lib.zf_last_error()
+        assert E.gap(d, P, None, 10) == -2 and b"zf_margins_gap" in lib.zf_last_error()
+        for short in (0, 3, 7):
+            assert E.gap(d, P, P, short) == -2 and b"fewer than 8" in lib.zf_last_error()
     for bad in (-1e-9, float("inf"), float("nan")):
-        assert lib.zf_gap_eval_weighted(P, P, P, 3, 2, 0.5, 0.1, bad, 0, 0.0, P, P, 10) == -2 and b"l2" in lib.zf_last_error()
-        assert lib.zf_spmat_gap_eval_weighted(P, P, P, 0.5, 0.1, bad, 0, 0.0, P, P, 10) == -2 and b"l2" in lib.zf_last_error()
-    assert lib.zf_gap_eval_weighted(P, P, P, 3, 2, 0.5, -0.1, 0.0, 0, 0.0, P, P, 10) == -2 and b"lam >= 0" in lib.zf_last_error()
-    assert lib.zf_gap_eval_weighted(P, P, P, 3, 2, 0.0, 0.1, 0.0, 0, 0.0, P, P, 10) == -2 and b"scale > 0" in lib.zf_last_error()
+        assert E.gap(E.dense(P, w=P, l2=bad), P, P, 10) == -2 and b"l2" in lib.zf_last_error()
+        assert E.gap(E.sparse(P, w=P, l2=bad), P, P, 10) == -2 and b"l2" in lib.zf_last_error()
+    assert E.gap(E.dense(P, w=P, lam=-0.1), P, P, 10) == -2 and b"lam >= 0" in lib.zf_last_error()
+    assert E.gap(E.dense(P, w=P, scale=0.0), P, P, 10) == -2 and b"scale > 0" in lib.zf_last_error()
     assert (out == -7.0).all() and f.value == -7.0, "nothing was written"
 
 

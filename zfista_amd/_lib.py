@@ -22,7 +22,7 @@ ZF_RUNNING, ZF_CONVERGED, ZF_MAXITER, ZF_BACKTRACK_FAILED = 0, 1, 2, 3
 ZF_PROBLEM_DIAG_QUAD_L1, ZF_PROBLEM_LEAST_SQUARES_L1, ZF_PROBLEM_BLUR_HAAR_L1 = 1, 2, 3
 ZF_PROBLEM_SPARSE_LS_L1 = 4
 ZF_PROBLEM_LOGISTIC_L1, ZF_PROBLEM_SPARSE_LOGISTIC_L1 = 5, 6
-ZF_LOSS_SQUARE, ZF_LOSS_LOGISTIC, ZF_LOSS_HUBER, ZF_LOSS_POISSON = 0, 1, 2, 3   # the loss of the weighted entry points (csrc/zf_kernels_wloss.h)
+ZF_LOSS_SQUARE, ZF_LOSS_LOGISTIC, ZF_LOSS_HUBER, ZF_LOSS_POISSON = 0, 1, 2, 3   # zf_eval_desc.loss (csrc/zf_loss_dispatch.h)
 ZF_MO_GENERIC, ZF_MO_JOS1, ZF_MO_FDS = 0, 1, 2
 ZF_PACK_LEN, ZF_TRACE_COLS, ZF_RING = 8, 8, 1024
 ZF_MAX_SUB_ITERS = 16
@@ -96,6 +96,18 @@ class SpmvPlan(C.Structure):
     _fields_ = [
         ("lanes", C.c_int32), ("reserved", C.c_int32), ("threshold", C.c_int64), ("nsplit", C.c_int64), ("nseg", C.c_int64),
         ("split_row", C.c_void_p), ("split_first", C.c_void_p), ("seg_start", C.c_void_p),
+    ]
+
+
+class EvalDesc(C.Structure):
+    """Mirror of ``zf_eval_desc``: the storage of A, the loss and the options of one margins problem, as zf_margins_eval /
+    zf_margins_gap / zf_margins_screen take it.  Exactly one of A / A32 / spmat is set; w and p may be NULL."""
+
+    _fields_ = [
+        ("A", C.c_void_p), ("A32", C.c_void_p), ("spmat", C.c_void_p), ("m_rows", C.c_int64), ("n", C.c_int64),
+        ("b", C.c_void_p), ("w", C.c_void_p), ("p", C.c_void_p),
+        ("scale", C.c_double), ("lam", C.c_double), ("l2", C.c_double), ("delta", C.c_double),
+        ("loss", C.c_int32), ("K", C.c_int32),
     ]
 
 
@@ -209,68 +221,35 @@ SIGNATURES = {
     "zf_mo_prox_host": (C.c_int, [_P, _P, _P, _P]),
     "zf_mo_post_terms": (C.c_int, [_P, C.c_double, _P, _P, _P]),
     "zf_op_eval": (C.c_int, [_P, C.c_int32, _P, C.c_int64, C.c_int64, C.c_double, _P, C.POINTER(C.c_double), _P]),
-    "zf_ls_eval": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_double, _P, C.POINTER(C.c_double), _P]),
-    "zf_logistic_eval": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_double, _P, C.POINTER(C.c_double), _P]),
     "zf_ls_remainder_eval": (C.c_int, [_P, _P, _P, C.c_int64, C.c_double, C.c_int32, C.c_double, C.c_int32, C.POINTER(C.c_double)]),
-    "zf_spmat_logistic_eval": (C.c_int, [_P, _P, C.c_double, _P, C.POINTER(C.c_double), _P]),
     "zf_spmat_create": (C.c_int, [C.POINTER(_P), C.c_int64, C.c_int64, C.c_int64, _P, _P, _P, C.POINTER(SpmvPlan),
                                   _P, _P, _P, C.POINTER(SpmvPlan), C.c_int64]),
     "zf_spmat_destroy": (C.c_int, [_P]),
-    "zf_spmat_eval": (C.c_int, [_P, _P, C.c_double, _P, C.POINTER(C.c_double), _P]),
-    "zf_gap_eval": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_int32, _P, _P, C.c_int64]),
-    "zf_spmat_gap_eval": (C.c_int, [_P, _P, C.c_double, C.c_double, C.c_int32, _P, _P, C.c_int64]),
     "zf_solver_duality_gap": (C.c_int, [_P, _P, C.c_int64]),
     "zf_solver_create_sparse": (C.c_int, [C.POINTER(_P), C.POINTER(ProblemDesc), _P, C.POINTER(Options), _P]),
     "zf_spmat_col_norms": (C.c_int, [_P, _P, _P]),
     "zf_dense_col_norms": (C.c_int, [_P, C.c_int64, C.c_int64, _P, _P]),
-    "zf_gap_screen_eval": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_int32, _P, _P, C.c_int64, _P, _P, _P, _P]),
-    "zf_spmat_gap_screen_eval": (C.c_int, [_P, _P, C.c_double, C.c_double, C.c_int32, _P, _P, C.c_int64, _P, _P, C.c_int64, C.c_int64,
-                                           _P, _P]),
     "zf_screen_scan": (C.c_int, [_P, C.c_int64, _P, C.POINTER(C.c_int64)]),
     "zf_spmat_restrict_count": (C.c_int, [_P, _P, _P, _P, _P, _P, C.POINTER(C.c_int64)]),
     "zf_spmat_restrict_fill": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int64, _P, _P, _P, _P, _P, _P]),
     "zf_dense_restrict": (C.c_int, [_P, C.c_int64, C.c_int64, _P, _P, C.c_int64, _P]),
     "zf_solver_set_l2": (C.c_int, [_P, C.c_double]),
-    "zf_gap_eval_enet": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_int32, _P, _P, C.c_int64]),
-    "zf_spmat_gap_eval_enet": (C.c_int, [_P, _P, C.c_double, C.c_double, C.c_double, C.c_int32, _P, _P, C.c_int64]),
     "zf_host_prox_enet_box": (C.c_int, [_P, _P, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int64]),
     "zf_host_enet_g": (C.c_int, [_P, C.c_int64, C.c_double, C.c_double, C.POINTER(C.c_double)]),
     "zf_solver_set_huber": (C.c_int, [_P, C.c_double]),
-    "zf_huber_eval": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_double, C.c_double, _P, C.POINTER(C.c_double), _P]),
-    "zf_spmat_huber_eval": (C.c_int, [_P, _P, C.c_double, C.c_double, _P, C.POINTER(C.c_double), _P]),
-    "zf_gap_eval_huber": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, _P, _P, C.c_int64]),
-    "zf_spmat_gap_eval_huber": (C.c_int, [_P, _P, C.c_double, C.c_double, C.c_double, C.c_double, _P, _P, C.c_int64]),
-    "zf_gap_screen_eval_huber": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_double, _P, _P, C.c_int64, _P, _P, _P, _P]),
-    "zf_spmat_gap_screen_eval_huber": (C.c_int, [_P, _P, C.c_double, C.c_double, C.c_double, _P, _P, C.c_int64, _P, _P, C.c_int64,
-                                                 C.c_int64, _P, _P]),
     "zf_solver_set_row_weights": (C.c_int, [_P, _P]),
-    "zf_wloss_eval": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_double, C.c_int32, C.c_double, _P, C.POINTER(C.c_double), _P]),
-    "zf_spmat_wloss_eval": (C.c_int, [_P, _P, _P, C.c_double, C.c_int32, C.c_double, _P, C.POINTER(C.c_double), _P]),
-    "zf_gap_eval_weighted": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_double, _P, _P,
-                                       C.c_int64]),
-    "zf_spmat_gap_eval_weighted": (C.c_int, [_P, _P, _P, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_double, _P, _P, C.c_int64]),
     "zf_solver_set_poisson": (C.c_int, [_P]),
-    "zf_poisson_eval": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_double, _P, C.POINTER(C.c_double), _P]),
-    "zf_spmat_poisson_eval": (C.c_int, [_P, _P, _P, C.c_double, _P, C.POINTER(C.c_double), _P]),
-    "zf_gap_eval_poisson": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_double, _P, _P, C.c_int64]),
-    "zf_spmat_gap_eval_poisson": (C.c_int, [_P, _P, _P, C.c_double, C.c_double, C.c_double, _P, _P, C.c_int64]),
     "zf_solver_set_penalty_factors": (C.c_int, [_P, _P]),
-    "zf_gap_eval_pf": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_int32, C.c_double, _P, _P, C.c_int64]),
-    "zf_spmat_gap_eval_pf": (C.c_int, [_P, _P, _P, _P, C.c_double, C.c_double, C.c_int32, C.c_double, _P, _P, C.c_int64]),
     "zf_host_prox_pf_box": (C.c_int, [_P, _P, _P, C.c_double, C.c_double, C.c_double, C.c_int64]),
     "zf_host_pf_g": (C.c_int, [_P, _P, C.c_int64, C.c_double, C.POINTER(C.c_double)]),
     "zf_solver_set_matrix_f32": (C.c_int, [_P, _P]),
-    "zf_f32_eval": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_double, C.c_int32, C.c_double, _P, C.POINTER(C.c_double), _P]),
-    "zf_f32_gap_eval": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_double, _P, _P,
-                                  C.c_int64]),
     "zf_solver_set_responses": (C.c_int, [_P, C.c_int32]),
-    "zf_mr_eval": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_int32, C.c_double, C.c_int32, _P, C.POINTER(C.c_double), _P]),
-    "zf_mr_gap_eval": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int64, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_int32, _P, _P,
-                                 C.c_int64]),
     "zf_solver_create_sparse_responses": (C.c_int, [C.POINTER(_P), C.POINTER(ProblemDesc), _P, C.c_int32, C.POINTER(Options), _P]),
-    "zf_spmat_mr_eval": (C.c_int, [_P, _P, _P, C.c_int32, C.c_double, C.c_int32, _P, C.POINTER(C.c_double), _P]),
-    "zf_spmat_mr_gap_eval": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_int32, _P, _P, C.c_int64]),
     "zf_spmat_mr_apply": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_double, _P, _P]),
+    "zf_sizeof_eval_desc": (C.c_int64, []),
+    "zf_margins_eval": (C.c_int, [C.POINTER(EvalDesc), C.c_int64, _P, C.POINTER(C.c_double), _P]),
+    "zf_margins_gap": (C.c_int, [C.POINTER(EvalDesc), C.c_int64, _P, _P, C.c_int64]),
+    "zf_margins_screen": (C.c_int, [C.POINTER(EvalDesc), C.c_int64, _P, _P, C.c_int64, _P, _P, C.c_int64, C.c_int64, _P, _P]),
 }
 
 _lib = None
@@ -312,6 +291,8 @@ def load():
         fn.argtypes = args
     if lib.zf_sizeof_control() != C.sizeof(Control):
         raise HipUnavailable("zf_control layout mismatch between library and Python mirror")
+    if lib.zf_sizeof_eval_desc() != C.sizeof(EvalDesc):
+        raise HipUnavailable("zf_eval_desc layout mismatch between library and Python mirror")
     _lib = lib
     return lib
 

@@ -2649,6 +2649,7 @@ extern "C" int zf_solver_trial_kernel_ms(zf_solver* s, double* avg_ms, int64_t* 
 extern "C" int zf_abi_version(void) { return ZF_ABI_VERSION; }
 extern "C" const char* zf_last_error(void) { return zf_errbuf; }
 extern "C" int64_t zf_sizeof_control(void) { return (int64_t)sizeof(zf_control); }
+extern "C" int64_t zf_sizeof_eval_desc(void) { return (int64_t)sizeof(zf_eval_desc); }
 
 extern "C" int zf_device_count(int* count) {
     ZF_REQUIRE(count, "zf_device_count: null argument");
@@ -2737,7 +2738,7 @@ extern "C" int zf_ls_remainder_eval(const double* s_plus_host, const double* s_k
 // ---------------------------------------------------------------------------
 struct zf_matview {
     const double* A;     // dense: m x n row-major (device), 16-byte aligned; NULL for CSR
-    int64_t m, n;        // (CSR: the handle's, filled in by zf_loss_args once the handle is known not to be NULL)
+    int64_t m, n;        // (CSR: the handle's)
     const zf_spmat* h;   // CSR: A and A^T with their plans; NULL for dense
     bool csr;
     const float* A32;    // dense, stored in fp32 (zf_kernels_gemv_f32.h): m x n row-major (device), 16-byte aligned - A is NULL then; NULL otherwise
@@ -2745,11 +2746,6 @@ struct zf_matview {
 };
 static int64_t zf_view_rows(const zf_matview& V) { return V.m * V.k; }   // length of a margins vector
 static int64_t zf_view_cols(const zf_matview& V) { return V.n * V.k; }   // length of a decision vector
-static zf_matview zf_dense_view(const double* A, int64_t m, int64_t n) { return zf_matview{A, m, n, nullptr, false, nullptr}; }
-static zf_matview zf_csr_view(const zf_spmat* h) { return zf_matview{nullptr, 0, 0, h, true, nullptr}; }
-static zf_matview zf_dense_view_f32(const float* A32, int64_t m, int64_t n) { return zf_matview{nullptr, m, n, nullptr, false, A32}; }
-static zf_matview zf_csr_view_mr(const zf_spmat* h, int k) { return zf_matview{nullptr, 0, 0, h, true, nullptr, k}; }
-static zf_matview zf_dense_view_mr(const double* A, int64_t m, int64_t n, int k) { return zf_matview{A, m, n, nullptr, false, nullptr, k}; }
 
 // what the sweeps write between their launches: the slab of the dense column sweep and its slices, or the segment sums of the
 // split rows of A / A^T (a call's own, or a solver's: the handle is shared with live solvers on other streams)
@@ -2830,20 +2826,38 @@ static void zf_launch_view_adjoint(const zf_matview& V, hipStream_t st, const do
     hipLaunchKernelGGL(zf_gemvT_combine_kernel, dim3(zf_grid_for(nk)), dim3(ZF_BLOCK), 0, st, nullptr, W.slab, g, factor, nk, W.slices);
 }
 
-// The checks every evaluation entry point shares (`who`: the entry's name).  First its pointers (`ok`) and its matrix ...
-static int zf_view_args(const char* who, const zf_matview& V, bool ok) {
-    if (V.csr && !(ok && V.h)) return zf_fail(ZF_ERR_ARG, "%s: null argument%s", who);
-    if (!V.csr && !(ok && (V.A || V.A32) && V.m >= 1 && V.n >= 1)) return zf_fail(ZF_ERR_ARG, "%s: bad argument%s", who);
+// The checks the three evaluation entries share (`who`: the entry's name; `io_ok`: its own host pointers), all before anything
+// touches a device or reads through the handle: the descriptor and its size, the matrix, the pointers, the loss, the responses.
+// Leaves the loss in *L.
+static int zf_desc_args(const char* who, const zf_eval_desc* d, int64_t desc_bytes, bool io_ok, zf_loss* L) {
+    if (!d || desc_bytes != (int64_t)sizeof(zf_eval_desc))
+        return zf_fail(ZF_ERR_ARG, "%s: null descriptor, or desc_bytes differs from zf_sizeof_eval_desc()%s", who);
+    if ((d->A != nullptr) + (d->A32 != nullptr) + (d->spmat != nullptr) != 1)
+        return zf_fail(ZF_ERR_ARG, "%s: exactly one of A, A32 and spmat must be set%s", who);
+    if (!(d->b && io_ok)) return zf_fail(ZF_ERR_ARG, "%s: null argument%s", who);
+    const bool csr = d->spmat != nullptr;
+    if (!csr && !(d->m_rows >= 1 && d->n >= 1)) return zf_fail(ZF_ERR_ARG, "%s: bad argument (m_rows and n must be >= 1)%s", who);
+    if (!csr && !zf_aligned16(d->A32 ? (const void*)d->A32 : (const void*)d->A)) return zf_fail(ZF_ERR_ARG, "%s: A must be 16-byte aligned%s", who);
+    if (!(d->K >= 1 && d->K <= ZF_MR_MAX_K)) return zf_fail(ZF_ERR_ARG, "%s: K must be 1 .. 16%s", who);
+    if (d->K > 1 && d->loss != ZF_LOSS_SQUARE && d->loss != ZF_LOSS_LOGISTIC)
+        return zf_fail(ZF_ERR_ARG, "%s: with K > 1 the loss must be ZF_LOSS_SQUARE or ZF_LOSS_LOGISTIC%s", who);
+    if (d->loss != ZF_LOSS_SQUARE && d->loss != ZF_LOSS_LOGISTIC && d->loss != ZF_LOSS_HUBER && d->loss != ZF_LOSS_POISSON)
+        return zf_fail(ZF_ERR_ARG, "%s: loss must be ZF_LOSS_SQUARE, ZF_LOSS_LOGISTIC, ZF_LOSS_HUBER or ZF_LOSS_POISSON%s", who);
+    if (d->loss == ZF_LOSS_HUBER && !(d->delta > 0.0 && d->delta <= DBL_MAX)) return zf_fail(ZF_ERR_ARG, "%s: delta must be finite and > 0%s", who);
+    if (d->K > 1 && d->A32) return zf_fail(ZF_ERR_ARG, "%s: not with K > 1 and a matrix stored in fp32 (the K-response sweeps read an fp64 A)%s", who);
+    *L = zf_loss{d->loss, d->loss == ZF_LOSS_HUBER ? d->delta : 0.0, d->w};
     return ZF_OK;
 }
-// ... then, behind zf_view_args, the loss code, Huber's delta and the alignment of a dense A; leaves the entry's loss in *L
-static int zf_loss_args(const char* who, zf_matview* V, int32_t kind, double delta, const double* w_dev, zf_loss* L) {
-    if (kind != ZF_LOSS_SQUARE && kind != ZF_LOSS_LOGISTIC && kind != ZF_LOSS_HUBER && kind != ZF_LOSS_POISSON)
-        return zf_fail(ZF_ERR_ARG, "%s: loss must be ZF_LOSS_SQUARE, ZF_LOSS_LOGISTIC, ZF_LOSS_HUBER or ZF_LOSS_POISSON%s", who);
-    if (kind == ZF_LOSS_HUBER && !(delta > 0.0 && delta <= DBL_MAX)) return zf_fail(ZF_ERR_ARG, "%s: delta must be finite and > 0%s", who);
-    if (!V->csr && !zf_aligned16(V->A32 ? (const void*)V->A32 : (const void*)V->A)) return zf_fail(ZF_ERR_ARG, "%s: A must be 16-byte aligned%s", who);
-    if (V->csr) V->m = V->h->m, V->n = V->h->n;
-    *L = zf_loss{kind, kind == ZF_LOSS_HUBER ? delta : 0.0, w_dev};
+// the matrix of a checked descriptor as the sweeps see it (a handle knows its own sizes)
+static zf_matview zf_view_of(const zf_eval_desc* d) {
+    if (d->spmat) return zf_matview{nullptr, d->spmat->m, d->spmat->n, d->spmat, true, nullptr, d->K};
+    return zf_matview{d->A, d->m_rows, d->n, nullptr, false, d->A32, d->K};
+}
+// ... and the two evaluations of the certificate add: the capacity of `out` and the three scalars of the penalty
+static int zf_gap_args(const char* who, const zf_eval_desc* d, int64_t count, int64_t need) {
+    if (count < need) return zf_fail(ZF_ERR_ARG, need == 8 ? "%s: the output buffer holds fewer than 8 doubles%s" : "%s: the output buffer holds fewer than 12 doubles%s", who);
+    if (!(d->scale > 0.0 && d->lam >= 0.0 && d->l2 >= 0.0 && d->l2 <= DBL_MAX))
+        return zf_fail(ZF_ERR_ARG, "%s: needs scale > 0, lam >= 0 and a finite l2 >= 0%s", who);
     return ZF_OK;
 }
 
@@ -2891,115 +2905,11 @@ static int zf_point_eval(const zf_matview& V, const double* b_dev, double scale,
     return rc;
 }
 
-// the point evaluation of one entry: the checks, then the launches.  kind / delta / w_dev: the entry's loss (w_dev NULL: unweighted)
-static int zf_point_entry(const char* who, zf_matview V, const double* b_dev, bool w_ok, const double* w_dev, double scale, int32_t kind,
-                          double delta, const double* x_host, double* f_out, double* grad_out_host) {
+// the one entry: any storage, any loss, weighted or not, 1 .. 16 responses (reads neither lam, l2 nor p of the descriptor)
+extern "C" int zf_margins_eval(const zf_eval_desc* d, int64_t desc_bytes, const double* x_host, double* f_out, double* grad_out_host) {
     zf_loss L;
-    int rc = zf_view_args(who, V, b_dev && w_ok && x_host && f_out);
-    if (rc == ZF_OK) rc = zf_loss_args(who, &V, kind, delta, w_dev, &L);
-    return rc ? rc : zf_point_eval(V, b_dev, scale, L, x_host, f_out, grad_out_host);
-}
-
-extern "C" int zf_ls_eval(const double* A_dev, const double* b_dev, int64_t m_rows, int64_t n, double scale,
-                          const double* x_host, double* f_out, double* grad_out_host) {
-    return zf_point_entry("zf_ls_eval", zf_dense_view(A_dev, m_rows, n), b_dev, true, nullptr, scale, ZF_LOSS_SQUARE, 0.0, x_host, f_out,
-                          grad_out_host);
-}
-
-// f = scale sum softplus(-b (A x)) and (grad_out_host != NULL) grad = scale A^T rho of ZF_PROBLEM_LOGISTIC_L1 for a host
-// vector: the callback bodies of zfista_amd.problems.LogisticL1, on the loss kernels the solver runs
-extern "C" int zf_logistic_eval(const double* A_dev, const double* b_dev, int64_t m_rows, int64_t n, double scale,
-                                const double* x_host, double* f_out, double* grad_out_host) {
-    return zf_point_entry("zf_logistic_eval", zf_dense_view(A_dev, m_rows, n), b_dev, true, nullptr, scale, ZF_LOSS_LOGISTIC, 0.0, x_host,
-                          f_out, grad_out_host);
-}
-
-// the same for a CSR matrix behind a handle (zf_spmat_create)
-extern "C" int zf_spmat_eval(const zf_spmat* h, const double* b_dev, double scale, const double* x_host, double* f_out,
-                             double* grad_out_host) {
-    return zf_point_entry("zf_spmat_eval", zf_csr_view(h), b_dev, true, nullptr, scale, ZF_LOSS_SQUARE, 0.0, x_host, f_out, grad_out_host);
-}
-
-// the logistic loss (ZF_PROBLEM_SPARSE_LOGISTIC_L1) over the same handle: zf_logistic_eval for a CSR matrix
-extern "C" int zf_spmat_logistic_eval(const zf_spmat* h, const double* b_dev, double scale, const double* x_host, double* f_out,
-                                      double* grad_out_host) {
-    return zf_point_entry("zf_spmat_logistic_eval", zf_csr_view(h), b_dev, true, nullptr, scale, ZF_LOSS_LOGISTIC, 0.0, x_host, f_out,
-                          grad_out_host);
-}
-
-// Huber's loss (zf_kernels_huber.h) on the same sweeps: f = scale sum H_delta(A x - b), grad = 2 scale A^T clip(A x - b)
-extern "C" int zf_huber_eval(const double* A_dev, const double* b_dev, int64_t m_rows, int64_t n, double scale, double delta,
-                             const double* x_host, double* f_out, double* grad_out_host) {
-    return zf_point_entry("zf_huber_eval", zf_dense_view(A_dev, m_rows, n), b_dev, true, nullptr, scale, ZF_LOSS_HUBER, delta, x_host, f_out,
-                          grad_out_host);
-}
-
-extern "C" int zf_spmat_huber_eval(const zf_spmat* h, const double* b_dev, double scale, double delta, const double* x_host, double* f_out,
-                                   double* grad_out_host) {
-    return zf_point_entry("zf_spmat_huber_eval", zf_csr_view(h), b_dev, true, nullptr, scale, ZF_LOSS_HUBER, delta, x_host, f_out,
-                          grad_out_host);
-}
-
-// the Poisson loss (zf_kernels_poisson.h) on the same sweeps: f = scale sum (exp(A x) - b o A x), grad = scale A^T (exp(A x) - b)
-// (w_dev: the row weights or NULL - the weighted form of this loss has no other entry)
-extern "C" int zf_poisson_eval(const double* A_dev, const double* b_dev, const double* w_dev, int64_t m_rows, int64_t n, double scale,
-                               const double* x_host, double* f_out, double* grad_out_host) {
-    return zf_point_entry("zf_poisson_eval", zf_dense_view(A_dev, m_rows, n), b_dev, true, w_dev, scale, ZF_LOSS_POISSON, 0.0, x_host, f_out,
-                          grad_out_host);
-}
-
-extern "C" int zf_spmat_poisson_eval(const zf_spmat* h, const double* b_dev, const double* w_dev, double scale, const double* x_host,
-                                     double* f_out, double* grad_out_host) {
-    return zf_point_entry("zf_spmat_poisson_eval", zf_csr_view(h), b_dev, true, w_dev, scale, ZF_LOSS_POISSON, 0.0, x_host, f_out,
-                          grad_out_host);
-}
-
-// the loss code of the four weighted entries below: the three losses they were built for.  The Poisson loss takes its weights through
-// its own entries, so its code is refused here as every unknown code is (zf_loss_args names the codes)
-static int32_t zf_wloss_code(int32_t loss) { return loss == ZF_LOSS_POISSON ? -1 : loss; }
-
-// per-row sample weights (zf_kernels_wloss.h) on the same sweeps: f = scale sum w phi, grad = gfac A^T (w o psi)
-extern "C" int zf_wloss_eval(const double* A_dev, const double* b_dev, const double* w_dev, int64_t m_rows, int64_t n, double scale,
-                             int32_t loss, double delta, const double* x_host, double* f_out, double* grad_out_host) {
-    return zf_point_entry("zf_wloss_eval", zf_dense_view(A_dev, m_rows, n), b_dev, w_dev != nullptr, w_dev, scale, zf_wloss_code(loss), delta, x_host, f_out,
-                          grad_out_host);
-}
-
-extern "C" int zf_spmat_wloss_eval(const zf_spmat* h, const double* b_dev, const double* w_dev, double scale, int32_t loss, double delta,
-                                   const double* x_host, double* f_out, double* grad_out_host) {
-    return zf_point_entry("zf_spmat_wloss_eval", zf_csr_view(h), b_dev, w_dev != nullptr, w_dev, scale, zf_wloss_code(loss), delta, x_host, f_out,
-                          grad_out_host);
-}
-
-// a dense matrix stored in fp32 (zf_kernels_gemv_f32.h) under any of the four losses, weighted or not: the rows kernels of the loss
-// dispatch on the fp32 sweeps.  (The unweighted squared loss goes through the residual kernels, as zf_ls_eval does.)
-extern "C" int zf_f32_eval(const float* A32_dev, const double* b_dev, const double* w_dev, int64_t m_rows, int64_t n, double scale,
-                           int32_t loss, double delta, const double* x_host, double* f_out, double* grad_out_host) {
-    return zf_point_entry("zf_f32_eval", zf_dense_view_f32(A32_dev, m_rows, n), b_dev, true, w_dev, scale, loss, delta, x_host, f_out,
-                          grad_out_host);
-}
-
-// K responses on one dense fp64 matrix (zf_kernels_mr.h), squared or logistic loss, weighted or not: A_dev is m_rows x n, b_dev /
-// w_dev hold m_rows K and x_host / grad_out_host n K doubles, response-interleaved.  The loss kernels see m_rows K rows.
-static int zf_mr_args(const char* who, int32_t K, int32_t loss) {
-    if (!(K >= 2 && K <= ZF_MR_MAX_K)) return zf_fail(ZF_ERR_ARG, "%s: K must be 2 .. 16%s", who);
-    if (loss != ZF_LOSS_SQUARE && loss != ZF_LOSS_LOGISTIC) return zf_fail(ZF_ERR_ARG, "%s: loss must be ZF_LOSS_SQUARE or ZF_LOSS_LOGISTIC%s", who);
-    return ZF_OK;
-}
-extern "C" int zf_mr_eval(const double* A_dev, const double* b_dev, const double* w_dev, int64_t m_rows, int64_t n, int32_t K, double scale,
-                          int32_t loss, const double* x_host, double* f_out, double* grad_out_host) {
-    const int rc = zf_mr_args("zf_mr_eval", K, loss);
-    if (rc) return rc;
-    return zf_point_entry("zf_mr_eval", zf_dense_view_mr(A_dev, m_rows, n, K), b_dev, true, w_dev, scale, loss, 0.0, x_host, f_out,
-                          grad_out_host);
-}
-
-// K responses on one CSR matrix behind a handle (zf_kernels_spmm.h): zf_mr_eval with the handle for A_dev, m_rows, n
-extern "C" int zf_spmat_mr_eval(const zf_spmat* h, const double* b_dev, const double* w_dev, int32_t K, double scale, int32_t loss,
-                                const double* x_host, double* f_out, double* grad_out_host) {
-    const int rc = zf_mr_args("zf_spmat_mr_eval", K, loss);
-    if (rc) return rc;
-    return zf_point_entry("zf_spmat_mr_eval", zf_csr_view_mr(h, K), b_dev, true, w_dev, scale, loss, 0.0, x_host, f_out, grad_out_host);
+    const int rc = zf_desc_args("zf_margins_eval", d, desc_bytes, x_host && f_out, &L);
+    return rc ? rc : zf_point_eval(zf_view_of(d), d->b, d->scale, L, x_host, f_out, grad_out_host);
 }
 
 // out = out_scale * A in (transpose == 0: in holds n K, out m K doubles) or out_scale * A^T in (in m K, out n K), host vectors,
@@ -3090,9 +3000,9 @@ static void zf_gap_ws_free(zf_gap_ws* ws) {
 
 // The gap at a host point x: z = A x, the rows pass of the loss, g = grad f(x) by the column sweep a solver of this shape runs
 // (dense: MFMA when n % 32 == 0 and ZF_GEMV_MFMA is not 0), the n-passes and the composition; l2 > 0: the elastic-net evaluation.
-// scr != NULL (the *_screen_eval entries): the screen of zf_kernels_screen.h over the call's g behind the same sequence - its four
+// scr != NULL (zf_margins_screen): the screen of zf_kernels_screen.h over the call's g behind the same sequence - its four
 // scalars follow the eight outputs; scr->cnt and scr->scal are allocated here
-// p_dev != NULL (the *_pf entries): penalty factors - g and the call's copy of x are scaled in place between step 2 and the tails
+// p_dev != NULL: penalty factors - g and the call's copy of x are scaled in place between step 2 and the tails
 static int zf_gap_eval_impl(const zf_matview& V, const double* b_dev, double scale, double lam, double l2, const zf_loss& L,
                             const double* x_host, double* out, int64_t out_count, const zf_screen_req* scr, const double* p_dev = nullptr) {
     const int64_t m = zf_view_rows(V), n = zf_view_cols(V);
@@ -3135,200 +3045,45 @@ static int zf_gap_eval_impl(const zf_matview& V, const double* b_dev, double sca
     return rc;
 }
 
-// The checks every gap entry shares, in front of those of zf_loss_args: the capacity of `out`, scale, lam and l2.  l2_arg: the entry
-// takes l2 (its message names it); the others pass l2 = 0.
-static int zf_gap_args(const char* who, zf_matview* V, bool ok, double scale, double lam, bool l2_arg, double l2, int64_t count, int32_t kind,
-                       double delta, const double* w_dev, zf_loss* L) {
-    const int rc = zf_view_args(who, *V, ok);
-    if (rc) return rc;
-    if (count < 8) return zf_fail(ZF_ERR_ARG, "%s: the output buffer holds fewer than 8 doubles%s", who);
-    if (!(scale > 0.0 && lam >= 0.0 && l2 >= 0.0 && l2 <= DBL_MAX))
-        return zf_fail(ZF_ERR_ARG, l2_arg ? "%s: needs scale > 0, lam >= 0 and a finite l2 >= 0%s" : "%s: needs scale > 0 and lam >= 0%s", who);
-    return zf_loss_args(who, V, kind, delta, w_dev, L);
-}
-
-// a gap entry without the screen; the elastic-net forms (l2_arg) run the l1 evaluation for l2 = 0 - its kernels, its eight values -
-// and write [8] = [9] = 0 when the buffer holds ten
-static int zf_gap_entry(const char* who, zf_matview V, const double* b_dev, bool w_ok, const double* w_dev, double scale, double lam,
-                        bool l2_arg, double l2, int32_t kind, double delta, const double* x_host, double* out, int64_t count) {
+// The certificate at a host point.  l2 = 0 runs the l1 evaluation - its kernels, its eight values - and writes [8] = [9] = 0 when the
+// buffer holds ten; with penalty factors (l2 = 0 only) the tails run on g / p and p o x
+extern "C" int zf_margins_gap(const zf_eval_desc* d, int64_t desc_bytes, const double* x_host, double* out, int64_t count) {
+    const char* who = "zf_margins_gap";
     zf_loss L;
-    int rc = zf_gap_args(who, &V, b_dev && w_ok && x_host && out, scale, lam, l2_arg, l2, count, kind, delta, w_dev, &L);
+    int rc = zf_desc_args(who, d, desc_bytes, x_host && out, &L);
+    if (rc == ZF_OK) rc = zf_gap_args(who, d, count, 8);
     if (rc) return rc;
-    rc = zf_gap_eval_impl(V, b_dev, scale, lam, l2, L, x_host, out, count, nullptr);
-    if (rc == ZF_OK && l2_arg && !(l2 > 0.0) && count >= 10) out[8] = out[9] = 0.0;
+    if (d->p && d->l2 > 0.0)
+        return zf_fail(ZF_ERR_ARG, "%s: not with penalty factors and l2 > 0 together (the ridge term would need the factors too)%s", who);
+    rc = zf_gap_eval_impl(zf_view_of(d), d->b, d->scale, d->lam, d->l2, L, x_host, out, count, nullptr, d->p);
+    if (rc == ZF_OK && !(d->l2 > 0.0) && count >= 10) out[8] = out[9] = 0.0;
     return rc;
 }
-static int32_t zf_loss_of_flag(int32_t logistic) { return logistic != 0 ? ZF_LOSS_LOGISTIC : ZF_LOSS_SQUARE; }
 
-extern "C" int zf_gap_eval(const double* A_dev, const double* b_dev, int64_t m_rows, int64_t n, double scale, double lam,
-                           int32_t logistic, const double* x_host, double* out, int64_t count) {
-    return zf_gap_entry("zf_gap_eval", zf_dense_view(A_dev, m_rows, n), b_dev, true, nullptr, scale, lam, false, 0.0, zf_loss_of_flag(logistic),
-                        0.0, x_host, out, count);
-}
-
-extern "C" int zf_spmat_gap_eval(const zf_spmat* h, const double* b_dev, double scale, double lam, int32_t logistic,
-                                 const double* x_host, double* out, int64_t count) {
-    return zf_gap_entry("zf_spmat_gap_eval", zf_csr_view(h), b_dev, true, nullptr, scale, lam, false, 0.0, zf_loss_of_flag(logistic), 0.0,
-                        x_host, out, count);
-}
-
-extern "C" int zf_gap_eval_enet(const double* A_dev, const double* b_dev, int64_t m_rows, int64_t n, double scale, double lam, double l2,
-                                int32_t logistic, const double* x_host, double* out, int64_t count) {
-    return zf_gap_entry("zf_gap_eval_enet", zf_dense_view(A_dev, m_rows, n), b_dev, true, nullptr, scale, lam, true, l2,
-                        zf_loss_of_flag(logistic), 0.0, x_host, out, count);
-}
-
-extern "C" int zf_spmat_gap_eval_enet(const zf_spmat* h, const double* b_dev, double scale, double lam, double l2, int32_t logistic,
-                                      const double* x_host, double* out, int64_t count) {
-    return zf_gap_entry("zf_spmat_gap_eval_enet", zf_csr_view(h), b_dev, true, nullptr, scale, lam, true, l2, zf_loss_of_flag(logistic), 0.0,
-                        x_host, out, count);
-}
-
-// Huber's loss (zf_kernels_huber.h): the certificate of the least-squares kinds with c = clip(A x - b) for r
-extern "C" int zf_gap_eval_huber(const double* A_dev, const double* b_dev, int64_t m_rows, int64_t n, double scale, double lam, double l2,
-                                 double delta, const double* x_host, double* out, int64_t count) {
-    return zf_gap_entry("zf_gap_eval_huber", zf_dense_view(A_dev, m_rows, n), b_dev, true, nullptr, scale, lam, true, l2, ZF_LOSS_HUBER, delta,
-                        x_host, out, count);
-}
-
-extern "C" int zf_spmat_gap_eval_huber(const zf_spmat* h, const double* b_dev, double scale, double lam, double l2, double delta,
-                                       const double* x_host, double* out, int64_t count) {
-    return zf_gap_entry("zf_spmat_gap_eval_huber", zf_csr_view(h), b_dev, true, nullptr, scale, lam, true, l2, ZF_LOSS_HUBER, delta, x_host,
-                        out, count);
-}
-
-// the Poisson loss (zf_kernels_poisson.h): the certificate with the conjugate v log v - v, v = alpha exp(z) + (1 - alpha) b
-// (w_dev: the row weights or NULL)
-extern "C" int zf_gap_eval_poisson(const double* A_dev, const double* b_dev, const double* w_dev, int64_t m_rows, int64_t n, double scale,
-                                   double lam, double l2, const double* x_host, double* out, int64_t count) {
-    return zf_gap_entry("zf_gap_eval_poisson", zf_dense_view(A_dev, m_rows, n), b_dev, true, w_dev, scale, lam, true, l2, ZF_LOSS_POISSON, 0.0,
-                        x_host, out, count);
-}
-
-extern "C" int zf_spmat_gap_eval_poisson(const zf_spmat* h, const double* b_dev, const double* w_dev, double scale, double lam, double l2,
-                                         const double* x_host, double* out, int64_t count) {
-    return zf_gap_entry("zf_spmat_gap_eval_poisson", zf_csr_view(h), b_dev, true, w_dev, scale, lam, true, l2, ZF_LOSS_POISSON, 0.0, x_host,
-                        out, count);
-}
-
-// per-row sample weights (zf_kernels_wloss.h): the certificate with every row term times w_i
-extern "C" int zf_gap_eval_weighted(const double* A_dev, const double* b_dev, const double* w_dev, int64_t m_rows, int64_t n, double scale,
-                                    double lam, double l2, int32_t loss, double delta, const double* x_host, double* out, int64_t count) {
-    return zf_gap_entry("zf_gap_eval_weighted", zf_dense_view(A_dev, m_rows, n), b_dev, w_dev != nullptr, w_dev, scale, lam, true, l2,
-                        zf_wloss_code(loss), delta, x_host, out, count);
-}
-
-extern "C" int zf_spmat_gap_eval_weighted(const zf_spmat* h, const double* b_dev, const double* w_dev, double scale, double lam, double l2,
-                                          int32_t loss, double delta, const double* x_host, double* out, int64_t count) {
-    return zf_gap_entry("zf_spmat_gap_eval_weighted", zf_csr_view(h), b_dev, w_dev != nullptr, w_dev, scale, lam, true, l2, zf_wloss_code(loss),
-                        delta, x_host, out, count);
-}
-
-// with penalty factors p > 0 (include/zfista_hip.h): the l1 evaluation of this loss on g / p and p o x; w_dev: the row weights or NULL
-static int zf_gap_pf_entry(const char* who, zf_matview V, const double* b_dev, const double* w_dev, const double* p_dev, double scale,
-                           double lam, int32_t loss, double delta, const double* x_host, double* out, int64_t count) {
-    zf_loss L;
-    const int rc = zf_gap_args(who, &V, b_dev && p_dev && x_host && out, scale, lam, false, 0.0, count, loss, delta, w_dev, &L);
-    if (rc) return rc;
-    return zf_gap_eval_impl(V, b_dev, scale, lam, 0.0, L, x_host, out, count, nullptr, p_dev);
-}
-extern "C" int zf_gap_eval_pf(const double* A_dev, const double* b_dev, const double* w_dev, const double* p_dev, int64_t m_rows, int64_t n,
-                              double scale, double lam, int32_t loss, double delta, const double* x_host, double* out, int64_t count) {
-    return zf_gap_pf_entry("zf_gap_eval_pf", zf_dense_view(A_dev, m_rows, n), b_dev, w_dev, p_dev, scale, lam, loss, delta, x_host, out, count);
-}
-extern "C" int zf_spmat_gap_eval_pf(const zf_spmat* h, const double* b_dev, const double* w_dev, const double* p_dev, double scale, double lam,
-                                    int32_t loss, double delta, const double* x_host, double* out, int64_t count) {
-    return zf_gap_pf_entry("zf_spmat_gap_eval_pf", zf_csr_view(h), b_dev, w_dev, p_dev, scale, lam, loss, delta, x_host, out, count);
-}
-
-// the certificate of a dense matrix stored in fp32: zf_gap_eval_pf with p_dev (l2 must be 0 then), else the elastic-net form of
-// this loss (l2 = 0: the l1 evaluation, [8] = [9] = 0 when the buffer holds ten)
-extern "C" int zf_f32_gap_eval(const float* A32_dev, const double* b_dev, const double* w_dev, const double* p_dev, int64_t m_rows,
-                               int64_t n, double scale, double lam, double l2, int32_t loss, double delta, const double* x_host,
-                               double* out, int64_t count) {
-    const zf_matview V = zf_dense_view_f32(A32_dev, m_rows, n);
-    if (!p_dev) return zf_gap_entry("zf_f32_gap_eval", V, b_dev, true, w_dev, scale, lam, true, l2, loss, delta, x_host, out, count);
-    ZF_REQUIRE(!(l2 > 0.0), "zf_f32_gap_eval: not with penalty factors and l2 > 0 together (the ridge term would need the factors too)");
-    return zf_gap_pf_entry("zf_f32_gap_eval", V, b_dev, w_dev, p_dev, scale, lam, loss, delta, x_host, out, count);
-}
-
-// the certificate of K responses on one dense fp64 matrix (zf_mr_eval's arguments; p_dev: n K positive factors or NULL): the
-// evaluation of the m_rows K x n K problem - the joint alpha is feasible for every response - with zf_f32_gap_eval's rules for l2 / p_dev
-extern "C" int zf_mr_gap_eval(const double* A_dev, const double* b_dev, const double* w_dev, const double* p_dev, int64_t m_rows, int64_t n,
-                              int32_t K, double scale, double lam, double l2, int32_t loss, const double* x_host, double* out, int64_t count) {
-    const int rc = zf_mr_args("zf_mr_gap_eval", K, loss);
-    if (rc) return rc;
-    const zf_matview V = zf_dense_view_mr(A_dev, m_rows, n, K);
-    if (!p_dev) return zf_gap_entry("zf_mr_gap_eval", V, b_dev, true, w_dev, scale, lam, true, l2, loss, 0.0, x_host, out, count);
-    ZF_REQUIRE(!(l2 > 0.0), "zf_mr_gap_eval: not with penalty factors and l2 > 0 together (the ridge term would need the factors too)");
-    return zf_gap_pf_entry("zf_mr_gap_eval", V, b_dev, w_dev, p_dev, scale, lam, loss, 0.0, x_host, out, count);
-}
-
-// the same certificate for K responses on one CSR matrix (zf_spmat_mr_eval's arguments): zf_solver_duality_gap of a solver of
-// zf_solver_create_sparse_responses writes the same values, bit for bit
-extern "C" int zf_spmat_mr_gap_eval(const zf_spmat* h, const double* b_dev, const double* w_dev, const double* p_dev, int32_t K, double scale,
-                                    double lam, double l2, int32_t loss, const double* x_host, double* out, int64_t count) {
-    const int rc = zf_mr_args("zf_spmat_mr_gap_eval", K, loss);
-    if (rc) return rc;
-    const zf_matview V = zf_csr_view_mr(h, K);
-    if (!p_dev) return zf_gap_entry("zf_spmat_mr_gap_eval", V, b_dev, true, w_dev, scale, lam, true, l2, loss, 0.0, x_host, out, count);
-    ZF_REQUIRE(!(l2 > 0.0), "zf_spmat_mr_gap_eval: not with penalty factors and l2 > 0 together (the ridge term would need the factors too)");
-    return zf_gap_pf_entry("zf_spmat_mr_gap_eval", V, b_dev, w_dev, p_dev, scale, lam, loss, 0.0, x_host, out, count);
-}
-
-// the gap evaluation followed by the gap-safe screen of its g (zf_kernels_screen.h), l2 = 0 only: out[0 .. 8) as zf_gap_eval - the
+// the gap evaluation followed by the gap-safe screen of its g (zf_kernels_screen.h), l2 = 0 only: out[0 .. 8) as zf_margins_gap - the
 // same kernels in the same order, the same bits - then [r, E, r_eff, kept count].  Huber's loss: the rule, the guard and the four
 // screen launches are the least-squares kinds' - L = 2 scale, |c|_2 from sum c^2 where they read sum r^2 (the clip is exact and
 // 1-Lipschitz; tests/huber_cases.py derives the guard line by line)
-static int zf_screen_args(const char* who, const double* norms_dev, const double* stats_dev, int64_t max_row, int64_t max_col,
-                          uint8_t* keep_dev, int32_t* index_dev, int64_t count, zf_screen_req* rq) {
-    if (!(norms_dev && stats_dev && keep_dev && index_dev)) return zf_fail(ZF_ERR_ARG, "%s: null argument%s", who);
-    if (count < 8 + ZF_SCREEN_SCAL) return zf_fail(ZF_ERR_ARG, "%s: the output buffer holds fewer than 12 doubles%s", who);
-    if (max_row < 0 || max_col < 0) return zf_fail(ZF_ERR_ARG, "%s: the longest row and column must be >= 0%s", who);
-    *rq = zf_screen_req{norms_dev, stats_dev, max_row, max_col, keep_dev, index_dev, nullptr, nullptr};
-    return ZF_OK;
-}
-
-// a screen entry.  gap_count: what zf_gap_args checks against 8 - the Huber entries' `count`; the two older entries pass 8 and
-// report every short buffer through zf_screen_args ("fewer than 12")
-static int zf_screen_entry(const char* who, zf_matview V, const double* b_dev, double scale, double lam, bool l2_arg, int64_t gap_count,
-                           int32_t kind, double delta, const double* x_host, double* out, int64_t count, const double* norms_dev,
-                           const double* stats_dev, int64_t max_row, int64_t max_col, uint8_t* keep_dev, int32_t* index_dev) {
+extern "C" int zf_margins_screen(const zf_eval_desc* d, int64_t desc_bytes, const double* x_host, double* out, int64_t count,
+                                 const double* norms_dev, const double* stats_dev, int64_t max_row, int64_t max_col, uint8_t* keep_dev,
+                                 int32_t* index_dev) {
+    const char* who = "zf_margins_screen";
     zf_loss L;
-    zf_screen_req rq;
-    int rc = zf_gap_args(who, &V, b_dev && x_host && out && (V.csr || V.n <= 0x7fffffffLL), scale, lam, l2_arg, 0.0, gap_count, kind, delta,
-                         nullptr, &L);
-    if (rc == ZF_OK) rc = zf_screen_args(who, norms_dev, stats_dev, max_row, max_col, keep_dev, index_dev, count, &rq);
-    return rc ? rc : zf_gap_eval_impl(V, b_dev, scale, lam, 0.0, L, x_host, out, 8, &rq);
-}
-
-extern "C" int zf_gap_screen_eval(const double* A_dev, const double* b_dev, int64_t m_rows, int64_t n, double scale, double lam,
-                                  int32_t logistic, const double* x_host, double* out, int64_t count, const double* norms_dev,
-                                  const double* stats_dev, uint8_t* keep_dev, int32_t* index_dev) {
-    return zf_screen_entry("zf_gap_screen_eval", zf_dense_view(A_dev, m_rows, n), b_dev, scale, lam, false, 8, zf_loss_of_flag(logistic), 0.0,
-                           x_host, out, count, norms_dev, stats_dev, n, m_rows, keep_dev, index_dev);
-}
-
-extern "C" int zf_spmat_gap_screen_eval(const zf_spmat* h, const double* b_dev, double scale, double lam, int32_t logistic,
-                                        const double* x_host, double* out, int64_t count, const double* norms_dev, const double* stats_dev,
-                                        int64_t max_row, int64_t max_col, uint8_t* keep_dev, int32_t* index_dev) {
-    return zf_screen_entry("zf_spmat_gap_screen_eval", zf_csr_view(h), b_dev, scale, lam, false, 8, zf_loss_of_flag(logistic), 0.0, x_host,
-                           out, count, norms_dev, stats_dev, max_row, max_col, keep_dev, index_dev);
-}
-
-extern "C" int zf_gap_screen_eval_huber(const double* A_dev, const double* b_dev, int64_t m_rows, int64_t n, double scale, double lam,
-                                        double delta, const double* x_host, double* out, int64_t count, const double* norms_dev,
-                                        const double* stats_dev, uint8_t* keep_dev, int32_t* index_dev) {
-    return zf_screen_entry("zf_gap_screen_eval_huber", zf_dense_view(A_dev, m_rows, n), b_dev, scale, lam, true, count, ZF_LOSS_HUBER, delta,
-                           x_host, out, count, norms_dev, stats_dev, n, m_rows, keep_dev, index_dev);
-}
-
-extern "C" int zf_spmat_gap_screen_eval_huber(const zf_spmat* h, const double* b_dev, double scale, double lam, double delta,
-                                              const double* x_host, double* out, int64_t count, const double* norms_dev,
-                                              const double* stats_dev, int64_t max_row, int64_t max_col, uint8_t* keep_dev,
-                                              int32_t* index_dev) {
-    return zf_screen_entry("zf_spmat_gap_screen_eval_huber", zf_csr_view(h), b_dev, scale, lam, true, count, ZF_LOSS_HUBER, delta, x_host,
-                           out, count, norms_dev, stats_dev, max_row, max_col, keep_dev, index_dev);
+    int rc = zf_desc_args(who, d, desc_bytes, x_host && out, &L);
+    if (rc == ZF_OK) rc = zf_gap_args(who, d, count, 8 + ZF_SCREEN_SCAL);
+    if (rc) return rc;
+    // what the rule and its rounding guard are not built for
+    if (d->loss == ZF_LOSS_POISSON) return zf_fail(ZF_ERR_ARG, "%s: not for ZF_LOSS_POISSON (exp is not globally Lipschitz: no gap-safe radius)%s", who);
+    if (d->w) return zf_fail(ZF_ERR_ARG, "%s: not with row weights (w)%s", who);
+    if (d->p) return zf_fail(ZF_ERR_ARG, "%s: not with penalty factors (p)%s", who);
+    if (d->l2 > 0.0) return zf_fail(ZF_ERR_ARG, "%s: not with l2 > 0%s", who);
+    if (d->A32) return zf_fail(ZF_ERR_ARG, "%s: not for a matrix stored in fp32 (A32)%s", who);
+    if (d->K > 1) return zf_fail(ZF_ERR_ARG, "%s: not with K > 1 responses%s", who);
+    if (!d->spmat && d->n > 0x7fffffffLL) return zf_fail(ZF_ERR_ARG, "%s: n must be below 2^31 (index_dev holds int32)%s", who);
+    if (!(norms_dev && stats_dev && keep_dev && index_dev)) return zf_fail(ZF_ERR_ARG, "%s: null argument%s", who);
+    if (d->spmat && (max_row < 0 || max_col < 0)) return zf_fail(ZF_ERR_ARG, "%s: the longest row and column must be >= 0%s", who);
+    const zf_screen_req rq = {norms_dev, stats_dev, d->spmat ? max_row : d->n, d->spmat ? max_col : d->m_rows, keep_dev, index_dev, nullptr, nullptr};
+    return zf_gap_eval_impl(zf_view_of(d), d->b, d->scale, d->lam, 0.0, L, x_host, out, 8, &rq);
 }
 
 // The gap at x_k of a live solver, on its stream: the margins A x_k are the ring's (no sweep over A), the dual candidate goes

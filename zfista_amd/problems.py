@@ -291,21 +291,11 @@ def add_intercept(A):
     return A1, p
 
 
-class _classattr:
-    """A read-only attribute computed from the class: it reads the same on the class and on an instance."""
-
-    def __init__(self, fn):
-        self.fn = fn
-
-    def __get__(self, obj, cls):
-        return self.fn(cls)
-
-
 class _GapMixin:
     """What the eight margins classes (LeastSquaresL1, SparseLeastSquaresL1, LogisticL1, SparseLogisticL1, HuberL1, SparseHuberL1,
     PoissonL1, SparsePoissonL1) share: f / jac_f at a host vector, the duality-gap certificate, lam_max, same-matrix siblings, gap-safe screening and column
-    restriction.  Which C entry point a call reaches is decided HERE, from the loss (``_loss``), the weights (``_w``), the penalty factors (``_pf``) and ``l2``;
-    the storage class below supplies the entry names (``_ENTRY``) and the matrix arguments they start with (``_lead``)."""
+    restriction.  The three C entries (zf_margins_eval / _gap / _screen) take one descriptor, built HERE (``_eval_desc``) from the loss (``_loss``), the weights
+    (``_w``), the penalty factors (``_pf``) and ``l2``; the storage class below supplies its matrix fields (``_matrix_fields``)."""
 
     has_duality_gap = True
     l2 = 0.0   # elastic net: g(x) = lam |x|_1 + (l2 / 2) |x|^2 (+ box)
@@ -318,29 +308,32 @@ class _GapMixin:
     _pf = None
     _pf_host = None
     _loss = _lib.ZF_LOSS_SQUARE   # the loss of the class: everything below that depends on it reads this one attribute
-    _gap_logistic = _classattr(lambda cls: int(cls._loss == _lib.ZF_LOSS_LOGISTIC))
-    _eval_name = _classattr(lambda cls: cls._ENTRY["eval"][cls._loss])   # f and jac_f of the unweighted problem
-    _longest = ()   # (sparse classes: the longest row and column, which their screen entries take)
-    _f32 = False    # (dense classes: A is stored in fp32 - f, jac_f and the certificate go to zf_f32_eval / zf_f32_gap_eval)
+    _longest = (0, 0)       # (sparse classes: the longest row and column, which the screen reads for a handle)
+    _f32 = False            # (dense classes: A is stored in fp32)
+
+    @staticmethod
+    def _flat(x):
+        return x
+
+    def _eval_desc(self):
+        """The ``zf_eval_desc`` every evaluation entry takes.  The loss, the weights, the penalty factors, l2, delta, scale, lam and K
+        are read HERE, once; the storage class supplies the matrix fields alone (``_matrix_fields``).  No site chooses an entry."""
+        return _lib.EvalDesc(b=self.b.data_ptr(), w=None if self._w is None else self._w.data_ptr(),
+                             p=None if self._pf is None else self._pf.data_ptr(), scale=self.scale, lam=self.lam, l2=self.l2,
+                             delta=float(self.delta) if self._loss == _lib.ZF_LOSS_HUBER else 0.0, loss=self._loss,
+                             K=getattr(self, "n_responses", 1), **self._matrix_fields())
 
     def _ls(self, x, want_grad):
         """(f, jac_f or None) at a host vector."""
-        x = _as_host(x)
+        x = _as_host(self._flat(x))
         if x.size != self.n_features:
             raise ValueError(f"len(x) should be equal to n_features, got {x}.")
         lib = _lib.require_gpu()
         fval = C.c_double(0.0)
         grad = np.empty_like(x) if want_grad else None
-        if self._f32:   # (one entry for every loss, weighted or not)
-            name, args = "zf_f32_eval", self._lead(_dp(self._w)) + (self.scale, self._loss, self._w_delta())
-        elif self._loss == _lib.ZF_LOSS_POISSON:   # (its entries take the weights, or NULL)
-            name, args = self._eval_name, self._lead(_dp(self._w)) + (self.scale,)
-        elif self._w is not None:
-            name, args = self._ENTRY["weval"], self._lead(_dp(self._w)) + (self.scale, self._loss, self._w_delta())
-        else:   # (unweighted least squares stays on its own entry: other kernels, other bits than the weighted ones with w = 1)
-            name, args = self._eval_name, self._lead() + (self.scale,) + ((self.delta,) if self._loss == _lib.ZF_LOSS_HUBER else ())
-        _lib.check(getattr(lib, name)(*args, C.c_void_p(_lib.ptr(x)), C.byref(fval), C.c_void_p(_lib.ptr(grad)) if want_grad else None),
-                   name)
+        d = self._eval_desc()
+        _lib.check(lib.zf_margins_eval(C.byref(d), C.sizeof(d), C.c_void_p(_lib.ptr(x)), C.byref(fval),
+                                       C.c_void_p(_lib.ptr(grad)) if want_grad else None), "zf_margins_eval")
         return np.float64(fval.value), grad
 
     def f(self, x):
@@ -350,34 +343,13 @@ class _GapMixin:
         return self._ls(x, True)[1]
 
     def _gap_call(self, lib, x, out):
-        if self._f32:   # (one entry for every loss; penalty factors and l2 > 0 are refused together)
-            _lib.check(lib.zf_f32_gap_eval(*self._lead_pf(), self.scale, self.lam, self.l2, self._loss, self._w_delta(),
-                                           C.c_void_p(_lib.ptr(x)), C.c_void_p(_lib.ptr(out)), out.size), "zf_f32_gap_eval")
-            return
-        if self._pf is not None:   # (l2 = 0: refused together)
-            name = self._ENTRY["gap_pf"]
-            _lib.check(getattr(lib, name)(*self._lead_pf(), self.scale, self.lam, self._loss, self._w_delta(), C.c_void_p(_lib.ptr(x)),
-                                          C.c_void_p(_lib.ptr(out)), out.size), name)
-            return
-        if self._loss == _lib.ZF_LOSS_POISSON:   # (its entries take the weights, or NULL)
-            name, args = "gap_poisson", self._lead(_dp(self._w)) + (self.scale, self.lam, self.l2)
-        elif self._w is not None:
-            name, args = "gap_weighted", self._lead(_dp(self._w)) + (self.scale, self.lam, self.l2, self._loss, self._w_delta())
-        elif self._loss == _lib.ZF_LOSS_HUBER:
-            name, args = "gap_huber", self._lead() + (self.scale, self.lam, self.l2, self.delta)
-        elif self.l2 > 0:
-            name, args = "gap_enet", self._lead() + (self.scale, self.lam, self.l2, self._gap_logistic)
-        else:
-            name, args = "gap", self._lead() + (self.scale, self.lam, self._gap_logistic)
-        name = self._ENTRY[name]
-        _lib.check(getattr(lib, name)(*args, C.c_void_p(_lib.ptr(x)), C.c_void_p(_lib.ptr(out)), out.size), name)
+        d = self._eval_desc()
+        _lib.check(lib.zf_margins_gap(C.byref(d), C.sizeof(d), C.c_void_p(_lib.ptr(x)), C.c_void_p(_lib.ptr(out)), out.size), "zf_margins_gap")
 
     def _screen_call(self, lib, x, out, h, keep, index):
-        huber = self._loss == _lib.ZF_LOSS_HUBER
-        name = self._ENTRY["screen_huber" if huber else "screen"]
-        _lib.check(getattr(lib, name)(*self._lead(), self.scale, self.lam, self.delta if huber else self._gap_logistic,
-                                      C.c_void_p(_lib.ptr(x)), C.c_void_p(_lib.ptr(out)), out.size, _dp(h.norms), _dp(h.stats),
-                                      *self._longest, _dp(keep), _dp(index)), name)
+        d = self._eval_desc()
+        _lib.check(lib.zf_margins_screen(C.byref(d), C.sizeof(d), C.c_void_p(_lib.ptr(x)), C.c_void_p(_lib.ptr(out)), out.size, _dp(h.norms),
+                                         _dp(h.stats), *self._longest, _dp(keep), _dp(index)), "zf_margins_screen")
 
     def _finish_descriptor(self, fields, keep):
         """The descriptor of a storage class with what has no field of zf_problem_desc: the engine calls zf_solver_set_l2 /
@@ -457,9 +429,6 @@ class _GapMixin:
         if self._w is not None:
             raise ValueError(f"{what} is not available with sample_weight: the weighted screening rule needs sum_i w_i a_ij^2 for "
                              "|a_j|^2 and a re-derived rounding guard, which are not built yet")
-
-    def _w_delta(self):
-        return float(getattr(self, "delta", 0.0)) if self._loss == _lib.ZF_LOSS_HUBER else 0.0
 
     # -- g / prox with the ridge term (l2 = 0: the shared l1 forms, the same calls as before) --------------------
     def prox_wsum_g(self, weight, x):
@@ -623,6 +592,7 @@ class _GapMixin:
         why = self._gap_refusal()
         if why:
             raise ValueError(f"duality_gap is not available: {why}")
+        x = self._flat(x)
         if type(x).__module__.split(".")[0] == "torch":
             x = x.detach().cpu().numpy()
         x = _as_host(x)
@@ -686,21 +656,15 @@ class _GapMixin:
 
 class _DenseMarginsL1(_GapMixin, NativeProblem):
     """What the dense single-GPU problems f(x) = scale * sum_i loss_i((Ax)_i), g = lam |x|_1 (+ (l2 / 2) |x|^2) (+ box) share: A (m x n, dense
-    row-major) and the m-vector b in HBM, the dense entry points and their leading arguments, the descriptor of one GPU.  The
+    row-major) and the m-vector b in HBM, the matrix fields of the evaluation descriptor, the descriptor of one GPU.  The
     loss is the subclass's: its ``kind``, its ``_loss``, what b means."""
 
     kind = None
-    _ENTRY = dict(eval=("zf_ls_eval", "zf_logistic_eval", "zf_huber_eval", "zf_poisson_eval"), weval="zf_wloss_eval",   # (eval: by ZF_LOSS_* code)
-                  gap="zf_gap_eval", gap_enet="zf_gap_eval_enet", gap_huber="zf_gap_eval_huber", gap_weighted="zf_gap_eval_weighted",
-                  gap_poisson="zf_gap_eval_poisson", gap_pf="zf_gap_eval_pf",
-                  screen="zf_gap_screen_eval", screen_huber="zf_gap_screen_eval_huber")
 
-    def _lead(self, *w):
-        """What every dense entry point starts with: A, b, (the weights,) m, n."""
-        return (_dp(self.A), _dp(self.b), *w, self.m_rows, self.n_features)
-
-    def _lead_pf(self):
-        return self._lead(_dp(self._w), _dp(self._pf))
+    def _matrix_fields(self):
+        """A (fp64 or fp32) and the MATRIX's sizes: with K responses m_rows and n_features are the flattened lengths."""
+        K = getattr(self, "n_responses", 1)
+        return {"A32" if self._f32 else "A": self.A.data_ptr(), "m_rows": self.m_rows // K, "n": self.n_features // K}
 
     @property
     def matrix_dtype(self):
@@ -850,22 +814,13 @@ class _SpmatHandle:
 
 class _SparseMarginsL1(_GapMixin, NativeProblem):
     """What the sparse single-GPU problems f(x) = scale * sum_i loss_i((Ax)_i), g = lam |x|_1 (+ box) share: the canonical
-    CSR of A and of A^T behind one immutable handle, b in HBM, the sparse entry points and their leading arguments, the
+    CSR of A and of A^T behind one immutable handle, b in HBM, the matrix field of the evaluation descriptor, the
     descriptor.  The loss is the subclass's: its ``kind``, its ``_loss``, what b means."""
 
     kind = None
-    _ENTRY = dict(eval=("zf_spmat_eval", "zf_spmat_logistic_eval", "zf_spmat_huber_eval", "zf_spmat_poisson_eval"),
-                  weval="zf_spmat_wloss_eval", gap_poisson="zf_spmat_gap_eval_poisson", gap_pf="zf_spmat_gap_eval_pf",
-                  gap="zf_spmat_gap_eval", gap_enet="zf_spmat_gap_eval_enet", gap_huber="zf_spmat_gap_eval_huber",
-                  gap_weighted="zf_spmat_gap_eval_weighted", screen="zf_spmat_gap_screen_eval",
-                  screen_huber="zf_spmat_gap_screen_eval_huber")
 
-    def _lead(self, *w):
-        """What every sparse entry point starts with: the matrix handle, b (, the weights)."""
-        return (self._spmat.value, _dp(self.b), *w)
-
-    def _lead_pf(self):
-        return self._lead(_dp(self._w), _dp(self._pf))
+    def _matrix_fields(self):
+        return {"spmat": self._spmat.value.value}
 
     def _set(self, A, b, lam, scale, bounds, l2=0.0, sample_weight=None, penalty_factor=None):
         import torch
@@ -1224,42 +1179,6 @@ class _MultiResponseMixin:
     def minimize_proximal_gradient(self, x0, **kwargs):
         return NativeProblem.minimize_proximal_gradient(self, self._flat(x0), **kwargs)
 
-    # -- entry points ---------------------------------------------------------------------------
-    _MR_ENTRY = ("zf_mr_eval", "zf_mr_gap_eval")   # (f / jac_f and the certificate at K > 1; the sparse classes name their own)
-
-    def _lead(self, *w):
-        return (_dp(self.A), _dp(self.b), *w, self._m, self._n)
-
-    def _ls(self, x, want_grad):
-        if self.n_responses == 1:
-            return super()._ls(self._flat(x), want_grad)
-        x = _as_host(self._flat(x))
-        if x.size != self.n_features:
-            raise ValueError(f"len(x) should be equal to n_features, got {x}.")
-        lib = _lib.require_gpu()
-        fval = C.c_double(0.0)
-        grad = np.empty_like(x) if want_grad else None
-        name = self._MR_ENTRY[0]
-        _lib.check(getattr(lib, name)(*self._lead(_dp(self._w)), self.n_responses, self.scale, self._loss, C.c_void_p(_lib.ptr(x)),
-                                      C.byref(fval), C.c_void_p(_lib.ptr(grad)) if want_grad else None), name)
-        return np.float64(fval.value), grad
-
-    def f(self, x):
-        return self._ls(x, False)[0]
-
-    def jac_f(self, x):
-        return self._ls(x, True)[1]
-
-    def _gap_call(self, lib, x, out):
-        if self.n_responses == 1:
-            return super()._gap_call(lib, x, out)
-        name = self._MR_ENTRY[1]
-        _lib.check(getattr(lib, name)(*self._lead_pf(), self.n_responses, self.scale, self.lam, self.l2, self._loss,
-                                      C.c_void_p(_lib.ptr(x)), C.c_void_p(_lib.ptr(out)), out.size), name)
-
-    def duality_gap(self, x):
-        return super().duality_gap(self._flat(x))
-
     def _descriptor(self):
         fields, keep = super()._descriptor()   # (m_rows and n_features are the flattened lengths already)
         if self.n_responses > 1:
@@ -1363,12 +1282,7 @@ class _SparseMultiResponseMixin(_MultiResponseMixin):
     times.  The two sweeps gather the K values of a stored element as K 8 contiguous bytes (csrc/zf_kernels_spmm.h): one index,
     one value and one gathered line serve K responses, and response k is summed exactly as the plain sweep sums a vector, so
     every output is bit-equal to the plain sparse class on the Kronecker matrix.  K = 1 is the plain sparse class, bit for bit
-    (the plain creator, the plain entries).  K <= 16.  No screening, no acceptance="remainder" / "resolved"."""
-
-    _MR_ENTRY = ("zf_spmat_mr_eval", "zf_spmat_mr_gap_eval")
-
-    def _lead(self, *w):
-        return (self._spmat.value, _dp(self.b), *w)
+    (the plain creator; K = 1 in the evaluation descriptor).  K <= 16.  No screening, no acceptance="remainder" / "resolved"."""
 
     def _set_mr(self, A, B, lam, scale, bounds, l2, sample_weight, penalty_factor, share=None):
         """``share``: a plain sparse problem whose matrix handle - the object itself - is adopted (``with_responses``)."""
