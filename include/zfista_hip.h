@@ -336,7 +336,11 @@ int zf_solver_get_x(zf_solver* s, double* x_host, int64_t count /* capacity in d
 /* checkpoint / resume: zf_solver_poll + zf_solver_get_x + zf_solver_get_x_prev are the state of a
  * solve (x_k, x_{k-1}, control block); zf_solver_restore puts it into a freshly created solver
  * instead of zf_solver_enqueue_init(+_commit), after which the host re-uploads the momentum
- * factors from accepted count `nit` on.  The resumed solve continues bit for bit. */
+ * factors from accepted count `nit` on.  The resumed solve continues bit for bit, provided it is advanced the way the saved
+ * one was: by zf_solver_enqueue_steps (with or without a communicator, attached before the restore), or by the host-driven
+ * sequence zf_solver_enqueue_trial / _trial_finish / _decide on caller-owned pack buffers (zf_solver_set_pack_buffers before
+ * the restore: that is how the solver tells the two apart - on a shape of the fused small-matrix path they sum A x in
+ * different orders, and the restore rebuilds A x_k, A x_{k-1} in the order of the sequence it expects). */
 int zf_solver_get_x_prev(zf_solver* s, double* x_host, int64_t count /* >= n */);
 int zf_solver_restore(zf_solver* s, const double* xk_dev, const double* xprev_dev, const zf_control* saved,
                       int64_t saved_bytes /* == zf_sizeof_control(): a block of another layout is refused */);

@@ -433,11 +433,11 @@ def test_thread_ranks_against_the_unsharded_remainder_solve(shard, world, monkey
 @pytest.mark.parametrize("name,env", [("D", {"ZF_LS_SMALL": "0"}), ("S2", {}), ("D", {})])
 def test_snapshot_and_resume_continue_bit_identically(name, env, monkeypatch):
     """A snapshot in the middle of a run of test 1 and its continuation.  The control block carries the mode; beta_next and
-    the margins s_k, s_{k-1} the remainder kernels read are rebuilt by the resume code as for every solve.  On the general
-    dense path and for the sparse class the continuation is the uninterrupted solve bit for bit.  The fused small-matrix
-    path rebuilds A x_k, A x_{k-1} with the general row sweep - another summation order than its own rows kernel, in either
-    mode - so there the line search must be the same and the iterates agree to the project's 1e-10."""
-    from conftest import rel_err
+    the margins s_k, s_{k-1} the remainder kernels read are rebuilt by the resume code as for every solve: each in the
+    order of the kernel that left it (the fused small-matrix path: its rows kernel's one wave per row, not the general row
+    sweep - zf_solver_restore).  On all three paths - general dense, sparse, fused small-matrix - the continuation is the
+    uninterrupted solve bit for bit, here past the point where the reference's evaluation of the test has stalled and one
+    other ulp in a margin can turn a decision."""
     from zfista_amd import _lib
 
     for k, v in env.items():
@@ -453,12 +453,7 @@ def test_snapshot_and_resume_continue_bit_identically(name, env, monkeypatch):
     assert cont["mode"] == _lib.ZF_ACCEPT_REMAINDER
     assert (cont["nit"], cont["status"], cont["lr"], cont["trials"]) == (whole["nit"], whole["status"], whole["lr"], whole["trials"])
     tail = whole["rows"][saved.nit:]
-    if name == "D" and not env:
-        assert np.array_equal(cont["rows"][:, _lib.TR_LR], tail[:, _lib.TR_LR])
-        assert rel_err(cont["x"], whole["x"]) <= 1e-10
-        np.testing.assert_allclose(cont["rows"][:, _lib.TR_F], tail[:, _lib.TR_F], rtol=1e-10)
-    else:
-        assert cont["F"] == whole["F"] and np.array_equal(cont["x"], whole["x"]) and np.array_equal(cont["rows"], tail)
+    assert cont["F"] == whole["F"] and np.array_equal(cont["x"], whole["x"]) and np.array_equal(cont["rows"], tail)
     with pytest.warns(UserWarning, match="acceptance='remainder'.*acceptance='reference'"):
         other = _run(prob, dict(max_iter=int(saved.nit) + 2), acceptance="reference", resume=state)
     assert other["mode"] == _lib.ZF_ACCEPT_REFERENCE

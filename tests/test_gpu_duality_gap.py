@@ -378,15 +378,14 @@ def test_the_gap_of_a_live_solve(name, monkeypatch):
     # the gap falls along the solve (not monotonically, but by a lot over 24 passes)
     assert probed["gaps"][passes - 1].gap < probed["gaps"][0].gap
     # the snapshot taken after the gap call of pass 11 is the snapshot of the solve that was never asked, byte for byte, and
-    # resumes as that one does; except on the fused small-matrix path (whose restore rebuilds the margins with the row sweep,
-    # in another order than its rows kernel left them) that is the uninterrupted solve
+    # resumes as that one does: as the uninterrupted solve, on every path (the fused small-matrix one included: its restore
+    # rebuilds the margins in the order its rows kernel left them)
     for key in ("x", "x_prev", "control"):
         assert np.array_equal(probed["state"][key], plain["state"][key]), key
     resumed = _walk(prob, passes - 12, resume=probed["state"])
     _same(resumed, _walk(prob, passes - 12, resume=plain["state"]))
-    if name != "small":
-        assert np.array_equal(resumed["x"], plain["x"]) and (resumed["nit"], resumed["lr"], resumed["F"]) == (plain["nit"], plain["lr"], plain["F"])
-        assert np.array_equal(resumed["rows"], plain["rows"][len(plain["rows"]) - len(resumed["rows"]):])
+    assert np.array_equal(resumed["x"], plain["x"]) and (resumed["nit"], resumed["lr"], resumed["F"]) == (plain["nit"], plain["lr"], plain["F"])
+    assert np.array_equal(resumed["rows"], plain["rows"][len(plain["rows"]) - len(resumed["rows"]):])
     # a solver that is never asked allocates nothing for the gap and launches what it launched: same launch counts
     assert plain["run"].solver.launch_counts() == probed["run"].solver.launch_counts()
 

@@ -141,6 +141,44 @@ __global__ __launch_bounds__(ZF_BLOCK) void zf_ls_small_step_kernel(zf_ls_small_
     }
 }
 
+// <A[row, :], x> as one wave forms it (n % 32 == 0, 16-byte aligned): lane l takes the pairs l, l + 64, ... - eight 16-byte
+// loads of the row (and of x) in flight while eight remain, the rest one by one - then the fixed shuffle tree; every lane
+// holds the sum.  The ONE place this order is written down: the rows kernel of a trial and the apply-only kernel that
+// rebuilds A x_k after a restore (zf_solver_restore) must leave the same bits.
+__device__ __forceinline__ double zf_ls_small_row_dot(const double* __restrict__ A, const double* __restrict__ x, int64_t row, int64_t n,
+                                                      int lane) {
+    const zf_row2* __restrict__ Ar = reinterpret_cast<const zf_row2*>(A + row * n);
+    const zf_row2* __restrict__ xv = reinterpret_cast<const zf_row2*>(x);
+    double acc = 0.0;
+    int64_t j = lane;
+    for (; j + 64 * 7 < n / 2; j += 64 * 8) {   // eight 16-byte loads of the row (and of x+) in flight
+        zf_row2 a[8], xx[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            a[u] = Ar[j + 64 * u];
+            xx[u] = xv[j + 64 * u];
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) acc += a[u].x * xx[u].x + a[u].y * xx[u].y;
+    }
+    for (; j < n / 2; j += 64) {
+        const zf_row2 a = Ar[j], xx = xv[j];
+        acc += a.x * xx.x + a.y * xx.y;
+    }
+    return zf_wave_sum(acc);
+}
+
+// s_out = A x in the rows kernel's order and nothing else: one wave per row, the rows kernel's grid (outside the solver
+// loop: zf_solver_restore rebuilds the margins of an iterate that kernel produced)
+__global__ __launch_bounds__(ZF_BLOCK) void zf_ls_small_apply_kernel(const double* __restrict__ A, const double* __restrict__ x,
+                                                                     double* __restrict__ s_out, int64_t m, int64_t n) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t row = (int64_t)blockIdx.x * ZF_WAVES + wave;
+    if (row >= m) return;
+    const double acc = zf_ls_small_row_dot(A, x, row, n, lane);
+    if (lane == 0) s_out[row] = acc;
+}
+
 // REM (ZF_ACCEPT_REMAINDER): beside (s+ - b)^2 every row also leaves (s+ - s_y)^2, s_y = s_k + beta (s_k - s_{k-1}) by the
 // step kernel's expression; the last arriver adds those workgroup sums in the same order -> R = scale |A (x+ - y)|^2, the
 // Taylor remainder of f, into ls_scal[2] and pack slot 7.  f(x+) is the same sum, the same bits, in both instantiations.
@@ -163,25 +201,7 @@ __global__ __launch_bounds__(ZF_BLOCK) void zf_ls_small_rows_kernel(zf_ls_small_
     const int64_t row = (int64_t)blockIdx.x * ZF_WAVES + wave;
     double sq = 0.0, sq_r = 0.0;
     if (row < m) {
-        const zf_row2* __restrict__ Ar = reinterpret_cast<const zf_row2*>(P.A + row * n);
-        const zf_row2* __restrict__ xv = reinterpret_cast<const zf_row2*>(x);
-        double acc = 0.0;
-        int64_t j = lane;
-        for (; j + 64 * 7 < n / 2; j += 64 * 8) {   // eight 16-byte loads of the row (and of x+) in flight
-            zf_row2 a[8], xx[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                a[u] = Ar[j + 64 * u];
-                xx[u] = xv[j + 64 * u];
-            }
-#pragma unroll
-            for (int u = 0; u < 8; ++u) acc += a[u].x * xx[u].x + a[u].y * xx[u].y;
-        }
-        for (; j < n / 2; j += 64) {
-            const zf_row2 a = Ar[j], xx = xv[j];
-            acc += a.x * xx.x + a.y * xx.y;
-        }
-        acc = zf_wave_sum(acc);
+        const double acc = zf_ls_small_row_dot(P.A, x, row, n, lane);
         if (lane == 0) {
             s_out[row] = acc;
             const double rv = acc - P.b[row];

@@ -1841,7 +1841,21 @@ extern "C" int zf_solver_enqueue_init(zf_solver* s, const double* x0_dev) {
 // the saved values; buffer indices and the chain geometry are this solver's.  The momentum ring is NOT part of the state: the
 // host re-uploads the factors from accepted count `nit` on (zf_solver_set_beta), which also
 // resolves beta_next.  Least squares: A x_k and A x_{k-1} are recomputed by the same kernel that
-// produced them (unsharded only).
+// produced them (unsharded only), so that the resumed solve continues bit for bit.  On the general paths that is
+// zf_launch_apply_A for every iterate.  On the fused small-matrix path (s->ls_small) the kernel depends on the iterate's
+// accepted count: x_0 got its margins from zf_solver_enqueue_init (zf_gemv_rows_kernel), every later iterate is the x+ of
+// an accepted trial of zf_ls_small_rows_kernel - another summation order, other last bits.  Index rule, from saved->nit:
+//     A x_k      in the small-matrix order (zf_ls_small_apply_kernel) iff nit >= 1
+//     A x_{k-1}  in the small-matrix order                            iff nit >= 2     (nit <= 1: x_{k-1} is x_0)
+// s->ls_small alone only says that the shape is eligible: the fused kernels run when a pass decides in its launch
+// (zf_solver_enqueue_steps without a communicator).  Behind a communicator (one rank too: zf_solver_set_comm comes before the
+// restore) and in the host-driven sequence trial / gather / decide every margin vector comes from the general row sweep, and
+// is rebuilt by it: zf_fused_small_runs.
+// Whether the passes of this solver run the fused small-matrix kernels (zf_launch_trial: ls_small and the decision in the
+// launch).  Not behind a communicator, whose steps decide in a launch of their own; not with caller-owned pack buffers
+// (zf_solver_set_pack_buffers), the mark of the host-driven sequence zf_solver_enqueue_trial / _trial_finish / _decide.
+static bool zf_fused_small_runs(const zf_solver* s) { return s->ls_small && !s->comm && s->own_packs; }
+
 extern "C" int zf_solver_restore(zf_solver* s, const double* xk_dev, const double* xprev_dev,
                                  const zf_control* saved, int64_t saved_bytes) {
     ZF_REQUIRE(s && xk_dev && xprev_dev && saved, "zf_solver_restore: null argument");
@@ -1888,6 +1902,13 @@ extern "C" int zf_solver_restore(zf_solver* s, const double* xk_dev, const doubl
         for (int k = 0; k < 2; ++k) {
             double* xsrc = s->xb[at[k]];
             double* dst = s->sring.p[at[k]];
+            // (small-matrix path: x_k has accepted count nit, x_{k-1} has nit - 1; count 0 - and x_{-1} - is x0, from the row
+            //  sweep of the initialisation; every other iterate is the x+ of an accepted trial of the rows kernel)
+            if (zf_fused_small_runs(s) && saved->nit >= 1 + k) {
+                const dim3 gr((unsigned)((d.m_rows + ZF_WAVES - 1) / ZF_WAVES));
+                hipLaunchKernelGGL(zf_ls_small_apply_kernel, gr, dim3(ZF_BLOCK), 0, s->stream, d.A, xsrc, dst, d.m_rows, d.n);
+                continue;
+            }
             zf_ring3 xr = {{xsrc, xsrc, xsrc}};
             zf_ring3 so = {{dst, dst, dst}};
             zf_launch_apply_A(s, nullptr, xr, so, -1);
