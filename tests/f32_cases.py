@@ -2,7 +2,7 @@
 
 A dense margins problem with ``matrix_dtype="float32"`` keeps A in HBM as floats and sweeps it with
 csrc/zf_kernels_gemv_f32.h: V floats per load, V = 4 when n % 4 == 0 (16-byte loads), 2 when n % 4 == 2, 1 for odd n; the
-column sweep splits the rows into slices by the rule of zf_dense_slices_f32 (panels of 256 V columns, at most 64 slices of
+column sweep splits the rows into slices by the rule of zf_view_slices for an fp32 view (panels of 256 V columns, at most 64 slices of
 at least 8 rows); the row sweep (4 rows per workgroup) loops over row groups once m > 65536; no small-matrix path.  float32 -> float64 is exact,
 so such a solve is the fp64 solve on A64 = float64(float32(A)) with sums in another order: every reference here gets A64.
 
@@ -49,7 +49,7 @@ def width(n):
 
 
 def dispatch_f32(m, n):
-    """zf_solver_set_matrix_f32's plan (zfista_amd/csrc/zf_solver.hip: zf_dense_slices_f32, zf_solver_ls_plan), restated:
+    """zf_solver_set_matrix_f32's plan (zfista_amd/csrc: zf_view_slices in zf_matview.h, zf_solver_ls_plan), restated:
     the table above must agree."""
     V = width(n)
     panels = -(-(n // V) // 256)                 # column panels: ZF_BLOCK threads x V columns

@@ -37,7 +37,7 @@ def rows_per_wg(K):
 
 
 def slices_of(m, n):
-    """(slices, rows per slice) of the column sweep: zf_mr_slices restated."""
+    """(slices, rows per slice) of the column sweep: zf_view_slices (csrc/zf_matview.h) for a K-response view, restated."""
     V = 2 if n % 2 == 0 else 1
     panels = (n // V + 255) // 256
     s = min((2048 + panels - 1) // panels, (m + 7) // 8, 64)

@@ -383,7 +383,7 @@ def test_the_standalone_certificate_slices_the_rows_as_the_solver_does(loss, wei
 
     m, n = WIDE
     assert F.dispatch_f32(m, n) == (F.COLS_V4, F.ROWS_V4, 64, 8)
-    panels64 = -(-(n // 2) // 256)   # zf_dense_slices, restated: the fp64 rule on this shape
+    panels64 = -(-(n // 2) // 256)   # zf_col_slices with V = 2, restated: the fp64 rule on this shape
     rps64 = -(-m // min(-(-2048 // panels64), -(-m // 8), 64))
     assert (-(-m // rps64), rps64) == (57, 9)
     D = F.Dense(m, n, seed=11)

@@ -96,7 +96,7 @@ __global__ __launch_bounds__(ZF_BLOCK) void zf_gemv_rows_f32_kernel(const zf_con
 }
 
 // ---- slab[slice][j] = sum_{i in slice} A[i][j] r[i]  (column sums) ----------
-// zf_gemvT_partial_kernel with float rows: grid (column panels of ZF_BLOCK * V, row slices - zf_dense_slices_f32); each
+// zf_gemvT_partial_kernel with float rows: grid (column panels of ZF_BLOCK * V, row slices - zf_view_slices, zf_matview.h); each
 // thread owns V adjacent columns, walks its row slice with GEMVT_UNROLL loads in flight and writes V doubles of the slab
 // [slices][n], which zf_gemvT_combine_kernel adds in slice order.
 template <int V>
@@ -128,4 +128,25 @@ __global__ __launch_bounds__(ZF_BLOCK) void zf_gemvT_partial_f32_kernel(const zf
     double* out = slab + (int64_t)blockIdx.y * n + colv * V;
 #pragma unroll
     for (int v = 0; v < V; ++v) out[v] = acc[v];
+}
+
+// ---- launches ---------------------------------------------------------------
+// sr = A xr (slot / ctl as zf_gemv_rows_kernel) ...
+static void zf_launch_rows_f32(hipStream_t st, const zf_control* ctl, const float* A32, zf_ring3 xr, zf_ring3 sr, int slot, int64_t m,
+                               int64_t n) {
+    int gr = (int)((m + GEMV_ROWS_F32 - 1) / GEMV_ROWS_F32);
+    if (gr > 8 * ZF_MAX_GRID) gr = 8 * ZF_MAX_GRID;
+    const int V = zf_f32_width(n);
+    if (V == 4) hipLaunchKernelGGL(zf_gemv_rows_f32_kernel<4>, dim3(gr), dim3(ZF_BLOCK), 0, st, ctl, A32, xr, sr, slot, m, n);
+    else if (V == 2) hipLaunchKernelGGL(zf_gemv_rows_f32_kernel<2>, dim3(gr), dim3(ZF_BLOCK), 0, st, ctl, A32, xr, sr, slot, m, n);
+    else hipLaunchKernelGGL(zf_gemv_rows_f32_kernel<1>, dim3(gr), dim3(ZF_BLOCK), 0, st, ctl, A32, xr, sr, slot, m, n);
+}
+// ... and the slice partials of A^T r (slices / rows_per_slice: zf_view_slices; zf_gemvT_combine_kernel follows)
+static void zf_launch_cols_f32(hipStream_t st, const zf_control* ctl, const float* A32, const double* r, double* slab, int64_t m,
+                               int64_t n, int slices, int64_t rows_per_slice) {
+    const int V = zf_f32_width(n);
+    const dim3 gT((unsigned)((n / V + ZF_BLOCK - 1) / ZF_BLOCK), (unsigned)slices);
+    if (V == 4) hipLaunchKernelGGL(zf_gemvT_partial_f32_kernel<4>, gT, dim3(ZF_BLOCK), 0, st, ctl, A32, r, slab, m, n, rows_per_slice);
+    else if (V == 2) hipLaunchKernelGGL(zf_gemvT_partial_f32_kernel<2>, gT, dim3(ZF_BLOCK), 0, st, ctl, A32, r, slab, m, n, rows_per_slice);
+    else hipLaunchKernelGGL(zf_gemvT_partial_f32_kernel<1>, gT, dim3(ZF_BLOCK), 0, st, ctl, A32, r, slab, m, n, rows_per_slice);
 }

@@ -162,18 +162,6 @@ __global__ __launch_bounds__(ZF_BLOCK) void zf_mr_cols_partial_kernel(const zf_c
 }
 
 // ---- launches -------------------------------------------------------------------------------
-// row slices of the column sweep: the rule of zf_dense_slices on the matrix A itself (the panels are A's columns)
-static void zf_mr_slices(int64_t m, int64_t n, int* slices_out, int64_t* rows_per_slice) {
-    const int V = (n % 2 == 0) ? 2 : 1;
-    const int64_t panels = (n / V + ZF_BLOCK - 1) / ZF_BLOCK;
-    int64_t slices = (ZF_MAX_GRID + panels - 1) / panels;
-    if (slices > (m + 7) / 8) slices = (m + 7) / 8;
-    if (slices < 1) slices = 1;
-    if (slices > 64) slices = 64;
-    *rows_per_slice = (m + slices - 1) / slices;
-    *slices_out = (int)((m + *rows_per_slice - 1) / *rows_per_slice);
-}
-
 template <int K>
 static void zf_mr_rows_k(hipStream_t st, const zf_control* ctl, const double* A, zf_ring3 xr, zf_ring3 sr, int slot, int64_t m, int64_t n) {
     const int per = zf_mr_rows_per_wg(K);

@@ -22,6 +22,7 @@
 #include "zf_kernels_mr.h"
 #include "zf_kernels_op.h"
 #include "zf_spmv.h"
+#include "zf_matview.h"
 #include "zf_screen.h"
 #include "zf_kernels_loss.h"
 #include "zf_kernels_gap.h"
@@ -243,20 +244,21 @@ struct zf_solver {
     double* sbuf = nullptr;       // 3 * m_pad
     zf_ring3 sring = {{nullptr, nullptr, nullptr}};
     double* resid = nullptr;      // m_rows
-    double* slab = nullptr;       // slices * n
     double* ls_scal = nullptr;    // [0] f(y) [1] f(x+) [2] the Taylor remainder R of the trial (ZF_ACCEPT_REMAINDER)
     double* s_part = nullptr;     // sharded: this rank's A_p x_p (m)
     double* s_all = nullptr;      // sharded: gathered parts (world x m, rank-major)
     bool own_svec = true;
-    int slices = 1;
-    int64_t rows_per_slice = 0;
     bool initialised = false;
     bool init_enqueued = false;   // zf_solver_enqueue_init(_all) ran: x0 is in the ring (zf_solver_set_comm may no longer reallocate it)
     bool own_packs = true;
-    bool gemv_mfma = false;       // A^T r on v_mfma_f64_16x16x4 (n % 32 == 0; ZF_GEMV_MFMA=0 disables)
     bool ls_small = false;        // cache-resident A: two fused launches per trial (zf_kernels_ls_small.h)
-    const float* A32 = nullptr;   // the matrix stored in fp32 (zf_solver_set_matrix_f32; borrowed as desc.A is): every sweep takes zf_kernels_gemv_f32.h and nothing reads desc.A; NULL: what ran before
-    int K = 1;                    // responses (zf_solver_set_responses): desc.A is (m_rows / K) x (n / K), the vectors are response-interleaved and every sweep takes zf_kernels_mr.h; 1: what ran before
+    // the matrix kinds: A as the two sweeps see it (zf_matview.h) - mat.A32: the matrix stored in fp32 (zf_solver_set_matrix_f32; borrowed
+    // as desc.A is; nothing reads desc.A then); mat.k: responses (zf_solver_set_responses, zf_solver_create_sparse_responses: mat.m x
+    // mat.n is the matrix, desc holds the flattened lengths); mat.h: the caller's CSR handle (never written through); mat.mfma:
+    // A^T r on v_mfma_f64_16x16x4 (n % 32 == 0; ZF_GEMV_MFMA=0 disables) - and what the sweeps write between their launches: the
+    // slab of ws.slices * n doubles, or this solver's segment sums of the split rows of A / of A^T
+    zf_matview mat = {nullptr, 0, 0, nullptr, false, nullptr, 1, false};
+    zf_sweep_ws ws = {nullptr, 1, 0, nullptr, nullptr};
     double huber = 0.0;           // Huber's loss (zf_solver_set_huber): delta > 0 swaps the residual kernels for zf_kernels_huber.h; 0: the squared loss
     bool poisson = false;         // the Poisson loss (zf_solver_set_poisson): the residual kernels swapped for zf_kernels_poisson.h
     bool loss_part = false;       // the dense least-squares kind holds the 2 x ZF_SPMV_RESID_MAX_CHUNKS chunk sums of the loss kernels (zf_loss_part)
@@ -264,8 +266,6 @@ struct zf_solver {
     double l2 = 0.0;              // elastic net (zf_solver_set_l2): g = lam |x|_1 + (l2 / 2) |x|^2; 0: every path is the l1 one
     const double* pf = nullptr;   // per-column penalty factors (zf_solver_set_penalty_factors; borrowed as b is): g = lam sum p_j |x_j|; NULL: what ran before
     double* gap_xp = nullptr;     // ... the certificate's scaled iterate p o x_k (n doubles, allocated by the first zf_solver_duality_gap)
-    const zf_spmat* spmat = nullptr;   // sparse least squares: A and A^T with their plans (the caller's handle: zf_solver_create_sparse; never written through)
-    double* sp_part_A = nullptr, *sp_part_At = nullptr;   // ... this solver's segment sums of the split rows of A / of A^T
     zf_op_plan op_plan = {};      // operator problem: which instantiation of the correlation kernels runs it (zf_op_make_plan)
     double* op_buf = nullptr;     // its taps as launched (zero-padded to K x K) and, behind them, the rank-1 factors u, v when the kernel is separable
     const double* op_taps = nullptr, *op_sep = nullptr;
@@ -404,10 +404,10 @@ static int zf_solver_free_all(zf_solver* s) {
     }
     if (s->ra_join) (void)hipEventDestroy(s->ra_join);
     if (s->ra_fork) (void)hipEventDestroy(s->ra_fork);
-    void* ptrs[] = {s->sp_part_A, s->sp_part_At, s->op_buf, s->row_part, s->ls_cnt, s->blk_part, s->slice_part, s->fin_cnt, s->grp_part, s->xbuf, s->partials, s->ctl_trace, s->beta_ring,
+    void* ptrs[] = {s->ws.part_A, s->ws.part_At, s->op_buf, s->row_part, s->ls_cnt, s->blk_part, s->slice_part, s->fin_cnt, s->grp_part, s->xbuf, s->partials, s->ctl_trace, s->beta_ring,
                     s->ra_word, s->ra_flags, s->blk_part2, s->grp_part2, s->fin_cnt2, s->pack2,
                     s->own_packs ? s->pack_local : nullptr, s->own_packs ? s->pack_all : nullptr,
-                    s->grad, s->sbuf, s->resid, s->slab, s->ls_scal, s->gap.rvec, s->gap.g, s->gap.part, s->gap.scal, s->gap_xp,
+                    s->grad, s->sbuf, s->resid, s->ws.slab, s->ls_scal, s->gap.rvec, s->gap.g, s->gap.part, s->gap.scal, s->gap_xp,
                     s->own_svec ? s->s_part : nullptr, s->own_svec ? s->s_all : nullptr};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
@@ -448,48 +448,6 @@ static zf_loss zf_loss_of(const zf_solver* s) {
                      : s->poisson                ? ZF_LOSS_POISSON
                                                  : ZF_LOSS_SQUARE;
     return zf_loss{kind, s->huber, s->roww};
-}
-// row slices of the dense column sweep A^T r: enough that panels x slices fills the chip (>= ~2048 workgroups)
-static void zf_dense_slices(int64_t m, int64_t n, int* slices_out, int64_t* rows_per_slice) {
-    const int V = (n % 2 == 0) ? 2 : 1;
-    const int64_t panels = (n / V + ZF_BLOCK - 1) / ZF_BLOCK;
-    int64_t slices = (ZF_MAX_GRID + panels - 1) / panels;
-    if (slices > (m + 7) / 8) slices = (m + 7) / 8;
-    if (slices < 1) slices = 1;
-    if (slices > 64) slices = 64;
-    *rows_per_slice = (m + slices - 1) / slices;
-    *slices_out = (int)((m + *rows_per_slice - 1) / *rows_per_slice);
-}
-// the same rule for a matrix stored in fp32 (zf_kernels_gemv_f32.h): panels of ZF_BLOCK * V columns with V up to 4, so a given n
-// has up to half the panels and takes up to twice the slices; the caps - 64 slices, at least 8 rows per slice - are the same
-static void zf_dense_slices_f32(int64_t m, int64_t n, int* slices_out, int64_t* rows_per_slice) {
-    const int V = zf_f32_width(n);
-    const int64_t panels = (n / V + ZF_BLOCK - 1) / ZF_BLOCK;
-    int64_t slices = (ZF_MAX_GRID + panels - 1) / panels;
-    if (slices > (m + 7) / 8) slices = (m + 7) / 8;
-    if (slices < 1) slices = 1;
-    if (slices > 64) slices = 64;
-    *rows_per_slice = (m + slices - 1) / slices;
-    *slices_out = (int)((m + *rows_per_slice - 1) / *rows_per_slice);
-}
-// the two sweeps over an fp32 matrix: sr = A xr (slot / ctl as zf_gemv_rows_kernel) ...
-static void zf_launch_rows_f32(hipStream_t st, const zf_control* ctl, const float* A32, zf_ring3 xr, zf_ring3 sr, int slot, int64_t m,
-                               int64_t n) {
-    int gr = (int)((m + GEMV_ROWS_F32 - 1) / GEMV_ROWS_F32);
-    if (gr > 8 * ZF_MAX_GRID) gr = 8 * ZF_MAX_GRID;
-    const int V = zf_f32_width(n);
-    if (V == 4) hipLaunchKernelGGL(zf_gemv_rows_f32_kernel<4>, dim3(gr), dim3(ZF_BLOCK), 0, st, ctl, A32, xr, sr, slot, m, n);
-    else if (V == 2) hipLaunchKernelGGL(zf_gemv_rows_f32_kernel<2>, dim3(gr), dim3(ZF_BLOCK), 0, st, ctl, A32, xr, sr, slot, m, n);
-    else hipLaunchKernelGGL(zf_gemv_rows_f32_kernel<1>, dim3(gr), dim3(ZF_BLOCK), 0, st, ctl, A32, xr, sr, slot, m, n);
-}
-// ... and the slice partials of A^T r (slices / rows_per_slice: zf_dense_slices_f32; zf_gemvT_combine_kernel follows)
-static void zf_launch_cols_f32(hipStream_t st, const zf_control* ctl, const float* A32, const double* r, double* slab, int64_t m,
-                               int64_t n, int slices, int64_t rows_per_slice) {
-    const int V = zf_f32_width(n);
-    const dim3 gT((unsigned)((n / V + ZF_BLOCK - 1) / ZF_BLOCK), (unsigned)slices);
-    if (V == 4) hipLaunchKernelGGL(zf_gemvT_partial_f32_kernel<4>, gT, dim3(ZF_BLOCK), 0, st, ctl, A32, r, slab, m, n, rows_per_slice);
-    else if (V == 2) hipLaunchKernelGGL(zf_gemvT_partial_f32_kernel<2>, gT, dim3(ZF_BLOCK), 0, st, ctl, A32, r, slab, m, n, rows_per_slice);
-    else hipLaunchKernelGGL(zf_gemvT_partial_f32_kernel<1>, gT, dim3(ZF_BLOCK), 0, st, ctl, A32, r, slab, m, n, rows_per_slice);
 }
 static zf_op_args zf_op_of(const zf_problem_desc& d, const zf_control* ctl, const zf_op_plan& pl, const double* taps, const double* sep) {
     zf_op_args P;
@@ -536,36 +494,14 @@ static int zf_op_prepare(const zf_env& env, const double* taps_dev, int k, int64
     return ZF_OK;
 }
 
-// s[(cur + slot) % 3] = A x[(cur + slot) % 3] inside the loop (ctl given), or sout.p[0] = A xr.p[0] outside it (ctl NULL)
+// s[(cur + slot) % 3] = A x[(cur + slot) % 3] inside the loop (ctl given), or sout.p[0] = A xr.p[0] outside it (ctl NULL): the
+// operator's own kernel, or the row sweep of the solver's matrix view
 static void zf_launch_apply_A(zf_solver* s, const zf_control* ctl, zf_ring3 xr, zf_ring3 sout, int slot) {
-    const zf_problem_desc& d = s->desc;
-    const int64_t n = d.n, m = d.m_rows;
-    if (d.kind == ZF_PROBLEM_BLUR_HAAR_L1) {
+    if (s->desc.kind == ZF_PROBLEM_BLUR_HAAR_L1)   // (the operator is no matrix view)
         zf_launch_op_apply(s->op_plan, s->stream, zf_op_of(s, ctl), xr.p[0], xr.p[1], xr.p[2], sout.p[0], sout.p[1], sout.p[2], slot,
                            zf_op_no_fuse());
-        return;
-    }
-    if (zf_is_sparse_mat(d.kind)) {
-        const zf_spmv_io io = {{xr.p[0], xr.p[1], xr.p[2]}, {sout.p[0], sout.p[1], sout.p[2]}};
-        if (s->K > 1) zf_launch_spmm(s->spmat->A, s->stream, ctl, false, io, slot, 1.0, s->K, s->sp_part_A);
-        else zf_launch_spmv(s->spmat->A, s->stream, ctl, false, io, slot, 1.0, s->sp_part_A);
-        return;
-    }
-    if (s->A32) {
-        zf_launch_rows_f32(s->stream, ctl, s->A32, xr, sout, slot, m, n);
-        return;
-    }
-    if (s->K > 1) {
-        zf_launch_mr_rows(s->stream, ctl, d.A, xr, sout, slot, m / s->K, n / s->K, s->K);
-        return;
-    }
-    const int V = (n % 2 == 0) ? 2 : 1;
-    int gr = (int)((m + GEMV_ROWS - 1) / GEMV_ROWS);
-    if (gr > 8 * ZF_MAX_GRID) gr = 8 * ZF_MAX_GRID;
-    if (V == 2)
-        hipLaunchKernelGGL(zf_gemv_rows_kernel<2>, dim3(gr), dim3(ZF_BLOCK), 0, s->stream, ctl, d.A, xr, sout, slot, m, n);
     else
-        hipLaunchKernelGGL(zf_gemv_rows_kernel<1>, dim3(gr), dim3(ZF_BLOCK), 0, s->stream, ctl, d.A, xr, sout, slot, m, n);
+        zf_launch_apply(s->mat, s->stream, ctl, xr, sout, slot, s->ws);
 }
 
 // What two passes in flight need: the second stream (non-blocking, at the highest priority: what runs there - a waiting
@@ -650,9 +586,10 @@ static int zf_solver_create_impl(zf_solver** out, const zf_problem_desc* desc, c
     if (!s) return zf_fail(ZF_ERR_ARG, "zf_solver_create: out of host memory");
     s->desc = *desc;
     s->opt = *opt;
-    s->spmat = sp;
-    s->K = K;
     s->env = zf_env_read();
+    if (zf_is_sparse_mat(desc->kind)) s->mat = zf_matview{nullptr, sp->m, sp->n, sp, true, nullptr, K, false};
+    if (zf_is_dense_mat(desc->kind))
+        s->mat = zf_matview{desc->A, desc->m_rows, desc->n, nullptr, false, nullptr, 1, desc->n % 32 == 0 && s->env.gemv_mfma};
     s->pass_seq = s->env.pass_seq_start;
     s->stream = reinterpret_cast<hipStream_t>(stream);
     s->box = !(desc->box_lo == -INFINITY && desc->box_hi == INFINITY);
@@ -768,13 +705,15 @@ static int zf_solver_create_impl(zf_solver** out, const zf_problem_desc* desc, c
     ZF_TRY(hipMemsetAsync(s->trace, 0, sizeof(double) * ZF_RING * ZF_TRACE_COLS, s->stream));
     ZF_TRY(hipMemsetAsync(s->beta_ring, 0, sizeof(double) * ZF_RING, s->stream));
     ZF_TRY(hipMemsetAsync(s->pack_all, 0, sizeof(double) * ZF_PACK_LEN * s->sub * desc->world, s->stream));
-    if (desc->kind == ZF_PROBLEM_BLUR_HAAR_L1) {
-        const int64_t m_pad = n_pad;
+    if (zf_has_margins(desc->kind)) {   // the gradient, the ring of margins A x, psi(y) and the scalars of a trial
+        const int64_t m_pad = (desc->m_rows + 63) & ~int64_t(63);   // (the operator: m_rows = n)
         ZF_TRY(hipMalloc(&s->grad, sizeof(double) * n_pad));
         ZF_TRY(hipMalloc(&s->sbuf, sizeof(double) * 3 * m_pad));
         for (int k = 0; k < 3; ++k) s->sring.p[k] = s->sbuf + k * m_pad;
         ZF_TRY(hipMalloc(&s->resid, sizeof(double) * m_pad));
         ZF_TRY(hipMalloc(&s->ls_scal, sizeof(double) * 8));
+    }
+    if (desc->kind == ZF_PROBLEM_BLUR_HAAR_L1) {
         if (zf_op_prepare(s->env, desc->op_taps, (int)desc->op_k, desc->op_h, desc->op_w, s->stream, &s->op_plan, &s->op_buf, &s->op_taps, &s->op_sep) != ZF_OK) {
             zf_solver_free_all(s);
             delete s;
@@ -785,31 +724,18 @@ static int zf_solver_create_impl(zf_solver** out, const zf_problem_desc* desc, c
         ZF_TRY(hipMalloc(&s->ls_cnt, 64));
         ZF_TRY(hipMemsetAsync(s->ls_cnt, 0, 64, s->stream));
     }
-    if (zf_is_sparse_mat(desc->kind)) {   // what the dense kind takes, minus the slab, plus the segment sums of split rows
+    if (zf_is_sparse_mat(desc->kind)) {   // the segment sums of split rows, where the dense kind has its slab
         // (per solver: solves that share a matrix handle may run at the same time on other streams)
         // (K responses: a segment holds K sums)
-        if (sp->A.nseg > 0) ZF_TRY(hipMalloc(&s->sp_part_A, sizeof(double) * sp->A.nseg * K));
-        if (sp->At.nseg > 0) ZF_TRY(hipMalloc(&s->sp_part_At, sizeof(double) * sp->At.nseg * K));
-        const int64_t m_pad = (desc->m_rows + 63) & ~int64_t(63);
-        ZF_TRY(hipMalloc(&s->grad, sizeof(double) * n_pad));
-        ZF_TRY(hipMalloc(&s->sbuf, sizeof(double) * 3 * m_pad));
-        for (int k = 0; k < 3; ++k) s->sring.p[k] = s->sbuf + k * m_pad;
-        ZF_TRY(hipMalloc(&s->resid, sizeof(double) * m_pad));
-        ZF_TRY(hipMalloc(&s->ls_scal, sizeof(double) * 8));
+        if (sp->A.nseg > 0) ZF_TRY(hipMalloc(&s->ws.part_A, sizeof(double) * sp->A.nseg * K));
+        if (sp->At.nseg > 0) ZF_TRY(hipMalloc(&s->ws.part_At, sizeof(double) * sp->At.nseg * K));
         // chunk sums of |r(y)|^2 and of |s+ - b|^2 (logistic: of the two losses); ZF_ACCEPT_REMAINDER: and of |s+ - s_y|^2
         ZF_TRY(hipMalloc(&s->row_part, sizeof(double) * 3 * ZF_SPMV_RESID_MAX_CHUNKS));
     }
     if (zf_is_dense_mat(desc->kind)) {
         const int64_t m = desc->m_rows;
-        const int64_t m_pad = (m + 63) & ~int64_t(63);
-        zf_dense_slices(m, n, &s->slices, &s->rows_per_slice);
-        s->gemv_mfma = (n % 32 == 0) && s->env.gemv_mfma;
-        ZF_TRY(hipMalloc(&s->grad, sizeof(double) * n_pad));
-        ZF_TRY(hipMalloc(&s->sbuf, sizeof(double) * 3 * m_pad));
-        for (int k = 0; k < 3; ++k) s->sring.p[k] = s->sbuf + k * m_pad;
-        ZF_TRY(hipMalloc(&s->resid, sizeof(double) * m_pad));
-        ZF_TRY(hipMalloc(&s->slab, sizeof(double) * s->slices * n));
-        ZF_TRY(hipMalloc(&s->ls_scal, sizeof(double) * 8));
+        zf_view_slices(s->mat, &s->ws.slices, &s->ws.rows_per_slice);
+        ZF_TRY(hipMalloc(&s->ws.slab, sizeof(double) * s->ws.slices * n));
         if (desc->world > 1) {   // exchanged vector: A_p x_p (m) for column blocks, A_p^T r_p (n) for row blocks
             const int64_t len = desc->row_sharded ? n : m;
             ZF_TRY(hipMalloc(&s->s_part, sizeof(double) * ((len + 63) & ~int64_t(63))));
@@ -1314,6 +1240,282 @@ static int zf_launch_ahead(zf_solver* s, zf_step_args a, const zf_control& befor
     return ZF_OK;
 }
 
+// ---- one trial, by problem kind (zf_launch_trial: the shared prologue and the dispatch) ----
+// the separable problem: chains of trials in registers, passes that run ahead of their predecessor's decision
+static int zf_trial_diag(zf_solver* s, zf_step_args& a, bool decide_in_launch, bool dry, bool* done_ahead, hipEvent_t e0, hipEvent_t e1) {
+    const zf_problem_desc& d = s->desc;
+    a.p0 = d.d;
+    a.p1 = d.c;
+    if (!dry) {
+        // the pass finalises itself (zf_pass_tail): packs, and - unsharded - the decide pass, in the same launch
+        a.fin_mode = 1;
+        zf_fin_groups(s->grid, &a.fin_gsz, &a.fin_ng);
+        a.grp_part = s->grp_part;
+        a.fin_cnt = s->fin_cnt;
+        a.fin_scale_f = 0.5;   // f = 0.5 * sum(d (x-c)^2)
+        a.fin_scale_g = d.lam; // g = lam * sum|x|
+        a.pack = s->pack_local;
+        a.ctl_rw = s->ctl;
+        a.decide = (d.world == 1 && decide_in_launch) ? 1 : 0;
+        a.trace = s->trace;
+        s->pass_seq = s->pass_seq >= 0x7ffffff0 ? 1 : s->pass_seq + 1;
+        a.pass_seq = s->pass_seq;
+    }
+    zf_control before;
+    // passes that run ahead of their predecessor's decision: at workgroup granularity (unsharded one-round grids), or
+    // at kernel granularity (through the library's communicator; ZF_AHEAD_UNSHARDED: other unsharded grids)
+    const bool two_streams = s->stream2 != nullptr && !dry && !s->hist && s->shadow_valid;
+    // (behind a communicator only from zf_solver_enqueue_steps, which hands over done_ahead: a caller that drives trial /
+    //  exchange / decide itself - zf_solver_enqueue_trial - gets one pass at a time, whatever is attached)
+    const bool ra_can = two_streams && s->ra && !s->ra_off &&
+                        (s->comm ? (!decide_in_launch && done_ahead != nullptr && s->ra_sharded && s->stream3 != nullptr) : decide_in_launch);
+    // (unsharded: what the run-ahead kernel does not take - grids of several rounds, clipped problems, and on its own
+    //  grids the mid chains of a shared tail)
+    const bool ah_can = two_streams && s->ah && s->ring >= 6 &&
+                        (s->comm ? (!decide_in_launch && done_ahead != nullptr) : (decide_in_launch && s->ah_unsharded && d.world == 1));
+    const bool have_before = ra_can || ah_can;
+    if (have_before) before = s->shadow;
+    s->part_mask = (dry || !(decide_in_launch || s->comm)) ? ZF_K_ALL : zf_predict_parts(s);
+    // the ONE kernel the shadow predicts (not a pair behind a chunk that saw rejections), nothing lagging
+    const bool exact = have_before && before.status == ZF_RUNNING && before.lag == 0 && before.pend_status == 0 &&
+                       before.ring_size == s->ring;
+    const int nf_before = exact ? zf_fresh_len(&before) : 0;
+    bool ra_ok = ra_can && exact && s->part_mask == ZF_K_FULL && nf_before == s->sub && s->grid <= s->ra_cap;
+    // A mid chain (the passes of a tail shared by two passes, the tail itself): its own kernel, its own capacity.  Behind a
+    // pass of the same run it always runs ahead (the alternative joins the two streams first).  A run that STARTS with
+    // one - blocks of K = 20: 10 + 10 - pays only in the middle of the one-round sizes (profiles/r05_runahead_mid_k20_by_size.jsonl:
+    // n = 4e6 .. 1e7 +2-3 %, with bench.py's events +4-7 %): below, two launches on one stream cost less than the fork and
+    // join of two; above, the chain of <= 10 trials is HBM-bound and its per-pass kernel loads through registers, 4 % faster
+    // than the DMA pipeline the coherent loads need.
+    const bool mid_run = (s->run_mode == 1 || s->run_mode == 3) && s->ra_last != 0;
+    if (ra_can && exact && !ra_ok && s->part_mask == ZF_K_MID && nf_before == s->mid_len && nf_before < ZF_MAX_SUB_ITERS &&
+        (mid_run || (s->tiles >= ZF_RA_MID_START_MIN_TILES && s->tiles <= ZF_RA_MID_START_MAX_TILES))) {
+        int& cap = s->ra_cap_mid[nf_before];
+        if (cap < 0) cap = zf_runahead_capacity(zf_sel_of(s), nf_before);
+        ra_ok = cap > 0 && s->grid <= cap;
+    }
+    const bool ah_ok = ah_can && !ra_ok && exact && ((s->part_mask == ZF_K_FULL && nf_before == s->sub) ||
+                                                      (s->part_mask == ZF_K_MID && nf_before == s->mid_len));
+    if (s->stream2 && a.pass_seq == 1 && !dry) {   // (the step counter started or wrapped: sequence numbers are compared)
+        int rc = zf_ra_join(s);
+        if (rc) return rc;
+        ZF_HIP(hipMemsetAsync(s->ra_word, 0, 128, s->stream));
+        ZF_HIP(hipMemsetAsync(s->ra_flags, 0, sizeof(unsigned) * (s->max_grid + 32), s->stream));
+        // (the second stream must not find the flags of the numbers before the wrap: they satisfy every wait)
+        ZF_HIP(hipEventRecord(s->ra_fork, s->stream));
+        ZF_HIP(hipStreamWaitEvent(s->stream2, s->ra_fork, 0));
+    }
+    if (!dry) {
+        s->steps_since_poll += 1;
+        const int shapes = s->part_mask & (s->sub >= 16 ? 31 : s->sub > 1 ? 3 : 1);
+        s->steps_issued += 1;
+        s->kernels_issued += __builtin_popcount(shapes);
+    }
+    if (ra_ok) {
+        int rc = zf_launch_runahead(s, a, before, nf_before, e0, e1);
+        if (rc) return rc;
+        if (s->comm && done_ahead) *done_ahead = true;   // (exchange and decide step are enqueued: third stream)
+    } else if (ah_ok) {
+        int rc = zf_launch_ahead(s, a, before, s->part_mask == ZF_K_FULL ? 0 : 3, nf_before, e0, e1);
+        if (rc) return rc;
+        if (done_ahead) *done_ahead = true;
+    } else {
+        if (s->stream2) {
+            int rc = zf_ra_join(s);
+            if (rc) return rc;
+        }
+        if (e0) ZF_HIP(hipEventRecord(e0, s->stream));
+        zf_launch_trial_kernels(s, a, true);
+        if (e1) ZF_HIP(hipEventRecord(e1, s->stream));
+    }
+    s->part_mask = ZF_K_ALL;
+    ZF_HIP(hipGetLastError());
+    return ZF_OK;
+}
+
+// cache-resident A: the whole trial in two launches (zf_kernels_ls_small.h)
+static int zf_trial_ls_small(zf_solver* s, const zf_step_args& a, hipEvent_t e0, hipEvent_t e1) {
+    const zf_problem_desc& d = s->desc;
+    zf_ls_small_args P;
+    P.ctl = s->ctl;
+    P.beta_ring = s->beta_ring;
+    for (int k = 0; k < 3; ++k) P.xb[k] = s->xb[k];
+    P.sring = s->sring;
+    P.A = d.A;
+    P.b = d.b;
+    P.m = d.m_rows;
+    P.n = d.n;
+    P.scale = d.scale;
+    P.lam = d.lam;
+    P.lo = d.box_lo;
+    P.hi = d.box_hi;
+    P.ls_scal = s->ls_scal;
+    P.blk_part = s->blk_part;
+    P.grid_step = (int)(d.n / LS_SMALL_COLS);
+    P.row_part = s->row_part;
+    P.row_part_r = s->row_part + (d.m_rows + ZF_WAVES - 1) / ZF_WAVES;
+    P.cnt = s->ls_cnt;
+    P.pack = s->pack_local;
+    P.trace = s->trace;
+    P.hist = s->hist;
+    P.hist_cap = s->hist_cap > 0 ? s->hist_cap : 1;
+    P.hist_stride = s->hist_stride;
+    P.pass_log = a.pass_log;
+    P.pass_slot = a.pass_slot;
+    P.pass_tag = a.pass_tag;
+    const bool nest = s->opt.nesterov != 0;
+    dim3 gs(P.grid_step), gr((unsigned)((d.m_rows + ZF_WAVES - 1) / ZF_WAVES)), b(ZF_BLOCK);
+    if (e0) ZF_HIP(hipEventRecord(e0, s->stream));
+    if (nest && s->box) hipLaunchKernelGGL((zf_ls_small_step_kernel<true, true>), gs, b, 0, s->stream, P);
+    else if (nest) hipLaunchKernelGGL((zf_ls_small_step_kernel<true, false>), gs, b, 0, s->stream, P);
+    else if (s->box) hipLaunchKernelGGL((zf_ls_small_step_kernel<false, true>), gs, b, 0, s->stream, P);
+    else hipLaunchKernelGGL((zf_ls_small_step_kernel<false, false>), gs, b, 0, s->stream, P);
+    if (e1) ZF_HIP(hipEventRecord(e1, s->stream));
+    if (s->rem) hipLaunchKernelGGL(zf_ls_small_rows_kernel<true>, gr, b, 0, s->stream, P);
+    else hipLaunchKernelGGL(zf_ls_small_rows_kernel<false>, gr, b, 0, s->stream, P);
+    ZF_HIP(hipGetLastError());
+    return ZF_OK;
+}
+
+// the blur o inverse-Haar operator
+static int zf_trial_op(zf_solver* s, zf_step_args& a, bool decide_in_launch, hipEvent_t e0, hipEvent_t e1) {
+    const zf_problem_desc& d = s->desc;
+    const int64_t m = d.m_rows;
+    // TWO launches per trial (unsharded, deciding in the launch): the adjoint kernel - the residual at y formed in its
+    // tile load, the PROX STEP in its epilogue (round 5; ZF_OP_FUSE_PROX=0 or a history ring: a launch of its own
+    // in between) - and s+ = B W^-1 x+ whose last workgroup sums f(y), f(x+) and the prox step's partials and decides
+    // (zf_op_fuse) - instead of resid_y / adjoint / prox / apply / resid_x / finalize
+    zf_op_fuse F;
+    memset(&F, 0, sizeof(F));
+    F.on = 1;
+    F.b = d.b;
+    for (int k = 0; k < 3; ++k) F.sk[k] = s->sring.p[k];
+    F.scale = d.scale;
+    F.lam = d.lam;
+    F.nesterov = s->opt.nesterov;
+    F.part_y = s->row_part;
+    F.part_x = s->row_part + s->op_plan.grid;
+    F.cnt = s->ls_cnt;
+    F.blk_part = s->blk_part;
+    F.grid_step = s->grid;
+    F.ls_scal = s->ls_scal;
+    F.pack = s->pack_local;
+    F.ctl_rw = s->ctl;
+    F.trace = s->trace;
+    F.beta_ring = s->beta_ring;
+    // (images whose six arrays - x_k, x_{k-1}, x+, the two cached B W^-1 x, b - no longer fit the 256 MB of memory-side
+    //  cache gain nothing: 3072^2 and 4096^2 -0.3 ... -0.7 %, the epilogue's 256-byte pieces of four coefficient
+    //  quadrants go to HBM at 0.56 of peak where the separate step streams at 0.74; up to 2048^2: +6 ... +16 %,
+    //  profiles/r05_operator_fuse_prox_ab.txt)
+    const bool fuse_prox = s->op_plan.fuse_prox && decide_in_launch && !s->hist;
+    if (fuse_prox) {
+        F.prox = 1;
+        F.box = s->box ? 1 : 0;
+        F.lo = d.box_lo;
+        F.hi = d.box_hi;
+        for (int k = 0; k < 3; ++k) F.xb[k] = s->xb[k];
+        F.step_part = s->blk_part;
+        F.grid_step = s->op_plan.grid;
+        F.pass_log = a.pass_log;
+        F.pass_slot = a.pass_slot;
+        F.pass_tag = a.pass_tag;
+        if (e0) ZF_HIP(hipEventRecord(e0, s->stream));
+        zf_launch_op_adjoint(s->op_plan, s->stream, zf_op_of(s, s->ctl), nullptr, s->grad, 2 * d.scale, F);
+        if (e1) ZF_HIP(hipEventRecord(e1, s->stream));
+    } else {
+        zf_launch_op_adjoint(s->op_plan, s->stream, zf_op_of(s, s->ctl), nullptr, s->grad, 2 * d.scale, F);
+        a.p0 = s->grad;
+        a.p1 = nullptr;
+        if (e0) ZF_HIP(hipEventRecord(e0, s->stream));
+        zf_launch_trial_kernels(s, a, false);
+        if (e1) ZF_HIP(hipEventRecord(e1, s->stream));
+    }
+    if (decide_in_launch) {
+        zf_launch_op_apply(s->op_plan, s->stream, zf_op_of(s, s->ctl), s->xb[0], s->xb[1], s->xb[2], s->sring.p[0], s->sring.p[1],
+                           s->sring.p[2], 1, F);
+    } else {   // (a host-driven step sequence: s+, f(x+) and the finalize launch as for a matrix)
+        zf_ring3 xr3 = {{s->xb[0], s->xb[1], s->xb[2]}};
+        zf_launch_apply_A(s, s->ctl, xr3, s->sring, 1);
+        hipLaunchKernelGGL(zf_resid_x_kernel, dim3(1), dim3(RESID_BLOCK), 0, s->stream, s->ctl, s->sring, 1, d.b,
+                           d.scale, m, s->ls_scal + 1);
+        zf_launch_finalize(s, false);
+    }
+    ZF_HIP(hipGetLastError());
+    return ZF_OK;
+}
+
+// the matrix kinds, dense and CSR, on the two sweeps of zf_matview.h: loss at y, adjoint, prox step, A x+, loss at x+, finalize
+static int zf_trial_matrix(zf_solver* s, zf_step_args& a, bool decide_in_launch, hipEvent_t e0, hipEvent_t e1) {
+    const zf_problem_desc& d = s->desc;
+    const int64_t m = d.m_rows;
+    // (the sparse kind times the whole trial - the event pair brackets every launch of it; the dense kind the prox step alone)
+    const bool time_whole = s->mat.csr;
+    // every loss but the unweighted squared one: psi(y), f(y) and f(x+) from its rows kernels, grad = gfac A^T psi by the same sweeps
+    const zf_loss loss = zf_loss_of(s);
+    const double gfac = zf_gfac(loss, d.scale);
+    if (time_whole && e0) ZF_HIP(hipEventRecord(e0, s->stream));
+    // (1) r = A y - b by linearity, f(y); grad = 2 scale A^T r   [only when y changed]
+    // (sparse matrices have 1e5 .. 1e7 rows: beyond what one workgroup should walk, the residuals take many - zf_kernels_spmv.h)
+    // (K responses: m is m K rows of the interleaved margins - the same threshold on the same count, so the order of f is a
+    //  function of the row count alone)
+    const bool wide_resid = (d.kind == ZF_PROBLEM_SPARSE_LS_L1 || (s->mat.k > 1 && d.kind == ZF_PROBLEM_LEAST_SQUARES_L1)) &&
+                            m > ZF_SPMV_WIDE_RESID_MIN_ROWS;
+    if (!zf_launch_loss_y(s->stream, s->ctl, s->sring.p[0], s->sring.p[1], s->sring.p[2], d.b, loss, s->resid, d.scale, m,
+                          (int)s->opt.nesterov, s->row_part, s->ls_scal + 0)) {
+        if (wide_resid)
+            zf_launch_spmv_resid_y(s->stream, s->ctl, s->sring.p[0], s->sring.p[1], s->sring.p[2], d.b, s->resid, d.scale, m,
+                                   (int)s->opt.nesterov, s->row_part, s->ls_scal + 0);
+        else
+            hipLaunchKernelGGL(zf_resid_y_kernel, dim3(1), dim3(RESID_BLOCK), 0, s->stream, s->ctl, s->beta_ring, s->sring, d.b,
+                               s->resid, d.scale, m, s->ls_scal + 0, (int)s->opt.nesterov);
+    }
+    // (row blocks: this rank's part 2 scale A_p^T r_p goes to s_part, its combine unguarded; the caller gathers the parts
+    //  and zf_solver_enqueue_trial_finish() adds them and runs the rest of the trial)
+    const bool rows = d.world > 1 && d.row_sharded;
+    zf_launch_adjoint(s->mat, s->stream, s->ctl, s->resid, rows ? s->s_part : s->grad, gfac, s->ws, !rows);
+    if (rows) {
+        // (the prox step of a row-sharded trial runs in zf_solver_enqueue_trial_finish, after the exchange: the
+        //  event pair and the log slot taken by zf_launch_trial belong to a launch that does not happen here - give them
+        //  back, or zf_collect_timing would read events that were never recorded)
+        if (s->timing) {
+            s->ev_used -= 1;
+            if (a.pass_log) s->launches -= 1;
+        }
+        ZF_HIP(hipGetLastError());
+        return ZF_OK;
+    }
+    // (2) fused prox step with the gradient vector in HBM
+    a.p0 = s->grad;
+    a.p1 = nullptr;
+    if (!time_whole && e0) ZF_HIP(hipEventRecord(e0, s->stream));
+    zf_launch_trial_kernels(s, a, false);
+    if (!time_whole && e1) ZF_HIP(hipEventRecord(e1, s->stream));
+    // (3) s+ = A x+ ; f(x+).  Sharded x (column blocks): this rank's A_p x_p+ goes to
+    // s_part; the caller gathers the parts and zf_solver_enqueue_trial_finish() adds them.
+    zf_ring3 xr = {{s->xb[0], s->xb[1], s->xb[2]}};
+    zf_ring3 sout = s->sring;
+    if (d.world > 1) sout = {{s->s_part, s->s_part, s->s_part}};   // (column blocks; row blocks returned above)
+    zf_launch_apply(s->mat, s->stream, s->ctl, xr, sout, 1, s->ws);
+    if (d.world == 1) {
+        if (!zf_launch_loss_x(s->stream, s->ctl, s->sring.p[0], s->sring.p[1], s->sring.p[2], 1, d.b, loss, d.scale, m,
+                              s->row_part + ZF_SPMV_RESID_MAX_CHUNKS, s->ls_scal + 1)) {
+            if (wide_resid && s->rem && s->mat.csr)   // (ZF_ACCEPT_REMAINDER beyond the threshold: the sparse kind only)
+                zf_launch_spmv_resid_x_rem(s->stream, s->ctl, s->sring.p[0], s->sring.p[1], s->sring.p[2], 1, d.b, d.scale, m,
+                                           (int)s->opt.nesterov, 0.0, s->row_part + ZF_SPMV_RESID_MAX_CHUNKS,
+                                           s->row_part + 2 * ZF_SPMV_RESID_MAX_CHUNKS, s->ls_scal + 1, s->ls_scal + 2);
+            else if (wide_resid)   // (the sparse kind, or K responses, beyond the threshold)
+                zf_launch_spmv_resid_x(s->stream, s->ctl, s->sring.p[0], s->sring.p[1], s->sring.p[2], 1, d.b, d.scale, m,
+                                       s->row_part + ZF_SPMV_RESID_MAX_CHUNKS, s->ls_scal + 1);
+            else
+                zf_launch_resid_x(s);
+        }
+        zf_launch_finalize(s, decide_in_launch);
+    }
+    if (time_whole && e1) ZF_HIP(hipEventRecord(e1, s->stream));
+    ZF_HIP(hipGetLastError());
+    return ZF_OK;
+}
+
 // returns in *done_ahead (if given) whether the step was a pass ahead: tail, exchange and decide are then enqueued too
 static int zf_launch_trial(zf_solver* s, bool decide_in_launch, bool dry = false, bool* done_ahead = nullptr) {
     const zf_problem_desc& d = s->desc;
@@ -1338,318 +1540,10 @@ static int zf_launch_trial(zf_solver* s, bool decide_in_launch, bool dry = false
         e1 = s->ev_pool[s->ev_used].second;
         s->ev_used++;
     }
-    if (d.kind == ZF_PROBLEM_DIAG_QUAD_L1) {
-        a.p0 = d.d;
-        a.p1 = d.c;
-        if (!dry) {
-            // the pass finalises itself (zf_pass_tail): packs, and - unsharded - the decide pass, in the same launch
-            a.fin_mode = 1;
-            zf_fin_groups(s->grid, &a.fin_gsz, &a.fin_ng);
-            a.grp_part = s->grp_part;
-            a.fin_cnt = s->fin_cnt;
-            a.fin_scale_f = 0.5;   // f = 0.5 * sum(d (x-c)^2)
-            a.fin_scale_g = d.lam; // g = lam * sum|x|
-            a.pack = s->pack_local;
-            a.ctl_rw = s->ctl;
-            a.decide = (d.world == 1 && decide_in_launch) ? 1 : 0;
-            a.trace = s->trace;
-            s->pass_seq = s->pass_seq >= 0x7ffffff0 ? 1 : s->pass_seq + 1;
-            a.pass_seq = s->pass_seq;
-        }
-        zf_control before;
-        // passes that run ahead of their predecessor's decision: at workgroup granularity (unsharded one-round grids), or
-        // at kernel granularity (through the library's communicator; ZF_AHEAD_UNSHARDED: other unsharded grids)
-        const bool two_streams = s->stream2 != nullptr && !dry && !s->hist && s->shadow_valid;
-        // (behind a communicator only from zf_solver_enqueue_steps, which hands over done_ahead: a caller that drives trial /
-        //  exchange / decide itself - zf_solver_enqueue_trial - gets one pass at a time, whatever is attached)
-        const bool ra_can = two_streams && s->ra && !s->ra_off &&
-                            (s->comm ? (!decide_in_launch && done_ahead != nullptr && s->ra_sharded && s->stream3 != nullptr) : decide_in_launch);
-        // (unsharded: what the run-ahead kernel does not take - grids of several rounds, clipped problems, and on its own
-        //  grids the mid chains of a shared tail)
-        const bool ah_can = two_streams && s->ah && s->ring >= 6 &&
-                            (s->comm ? (!decide_in_launch && done_ahead != nullptr) : (decide_in_launch && s->ah_unsharded && d.world == 1));
-        const bool have_before = ra_can || ah_can;
-        if (have_before) before = s->shadow;
-        s->part_mask = (dry || !(decide_in_launch || s->comm)) ? ZF_K_ALL : zf_predict_parts(s);
-        // the ONE kernel the shadow predicts (not a pair behind a chunk that saw rejections), nothing lagging
-        const bool exact = have_before && before.status == ZF_RUNNING && before.lag == 0 && before.pend_status == 0 &&
-                           before.ring_size == s->ring;
-        const int nf_before = exact ? zf_fresh_len(&before) : 0;
-        bool ra_ok = ra_can && exact && s->part_mask == ZF_K_FULL && nf_before == s->sub && s->grid <= s->ra_cap;
-        // A mid chain (the passes of a tail shared by two passes, the tail itself): its own kernel, its own capacity.  Behind a
-        // pass of the same run it always runs ahead (the alternative joins the two streams first).  A run that STARTS with
-        // one - blocks of K = 20: 10 + 10 - pays only in the middle of the one-round sizes (profiles/r05_runahead_mid_k20_by_size.jsonl:
-        // n = 4e6 .. 1e7 +2-3 %, with bench.py's events +4-7 %): below, two launches on one stream cost less than the fork and
-        // join of two; above, the chain of <= 10 trials is HBM-bound and its per-pass kernel loads through registers, 4 % faster
-        // than the DMA pipeline the coherent loads need.
-        const bool mid_run = (s->run_mode == 1 || s->run_mode == 3) && s->ra_last != 0;
-        if (ra_can && exact && !ra_ok && s->part_mask == ZF_K_MID && nf_before == s->mid_len && nf_before < ZF_MAX_SUB_ITERS &&
-            (mid_run || (s->tiles >= ZF_RA_MID_START_MIN_TILES && s->tiles <= ZF_RA_MID_START_MAX_TILES))) {
-            int& cap = s->ra_cap_mid[nf_before];
-            if (cap < 0) cap = zf_runahead_capacity(zf_sel_of(s), nf_before);
-            ra_ok = cap > 0 && s->grid <= cap;
-        }
-        const bool ah_ok = ah_can && !ra_ok && exact && ((s->part_mask == ZF_K_FULL && nf_before == s->sub) ||
-                                                          (s->part_mask == ZF_K_MID && nf_before == s->mid_len));
-        if (s->stream2 && a.pass_seq == 1 && !dry) {   // (the step counter started or wrapped: sequence numbers are compared)
-            int rc = zf_ra_join(s);
-            if (rc) return rc;
-            ZF_HIP(hipMemsetAsync(s->ra_word, 0, 128, s->stream));
-            ZF_HIP(hipMemsetAsync(s->ra_flags, 0, sizeof(unsigned) * (s->max_grid + 32), s->stream));
-            // (the second stream must not find the flags of the numbers before the wrap: they satisfy every wait)
-            ZF_HIP(hipEventRecord(s->ra_fork, s->stream));
-            ZF_HIP(hipStreamWaitEvent(s->stream2, s->ra_fork, 0));
-        }
-        if (!dry) {
-            s->steps_since_poll += 1;
-            const int shapes = s->part_mask & (s->sub >= 16 ? 31 : s->sub > 1 ? 3 : 1);
-            s->steps_issued += 1;
-            s->kernels_issued += __builtin_popcount(shapes);
-        }
-        if (ra_ok) {
-            int rc = zf_launch_runahead(s, a, before, nf_before, e0, e1);
-            if (rc) return rc;
-            if (s->comm && done_ahead) *done_ahead = true;   // (exchange and decide step are enqueued: third stream)
-        } else if (ah_ok) {
-            int rc = zf_launch_ahead(s, a, before, s->part_mask == ZF_K_FULL ? 0 : 3, nf_before, e0, e1);
-            if (rc) return rc;
-            if (done_ahead) *done_ahead = true;
-        } else {
-            if (s->stream2) {
-                int rc = zf_ra_join(s);
-                if (rc) return rc;
-            }
-            if (e0) ZF_HIP(hipEventRecord(e0, s->stream));
-            zf_launch_trial_kernels(s, a, true);
-            if (e1) ZF_HIP(hipEventRecord(e1, s->stream));
-        }
-        s->part_mask = ZF_K_ALL;
-    } else if (s->ls_small && !dry && decide_in_launch) {
-        // cache-resident A: the whole trial in two launches (zf_kernels_ls_small.h)
-        zf_ls_small_args P;
-        P.ctl = s->ctl;
-        P.beta_ring = s->beta_ring;
-        for (int k = 0; k < 3; ++k) P.xb[k] = s->xb[k];
-        P.sring = s->sring;
-        P.A = d.A;
-        P.b = d.b;
-        P.m = d.m_rows;
-        P.n = d.n;
-        P.scale = d.scale;
-        P.lam = d.lam;
-        P.lo = d.box_lo;
-        P.hi = d.box_hi;
-        P.ls_scal = s->ls_scal;
-        P.blk_part = s->blk_part;
-        P.grid_step = (int)(d.n / LS_SMALL_COLS);
-        P.row_part = s->row_part;
-        P.row_part_r = s->row_part + (d.m_rows + ZF_WAVES - 1) / ZF_WAVES;
-        P.cnt = s->ls_cnt;
-        P.pack = s->pack_local;
-        P.trace = s->trace;
-        P.hist = s->hist;
-        P.hist_cap = s->hist_cap > 0 ? s->hist_cap : 1;
-        P.hist_stride = s->hist_stride;
-        P.pass_log = a.pass_log;
-        P.pass_slot = a.pass_slot;
-        P.pass_tag = a.pass_tag;
-        const bool nest = s->opt.nesterov != 0;
-        dim3 gs(P.grid_step), gr((unsigned)((d.m_rows + ZF_WAVES - 1) / ZF_WAVES)), b(ZF_BLOCK);
-        if (e0) ZF_HIP(hipEventRecord(e0, s->stream));
-        if (nest && s->box) hipLaunchKernelGGL((zf_ls_small_step_kernel<true, true>), gs, b, 0, s->stream, P);
-        else if (nest) hipLaunchKernelGGL((zf_ls_small_step_kernel<true, false>), gs, b, 0, s->stream, P);
-        else if (s->box) hipLaunchKernelGGL((zf_ls_small_step_kernel<false, true>), gs, b, 0, s->stream, P);
-        else hipLaunchKernelGGL((zf_ls_small_step_kernel<false, false>), gs, b, 0, s->stream, P);
-        if (e1) ZF_HIP(hipEventRecord(e1, s->stream));
-        if (s->rem) hipLaunchKernelGGL(zf_ls_small_rows_kernel<true>, gr, b, 0, s->stream, P);
-        else hipLaunchKernelGGL(zf_ls_small_rows_kernel<false>, gr, b, 0, s->stream, P);
-    } else {
-        const int64_t n = d.n, m = d.m_rows;
-        const int V = (n % 2 == 0) ? 2 : 1;
-        // (the sparse kind times the whole trial - the event pair brackets every launch of it, not the prox step alone)
-        const bool time_whole = zf_is_sparse_mat(d.kind);
-        // every loss but the unweighted squared one: psi(y), f(y) and f(x+) from its rows kernels, grad = gfac A^T psi by the same sweeps
-        const zf_loss loss = zf_loss_of(s);
-        const double gfac = zf_gfac(loss, d.scale);
-        if (time_whole && e0) ZF_HIP(hipEventRecord(e0, s->stream));
-        // (1) r = A y - b by linearity, f(y); grad = 2 scale A^T r   [only when y changed]
-        // (sparse matrices have 1e5 .. 1e7 rows: beyond what one workgroup should walk, the residuals take many - zf_kernels_spmv.h)
-        // (K responses: m is m K rows of the interleaved margins - the same threshold on the same count, so the order of f is a
-        //  function of the row count alone)
-        const bool wide_resid = (d.kind == ZF_PROBLEM_SPARSE_LS_L1 || (s->K > 1 && d.kind == ZF_PROBLEM_LEAST_SQUARES_L1)) &&
-                                m > ZF_SPMV_WIDE_RESID_MIN_ROWS;
-        if (!zf_launch_loss_y(s->stream, s->ctl, s->sring.p[0], s->sring.p[1], s->sring.p[2], d.b, loss, s->resid, d.scale, m,
-                              (int)s->opt.nesterov, s->row_part, s->ls_scal + 0)) {
-            if (wide_resid)
-                zf_launch_spmv_resid_y(s->stream, s->ctl, s->sring.p[0], s->sring.p[1], s->sring.p[2], d.b, s->resid, d.scale, m,
-                                       (int)s->opt.nesterov, s->row_part, s->ls_scal + 0);
-            else if (d.kind != ZF_PROBLEM_BLUR_HAAR_L1)   // (the operator problem forms r inside its adjoint kernel)
-                hipLaunchKernelGGL(zf_resid_y_kernel, dim3(1), dim3(RESID_BLOCK), 0, s->stream, s->ctl,
-                                   s->beta_ring, s->sring, d.b, s->resid, d.scale, m, s->ls_scal + 0,
-                                   (int)s->opt.nesterov);
-        }
-        const int64_t nv = n / V;
-        dim3 gT((unsigned)((nv + ZF_BLOCK - 1) / ZF_BLOCK), (unsigned)s->slices);
-        if (d.kind == ZF_PROBLEM_BLUR_HAAR_L1) {
-            // TWO launches per trial (unsharded, deciding in the launch): the adjoint kernel - the residual at y formed in its
-            // tile load, the PROX STEP in its epilogue (round 5; ZF_OP_FUSE_PROX=0 or a history ring: a launch of its own
-            // in between) - and s+ = B W^-1 x+ whose last workgroup sums f(y), f(x+) and the prox step's partials and decides
-            // (zf_op_fuse) - instead of resid_y / adjoint / prox / apply / resid_x / finalize
-            zf_op_fuse F;
-            memset(&F, 0, sizeof(F));
-            F.on = 1;
-            F.b = d.b;
-            for (int k = 0; k < 3; ++k) F.sk[k] = s->sring.p[k];
-            F.scale = d.scale;
-            F.lam = d.lam;
-            F.nesterov = s->opt.nesterov;
-            F.part_y = s->row_part;
-            F.part_x = s->row_part + s->op_plan.grid;
-            F.cnt = s->ls_cnt;
-            F.blk_part = s->blk_part;
-            F.grid_step = s->grid;
-            F.ls_scal = s->ls_scal;
-            F.pack = s->pack_local;
-            F.ctl_rw = s->ctl;
-            F.trace = s->trace;
-            F.beta_ring = s->beta_ring;
-            // (images whose six arrays - x_k, x_{k-1}, x+, the two cached B W^-1 x, b - no longer fit the 256 MB of memory-side
-            //  cache gain nothing: 3072^2 and 4096^2 -0.3 ... -0.7 %, the epilogue's 256-byte pieces of four coefficient
-            //  quadrants go to HBM at 0.56 of peak where the separate step streams at 0.74; up to 2048^2: +6 ... +16 %,
-            //  profiles/r05_operator_fuse_prox_ab.txt)
-            const bool fuse_prox = s->op_plan.fuse_prox && decide_in_launch && !s->hist;
-            if (fuse_prox) {
-                F.prox = 1;
-                F.box = s->box ? 1 : 0;
-                F.lo = d.box_lo;
-                F.hi = d.box_hi;
-                for (int k = 0; k < 3; ++k) F.xb[k] = s->xb[k];
-                F.step_part = s->blk_part;
-                F.grid_step = s->op_plan.grid;
-                F.pass_log = a.pass_log;
-                F.pass_slot = a.pass_slot;
-                F.pass_tag = a.pass_tag;
-                if (e0) ZF_HIP(hipEventRecord(e0, s->stream));
-                zf_launch_op_adjoint(s->op_plan, s->stream, zf_op_of(s, s->ctl), nullptr, s->grad, 2 * d.scale, F);
-                if (e1) ZF_HIP(hipEventRecord(e1, s->stream));
-            } else {
-                zf_launch_op_adjoint(s->op_plan, s->stream, zf_op_of(s, s->ctl), nullptr, s->grad, 2 * d.scale, F);
-                a.p0 = s->grad;
-                a.p1 = nullptr;
-                if (e0) ZF_HIP(hipEventRecord(e0, s->stream));
-                zf_launch_trial_kernels(s, a, false);
-                if (e1) ZF_HIP(hipEventRecord(e1, s->stream));
-            }
-            if (decide_in_launch) {
-                zf_launch_op_apply(s->op_plan, s->stream, zf_op_of(s, s->ctl), s->xb[0], s->xb[1], s->xb[2], s->sring.p[0], s->sring.p[1],
-                                   s->sring.p[2], 1, F);
-            } else {   // (a host-driven step sequence: s+, f(x+) and the finalize launch as for a matrix)
-                zf_ring3 xr3 = {{s->xb[0], s->xb[1], s->xb[2]}};
-                zf_launch_apply_A(s, s->ctl, xr3, s->sring, 1);
-                hipLaunchKernelGGL(zf_resid_x_kernel, dim3(1), dim3(RESID_BLOCK), 0, s->stream, s->ctl, s->sring, 1, d.b,
-                                   d.scale, m, s->ls_scal + 1);
-                zf_launch_finalize(s, false);
-            }
-            ZF_HIP(hipGetLastError());
-            return ZF_OK;
-        }
-        if (zf_is_sparse_mat(d.kind)) {
-            // the trial of a dense matrix with its two sweeps swapped for the CSR row sums: grad = 2 scale A^T r over the
-            // stored A^T (only when y changed), the prox step, s+ = A x+, f(x+), finalize
-            const zf_spmv_io gio = {{s->resid, s->resid, s->resid}, {s->grad, s->grad, s->grad}};
-            if (s->K > 1) zf_launch_spmm(s->spmat->At, s->stream, s->ctl, true, gio, -1, gfac, s->K, s->sp_part_At);
-            else zf_launch_spmv(s->spmat->At, s->stream, s->ctl, true, gio, -1, gfac, s->sp_part_At);
-            a.p0 = s->grad;
-            a.p1 = nullptr;
-            zf_launch_trial_kernels(s, a, false);
-            zf_ring3 xr3 = {{s->xb[0], s->xb[1], s->xb[2]}};
-            zf_launch_apply_A(s, s->ctl, xr3, s->sring, 1);
-            if (!zf_launch_loss_x(s->stream, s->ctl, s->sring.p[0], s->sring.p[1], s->sring.p[2], 1, d.b, loss, d.scale, m,
-                                  s->row_part + ZF_SPMV_RESID_MAX_CHUNKS, s->ls_scal + 1)) {
-                if (wide_resid && s->rem)
-                    zf_launch_spmv_resid_x_rem(s->stream, s->ctl, s->sring.p[0], s->sring.p[1], s->sring.p[2], 1, d.b, d.scale, m,
-                                               (int)s->opt.nesterov, 0.0, s->row_part + ZF_SPMV_RESID_MAX_CHUNKS,
-                                               s->row_part + 2 * ZF_SPMV_RESID_MAX_CHUNKS, s->ls_scal + 1, s->ls_scal + 2);
-                else if (wide_resid)
-                    zf_launch_spmv_resid_x(s->stream, s->ctl, s->sring.p[0], s->sring.p[1], s->sring.p[2], 1, d.b, d.scale, m,
-                                           s->row_part + ZF_SPMV_RESID_MAX_CHUNKS, s->ls_scal + 1);
-                else
-                    zf_launch_resid_x(s);
-            }
-            zf_launch_finalize(s, decide_in_launch);
-            if (e1) ZF_HIP(hipEventRecord(e1, s->stream));
-            ZF_HIP(hipGetLastError());
-            return ZF_OK;
-        }
-        if (s->A32) {
-            zf_launch_cols_f32(s->stream, s->ctl, s->A32, s->resid, s->slab, m, n, s->slices, s->rows_per_slice);
-        } else if (s->K > 1) {
-            zf_launch_mr_cols(s->stream, s->ctl, d.A, s->resid, s->slab, m / s->K, n / s->K, s->K, s->slices, s->rows_per_slice);
-        } else if (s->gemv_mfma) {
-            dim3 gM((unsigned)((n + GEMVT_MFMA_COLS - 1) / GEMVT_MFMA_COLS), (unsigned)s->slices);
-            hipLaunchKernelGGL(zf_gemvT_partial_mfma_kernel, gM, dim3(ZF_BLOCK), 0, s->stream, s->ctl, d.A,
-                               s->resid, s->slab, m, n, s->rows_per_slice);
-        } else if (nv > 0) {
-            if (V == 2)
-                hipLaunchKernelGGL(zf_gemvT_partial_kernel<2>, gT, dim3(ZF_BLOCK), 0, s->stream, s->ctl,
-                                   d.A, s->resid, s->slab, m, n, s->rows_per_slice);
-            else
-                hipLaunchKernelGGL(zf_gemvT_partial_kernel<1>, gT, dim3(ZF_BLOCK), 0, s->stream, s->ctl,
-                                   d.A, s->resid, s->slab, m, n, s->rows_per_slice);
-        }
-        const bool rows = d.world > 1 && d.row_sharded;
-        // (row blocks: this rank's part 2 scale A_p^T r_p goes to s_part; the caller gathers the parts
-        //  and zf_solver_enqueue_trial_finish() adds them and runs the rest of the trial)
-        hipLaunchKernelGGL(zf_gemvT_combine_kernel, dim3(zf_grid_for(n)), dim3(ZF_BLOCK), 0, s->stream,
-                           rows ? nullptr : s->ctl, s->slab, rows ? s->s_part : s->grad, gfac, n, s->slices);
-        if (rows) {
-            // (the prox step of a row-sharded trial runs in zf_solver_enqueue_trial_finish, after the exchange: the
-            //  event pair and the log slot taken above belong to a launch that does not happen here - give them back,
-            //  or zf_collect_timing would read events that were never recorded)
-            if (s->timing) {
-                s->ev_used -= 1;
-                if (a.pass_log) s->launches -= 1;
-            }
-            ZF_HIP(hipGetLastError());
-            return ZF_OK;
-        }
-        // (2) fused prox step with the gradient vector in HBM
-        a.p0 = s->grad;
-        a.p1 = nullptr;
-        if (e0) ZF_HIP(hipEventRecord(e0, s->stream));
-        zf_launch_trial_kernels(s, a, false);
-        if (e1) ZF_HIP(hipEventRecord(e1, s->stream));
-        // (3) s+ = A x+ ; f(x+).  Sharded x (column blocks): this rank's A_p x_p+ goes to
-        // s_part; the caller gathers the parts and zf_solver_enqueue_trial_finish() adds them.
-        zf_ring3 xr = {{s->xb[0], s->xb[1], s->xb[2]}};
-        zf_ring3 sout = s->sring;
-        if (d.world > 1) sout = {{s->s_part, s->s_part, s->s_part}};   // (column blocks; row blocks returned above)
-        int gr = (int)((m + GEMV_ROWS - 1) / GEMV_ROWS);
-        if (gr > 8 * ZF_MAX_GRID) gr = 8 * ZF_MAX_GRID;
-        if (s->A32)
-            zf_launch_rows_f32(s->stream, s->ctl, s->A32, xr, sout, 1, m, n);
-        else if (s->K > 1)
-            zf_launch_mr_rows(s->stream, s->ctl, d.A, xr, sout, 1, m / s->K, n / s->K, s->K);
-        else if (V == 2)
-            hipLaunchKernelGGL(zf_gemv_rows_kernel<2>, dim3(gr), dim3(ZF_BLOCK), 0, s->stream, s->ctl, d.A,
-                               xr, sout, 1, m, n);
-        else
-            hipLaunchKernelGGL(zf_gemv_rows_kernel<1>, dim3(gr), dim3(ZF_BLOCK), 0, s->stream, s->ctl, d.A,
-                               xr, sout, 1, m, n);
-        if (d.world == 1) {
-            if (!zf_launch_loss_x(s->stream, s->ctl, s->sring.p[0], s->sring.p[1], s->sring.p[2], 1, d.b, loss, d.scale, m,
-                                  s->row_part + ZF_SPMV_RESID_MAX_CHUNKS, s->ls_scal + 1)) {
-                if (wide_resid)   // (K responses beyond the threshold; the sparse kind returned above)
-                    zf_launch_spmv_resid_x(s->stream, s->ctl, s->sring.p[0], s->sring.p[1], s->sring.p[2], 1, d.b, d.scale, m,
-                                           s->row_part + ZF_SPMV_RESID_MAX_CHUNKS, s->ls_scal + 1);
-                else
-                    zf_launch_resid_x(s);
-            }
-            zf_launch_finalize(s, decide_in_launch);
-        }
-    }
-    ZF_HIP(hipGetLastError());
-    return ZF_OK;
+    if (d.kind == ZF_PROBLEM_DIAG_QUAD_L1) return zf_trial_diag(s, a, decide_in_launch, dry, done_ahead, e0, e1);
+    if (s->ls_small && !dry && decide_in_launch) return zf_trial_ls_small(s, a, e0, e1);
+    if (d.kind == ZF_PROBLEM_BLUR_HAAR_L1) return zf_trial_op(s, a, decide_in_launch, e0, e1);
+    return zf_trial_matrix(s, a, decide_in_launch, e0, e1);
 }
 
 // sharded least squares, second half of a trial: s+ = sum over ranks of A_p x_p+ (rank
@@ -1672,16 +1566,8 @@ extern "C" int zf_solver_enqueue_trial_finish(zf_solver* s) {
         a.p0 = s->grad;
         a.p1 = nullptr;
         zf_launch_trial_kernels(s, a, false);
-        const int V = (n % 2 == 0) ? 2 : 1;
         zf_ring3 xr = {{s->xb[0], s->xb[1], s->xb[2]}};
-        int gr = (int)((m + GEMV_ROWS - 1) / GEMV_ROWS);
-        if (gr > 8 * ZF_MAX_GRID) gr = 8 * ZF_MAX_GRID;
-        if (V == 2)
-            hipLaunchKernelGGL(zf_gemv_rows_kernel<2>, dim3(gr), dim3(ZF_BLOCK), 0, s->stream, s->ctl, d.A, xr, s->sring,
-                               1, m, n);
-        else
-            hipLaunchKernelGGL(zf_gemv_rows_kernel<1>, dim3(gr), dim3(ZF_BLOCK), 0, s->stream, s->ctl, d.A, xr, s->sring,
-                               1, m, n);
+        zf_launch_apply(s->mat, s->stream, s->ctl, xr, s->sring, 1, s->ws);
         zf_launch_resid_x(s);
         zf_launch_finalize(s, false);
         ZF_HIP(hipGetLastError());
@@ -2066,7 +1952,7 @@ extern "C" int zf_solver_set_huber(zf_solver* s, double delta) {
     ZF_REQUIRE(delta > 0.0 && delta <= DBL_MAX, "zf_solver_set_huber: delta must be finite and > 0");
     ZF_REQUIRE(!s->rem, "zf_solver_set_huber: not with ZF_ACCEPT_REMAINDER (scale |A (x+ - y)|^2 is not the Taylor remainder of this loss)");
     ZF_REQUIRE(!s->poisson, "zf_solver_set_huber: the solver already has the Poisson loss (zf_solver_set_poisson)");
-    ZF_REQUIRE(s->K == 1, "zf_solver_set_huber: not with several responses (zf_solver_set_responses)");
+    ZF_REQUIRE(s->mat.k == 1, "zf_solver_set_huber: not with several responses (zf_solver_set_responses)");
     const int rc = zf_loss_part(s);
     if (rc) return rc;
     s->huber = delta;
@@ -2086,7 +1972,7 @@ extern "C" int zf_solver_set_poisson(zf_solver* s) {
     ZF_REQUIRE(!s->rem, "zf_solver_set_poisson: not with ZF_ACCEPT_REMAINDER (scale |A (x+ - y)|^2 is not the Taylor remainder of this loss)");
     ZF_REQUIRE(!s->res, "zf_solver_set_poisson: not with ZF_ACCEPT_RESOLVED");
     ZF_REQUIRE(!(s->huber > 0.0), "zf_solver_set_poisson: the solver already has Huber's loss (zf_solver_set_huber)");
-    ZF_REQUIRE(s->K == 1, "zf_solver_set_poisson: not with several responses (zf_solver_set_responses)");
+    ZF_REQUIRE(s->mat.k == 1, "zf_solver_set_poisson: not with several responses (zf_solver_set_responses)");
     const int rc = zf_loss_part(s);
     if (rc) return rc;
     s->poisson = true;
@@ -2113,6 +1999,25 @@ extern "C" int zf_solver_set_row_weights(zf_solver* s, const double* w_dev) {
     return ZF_OK;
 }
 
+// What the two setters that change the storage form of a dense A share: the slices of the column sweep over the new view, a slab
+// that holds them - regrown only when the new rule takes more slices than the present one, the new one allocated before the old
+// one is freed - and then the view itself.  A failed allocation leaves the solver as it was.
+static int zf_solver_adopt_view(zf_solver* s, const zf_matview& V) {
+    int slices = 1;
+    int64_t rows_per_slice = V.m;
+    zf_view_slices(V, &slices, &rows_per_slice);
+    if (slices > s->ws.slices) {
+        double* slab = nullptr;
+        ZF_HIP(hipMalloc(&slab, sizeof(double) * slices * s->desc.n));
+        if (s->ws.slab) (void)hipFree(s->ws.slab);
+        s->ws.slab = slab;
+    }
+    s->ws.slices = slices;
+    s->ws.rows_per_slice = rows_per_slice;
+    s->mat = V;
+    return ZF_OK;
+}
+
 // The matrix stored in fp32 (include/zfista_hip.h): between create and init, on the two dense kinds.
 extern "C" int zf_solver_set_matrix_f32(zf_solver* s, const float* A32_dev) {
     ZF_REQUIRE(s && A32_dev, "zf_solver_set_matrix_f32: null argument");
@@ -2122,20 +2027,13 @@ extern "C" int zf_solver_set_matrix_f32(zf_solver* s, const float* A32_dev) {
     ZF_REQUIRE(zf_is_dense_mat(d.kind),"zf_solver_set_matrix_f32: only for ZF_PROBLEM_LEAST_SQUARES_L1 and ZF_PROBLEM_LOGISTIC_L1");
     ZF_REQUIRE(d.world == 1, "zf_solver_set_matrix_f32: not for a sharded solve (world > 1)");
     ZF_REQUIRE(zf_aligned16(A32_dev), "zf_solver_set_matrix_f32: the matrix must be 16-byte aligned");
-    ZF_REQUIRE(s->K == 1, "zf_solver_set_matrix_f32: not with several responses (zf_solver_set_responses)");
-    int slices = 1;
-    int64_t rows_per_slice = d.m_rows;
-    zf_dense_slices_f32(d.m_rows, d.n, &slices, &rows_per_slice);
-    if (slices > s->slices) {   // (wider panels, so fewer of them: the fp32 rule may take more slices than the slab of zf_solver_create holds)
-        double* slab = nullptr;
-        ZF_HIP(hipMalloc(&slab, sizeof(double) * slices * d.n));
-        if (s->slab) (void)hipFree(s->slab);
-        s->slab = slab;
-    }
-    s->slices = slices;
-    s->rows_per_slice = rows_per_slice;
-    s->A32 = A32_dev;
-    s->gemv_mfma = false;  // (the MFMA column sweep reads fp64 A: ZF_GEMV_MFMA has no effect here)
+    ZF_REQUIRE(s->mat.k == 1, "zf_solver_set_matrix_f32: not with several responses (zf_solver_set_responses)");
+    zf_matview V = s->mat;
+    V.A = nullptr;
+    V.A32 = A32_dev;
+    V.mfma = false;   // (the MFMA column sweep reads fp64 A: ZF_GEMV_MFMA has no effect here)
+    const int rc = zf_solver_adopt_view(s, V);   // (wider panels, so fewer of them: the fp32 rule may take more slices than the slab of zf_solver_create holds)
+    if (rc) return rc;
     s->ls_small = false;   // (the fused small-matrix kernels read fp64 A: the general path, as the logistic kind)
     return ZF_OK;
 }
@@ -2149,26 +2047,20 @@ extern "C" int zf_solver_set_responses(zf_solver* s, int32_t K) {
     ZF_REQUIRE(zf_is_dense_mat(d.kind), "zf_solver_set_responses: only for ZF_PROBLEM_LEAST_SQUARES_L1 and ZF_PROBLEM_LOGISTIC_L1");
     ZF_REQUIRE(d.world == 1, "zf_solver_set_responses: not for a sharded solve (world > 1)");
     ZF_REQUIRE(K >= 2 && K <= ZF_MR_MAX_K, "zf_solver_set_responses: K must be 2 .. 16");
-    ZF_REQUIRE(s->K == 1, "zf_solver_set_responses: the solver already has its responses");
+    ZF_REQUIRE(s->mat.k == 1, "zf_solver_set_responses: the solver already has its responses");
     ZF_REQUIRE(d.m_rows % K == 0 && d.n % K == 0, "zf_solver_set_responses: m_rows and n of the solver must be multiples of K (they are m K and n K)");
     ZF_REQUIRE(!s->rem && !s->res, "zf_solver_set_responses: not with ZF_ACCEPT_REMAINDER or ZF_ACCEPT_RESOLVED");
     ZF_REQUIRE(!(s->huber > 0.0) && !s->poisson, "zf_solver_set_responses: not with Huber's or the Poisson loss (zf_solver_set_huber, zf_solver_set_poisson)");
-    ZF_REQUIRE(!s->A32, "zf_solver_set_responses: not with a matrix stored in fp32 (zf_solver_set_matrix_f32)");
-    const int rc = zf_loss_part(s);   // (the wide residual kernels beyond ZF_SPMV_WIDE_RESID_MIN_ROWS rows write chunk sums)
+    ZF_REQUIRE(!s->mat.A32, "zf_solver_set_responses: not with a matrix stored in fp32 (zf_solver_set_matrix_f32)");
+    int rc = zf_loss_part(s);   // (the wide residual kernels beyond ZF_SPMV_WIDE_RESID_MIN_ROWS rows write chunk sums)
     if (rc) return rc;
-    int slices = 1;
-    int64_t rows_per_slice = d.m_rows / K;
-    zf_mr_slices(d.m_rows / K, d.n / K, &slices, &rows_per_slice);
-    if (slices > s->slices) {   // (the rule runs on A's own shape: it may take more slices than the slab of zf_solver_create holds)
-        double* slab = nullptr;
-        ZF_HIP(hipMalloc(&slab, sizeof(double) * slices * d.n));
-        if (s->slab) (void)hipFree(s->slab);
-        s->slab = slab;
-    }
-    s->slices = slices;
-    s->rows_per_slice = rows_per_slice;
-    s->K = K;
-    s->gemv_mfma = false;  // (no MFMA form of the K-response sweeps)
+    zf_matview V = s->mat;
+    V.m = d.m_rows / K;
+    V.n = d.n / K;
+    V.k = K;
+    V.mfma = false;   // (no MFMA form of the K-response sweeps)
+    rc = zf_solver_adopt_view(s, V);   // (the rule runs on A's own shape: it may take more slices than the slab of zf_solver_create holds)
+    if (rc) return rc;
     s->ls_small = false;   // (the fused small-matrix kernels hold one response: the general path, as the logistic kind)
     return ZF_OK;
 }
@@ -2211,33 +2103,34 @@ extern "C" int zf_solver_ls_plan(zf_solver* s, int64_t* out, int64_t count) {
     }
     if (zf_is_sparse_mat(s->desc.kind)) {
         out[0] = 5;
-        out[1] = s->spmat->A.lanes;
-        out[2] = s->spmat->At.lanes;
-        out[3] = s->spmat->A.nsplit + s->spmat->At.nsplit;
+        out[1] = s->mat.h->A.lanes;
+        out[2] = s->mat.h->At.lanes;
+        out[3] = s->mat.h->A.nsplit + s->mat.h->At.nsplit;
         if (count >= 6) {   // responses (zf_solver_create_sparse_responses; 1 otherwise)
-            out[4] = s->K;
+            out[4] = s->mat.k;
             out[5] = 0;
         }
         return ZF_OK;
     }
     if (!zf_is_dense_mat(s->desc.kind)) return ZF_OK;
-    const bool odd = (s->desc.n / s->K) % 2 != 0;   // (K responses: the parity of the matrix's own column count)
-    out[0] = s->ls_small ? 1 : s->gemv_mfma ? 2 : odd ? 4 : 3;
+    const zf_matview& V = s->mat;
+    const bool odd = V.n % 2 != 0;   // (K responses: the parity of the matrix's own column count)
+    out[0] = s->ls_small ? 1 : V.mfma ? 2 : odd ? 4 : 3;
     out[1] = s->ls_small ? 1 : odd ? 3 : 2;
-    if (s->A32) {   // zf_kernels_gemv_f32.h: 16-byte, 8-byte or scalar loads of floats
-        const int V = zf_f32_width(s->desc.n);
-        out[0] = V == 4 ? 6 : V == 2 ? 7 : 8;
-        out[1] = V == 4 ? 4 : V == 2 ? 5 : 6;
+    if (V.A32) {   // zf_kernels_gemv_f32.h: 16-byte, 8-byte or scalar loads of floats
+        const int w = zf_f32_width(V.n);
+        out[0] = w == 4 ? 6 : w == 2 ? 7 : 8;
+        out[1] = w == 4 ? 4 : w == 2 ? 5 : 6;
     }
-    if (s->K > 1) {   // zf_kernels_mr.h: 16-byte or scalar loads of A, K right-hand sides
+    if (V.k > 1) {   // zf_kernels_mr.h: 16-byte or scalar loads of A, K right-hand sides
         out[0] = odd ? 10 : 9;
         out[1] = odd ? 8 : 7;
     }
-    out[2] = s->slices;
-    out[3] = s->rows_per_slice;
+    out[2] = s->ws.slices;
+    out[3] = s->ws.rows_per_slice;
     if (count >= 6) {   // responses, and the rows a workgroup of the row sweep owns (0: the plain sweeps' own constant)
-        out[4] = s->K;
-        out[5] = s->K > 1 ? zf_mr_rows_per_wg(s->K) : 0;
+        out[4] = V.k;
+        out[5] = V.k > 1 ? zf_mr_rows_per_wg(V.k) : 0;
     }
     return ZF_OK;
 }
@@ -2755,27 +2648,8 @@ extern "C" int zf_ls_remainder_eval(const double* s_plus_host, const double* s_k
 }
 
 // ---------------------------------------------------------------------------
-// A as the evaluations outside the loop see it: dense row-major, or CSR behind a handle - and its two sweeps
+// the evaluations outside the loop: a view of the caller's matrix (zf_matview.h) and a workspace of the call's own
 // ---------------------------------------------------------------------------
-struct zf_matview {
-    const double* A;     // dense: m x n row-major (device), 16-byte aligned; NULL for CSR
-    int64_t m, n;        // (CSR: the handle's)
-    const zf_spmat* h;   // CSR: A and A^T with their plans; NULL for dense
-    bool csr;
-    const float* A32;    // dense, stored in fp32 (zf_kernels_gemv_f32.h): m x n row-major (device), 16-byte aligned - A is NULL then; NULL otherwise
-    int k = 1;           // responses (zf_kernels_mr.h for dense fp64, zf_kernels_spmm.h for CSR): m and n stay the matrix's, the vectors hold m k and n k doubles
-};
-static int64_t zf_view_rows(const zf_matview& V) { return V.m * V.k; }   // length of a margins vector
-static int64_t zf_view_cols(const zf_matview& V) { return V.n * V.k; }   // length of a decision vector
-
-// what the sweeps write between their launches: the slab of the dense column sweep and its slices, or the segment sums of the
-// split rows of A / A^T (a call's own, or a solver's: the handle is shared with live solvers on other streams)
-struct zf_sweep_ws {
-    double* slab;
-    int slices;
-    int64_t rows_per_slice;
-    double *part_A, *part_At;
-};
 // (adjoint false: what z = A x alone needs)
 static int zf_sweep_ws_alloc(const zf_matview& V, bool adjoint, zf_sweep_ws* W) {
     int rc = ZF_OK;
@@ -2784,9 +2658,7 @@ static int zf_sweep_ws_alloc(const zf_matview& V, bool adjoint, zf_sweep_ws* W) 
         if (V.h->A.nseg > 0) ZF_KEEP_FIRST(hipMalloc(&W->part_A, sizeof(double) * V.h->A.nseg * V.k));
         if (adjoint && V.h->At.nseg > 0) ZF_KEEP_FIRST(hipMalloc(&W->part_At, sizeof(double) * V.h->At.nseg * V.k));
     } else if (adjoint) {
-        if (V.A32) zf_dense_slices_f32(V.m, V.n, &W->slices, &W->rows_per_slice);
-        else if (V.k > 1) zf_mr_slices(V.m, V.n, &W->slices, &W->rows_per_slice);
-        else zf_dense_slices(V.m, V.n, &W->slices, &W->rows_per_slice);
+        zf_view_slices(V, &W->slices, &W->rows_per_slice);
         ZF_KEEP_FIRST(hipMalloc(&W->slab, sizeof(double) * W->slices * zf_view_cols(V)));
     }
     return rc;
@@ -2794,57 +2666,6 @@ static int zf_sweep_ws_alloc(const zf_matview& V, bool adjoint, zf_sweep_ws* W) 
 static void zf_sweep_ws_free(zf_sweep_ws* W) {
     for (void* p : {(void*)W->slab, (void*)W->part_A, (void*)W->part_At})
         if (p) (void)hipFree(p);
-}
-
-// z = A x, outside the loop (ctl = NULL)
-static void zf_launch_view_apply(const zf_matview& V, hipStream_t st, double* x, double* z, const zf_sweep_ws& W) {
-    if (V.csr) {
-        const zf_spmv_io aio = {{x, x, x}, {z, z, z}};
-        if (V.k > 1) zf_launch_spmm(V.h->A, st, nullptr, false, aio, -1, 1.0, V.k, W.part_A);
-        else zf_launch_spmv(V.h->A, st, nullptr, false, aio, -1, 1.0, W.part_A);
-        return;
-    }
-    zf_ring3 xr = {{x, x, x}}, sr = {{z, z, z}};
-    if (V.A32) {
-        zf_launch_rows_f32(st, nullptr, V.A32, xr, sr, -1, V.m, V.n);
-        return;
-    }
-    if (V.k > 1) {
-        zf_launch_mr_rows(st, nullptr, V.A, xr, sr, -1, V.m, V.n, V.k);
-        return;
-    }
-    int gr = (int)((V.m + GEMV_ROWS - 1) / GEMV_ROWS);
-    if (gr > 8 * ZF_MAX_GRID) gr = 8 * ZF_MAX_GRID;
-    if (V.n % 2 == 0) hipLaunchKernelGGL(zf_gemv_rows_kernel<2>, dim3(gr), dim3(ZF_BLOCK), 0, st, nullptr, V.A, xr, sr, -1, V.m, V.n);
-    else hipLaunchKernelGGL(zf_gemv_rows_kernel<1>, dim3(gr), dim3(ZF_BLOCK), 0, st, nullptr, V.A, xr, sr, -1, V.m, V.n);
-}
-
-// g = factor * A^T r, outside the loop.  Dense: the column sweep over W's slices - on v_mfma_f64_16x16x4 when `mfma` (the caller
-// knows n % 32 == 0 and asked the environment), else the VALU sweep; the two sum in different orders - and the slice combine.
-static void zf_launch_view_adjoint(const zf_matview& V, hipStream_t st, const double* r, double* g, double factor, bool mfma,
-                                   const zf_sweep_ws& W) {
-    if (V.csr) {
-        const zf_spmv_io gio = {{r, r, r}, {g, g, g}};
-        if (V.k > 1) zf_launch_spmm(V.h->At, st, nullptr, false, gio, -1, factor, V.k, W.part_At);
-        else zf_launch_spmv(V.h->At, st, nullptr, false, gio, -1, factor, W.part_At);
-        return;
-    }
-    const int64_t m = V.m, n = V.n;
-    const int vw = (n % 2 == 0) ? 2 : 1;
-    if (V.A32) {   // (`mfma` does not apply: that sweep reads fp64 A)
-        zf_launch_cols_f32(st, nullptr, V.A32, r, W.slab, m, n, W.slices, W.rows_per_slice);
-    } else if (V.k > 1) {   // (nor here: the K-response sweep has no MFMA form)
-        zf_launch_mr_cols(st, nullptr, V.A, r, W.slab, m, n, V.k, W.slices, W.rows_per_slice);
-    } else if (mfma) {
-        dim3 gM((unsigned)((n + GEMVT_MFMA_COLS - 1) / GEMVT_MFMA_COLS), (unsigned)W.slices);
-        hipLaunchKernelGGL(zf_gemvT_partial_mfma_kernel, gM, dim3(ZF_BLOCK), 0, st, nullptr, V.A, r, W.slab, m, n, W.rows_per_slice);
-    } else {
-        dim3 gT((unsigned)((n / vw + ZF_BLOCK - 1) / ZF_BLOCK), (unsigned)W.slices);
-        if (vw == 2) hipLaunchKernelGGL(zf_gemvT_partial_kernel<2>, gT, dim3(ZF_BLOCK), 0, st, nullptr, V.A, r, W.slab, m, n, W.rows_per_slice);
-        else hipLaunchKernelGGL(zf_gemvT_partial_kernel<1>, gT, dim3(ZF_BLOCK), 0, st, nullptr, V.A, r, W.slab, m, n, W.rows_per_slice);
-    }
-    const int64_t nk = zf_view_cols(V);
-    hipLaunchKernelGGL(zf_gemvT_combine_kernel, dim3(zf_grid_for(nk)), dim3(ZF_BLOCK), 0, st, nullptr, W.slab, g, factor, nk, W.slices);
 }
 
 // The checks the three evaluation entries share (`who`: the entry's name; `io_ok`: its own host pointers), all before anything
@@ -2886,7 +2707,7 @@ static int zf_gap_args(const char* who, const zf_eval_desc* d, int64_t count, in
 // f and grad f at a host point (callback contract, not the hot loop)
 // ---------------------------------------------------------------------------
 // f = scale sum w phi(A x) and (grad_out_host != NULL) grad = gfac A^T (w o psi(A x)), on the rows kernels and the sweeps a solver
-// of this loss runs.  The column sweep of a dense A is always the VALU one: jac_f has the same bits whatever n % 32 is.
+// of this loss runs.  The column sweep of a dense A is always the VALU one (V.mfma stays false): jac_f has the same bits whatever n % 32 is.
 static int zf_point_eval(const zf_matview& V, const double* b_dev, double scale, const zf_loss& L, const double* x_host, double* f_out,
                          double* grad_out_host) {
     const int64_t m = zf_view_rows(V), n = zf_view_cols(V);
@@ -2904,7 +2725,7 @@ static int zf_point_eval(const zf_matview& V, const double* b_dev, double scale,
     if (grad_out_host) ZF_KEEP_FIRST(hipMalloc(&grad, sizeof(double) * n));
     if (rc == ZF_OK) {
         ZF_KEEP_FIRST(hipMemcpyAsync(x, x_host, sizeof(double) * n, hipMemcpyHostToDevice, nullptr));
-        zf_launch_view_apply(V, nullptr, x, z, W);
+        zf_launch_apply(V, nullptr, nullptr, {{x, x, x}}, {{z, z, z}}, -1, W);
         const bool launched = grad_out_host ? zf_launch_loss_y(nullptr, nullptr, z, z, z, b_dev, L, rho, scale, m, 0, part, fdev)
                                             : zf_launch_loss_x(nullptr, nullptr, z, z, z, -1, b_dev, L, scale, m, part, fdev);
         if (!launched) {   // the unweighted squared loss: f from the residual kernel, then r = z - b in place for the sweep
@@ -2913,7 +2734,7 @@ static int zf_point_eval(const zf_matview& V, const double* b_dev, double scale,
             if (grad_out_host) hipLaunchKernelGGL(zf_axmb_kernel, dim3(zf_grid_for(m)), dim3(ZF_BLOCK), 0, nullptr, z, b_dev, m);
         }
         if (grad_out_host) {
-            zf_launch_view_adjoint(V, nullptr, launched ? rho : z, grad, zf_gfac(L, scale), false, W);
+            zf_launch_adjoint(V, nullptr, nullptr, launched ? rho : z, grad, zf_gfac(L, scale), W);
             ZF_KEEP_FIRST(hipMemcpyAsync(grad_out_host, grad, sizeof(double) * n, hipMemcpyDeviceToHost, nullptr));
         }
         ZF_KEEP_FIRST(hipGetLastError());
@@ -3020,11 +2841,11 @@ static void zf_gap_ws_free(zf_gap_ws* ws) {
 }
 
 // The gap at a host point x: z = A x, the rows pass of the loss, g = grad f(x) by the column sweep a solver of this shape runs
-// (dense: MFMA when n % 32 == 0 and ZF_GEMV_MFMA is not 0), the n-passes and the composition; l2 > 0: the elastic-net evaluation.
+// (dense: MFMA when n % 32 == 0 and ZF_GEMV_MFMA is not 0 - V.mfma is set here by that rule), the n-passes and the composition; l2 > 0: the elastic-net evaluation.
 // scr != NULL (zf_margins_screen): the screen of zf_kernels_screen.h over the call's g behind the same sequence - its four
 // scalars follow the eight outputs; scr->cnt and scr->scal are allocated here
 // p_dev != NULL: penalty factors - g and the call's copy of x are scaled in place between step 2 and the tails
-static int zf_gap_eval_impl(const zf_matview& V, const double* b_dev, double scale, double lam, double l2, const zf_loss& L,
+static int zf_gap_eval_impl(zf_matview V, const double* b_dev, double scale, double lam, double l2, const zf_loss& L,
                             const double* x_host, double* out, int64_t out_count, const zf_screen_req* scr, const double* p_dev = nullptr) {
     const int64_t m = zf_view_rows(V), n = zf_view_cols(V);
     zf_gap_ws ws = {nullptr, nullptr, nullptr, nullptr};
@@ -3040,11 +2861,11 @@ static int zf_gap_eval_impl(const zf_matview& V, const double* b_dev, double sca
     ZF_KEEP_FIRST(hipMalloc(&x, sizeof(double) * (n + 2)));
     ZF_KEEP_FIRST(hipMalloc(&z, sizeof(double) * (m + 2)));
     if (rc == ZF_OK) {
-        const bool mfma = !V.csr && V.k == 1 && n % 32 == 0 && zf_env_read().gemv_mfma;
+        V.mfma = !V.csr && V.k == 1 && n % 32 == 0 && zf_env_read().gemv_mfma;
         ZF_KEEP_FIRST(hipMemcpyAsync(x, x_host, sizeof(double) * n, hipMemcpyHostToDevice, nullptr));
-        zf_launch_view_apply(V, nullptr, x, z, W);
+        zf_launch_apply(V, nullptr, nullptr, {{x, x, x}}, {{z, z, z}}, -1, W);
         zf_launch_loss_gap_rows(nullptr, L, z, b_dev, m, scale, ws);
-        zf_launch_view_adjoint(V, nullptr, ws.rvec, ws.g, zf_gfac(L, scale), mfma, W);
+        zf_launch_adjoint(V, nullptr, nullptr, ws.rvec, ws.g, zf_gfac(L, scale), W);
         if (p_dev) zf_launch_gap_pf_scale(nullptr, ws.g, x, p_dev, x, n);
         const zf_gap_out res = zf_launch_loss_gap_tail(nullptr, L, z, b_dev, x, m, n, scale, lam, l2, ws, out_count);
         if (scr) {
@@ -3140,10 +2961,8 @@ extern "C" int zf_solver_duality_gap(zf_solver* s, double* out, int64_t count) {
     const double* x = s->xb[c.cur];
     const double* z = s->sring.p[c.cur];   // A x_k: every path of these kinds keeps it there (the fused small-matrix path too)
     const zf_gap_ws& ws = s->gap;
-    const zf_matview V = {s->A32 ? nullptr : d.A, m / s->K, n / s->K, s->spmat, zf_is_sparse_mat(d.kind), s->A32, s->K};
-    const zf_sweep_ws W = {s->slab, s->slices, s->rows_per_slice, s->sp_part_A, s->sp_part_At};
     zf_launch_loss_gap_rows(s->stream, loss, z, d.b, m, d.scale, ws);
-    zf_launch_view_adjoint(V, s->stream, ws.rvec, ws.g, zf_gfac(loss, d.scale), s->gemv_mfma, W);
+    zf_launch_adjoint(s->mat, s->stream, nullptr, ws.rvec, ws.g, zf_gfac(loss, d.scale), s->ws);
     if (s->pf) {   // (penalty factors: the tails run on g / p and p o x_k)
         zf_launch_gap_pf_scale(s->stream, ws.g, x, s->pf, s->gap_xp, n);
         x = s->gap_xp;
