@@ -592,7 +592,7 @@ int zf_spmat_restrict_fill(const zf_spmat* h, const uint8_t* keep_dev, const int
 int zf_dense_restrict(const double* A_dev, int64_t m_rows, int64_t n, const uint8_t* keep_dev, int32_t* index_dev, int64_t k,
                       double* out_dev);
 
-/* ---- Huber's loss on the least-squares kinds 2 and 4 (csrc/zf_kernels_huber.h) -------------------------------------------
+/* ---- Huber's loss on the least-squares kinds 2 and 4 (csrc/zf_kernels_loss.h) -------------------------------------------
  * f(x) = scale sum_i H(r_i), r = A x - b, H(r) = r^2 for |r| <= delta and delta (2 |r| - delta) beyond (scale = 1/2: the textbook
  * function); grad f = 2 scale A^T c, c = clip(r, -delta, delta).  Every kernel forms c = copysign(min(|r|, delta), r) - exact
  * given r - and H = c (2 r - c): two roundings, never negative, r r on an unclipped row.  The sum is a plain sum.  A NaN margin
@@ -607,7 +607,7 @@ int zf_dense_restrict(const double* A_dev, int64_t m_rows, int64_t n, const uint
  * sets delta again before zf_solver_restore. */
 int zf_solver_set_huber(zf_solver* s, double delta);
 
-/* ---- per-row sample weights on the four margins kinds 2, 4, 5, 6 (csrc/zf_kernels_wloss.h) -----------------------------------
+/* ---- per-row sample weights on the four margins kinds 2, 4, 5, 6 (csrc/zf_kernels_loss.h) -----------------------------------
  * f(x) = scale sum_i w_i phi_i(z_i) - a weighted SUM, not a mean; the weights are used as given - and
  * grad f = gfac A^T (w o psi(z)), gfac = 2 scale (square, Huber) | scale (logistic), phi and psi per row as the unweighted
  * kernels form them, then one product for each output: rho_i = w_i psi_i, acc += w_i phi_i (two roundings per row).  The sum is a
@@ -625,7 +625,7 @@ enum { ZF_LOSS_SQUARE = 0, ZF_LOSS_LOGISTIC = 1, ZF_LOSS_HUBER = 2 };
  * never asked launches and allocates what it did.  A resumed solve sets the weights again before zf_solver_restore. */
 int zf_solver_set_row_weights(zf_solver* s, const double* w_dev);
 
-/* ---- the Poisson loss with a log link on the least-squares kinds 2 and 4 (csrc/zf_kernels_poisson.h) ------------------------
+/* ---- the Poisson loss with a log link on the least-squares kinds 2 and 4 (csrc/zf_kernels_loss.h) ------------------------
  * f(x) = scale sum_i w_i (exp(z_i) - b_i z_i), z = A x, with counts b_i >= 0, finite, not necessarily integers (a rate
  * count / exposure with the exposure as the row weight is the exposure model); the constant log b! is dropped.
  * grad f = scale A^T (w o psi), psi_i = exp(z_i) - b_i.  Every kernel forms ONE e = exp(z) per row, psi = e - b and

@@ -34,7 +34,7 @@ on every bound).  The device's exp carries the allowance of the logistic bound (
   v         alpha e + oma b, two products and one sum of non-negative terms:   dv_i = d(alpha) e + alpha de + d(oma) b + 2 u v
   conjugate c_i = v log v - v, dc/dv = log v; log: 2 u relative; one product, one subtraction:
             d(c_i) = dv |log v| + 3 u |v log v| + u |c_i|;    D = -scale sum w c:  d(D) = scale (sum w d(c_i) + gamma_(m+1) sum w |c_i|) + u |D|
-  row gap   the kernel's three forms (zf_kernels_poisson.h), each bounded in its own terms:
+  row gap   the kernel's three forms (zf_kernels_gap.h), each bounded in its own terms:
             b = 0      t = e (aloga + oma):        dt = de |aloga + oma| + e (d(aloga) + d(oma) + u (|aloga| + oma)) + u t
             d <= 1     d = oma (b - e) / e:        d(d) = (d(oma) |b - e| + oma (de + u |b - e|)) / e + |d| de / e + 2 u |d|
                        vr = alpha + oma (b / e):   d(vr) = d(alpha) + d(oma) b / e + oma (b / e)(de / e + u) + 2 u vr

@@ -1,5 +1,5 @@
-"""GPU: the rows passes of the margins family beyond the chunk cap.  Every loss kernel (zf_logit_kernel, zf_huber_kernel,
-zf_poisson_kernel, zf_wloss_kernel, zf_spmv_resid_kernel, with their finish kernels) and every gap rows kernel is launched on
+"""GPU: the rows passes of the margins family beyond the chunk cap.  Every loss kernel (the instantiations of
+zf_loss_rows_kernel for the four losses, weighted and not, and zf_spmv_resid_kernel, with their finish kernels) and every gap rows kernel is launched on
 zf_spmv_resid_chunks(m) = min(ceil(m / 1024), 1024) workgroups of 256 threads.  Up to m = 2^20 a thread makes at most four
 trips of its `#pragma unroll 2` loop; beyond it the chunks grow, threads make five trips and more, and the last chunk is short.
 The sizes (tests/row_chunk_cases.py; tests/test_row_chunk_cases.py proves them on the CPU): M0 = 2^20 (the last size before the

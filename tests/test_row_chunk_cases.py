@@ -24,12 +24,12 @@ def test_the_launch_shape_is_restated_from_the_source():
     lines = [" ".join(l.split()) for l in body.strip().splitlines()]
     assert lines == ["int64_t chunks = (m + 1023) / 1024;", "if (chunks < 1) chunks = 1;",
                      "if (chunks > ZF_SPMV_RESID_MAX_CHUNKS) chunks = ZF_SPMV_RESID_MAX_CHUNKS;", "return (int)chunks;"]
-    for name in ("zf_kernels_loss.h", "zf_kernels_wloss.h", "zf_kernels_poisson.h", "zf_kernels_huber.h"):
-        with open(os.path.join(CSRC, name)) as fh:
-            text = fh.read()
-        assert "const int64_t per = (m + gridDim.x - 1) / gridDim.x;" in text, name
-        assert "const int64_t lo = (int64_t)blockIdx.x * per, hi = lo + per < m ? lo + per : m;" in text, name
-        assert "for (int64_t i = lo + threadIdx.x; i < hi; i += BLOCK) {" in text, name
+    with open(os.path.join(CSRC, "zf_kernels_loss.h")) as fh:   # the ONE rows kernel of the four losses, with or without weights
+        text = fh.read()
+    assert text.count("__global__") == 2 and "void zf_loss_rows_kernel(" in text and "void zf_rows_finish_kernel(" in text
+    assert "const int64_t per = (m + gridDim.x - 1) / gridDim.x;" in text
+    assert "const int64_t lo = (int64_t)blockIdx.x * per, hi = lo + per < m ? lo + per : m;" in text
+    assert "for (int64_t i = lo + threadIdx.x; i < hi; i += BLOCK) {" in text
 
 
 def test_the_sizes_sit_on_the_edges_of_the_cap():

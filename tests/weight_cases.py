@@ -7,7 +7,7 @@ here; tests/test_weight_cases.py proves the closures on the CPU).
     huber     r = z - b                psi = c = copysign(min(|r|, delta), r)  phi = c (2 r - c)
     logistic  t = -b z, e = exp(-|t|)  psi = -b sigma(t)                     phi = max(t, 0) + log1p(e)
     per row one product for each output: rho_i = w_i psi_i, term_i = w_i phi_i; a row with w_i == 0 gives +0 for both, whatever
-    b_i holds (csrc/zf_kernels_wloss.h).  The sum is a plain sum, times scale once.
+    b_i holds (csrc/zf_kernels_loss.h).  The sum is a plain sum, times scale once.
 
 The reference project has no sample weights.  The yardsticks are its SOLVER on these closures and two exact equivalences:
 0 / 1 weights are the row subset, integer weights are duplicated rows (tests/test_weight_cases.py).

@@ -18,7 +18,7 @@ With w = 1 the logistic and Huber solves are bit-identical to their siblings (te
 solve equal to rounding: both windows hold the same trials.  Reported per side: ms per trial (wall) of every repeat with median
 and spread, accepted iterations per second, the solver's own event time, the plan; the difference of the medians when every
 timed trial of both sides was accepted; `byte_share` = the 16 m bytes the weighted loss kernels read beyond their siblings per
-accepted trial (8 m at y, 8 m at x+; csrc/zf_kernels_wloss.h) over the algorithmic bytes of a trial.  The rule of DESIGN 4.5h:
+accepted trial (8 m at y, 8 m at x+; csrc/zf_kernels_loss.h) over the algorithmic bytes of a trial.  The rule of DESIGN 4.5h:
 a weighted trial may exceed a sibling trial by that share of the sibling's time plus the summed spread of the two sets of
 repeats; beyond it, the kernel-trace durations of the loss kernels say where the time went."""
 from __future__ import annotations

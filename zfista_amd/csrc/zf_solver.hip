@@ -26,9 +26,6 @@
 #include "zf_screen.h"
 #include "zf_kernels_loss.h"
 #include "zf_kernels_gap.h"
-#include "zf_kernels_huber.h"
-#include "zf_kernels_poisson.h"
-#include "zf_kernels_wloss.h"
 #include "zf_loss_dispatch.h"
 #include "zf_kernels_step.h"
 #include "zf_trial_launch.h"
@@ -259,10 +256,10 @@ struct zf_solver {
     // slab of ws.slices * n doubles, or this solver's segment sums of the split rows of A / of A^T
     zf_matview mat = {nullptr, 0, 0, nullptr, false, nullptr, 1, false};
     zf_sweep_ws ws = {nullptr, 1, 0, nullptr, nullptr};
-    double huber = 0.0;           // Huber's loss (zf_solver_set_huber): delta > 0 swaps the residual kernels for zf_kernels_huber.h; 0: the squared loss
-    bool poisson = false;         // the Poisson loss (zf_solver_set_poisson): the residual kernels swapped for zf_kernels_poisson.h
+    double huber = 0.0;           // Huber's loss (zf_solver_set_huber): delta > 0 swaps the residual kernels for the rows kernel of zf_kernels_loss.h; 0: the squared loss
+    bool poisson = false;         // the Poisson loss (zf_solver_set_poisson): the residual kernels swapped for the rows kernel of zf_kernels_loss.h
     bool loss_part = false;       // the dense least-squares kind holds the 2 x ZF_SPMV_RESID_MAX_CHUNKS chunk sums of the loss kernels (zf_loss_part)
-    const double* roww = nullptr; // per-row sample weights (zf_solver_set_row_weights; borrowed as b is): the loss sites take zf_kernels_wloss.h; NULL: what ran before
+    const double* roww = nullptr; // per-row sample weights (zf_solver_set_row_weights; borrowed as b is): the loss sites take the weighted rows kernels; NULL: what ran before
     double l2 = 0.0;              // elastic net (zf_solver_set_l2): g = lam |x|_1 + (l2 / 2) |x|^2; 0: every path is the l1 one
     const double* pf = nullptr;   // per-column penalty factors (zf_solver_set_penalty_factors; borrowed as b is): g = lam sum p_j |x_j|; NULL: what ran before
     double* gap_xp = nullptr;     // ... the certificate's scaled iterate p o x_k (n doubles, allocated by the first zf_solver_duality_gap)

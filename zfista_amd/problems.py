@@ -300,7 +300,7 @@ class _GapMixin:
     has_duality_gap = True
     l2 = 0.0   # elastic net: g(x) = lam |x|_1 + (l2 / 2) |x|^2 (+ box)
     # per-row sample weights: f(x) = scale sum_i w_i loss_i - a weighted SUM, not a mean; the weights are used as given
-    # (csrc/zf_kernels_wloss.h).  _w: the device vector, shared by every sibling; None: the unweighted problem, every call as before
+    # (csrc/zf_kernels_loss.h).  _w: the device vector, shared by every sibling; None: the unweighted problem, every call as before
     _w = None
     _w_host = None
     # per-column penalty factors: g(x) = lam sum_j p_j |x_j|, p_j >= 0 (0: an unpenalised column).  _pf: the device vector, shared
@@ -962,7 +962,7 @@ def _check_delta(delta):
 
 class _HuberMixin:
     """Huber's loss on the trial of a least-squares class: f(x) = scale sum_i H(r_i), r = A x - b, H(r) = r^2 for
-    |r| <= delta and delta (2 |r| - delta) beyond; grad f = 2 scale A^T clip(r, -delta, delta) (csrc/zf_kernels_huber.h).  The
+    |r| <= delta and delta (2 |r| - delta) beyond; grad f = 2 scale A^T clip(r, -delta, delta) (csrc/zf_kernels_loss.h).  The
     problem kind is the least-squares one; ``huber_delta`` in the descriptor fields makes the engine call
     ``zf_solver_set_huber``.  No ``taylor_remainder``: scale |A (x+ - y)|^2 is not this loss's remainder, so
     ``acceptance="remainder"`` is refused as for the logistic classes."""
@@ -1017,7 +1017,7 @@ def _check_counts(b, m=None):
 
 class _PoissonMixin:
     """The Poisson loss with a log link on the trial of a least-squares class: f(x) = scale sum_i w_i (exp(z_i) - b_i z_i),
-    z = A x; grad f = scale A^T (w o (exp(z) - b)) (csrc/zf_kernels_poisson.h: one exp per row).  The problem kind is the
+    z = A x; grad f = scale A^T (w o (exp(z) - b)) (csrc/zf_kernels_loss.h: one exp per row).  The problem kind is the
     least-squares one; ``poisson`` in the descriptor fields makes the engine call ``zf_solver_set_poisson``.  No
     ``taylor_remainder`` and not separable: ``acceptance="remainder"`` / ``"resolved"`` are refused.  No screening: exp is not
     globally Lipschitz, so the gap-safe radius sqrt(2 L gap) does not apply."""
