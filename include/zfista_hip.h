@@ -697,6 +697,28 @@ int zf_solver_set_matrix_f32(zf_solver* s, const float* A32_dev);
  * again before zf_solver_restore.  A solver that was never asked launches and allocates what it did. */
 int zf_solver_set_responses(zf_solver* s, int32_t K);
 
+/* ---- the multinomial (softmax) loss on K responses, on the least-squares kinds 2 and 4 (csrc/zf_kernels_softmax.h) ---------------
+ * Y in R^{m x K} with rows on the probability simplex (a one-hot row is a class label), X in R^{n x K}, flattened as above:
+ *     f(X) = scale sum_i w_i [logsumexp(z_i) - <y_i, z_i>],  z_i = (A X)_i in R^K,   grad f = scale A^T (w o (softmax(Z) - Y)).
+ * The one loss that couples the K margins of a row; penalty, prox step, decision, history, snapshots and both K-response sweeps are
+ * the K-response solver's own.  One row, in every kernel: mx = max_k z_k, d_k = z_k - mx, e_k = exp(d_k), S = sum_k e_k (k order),
+ * rS = 1 / S (one division), p_k = e_k rS, psi_k = p_k - y_k, phi = log S + sum_k y_k (-d_k) (every term >= 0; equal to
+ * logsumexp - <y, z> because sum_k y_k = 1: the caller's check, the library does not read Y on the host).  Nothing overflows for a
+ * finite margin; a NaN or +inf margin gives a NaN f, and so does a -inf margin on a class with y_k = 0 (0 * inf); a -inf margin on a
+ * class with y_k > 0 gives f = +inf (phi = y_k * inf), which the acceptance test rejects.
+ * Row weights stay one double per FLATTENED entry (m K of them, zf_solver_set_row_weights as before) so that neither the ABI nor
+ * the snapshot format changes, but a row of this loss has ONE weight: the kernels read w[i K] alone - the caller repeats w_i K
+ * times - and w_i == 0 is a row that is not there, whatever y_i holds.
+ * zf_solver_set_multinomial: after zf_solver_create(_sparse_responses), before zf_solver_enqueue_init / zf_solver_restore
+ * (ZF_ERR_STATE afterwards).  The solver already has its K >= 2 responses: a dense one by zf_solver_set_responses BEFORE this call
+ * (the reverse order is ZF_ERR_ARG), a sparse one from zf_solver_create_sparse_responses.  ZF_ERR_ARG also: a kind other than
+ * ZF_PROBLEM_LEAST_SQUARES_L1 / ZF_PROBLEM_SPARSE_LS_L1, world > 1, ZF_ACCEPT_REMAINDER / ZF_ACCEPT_RESOLVED, a solver with Huber's or
+ * the Poisson loss (and those two setters after this call), a second call.  Composes with zf_solver_set_l2 / _row_weights /
+ * _penalty_factors in any order.  A resumed solve calls it again before zf_solver_restore.  A solver that was never asked launches
+ * and allocates what it did.  Additive to ABI 7: one enumerator, one entry, no struct change. */
+enum { ZF_LOSS_MULTINOMIAL = 4 };   /* the fifth ZF_LOSS_* code */
+int zf_solver_set_multinomial(zf_solver* s);
+
 /* ---- the margins problems at a host point: f / grad, the certificate, the screen (ABI 7) --------------------------------------------
  * One descriptor names the storage of A, the loss and the options of the problem
  *     f(x) = scale sum_i w_i phi((A x)_i ; b_i),   g(x) = lam sum_j p_j |x_j| + (l2 / 2) |x|^2
@@ -704,7 +726,8 @@ int zf_solver_set_responses(zf_solver* s, int32_t K);
  * solver of that storage and loss runs.  These back f, jac_f, duality_gap and screen of zfista_amd.problems.*.  A new loss or a new
  * storage is a new value of a field: no entry is added.  (They replace the 32 per-loss entries of ABI 6: INTEGRATION.md lists them.)
  * Exactly one of A / A32 / spmat is set.  Dense: m_rows x n row-major in device memory, 16-byte aligned; a handle knows its own
- * sizes and m_rows, n are ignored.  K responses (1 .. 16; K > 1: ZF_LOSS_SQUARE / ZF_LOSS_LOGISTIC on A or spmat only): m_rows and n
+ * sizes and m_rows, n are ignored.  K responses (1 .. 16; K > 1: ZF_LOSS_SQUARE / ZF_LOSS_LOGISTIC / ZF_LOSS_MULTINOMIAL on A or spmat
+ * only; ZF_LOSS_MULTINOMIAL needs K >= 2, b holds the rows of Y and w one weight per row repeated K times): m_rows and n
  * stay the MATRIX's, b / w hold m_rows K, p / x_host / grad_out_host n K doubles, response-interleaved (x[j K + k] = X[j][k]); K = 1
  * is the plain problem.  w (row weights, finite and >= 0) and p (penalty factors, > 0) may each be NULL: the unweighted / unfactored
  * problem - other kernels, other bits than w = 1.  delta: Huber's, finite and > 0; ignored for the other losses. */
@@ -717,13 +740,14 @@ typedef struct zf_eval_desc {
     const double* w;          /* dev, m_rows K, or NULL                                                */
     const double* p;          /* dev, n K, or NULL (the certificate only)                              */
     double scale, lam, l2, delta;
-    int32_t loss;             /* ZF_LOSS_SQUARE / _LOGISTIC / _HUBER / _POISSON                        */
+    int32_t loss;             /* ZF_LOSS_SQUARE / _LOGISTIC / _HUBER / _POISSON / _MULTINOMIAL         */
     int32_t K;
 } zf_eval_desc;
 int64_t zf_sizeof_eval_desc(void);
 /* ZF_ERR_ARG from all three, before anything touches a device or is written: d NULL or desc_bytes != zf_sizeof_eval_desc(); not exactly
  * one matrix; b, x_host or the output pointer NULL; dense m_rows or n < 1, a misaligned matrix; an unknown loss; a bad delta with
- * ZF_LOSS_HUBER; K outside 1 .. 16, K > 1 with another loss than square / logistic or with A32.
+ * ZF_LOSS_HUBER; K outside 1 .. 16, K > 1 with another loss than square / logistic / multinomial or with A32; ZF_LOSS_MULTINOMIAL
+ * with K = 1 or with A32.
  *
  * zf_margins_eval: *f_out = f(x) and (grad_out_host != NULL) grad f(x) = gfac A^T (w o psi(A x)), gfac = 2 scale (square, Huber) |
  * scale (logistic, Poisson).  Reads neither lam, l2 nor p.  The column sweep of a dense fp64 A is always the VALU one: jac_f has the
@@ -733,6 +757,8 @@ int64_t zf_sizeof_eval_desc(void);
  *             softplus(t) = max(t, 0) + log1p(e) and sigma(t) = t >= 0 ? 1 / (1 + e) : e / (1 + e)
  *   Huber     phi = H(r), psi = c = clip(r, -delta, delta), r = z - b (the section of zf_solver_set_huber)
  *   Poisson   phi = exp(z) - b z, psi = exp(z) - b (the section of zf_solver_set_poisson)
+ *   multinomial  per row of K margins: phi = log S + sum_k y_k (mx - z_k), psi_k = e_k / S - y_k; gfac = scale (the section of
+ *             zf_solver_set_multinomial)
  * weighted: rho_i = w_i psi_i, acc += w_i phi_i (the section of zf_solver_set_row_weights). */
 int zf_margins_eval(const zf_eval_desc* d, int64_t desc_bytes, const double* x_host, double* f_out, double* grad_out_host /* or NULL */);
 
@@ -764,6 +790,10 @@ int zf_margins_eval(const zf_eval_desc* d, int64_t desc_bytes, const double* x_h
  *   P = f + lam |x|_1                                D = -scale sum w (v log v - v)
  *   rows = scale sum w [e^z - v + v (log v - z)]     every term >= 0, exactly 0 at alpha = 1
  * The row terms depend on alpha: a second rows pass follows the n-passes, as for the logistic loss.
+ * Multinomial.  The conjugate of logsumexp(z) - <y, z> at theta is sum_k v_k log v_k with v = theta + y on the simplex; theta = alpha psi
+ * gives v = alpha p + (1 - alpha) y, a convex combination: feasible for every alpha in [0, 1].
+ *   D = -scale sum_i w_i sum_k v_ik log v_ik (0 log 0 = 0)     rows = scale sum_i w_i KL(v_i || p_i), log p_k = d_k - log S
+ * each row term clamped at 0, not formed at alpha = 1, finite for every finite margin; the composition is the logistic one.
  * Row weights (w).  Every row term times w_i ((w phi)^*(w u) = w phi^*(u); the dual point is nu = alpha grad phi(z) as before):
  * square sum w r^2, sum w b r; Huber sum w H, sum w c^2, sum w b c, sum w |c| (|r| - |c|); logistic sum w KL,
  * sum w [p log p + (1 - p) log(1 - p)].  The n-passes and the compositions are unchanged.
@@ -793,7 +823,7 @@ int zf_margins_gap(const zf_eval_desc* d, int64_t desc_bytes, const double* x_ho
  * Huber's loss: the rule with L = 2 scale and the guard with c for r, |c|_2 = sqrt(sum c^2) - the clip is exact and 1-Lipschitz.  The
  * radius, mask, scan and restriction kernels are the same.
  * ZF_ERR_ARG also, each with a message of its own: count < 12; ZF_LOSS_POISSON (exp is not globally Lipschitz, so the gap-safe radius
- * does not apply); w, p, l2 > 0, A32 or K > 1 (the rule and its rounding guard are not built for them); dense n > 2^31 - 1; norms_dev,
+ * does not apply); ZF_LOSS_MULTINOMIAL (screening needs per-response gaps); w, p, l2 > 0, A32 or K > 1 (the rule and its rounding guard are not built for them); dense n > 2^31 - 1; norms_dev,
  * stats_dev, keep_dev or index_dev NULL; a handle with max_row or max_col < 0. */
 int zf_margins_screen(const zf_eval_desc* d, int64_t desc_bytes, const double* x_host, double* out, int64_t count /* >= 12 */,
                       const double* norms_dev, const double* stats_dev, int64_t max_row, int64_t max_col, uint8_t* keep_dev,

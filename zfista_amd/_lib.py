@@ -22,7 +22,7 @@ ZF_RUNNING, ZF_CONVERGED, ZF_MAXITER, ZF_BACKTRACK_FAILED = 0, 1, 2, 3
 ZF_PROBLEM_DIAG_QUAD_L1, ZF_PROBLEM_LEAST_SQUARES_L1, ZF_PROBLEM_BLUR_HAAR_L1 = 1, 2, 3
 ZF_PROBLEM_SPARSE_LS_L1 = 4
 ZF_PROBLEM_LOGISTIC_L1, ZF_PROBLEM_SPARSE_LOGISTIC_L1 = 5, 6
-ZF_LOSS_SQUARE, ZF_LOSS_LOGISTIC, ZF_LOSS_HUBER, ZF_LOSS_POISSON = 0, 1, 2, 3   # zf_eval_desc.loss (csrc/zf_loss_dispatch.h)
+ZF_LOSS_SQUARE, ZF_LOSS_LOGISTIC, ZF_LOSS_HUBER, ZF_LOSS_POISSON, ZF_LOSS_MULTINOMIAL = 0, 1, 2, 3, 4   # zf_eval_desc.loss (csrc/zf_loss_dispatch.h)
 ZF_MO_GENERIC, ZF_MO_JOS1, ZF_MO_FDS = 0, 1, 2
 ZF_PACK_LEN, ZF_TRACE_COLS, ZF_RING = 8, 8, 1024
 ZF_MAX_SUB_ITERS = 16
@@ -239,6 +239,7 @@ SIGNATURES = {
     "zf_solver_set_huber": (C.c_int, [_P, C.c_double]),
     "zf_solver_set_row_weights": (C.c_int, [_P, _P]),
     "zf_solver_set_poisson": (C.c_int, [_P]),
+    "zf_solver_set_multinomial": (C.c_int, [_P]),
     "zf_solver_set_penalty_factors": (C.c_int, [_P, _P]),
     "zf_host_prox_pf_box": (C.c_int, [_P, _P, _P, C.c_double, C.c_double, C.c_double, C.c_int64]),
     "zf_host_pf_g": (C.c_int, [_P, _P, C.c_int64, C.c_double, C.POINTER(C.c_double)]),

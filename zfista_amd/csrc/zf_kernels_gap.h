@@ -20,7 +20,8 @@
 //   2  g = factor * A^T rvec by the caller's column sweep (zf_solver.hip); penalty factors: zf_gap_pf_scale_kernel
 //   3  zf_gap_ginf[_enet]_kernel (+ finish): |g|_inf -> alpha, 1 - alpha, alpha log alpha, left in device memory
 //   4  zf_gap_cols[_enet]_kernel (+ finish): sum_j (lam |x_j| + alpha g_j x_j), sum |x_j| (, sum x_j^2)   (3, 4: zf_launch_gap_npasses)
-//   5  the rows that need alpha (zf_launch_gap_alpha_rows): logistic zf_gap_kl_kernel, Poisson zf_gap_poisson_kernel (+ finish)
+//   5  the rows that need alpha (zf_launch_gap_alpha_rows in zf_loss_dispatch.h): logistic zf_gap_kl_kernel, Poisson zf_gap_poisson_kernel, multinomial
+//      zf_gap_softmax_kernel of zf_kernels_softmax.h (+ finish)
 //   6  composition (one thread): zf_gap_compose_kernel / _enet_kernel / _huber_kernel
 // Shapes: the n-vectors take ONE workgroup up to ZF_GAP_ONE_WG_MAX_N elements and zf_gap_chunks(n) workgroups on a
 // contiguous chunk each beyond (chunk results combined in chunk order by one workgroup); the m-vectors the two shapes of
@@ -670,20 +671,4 @@ static inline void zf_launch_gap_npasses(hipStream_t st, const double* x, int64_
         zf_launch_gap_sum_finish(st, ws, nc, ZF_GS_COLS, ZF_GS_ASUM);
         if (enet) hipLaunchKernelGGL(zf_gap_sum_third_kernel, dim3(1), dim3(ZF_BLOCK), 0, st, ws.part, nc, (int)ZF_GS_XX, ws.scal);
     }
-}
-
-// step 5: the rows pass that needs alpha - the logistic and the Poisson loss (w: the row weights or NULL); none for the others,
-// whose composition reads the sums of step 1
-static inline void zf_launch_gap_alpha_rows(hipStream_t st, int loss, const double* z, const double* b, const double* w, int64_t m,
-                                            const zf_gap_ws& ws) {
-    int chunks;
-    if (loss == ZF_LOSS_LOGISTIC)
-        chunks = zf_launch_rows_shapes(st, w ? zf_gap_kl_kernel<ZF_ROWS_BLOCK, true> : zf_gap_kl_kernel<ZF_ROWS_BLOCK, false>,
-                                       w ? zf_gap_kl_kernel<ZF_BLOCK, true> : zf_gap_kl_kernel<ZF_BLOCK, false>, m, z, b, w, m, ws.part, ws.scal);
-    else if (loss == ZF_LOSS_POISSON)
-        chunks = zf_launch_rows_shapes(st, w ? zf_gap_poisson_kernel<ZF_ROWS_BLOCK, true> : zf_gap_poisson_kernel<ZF_ROWS_BLOCK, false>,
-                                       w ? zf_gap_poisson_kernel<ZF_BLOCK, true> : zf_gap_poisson_kernel<ZF_BLOCK, false>, m, z, b, w, m, ws.part,
-                                       ws.scal);
-    else return;
-    if (chunks) zf_launch_gap_sum_finish(st, ws, chunks, ZF_GS_KL, ZF_GS_ENT);
 }

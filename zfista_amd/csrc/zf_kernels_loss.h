@@ -198,6 +198,7 @@ struct zf_rows_call {
     int64_t m;
     int nesterov;
     double *part, *f_out;
+    int K;   // the responses a row of the multinomial loss couples (zf_kernels_softmax.h); unread by the row losses here
 };
 
 template <int LOSS, bool W, int WHICH>

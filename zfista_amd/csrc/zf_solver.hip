@@ -26,6 +26,7 @@
 #include "zf_screen.h"
 #include "zf_kernels_loss.h"
 #include "zf_kernels_gap.h"
+#include "zf_kernels_softmax.h"
 #include "zf_loss_dispatch.h"
 #include "zf_kernels_step.h"
 #include "zf_trial_launch.h"
@@ -257,6 +258,7 @@ struct zf_solver {
     zf_matview mat = {nullptr, 0, 0, nullptr, false, nullptr, 1, false};
     zf_sweep_ws ws = {nullptr, 1, 0, nullptr, nullptr};
     double huber = 0.0;           // Huber's loss (zf_solver_set_huber): delta > 0 swaps the residual kernels for the rows kernel of zf_kernels_loss.h; 0: the squared loss
+    bool multinomial = false;     // the multinomial loss on K responses (zf_solver_set_multinomial): the rows kernels of zf_kernels_softmax.h
     bool poisson = false;         // the Poisson loss (zf_solver_set_poisson): the residual kernels swapped for the rows kernel of zf_kernels_loss.h
     bool loss_part = false;       // the dense least-squares kind holds the 2 x ZF_SPMV_RESID_MAX_CHUNKS chunk sums of the loss kernels (zf_loss_part)
     const double* roww = nullptr; // per-row sample weights (zf_solver_set_row_weights; borrowed as b is): the loss sites take the weighted rows kernels; NULL: what ran before
@@ -437,14 +439,15 @@ static bool zf_is_dense_mat(int kind) { return kind == ZF_PROBLEM_LEAST_SQUARES_
 static bool zf_is_sparse_mat(int kind) { return kind == ZF_PROBLEM_SPARSE_LS_L1 || kind == ZF_PROBLEM_SPARSE_LOGISTIC_L1; }
 // f is a loss of A x: the margins of x_k, x_{k-1} are kept in a ring and A y follows by linearity
 static bool zf_has_margins(int kind) { return zf_is_ls(kind) || zf_is_logistic(kind); }
-// the loss of a solver (zf_loss_dispatch.h): the one place that reads the problem kind, zf_solver_set_huber, zf_solver_set_poisson and
-// zf_solver_set_row_weights for it
+// the loss of a solver (zf_loss_dispatch.h): the one place that reads the problem kind, zf_solver_set_huber, zf_solver_set_poisson,
+// zf_solver_set_multinomial and zf_solver_set_row_weights for it
 static zf_loss zf_loss_of(const zf_solver* s) {
     const int kind = zf_is_logistic(s->desc.kind) ? ZF_LOSS_LOGISTIC
                      : s->huber > 0.0            ? ZF_LOSS_HUBER
                      : s->poisson                ? ZF_LOSS_POISSON
+                     : s->multinomial            ? ZF_LOSS_MULTINOMIAL
                                                  : ZF_LOSS_SQUARE;
-    return zf_loss{kind, s->huber, s->roww};
+    return zf_loss{kind, s->huber, s->roww, s->mat.k};
 }
 static zf_op_args zf_op_of(const zf_problem_desc& d, const zf_control* ctl, const zf_op_plan& pl, const double* taps, const double* sep) {
     zf_op_args P;
@@ -1949,6 +1952,7 @@ extern "C" int zf_solver_set_huber(zf_solver* s, double delta) {
     ZF_REQUIRE(delta > 0.0 && delta <= DBL_MAX, "zf_solver_set_huber: delta must be finite and > 0");
     ZF_REQUIRE(!s->rem, "zf_solver_set_huber: not with ZF_ACCEPT_REMAINDER (scale |A (x+ - y)|^2 is not the Taylor remainder of this loss)");
     ZF_REQUIRE(!s->poisson, "zf_solver_set_huber: the solver already has the Poisson loss (zf_solver_set_poisson)");
+    ZF_REQUIRE(!s->multinomial, "zf_solver_set_huber: the solver already has the multinomial loss (zf_solver_set_multinomial)");
     ZF_REQUIRE(s->mat.k == 1, "zf_solver_set_huber: not with several responses (zf_solver_set_responses)");
     const int rc = zf_loss_part(s);
     if (rc) return rc;
@@ -1969,10 +1973,36 @@ extern "C" int zf_solver_set_poisson(zf_solver* s) {
     ZF_REQUIRE(!s->rem, "zf_solver_set_poisson: not with ZF_ACCEPT_REMAINDER (scale |A (x+ - y)|^2 is not the Taylor remainder of this loss)");
     ZF_REQUIRE(!s->res, "zf_solver_set_poisson: not with ZF_ACCEPT_RESOLVED");
     ZF_REQUIRE(!(s->huber > 0.0), "zf_solver_set_poisson: the solver already has Huber's loss (zf_solver_set_huber)");
+    ZF_REQUIRE(!s->multinomial, "zf_solver_set_poisson: the solver already has the multinomial loss (zf_solver_set_multinomial)");
     ZF_REQUIRE(s->mat.k == 1, "zf_solver_set_poisson: not with several responses (zf_solver_set_responses)");
     const int rc = zf_loss_part(s);
     if (rc) return rc;
     s->poisson = true;
+    s->ls_small = false;   // (the fused small-matrix kernels hold the squared loss: the general path, as the logistic kind)
+    return ZF_OK;
+}
+
+// The multinomial loss (include/zfista_hip.h): between create and init, on the two least-squares kinds with K >= 2 responses.
+extern "C" int zf_solver_set_multinomial(zf_solver* s) {
+    ZF_REQUIRE(s, "zf_solver_set_multinomial: null argument");
+    if (s->init_enqueued || s->initialised)
+        return zf_fail(ZF_ERR_STATE, "zf_solver_set_multinomial: call after zf_solver_create and before zf_solver_enqueue_init / zf_solver_restore%s%s");
+    const zf_problem_desc& d = s->desc;
+    ZF_REQUIRE(d.kind == ZF_PROBLEM_LEAST_SQUARES_L1 || d.kind == ZF_PROBLEM_SPARSE_LS_L1,
+               "zf_solver_set_multinomial: only for ZF_PROBLEM_LEAST_SQUARES_L1 and ZF_PROBLEM_SPARSE_LS_L1");
+    ZF_REQUIRE(d.world == 1, "zf_solver_set_multinomial: not for a sharded solve (world > 1)");
+    ZF_REQUIRE(!s->rem, "zf_solver_set_multinomial: not with ZF_ACCEPT_REMAINDER (scale |A (x+ - y)|^2 is not the Taylor remainder of this loss)");
+    ZF_REQUIRE(!s->res, "zf_solver_set_multinomial: not with ZF_ACCEPT_RESOLVED");
+    ZF_REQUIRE(!(s->huber > 0.0), "zf_solver_set_multinomial: the solver already has Huber's loss (zf_solver_set_huber)");
+    ZF_REQUIRE(!s->poisson, "zf_solver_set_multinomial: the solver already has the Poisson loss (zf_solver_set_poisson)");
+    ZF_REQUIRE(!s->multinomial, "zf_solver_set_multinomial: the solver already has the multinomial loss");
+    ZF_REQUIRE(s->mat.k >= 2,
+               "zf_solver_set_multinomial: the solver has no responses yet - a dense solver calls zf_solver_set_responses (K >= 2) BEFORE this "
+               "setter, a sparse one comes from zf_solver_create_sparse_responses");
+    ZF_REQUIRE(zf_aligned16(d.b), "zf_solver_set_multinomial: b (the rows of Y) must be 16-byte aligned");
+    const int rc = zf_loss_part(s);
+    if (rc) return rc;
+    s->multinomial = true;
     s->ls_small = false;   // (the fused small-matrix kernels hold the squared loss: the general path, as the logistic kind)
     return ZF_OK;
 }
@@ -2048,6 +2078,7 @@ extern "C" int zf_solver_set_responses(zf_solver* s, int32_t K) {
     ZF_REQUIRE(d.m_rows % K == 0 && d.n % K == 0, "zf_solver_set_responses: m_rows and n of the solver must be multiples of K (they are m K and n K)");
     ZF_REQUIRE(!s->rem && !s->res, "zf_solver_set_responses: not with ZF_ACCEPT_REMAINDER or ZF_ACCEPT_RESOLVED");
     ZF_REQUIRE(!(s->huber > 0.0) && !s->poisson, "zf_solver_set_responses: not with Huber's or the Poisson loss (zf_solver_set_huber, zf_solver_set_poisson)");
+    ZF_REQUIRE(!s->multinomial, "zf_solver_set_responses: zf_solver_set_multinomial comes after this setter, not before");
     ZF_REQUIRE(!s->mat.A32, "zf_solver_set_responses: not with a matrix stored in fp32 (zf_solver_set_matrix_f32)");
     int rc = zf_loss_part(s);   // (the wide residual kernels beyond ZF_SPMV_WIDE_RESID_MIN_ROWS rows write chunk sums)
     if (rc) return rc;
@@ -2678,13 +2709,18 @@ static int zf_desc_args(const char* who, const zf_eval_desc* d, int64_t desc_byt
     if (!csr && !(d->m_rows >= 1 && d->n >= 1)) return zf_fail(ZF_ERR_ARG, "%s: bad argument (m_rows and n must be >= 1)%s", who);
     if (!csr && !zf_aligned16(d->A32 ? (const void*)d->A32 : (const void*)d->A)) return zf_fail(ZF_ERR_ARG, "%s: A must be 16-byte aligned%s", who);
     if (!(d->K >= 1 && d->K <= ZF_MR_MAX_K)) return zf_fail(ZF_ERR_ARG, "%s: K must be 1 .. 16%s", who);
-    if (d->K > 1 && d->loss != ZF_LOSS_SQUARE && d->loss != ZF_LOSS_LOGISTIC)
-        return zf_fail(ZF_ERR_ARG, "%s: with K > 1 the loss must be ZF_LOSS_SQUARE or ZF_LOSS_LOGISTIC%s", who);
-    if (d->loss != ZF_LOSS_SQUARE && d->loss != ZF_LOSS_LOGISTIC && d->loss != ZF_LOSS_HUBER && d->loss != ZF_LOSS_POISSON)
-        return zf_fail(ZF_ERR_ARG, "%s: loss must be ZF_LOSS_SQUARE, ZF_LOSS_LOGISTIC, ZF_LOSS_HUBER or ZF_LOSS_POISSON%s", who);
+    if (d->K > 1 && d->loss != ZF_LOSS_SQUARE && d->loss != ZF_LOSS_LOGISTIC && d->loss != ZF_LOSS_MULTINOMIAL)
+        return zf_fail(ZF_ERR_ARG, "%s: with K > 1 the loss must be ZF_LOSS_SQUARE or ZF_LOSS_LOGISTIC (or ZF_LOSS_MULTINOMIAL, whose rows couple the K responses)%s", who);
+    if (d->loss == ZF_LOSS_MULTINOMIAL && (d->K < 2 || d->A32))
+        return zf_fail(ZF_ERR_ARG, "%s: ZF_LOSS_MULTINOMIAL needs K = 2 .. 16 responses on A or spmat, not a matrix stored in fp32 (the other codes: ZF_LOSS_SQUARE, "
+                       "ZF_LOSS_LOGISTIC, ZF_LOSS_HUBER, ZF_LOSS_POISSON)%s", who);
+    if (d->loss != ZF_LOSS_SQUARE && d->loss != ZF_LOSS_LOGISTIC && d->loss != ZF_LOSS_HUBER && d->loss != ZF_LOSS_POISSON &&
+        d->loss != ZF_LOSS_MULTINOMIAL)
+        return zf_fail(ZF_ERR_ARG, "%s: loss must be ZF_LOSS_SQUARE, ZF_LOSS_LOGISTIC, ZF_LOSS_HUBER, ZF_LOSS_POISSON or ZF_LOSS_MULTINOMIAL%s", who);
+    if (d->loss == ZF_LOSS_MULTINOMIAL && !zf_aligned16(d->b)) return zf_fail(ZF_ERR_ARG, "%s: with ZF_LOSS_MULTINOMIAL b must be 16-byte aligned%s", who);
     if (d->loss == ZF_LOSS_HUBER && !(d->delta > 0.0 && d->delta <= DBL_MAX)) return zf_fail(ZF_ERR_ARG, "%s: delta must be finite and > 0%s", who);
     if (d->K > 1 && d->A32) return zf_fail(ZF_ERR_ARG, "%s: not with K > 1 and a matrix stored in fp32 (the K-response sweeps read an fp64 A)%s", who);
-    *L = zf_loss{d->loss, d->loss == ZF_LOSS_HUBER ? d->delta : 0.0, d->w};
+    *L = zf_loss{d->loss, d->loss == ZF_LOSS_HUBER ? d->delta : 0.0, d->w, d->K};
     return ZF_OK;
 }
 // the matrix of a checked descriptor as the sweeps see it (a handle knows its own sizes)
@@ -2913,6 +2949,7 @@ extern "C" int zf_margins_screen(const zf_eval_desc* d, int64_t desc_bytes, cons
     if (rc) return rc;
     // what the rule and its rounding guard are not built for
     if (d->loss == ZF_LOSS_POISSON) return zf_fail(ZF_ERR_ARG, "%s: not for ZF_LOSS_POISSON (exp is not globally Lipschitz: no gap-safe radius)%s", who);
+    if (d->loss == ZF_LOSS_MULTINOMIAL) return zf_fail(ZF_ERR_ARG, "%s: not for ZF_LOSS_MULTINOMIAL (screening needs per-response gaps)%s", who);
     if (d->w) return zf_fail(ZF_ERR_ARG, "%s: not with row weights (w)%s", who);
     if (d->p) return zf_fail(ZF_ERR_ARG, "%s: not with penalty factors (p)%s", who);
     if (d->l2 > 0.0) return zf_fail(ZF_ERR_ARG, "%s: not with l2 > 0%s", who);

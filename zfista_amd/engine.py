@@ -82,12 +82,13 @@ class DeviceSolver:
         l2 = float(desc_fields.get("l2", 0.0) or 0.0)   # elastic net: no descriptor field either (zf_solver_set_l2)
         huber = float(desc_fields.get("huber_delta", 0.0) or 0.0)   # Huber's loss on a least-squares kind: likewise (zf_solver_set_huber)
         poisson = bool(desc_fields.get("poisson", False))   # the Poisson loss on a least-squares kind: likewise (zf_solver_set_poisson)
+        multinomial = bool(desc_fields.get("multinomial", False))   # the multinomial loss on K responses: likewise (zf_solver_set_multinomial, after the responses)
         roww = desc_fields.get("row_weights")   # per-row sample weights (a device pointer): likewise (zf_solver_set_row_weights)
         pf = desc_fields.get("penalty_factors")   # per-column penalty factors (a device pointer): likewise (zf_solver_set_penalty_factors)
         a32 = desc_fields.get("matrix_f32")   # the matrix stored in fp32 (a device pointer): likewise (zf_solver_set_matrix_f32)
         responses = int(desc_fields.get("responses", 1) or 1)   # K responses on one matrix: likewise (dense: zf_solver_set_responses; with spmat: zf_solver_create_sparse_responses)
         for k, v in desc_fields.items():
-            if k not in ("spmat", "l2", "huber_delta", "poisson", "row_weights", "penalty_factors", "matrix_f32", "responses"):
+            if k not in ("spmat", "l2", "huber_delta", "poisson", "multinomial", "row_weights", "penalty_factors", "matrix_f32", "responses"):
                 setattr(d, k, v)
         o = _lib.Options()
         for k, v in options.items():
@@ -119,6 +120,8 @@ class DeviceSolver:
             _lib.check(self.lib.zf_solver_set_matrix_f32(h, C.c_void_p(a32)), "zf_solver_set_matrix_f32")
         if responses > 1 and spmat is None:   # (K = 1 is the plain problem: the setter is not called)
             _lib.check(self.lib.zf_solver_set_responses(h, responses), "zf_solver_set_responses")
+        if multinomial:   # (call order: the responses first - the setter refuses a solver without them)
+            _lib.check(self.lib.zf_solver_set_multinomial(h), "zf_solver_set_multinomial")
         sub = C.c_int32(1)
         _lib.check(self.lib.zf_solver_sub_iters(h, C.byref(sub)), "zf_solver_sub_iters")
         self.sub_iters = int(sub.value)   # iterations one pass may accept (temporal blocking)

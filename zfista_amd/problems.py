@@ -363,6 +363,8 @@ class _GapMixin:
             fields["huber_delta"] = self.delta
         if self._loss == _lib.ZF_LOSS_POISSON:
             fields["poisson"] = True
+        if self._loss == _lib.ZF_LOSS_MULTINOMIAL:   # (the engine calls the setter after the responses)
+            fields["multinomial"] = True
         if self._f32:   # (zf_solver_create takes the same address as A; after zf_solver_set_matrix_f32 nothing reads it)
             fields["matrix_f32"] = self.A.data_ptr()
         if self._pf is not None:
@@ -1290,7 +1292,7 @@ class _SparseMultiResponseMixin(_MultiResponseMixin):
 
         shape = (share.m_rows, share.n_features) if share is not None else tuple(getattr(A, "shape", None) or ())
         checked = self._check_mr(shape, B, l2, sample_weight, penalty_factor)
-        if not np.isfinite(checked[0]).all():
+        if self._loss != _lib.ZF_LOSS_MULTINOMIAL and not np.isfinite(checked[0]).all():   # (the multinomial classes check Y row by row)
             raise ValueError("B holds non-finite values")
         if share is not None:
             self._spmat, self.nnz, self.plan, self._longest = share._spmat, share.nnz, share.plan, share._longest
@@ -1348,6 +1350,167 @@ def _sparse_logistic_with_responses(self, B, sample_weight=None):
 
 SparseLeastSquaresL1.with_responses = _sparse_ls_with_responses
 SparseLogisticL1.with_responses = _sparse_logistic_with_responses
+
+
+# ---------------------------------------------------------------------------
+# multinomial (softmax) regression on the K-response sweeps (csrc/zf_kernels_softmax.h)
+# ---------------------------------------------------------------------------
+def _check_classes(y, m, n_classes=None, weights=None):
+    """The targets of a multinomial problem as ``(Y, classes)``: Y a host (m, K) float64 array with rows on the probability simplex,
+    ``classes`` the K labels 0 .. K-1.  ``y``: a 1-D integer vector of m labels in 0 .. K-1 (K = max + 1, or ``n_classes``), expanded to
+    one-hot rows, or an (m, K) matrix of probabilities - finite, >= 0, every row summing to 1 within 1e-12.  A row whose weight is 0
+    is a row that is not there: it is not checked.  ValueError otherwise - on the host, before anything touches the device."""
+    host = y.detach().cpu().numpy() if hasattr(y, "detach") else np.asarray(y)
+    if np.dtype(host.dtype).kind not in "biuf":
+        raise ValueError(f"y must be integer class labels or a matrix of probabilities, got dtype {host.dtype}")
+    if n_classes is not None and (int(n_classes) != n_classes or not 2 <= int(n_classes) <= MAX_RESPONSES):
+        raise ValueError(f"n_classes must be an integer in 2 .. {MAX_RESPONSES}, got {n_classes!r}")
+    there = np.ones(m, dtype=bool) if weights is None else np.asarray(weights) != 0
+    if host.ndim == 1:
+        if host.shape[0] != m:
+            raise ValueError(f"y must hold {m} class labels (one per row of A), got shape {host.shape}")
+        if np.dtype(host.dtype).kind not in "biu":
+            raise ValueError(f"a 1-D y must be INTEGER class labels 0 .. K-1, got dtype {host.dtype} (probabilities are an (m, K) matrix)")
+        lab = host.astype(np.int64)
+        if lab.size == 0 or lab.min() < 0:
+            raise ValueError("the class labels must be >= 0 (and there must be at least one row)")
+        K = int(lab.max()) + 1 if n_classes is None else int(n_classes)
+        if lab.max() >= K:
+            raise ValueError(f"a class label {int(lab.max())} is outside 0 .. n_classes - 1 = {K - 1}")
+        if not 2 <= K <= MAX_RESPONSES:
+            raise ValueError(f"the number of classes must be 2 .. {MAX_RESPONSES} (the register tiles of the K-response sweeps), got K = {K}")
+        Y = np.zeros((m, K))
+        Y[np.arange(m), lab] = 1.0
+        return Y, np.arange(K)
+    if host.ndim != 2 or host.shape[0] != m:
+        raise ValueError(f"y must be {m} class labels or an ({m}, K) matrix of probabilities, got shape {host.shape}")
+    K = int(host.shape[1])
+    if n_classes is not None and int(n_classes) != K:
+        raise ValueError(f"n_classes = {n_classes} but y has {K} columns")
+    if not 2 <= K <= MAX_RESPONSES:
+        raise ValueError(f"the number of classes must be 2 .. {MAX_RESPONSES} (the register tiles of the K-response sweeps), got K = {K}")
+    Y = np.array(host, dtype=np.float64, order="C", copy=True)
+    rows = Y[there]
+    if not np.all(np.isfinite(rows)) or np.any(rows < 0):
+        raise ValueError("the probabilities y must be finite and >= 0")
+    if np.any(np.abs(rows.sum(axis=1) - 1.0) > 1e-12):
+        raise ValueError("every row of y must sum to 1 (within 1e-12): the loss is logsumexp(z) - <y, z> only on the simplex")
+    return Y, np.arange(K)
+
+
+class _MultinomialMixin:
+    r"""Multinomial (softmax) regression on the K-response problem: Y (m, K) with rows on the probability simplex, X (n, K),
+
+        f(X) = scale \sum_i w_i [ logsumexp(z_i) - <y_i, z_i> ],  z_i = (A X)_i,   grad f = scale A^T (w o (softmax(Z) - Y)),
+
+    with the penalty, the flattening (``x[j K + k] = X[j, k]``), the two sweeps and everything element-wise of ``_MultiResponseMixin``;
+    only the loss couples the K margins of a row (csrc/zf_kernels_softmax.h).  The problem kind is the least-squares one;
+    ``multinomial`` in the descriptor fields makes the engine call ``zf_solver_set_multinomial`` after the responses.  A row has ONE
+    weight: ``sample_weight`` is (m,), repeated K times for the library.  2 <= K <= 16.  No screening, no fp32 matrix, no process
+    group, no acceptance="remainder" / "resolved", no ``l1_cv_lockstep`` (the responses are taken)."""
+
+    _loss = _lib.ZF_LOSS_MULTINOMIAL
+    # The problem kind is the instance's (``_set_multinomial`` copies ``_ls_kind``), the class keeps ``kind = None``: a class-level
+    # kind enters a class into the descriptor table of the losses that are a function of ONE margin (tests/test_evaldesc_host.py);
+    # the descriptor of these classes is checked in tests/test_multinomial_host.py.
+    _ls_kind = None
+
+    def _row_weights(self, w, m):
+        """(m,) weights -> the (m, K)-shaped repeat the K-response layer takes; (m, K) and everything else: ValueError."""
+        if w is None:
+            return None
+        return _check_weights(w, m)
+
+    def _set_multinomial(self, A, y, lam, scale, bounds, l2, sample_weight, penalty_factor, n_classes, group, share):
+        if group is not None:
+            raise ValueError("group= is not available: the multinomial loss kernels, their certificate and zf_solver_set_multinomial "
+                             "are built for one GPU (world = 1)")
+        self.kind = self._ls_kind
+        shape = self._share_shape(share) if share is not None else tuple(getattr(A, "shape", None) or np.shape(A))
+        if len(shape) != 2:
+            raise ValueError(f"A must be (m, n), got shape {shape}")
+        m = int(shape[0])
+        w = self._row_weights(sample_weight, m)
+        Y, self.classes = _check_classes(y, m, n_classes, w)
+        K = Y.shape[1]
+        self._set_mr(A, Y, lam, scale, bounds, l2, None if w is None else np.repeat(w.reshape(m, 1), K, axis=1), penalty_factor, share)
+
+    @staticmethod
+    def _share_shape(share):
+        return tuple(share.A.shape) if hasattr(share, "A") else (share.m_rows, share.n_features)
+
+    @property
+    def sample_weight(self):
+        """The per-row sample weights, (m,) (a host copy), or None."""
+        return None if self._w_host is None else self._w_host.reshape(self._m, self.n_responses)[:, 0].copy()
+
+    def with_sample_weight(self, w):
+        """A sibling with the per-row weights ``w`` - (m,) only: a row of this loss has one weight - on the same device matrix and Y.
+        The rows of Y with a positive weight must lie on the simplex - with ``None`` every row: ValueError otherwise."""
+        w = self._row_weights(w, self._m)   # (None: every row is there again, so every row of Y is checked)
+        _check_classes(self.b.detach().cpu().numpy().reshape(self._m, self.n_responses), self._m, None, w)
+        return super().with_sample_weight(None if w is None else np.repeat(w.reshape(self._m, 1), self.n_responses, axis=1))
+
+    def predict_proba(self, x, A=None):
+        """softmax(A X) -> (rows of A, K), on the host from ``coef(x)`` (a convenience, not a kernel).  ``A``: a host matrix (dense
+        or scipy.sparse) with n columns; None: the problem's own matrix, copied from the device."""
+        X = self.coef(_as_host(self._flat(x)))
+        if A is None:
+            A = self._host_matrix()
+        Z = np.asarray(A @ X, dtype=np.float64)
+        Z = Z - Z.max(axis=1, keepdims=True)
+        E = np.exp(Z)
+        return E / E.sum(axis=1, keepdims=True)
+
+
+class MultinomialL1(_MultinomialMixin, _MultiResponseMixin, _DenseMarginsL1):
+    r"""L1-regularised multinomial (softmax) regression, A dense row-major: glmnet's ``family="multinomial"``, sklearn's
+    ``LogisticRegression(penalty="l1")`` with several classes.  ``y``: m integer class labels 0 .. K-1 (``n_classes=`` when the largest
+    does not occur) or an (m, K) matrix of probabilities.  ``coef(x)`` -> (n, K), ``predict_proba(x)`` -> (m, K), ``classes`` the K
+    labels; f, jac_f, duality_gap, gap_tol, lam_max, l1_path, snapshots and the siblings as for the K-response classes.
+    See ``_MultinomialMixin``."""
+
+    _ls_kind = _lib.ZF_PROBLEM_LEAST_SQUARES_L1
+
+    def __init__(self, A, y, lam, scale=1.0, bounds=None, l2=0.0, *, sample_weight=None, penalty_factor=None, n_classes=None, group=None,
+                 _share=None):
+        self._set_multinomial(A, y, lam, scale, bounds, l2, sample_weight, penalty_factor, n_classes, group, _share)
+
+    def _host_matrix(self):
+        return self.A.detach().cpu().numpy()
+
+
+class SparseMultinomialL1(_MultinomialMixin, _SparseMultiResponseMixin, _SparseMarginsL1):
+    r"""``MultinomialL1`` with a SPARSE A (any scipy.sparse matrix): the handle, plans and sweeps of the sparse K-response classes,
+    the loss kernels of the dense class - the rows of the same (m, K) are summed in the same order."""
+
+    _ls_kind = _lib.ZF_PROBLEM_SPARSE_LS_L1
+
+    def __init__(self, A, y, lam, scale=1.0, bounds=None, l2=0.0, *, sample_weight=None, penalty_factor=None, n_classes=None, group=None,
+                 _share=None):
+        self._set_multinomial(A, y, lam, scale, bounds, l2, sample_weight, penalty_factor, n_classes, group, _share)
+
+    def _host_matrix(self):
+        import scipy.sparse as sp
+
+        d = self._spmat.dev
+        return sp.csr_matrix((d["data"].cpu().numpy(), d["indices"].cpu().numpy(), d["indptr"].cpu().numpy()), shape=(self._m, self._n))
+
+
+def _logistic_with_classes(self, y, sample_weight=None, n_classes=None):
+    """A ``MultinomialL1`` on this problem's device matrix (shared, nothing but Y is uploaded) with its lam, scale, bounds, l2 and
+    penalty factors (repeated for every class).  ``y``: m class labels or (m, K) probabilities; ``sample_weight``: (m,) or None."""
+    return _with_responses(self, lambda A, B, *a, **kw: MultinomialL1(A, B, *a, n_classes=n_classes, **kw), y, sample_weight)
+
+
+def _sparse_logistic_with_classes(self, y, sample_weight=None, n_classes=None):
+    """A ``SparseMultinomialL1`` on this problem's matrix handle (the same object; only Y is uploaded) with its lam, scale, bounds,
+    l2 and penalty factors (repeated for every class).  ``y``: m class labels or (m, K) probabilities; ``sample_weight``: (m,) or None."""
+    return _sparse_with_responses(self, lambda A, B, *a, **kw: SparseMultinomialL1(A, B, *a, n_classes=n_classes, **kw), y, sample_weight)
+
+
+LogisticL1.with_classes = _logistic_with_classes
+SparseLogisticL1.with_classes = _sparse_logistic_with_classes
 
 
 class BlurHaarL1(NativeProblem):
