@@ -525,9 +525,9 @@ int zf_solver_create_sparse(zf_solver** out, const zf_problem_desc* desc, const 
  * loss forms its residuals with up to 1024 workgroups, as the sparse kind does by its row count).  Additive to ABI 6.
  * zf_solver_create_sparse_responses: zf_solver_create_sparse with desc->m_rows = K h->m, desc->n = K h->n, desc->b of m K values.
  * ZF_ERR_ARG: K outside 2 .. 16, dimensions that are not K times the handle's, a kind other than 4 / 6, world > 1,
- * ZF_ACCEPT_REMAINDER / ZF_ACCEPT_RESOLVED.  zf_solver_set_huber / _poisson / _matrix_f32 refuse such a solver; it composes with
- * zf_solver_set_l2 / _row_weights (m K weights) / _penalty_factors (n K factors).  zf_solver_create_sparse keeps its dimension check
- * and zf_solver_set_responses keeps refusing the sparse kinds: K is set at creation or never.  A solver not created here launches and
+ * ZF_ACCEPT_REMAINDER / ZF_ACCEPT_RESOLVED.  Such a solver has the option "responses" of the options table below (m K row weights,
+ * n K penalty factors).  zf_solver_create_sparse keeps its dimension check and zf_solver_set_responses keeps refusing the sparse
+ * kinds: K is set at creation or never.  A solver not created here launches and
  * allocates what it did.  Vectors of n K >= 2^31 entries are indexed in 64 bits (n < 2^31, n K is not). */
 int zf_solver_create_sparse_responses(zf_solver** out, const zf_problem_desc* desc, const zf_spmat* h, int32_t K, const zf_options* opt,
                                       void* stream);
@@ -547,16 +547,62 @@ int zf_spmat_mr_apply(const zf_spmat* h, int32_t transpose, int32_t K, double ou
  * one).  ZF_ERR_STATE: not initialised. */
 int zf_solver_duality_gap(zf_solver* s, double* out, int64_t count /* >= 8 */);
 
+/* ---- the options of a margins solver: which of the eight zf_solver_set_* entries exist together -----------------------------------
+ * The sections below say what each option computes.  All eight are called after zf_solver_create(_sparse, _sparse_responses) and
+ * before zf_solver_enqueue_init / zf_solver_restore: ZF_ERR_STATE afterwards (zf_solver_set_matrix_f32: ZF_ERR_ARG).  Every other
+ * refusal is ZF_ERR_ARG: a NULL solver or pointer, world > 1, a bad argument (its section), and what the three tables refuse.  A
+ * refused call leaves the solver as it was, and zf_last_error names the entry and - for a pair - the option already present.  One
+ * record and one rule table hold all of this (csrc/zf_solver_options.h); a resumed solve sets its options again before
+ * zf_solver_restore (a snapshot carries none of them).  Every option but an explicit l2 = 0 takes a matrix small enough for the
+ * two fused small-matrix launches to the general path, for good, and zf_solver_ls_plan says so.
+ *
+ * options by kinds (+: admitted; kinds 1 and 3 admit none)
+ *                      2 least squares  4 sparse LS  5 logistic  6 sparse logistic
+ *   l2                 +                +            +           +
+ *   penalty_factors    +                +            +           +
+ *   huber              +                +            .           .
+ *   poisson            +                +            .           .
+ *   multinomial        +                +            .           .
+ *   row_weights        +                +            +           +
+ *   matrix_f32         +                .            +           .
+ *   responses          +                .            +           .            (sparse: K comes from zf_solver_create_sparse_responses)
+ *
+ * options by accept modes (x: refused; ZF_ACCEPT_RESOLVED exists for kind 1 only, which admits no option)
+ *                      ZF_ACCEPT_REFERENCE  ZF_ACCEPT_REMAINDER
+ *   l2                 +                    +
+ *   penalty_factors    +                    +          (both touch g only)
+ *   huber              +                    x          (scale |A (x+ - y)|^2 is the Taylor remainder of the squared loss alone)
+ *   poisson            +                    x
+ *   multinomial        +                    x
+ *   row_weights        +                    x          (the residual kernels that form the remainder carry no weights)
+ *   matrix_f32         +                    +
+ *   responses          +                    x
+ *
+ * options by options (x: refused together, in either call order; +: compose, in any order; o: compose in ONE order; diagonal: a second call - 2 replaces the value, x is refused)
+ *                      l2  penalty_factors  huber  poisson  multinomial  row_weights  matrix_f32  responses
+ *   l2                 2   x                +      +        +            +            +           +
+ *   penalty_factors    x   2                +      +        +            +            +           +
+ *   huber              +   +                2      x        x            +            +           x
+ *   poisson            +   +                x      2        x            +            +           x
+ *   multinomial        +   +                x      x        x            +            x           o
+ *   row_weights        +   +                +      +        +            2            +           +
+ *   matrix_f32         +   +                +      +        x            +            2           x
+ *   responses          +   +                x      x        o            +            x           x
+ *
+ * l2 x penalty_factors: the ridge term would need the factors too (not built); l2 = 0 is "not set" and is accepted beside them.
+ * One loss per solver.  The K-response sweeps read an fp64 A and carry the square, the logistic and the multinomial loss.
+ * The one ordering rule (o): zf_solver_set_multinomial needs the K >= 2 responses already there - a dense solver calls
+ * zf_solver_set_responses BEFORE it, a sparse one comes from zf_solver_create_sparse_responses - so it is refused on a matrix
+ * stored in fp32 and, like the responses, cannot be called twice. */
+
 /* ---- elastic net: g(x) = lam |x|_1 + (l2 / 2) |x|^2 (+ box) for the margins kinds 2, 4, 5, 6 ------------------------------
  * Additive to ABI 6: no struct field, no version change.  prox_{w g}(v) = clip(soft_threshold(v, lam w) * shrink, lo, hi) with
  * shrink = 1 / (1 + l2 w) formed once per trial as a scalar; the element is multiplied by it (no division per element), the
  * iterate arithmetic stays uncontracted: x+ is that expression bit for bit.  The clip behind the shrink is the exact prox.
- * zf_solver_set_l2: after zf_solver_create(_sparse), before zf_solver_enqueue_init / zf_solver_restore (ZF_ERR_STATE afterwards).
- * ZF_ERR_ARG: another problem kind, world > 1, l2 < 0 or not finite.  With l2 > 0 every trial runs the elastic-net step kernel
- * (zf_trial_enet_kernel: the general vector path; a matrix small enough for the two fused small-matrix launches takes the
- * general path too, and zf_solver_ls_plan says so), F(x0) includes the ridge term, and zf_solver_duality_gap evaluates the
- * ridge form of the certificate (zf_margins_gap).  l2 = 0 changes nothing: the launches, allocations and bits of a solver that was never asked.  A resumed
- * solve sets l2 again before zf_solver_restore (the snapshot carries nothing new). */
+ * zf_solver_set_l2 (when, and with what: the options table above).  ZF_ERR_ARG of its own: l2 < 0 or not finite.  With l2 > 0 every
+ * trial runs the elastic-net step kernel (zf_trial_enet_kernel: the general vector path), F(x0) includes the ridge term, and
+ * zf_solver_duality_gap evaluates the ridge form of the certificate (zf_margins_gap).  l2 = 0 changes nothing: the launches,
+ * allocations and bits of a solver that was never asked. */
 int zf_solver_set_l2(zf_solver* s, double l2);
 /* out = clip(soft_threshold(x, tau) * shrink, lo, hi) at a host vector: the elastic-net prox with tau = lam w and the caller's
  * scalar shrink = 1 / (1 + l2 w) */
@@ -597,14 +643,10 @@ int zf_dense_restrict(const double* A_dev, int64_t m_rows, int64_t n, const uint
  * function); grad f = 2 scale A^T c, c = clip(r, -delta, delta).  Every kernel forms c = copysign(min(|r|, delta), r) - exact
  * given r - and H = c (2 r - c): two roundings, never negative, r r on an unclipped row.  The sum is a plain sum.  A NaN margin
  * gives a NaN f.  Additive to ABI 6: no problem kind, no struct field, no version change.
- * zf_solver_set_huber: after zf_solver_create(_sparse), before zf_solver_enqueue_init / zf_solver_restore (ZF_ERR_STATE
- * afterwards).  ZF_ERR_ARG: a kind other than ZF_PROBLEM_LEAST_SQUARES_L1 / ZF_PROBLEM_SPARSE_LS_L1, world > 1, delta not finite
- * or <= 0, a solver created with ZF_ACCEPT_REMAINDER (scale |A (x+ - y)|^2 is not this loss's Taylor remainder).  A trial then
- * runs the loss kernels where it ran the residual kernels - at y (c to the residual buffer, f(y)) and at x+ (f(x+)); the A^T
- * sweep (with the same 2 scale), the prox step (zf_solver_set_l2 composes, in either order), the decision, history and
- * snapshots are the least-squares kinds' own.  A matrix small enough for the two fused small-matrix launches takes the general
- * path, and zf_solver_ls_plan says so.  A solver that was never asked launches and allocates what it did.  A resumed solve
- * sets delta again before zf_solver_restore. */
+ * zf_solver_set_huber (when, and with what: the options table above).  ZF_ERR_ARG of its own: delta not finite or <= 0.  A trial
+ * then runs the loss kernels where it ran the residual kernels - at y (c to the residual buffer, f(y)) and at x+ (f(x+)); the A^T
+ * sweep (with the same 2 scale), the prox step, the decision, history and snapshots are the least-squares kinds' own.  A solver
+ * that was never asked launches and allocates what it did. */
 int zf_solver_set_huber(zf_solver* s, double delta);
 
 /* ---- per-row sample weights on the four margins kinds 2, 4, 5, 6 (csrc/zf_kernels_loss.h) -----------------------------------
@@ -616,13 +658,9 @@ int zf_solver_set_huber(zf_solver* s, double delta);
  * w_dev: m_rows doubles in device memory, finite and >= 0 with at least one > 0 (the caller's check: the library does not read
  * them on the host).  Additive to ABI 6: no problem kind, no struct field, no version change. */
 enum { ZF_LOSS_SQUARE = 0, ZF_LOSS_LOGISTIC = 1, ZF_LOSS_HUBER = 2 };
-/* zf_solver_set_row_weights: after zf_solver_create(_sparse), before zf_solver_enqueue_init / zf_solver_restore (ZF_ERR_STATE
- * afterwards).  ZF_ERR_ARG: a null argument, a kind other than the four margins kinds, world > 1, a solver created with
- * ZF_ACCEPT_REMAINDER or ZF_ACCEPT_RESOLVED.  The pointer is borrowed, as b is.  Composes with zf_solver_set_huber and
- * zf_solver_set_l2 in any order.  The three loss sites of a trial, f of the initial point and zf_solver_duality_gap then take
- * the weighted kernels; the two sweeps, the prox step, the decision, history and snapshots stay as they are.  A matrix small
- * enough for the two fused small-matrix launches takes the general path, and zf_solver_ls_plan says so.  A solver that was
- * never asked launches and allocates what it did.  A resumed solve sets the weights again before zf_solver_restore. */
+/* zf_solver_set_row_weights (when, and with what: the options table above).  The pointer is borrowed, as b is.  The three loss
+ * sites of a trial, f of the initial point and zf_solver_duality_gap then take the weighted kernels; the two sweeps, the prox
+ * step, the decision, history and snapshots stay as they are.  A solver that was never asked launches and allocates what it did. */
 int zf_solver_set_row_weights(zf_solver* s, const double* w_dev);
 
 /* ---- the Poisson loss with a log link on the least-squares kinds 2 and 4 (csrc/zf_kernels_loss.h) ------------------------
@@ -632,14 +670,10 @@ int zf_solver_set_row_weights(zf_solver* s, const double* w_dev);
  * phi = e - b z (two roundings); the sum is a plain sum times scale.  A margin beyond the range of exp gives f = +inf, never NaN:
  * the acceptance test rejects such a trial and the line search backtracks.  A NaN margin gives a NaN f.  The library does not
  * read b on the host: b >= 0 is the caller's check.  Additive to ABI 6: no problem kind, no struct field, no version change.
- * zf_solver_set_poisson: after zf_solver_create(_sparse), before zf_solver_enqueue_init / zf_solver_restore (ZF_ERR_STATE
- * afterwards).  ZF_ERR_ARG: a kind other than ZF_PROBLEM_LEAST_SQUARES_L1 / ZF_PROBLEM_SPARSE_LS_L1, world > 1, a solver
- * created with ZF_ACCEPT_REMAINDER or ZF_ACCEPT_RESOLVED, a solver that has Huber's loss (and zf_solver_set_huber after this
- * call likewise).  Composes with zf_solver_set_l2 and zf_solver_set_row_weights in any order.  A trial then runs the loss
- * kernels where it ran the residual kernels - at y (psi to the residual buffer, f(y)) and at x+ (f(x+)); the A^T sweep runs with
- * `scale` for `2 scale`; the prox step, the decision, history and snapshots are the least-squares kinds' own.  A matrix small
- * enough for the two fused small-matrix launches takes the general path, and zf_solver_ls_plan says so.  A solver that was never
- * asked launches and allocates what it did.  A resumed solve calls it again before zf_solver_restore. */
+ * zf_solver_set_poisson (when, and with what: the options table above).  A trial then runs the loss kernels where it ran the
+ * residual kernels - at y (psi to the residual buffer, f(y)) and at x+ (f(x+)); the A^T sweep runs with `scale` for `2 scale`;
+ * the prox step, the decision, history and snapshots are the least-squares kinds' own.  A solver that was never asked launches
+ * and allocates what it did. */
 enum { ZF_LOSS_POISSON = 3 };   /* the fourth ZF_LOSS_* code (struct zf_loss of csrc/zf_loss_dispatch.h) */
 int zf_solver_set_poisson(zf_solver* s);
 
@@ -650,12 +684,8 @@ int zf_solver_set_poisson(zf_solver* s);
  * prox_{w g}(v)_j = clip(soft_threshold(v_j, (lam w) p_j), lo, hi): t = lam w once per trial, tau_j = t * p_j per element, the
  * fourth running sum takes fma(p_j, |x+_j|, sum) and keeps its scale lam (zf_trial_pf_kernel; 8 n bytes more per trial).  p = 1
  * gives the iterates and packs of a solver that was never asked, bit for bit; p_j = 0 gives x+_j = v_j exactly.
- * zf_solver_set_penalty_factors: after zf_solver_create(_sparse), before zf_solver_enqueue_init / zf_solver_restore
- * (ZF_ERR_STATE afterwards).  ZF_ERR_ARG: a null pointer, a misaligned one, another problem kind, world > 1, and together with
- * l2 > 0 in either call order (the ridge term would need the factors too; not built).  Every trial then runs the general vector
- * path (a matrix small enough for the two fused small-matrix launches too, and zf_solver_ls_plan says so).  Composes with
- * zf_solver_set_huber / _poisson / _row_weights in any order, and with ZF_ACCEPT_REMAINDER, which touches f only.  A resumed
- * solve sets the factors again before zf_solver_restore (the snapshot carries nothing new). */
+ * zf_solver_set_penalty_factors (when, and with what: the options table above).  ZF_ERR_ARG of its own: a misaligned pointer.
+ * Every trial then runs the general vector path. */
 int zf_solver_set_penalty_factors(zf_solver* s, const double* p_dev);
 /* out = clip(sign(x) * max(|x| - t * p, 0), lo, hi) at host vectors, NumPy's expression operation by operation */
 int zf_host_prox_pf_box(double* out_host, const double* x_host, const double* p_host, double t, double lo, double hi, int64_t n);
@@ -673,10 +703,8 @@ int zf_host_pf_g(const double* x_host, const double* p_host, int64_t n, double l
  * the initial evaluation, zf_solver_duality_gap - takes the fp32 kernels, the slices are those of the fp32 rule (panels of
  * 256 * V columns, V = 4 / 2 / 1 for n % 4 == 0 / n % 4 == 2 / odd n; at most 64 slices of at least 8 rows), a matrix small enough
  * for the two fused small-matrix launches takes the general path, ZF_GEMV_MFMA has no effect, and zf_solver_ls_plan says so.
- * ZF_ERR_ARG: a null or misaligned pointer, a kind other than ZF_PROBLEM_LEAST_SQUARES_L1 / ZF_PROBLEM_LOGISTIC_L1, world > 1, a
- * solver that is already initialised.  Composes with zf_solver_set_l2 / _huber / _poisson / _row_weights / _penalty_factors in
- * any order.  A resumed solve sets the matrix again before zf_solver_restore (the snapshot carries nothing new).  A solver that
- * was never asked launches and allocates what it did. */
+ * When, and with what: the options table above.  ZF_ERR_ARG of its own: a misaligned pointer, and - where the other seven answer
+ * ZF_ERR_STATE - a solver that is already initialised.  A solver that was never asked launches and allocates what it did. */
 int zf_solver_set_matrix_f32(zf_solver* s, const float* A32_dev);
 
 /* ---- K responses on one dense matrix, on the two dense kinds 2, 5 ---------------------------------------------------------------
@@ -690,11 +718,8 @@ int zf_solver_set_matrix_f32(zf_solver* s, const float* A32_dev);
  * K-response kernels, the slices are those of the rule on m x n, the unweighted squared loss forms its residuals with up to 1024
  * workgroups beyond 32768 rows of m K (as the sparse kind does), a matrix small enough for the two fused small-matrix launches takes
  * the general path, ZF_GEMV_MFMA has no effect, and zf_solver_ls_plan says so.
- * ZF_ERR_ARG: K outside 2 .. 16, m_rows or n not a multiple of K, a kind other than ZF_PROBLEM_LEAST_SQUARES_L1 /
- * ZF_PROBLEM_LOGISTIC_L1, world > 1, ZF_ACCEPT_REMAINDER / ZF_ACCEPT_RESOLVED, a solver with zf_solver_set_huber / _poisson /
- * _matrix_f32 (and those three after this one), a second call.  ZF_ERR_STATE: a solver that is already initialised.  Composes with
- * zf_solver_set_l2 / _row_weights (m K weights) / _penalty_factors (n K factors) in any order.  A resumed solve sets the responses
- * again before zf_solver_restore.  A solver that was never asked launches and allocates what it did. */
+ * When, and with what: the options table above (row weights are m K weights then, penalty factors n K factors).  ZF_ERR_ARG of
+ * its own: K outside 2 .. 16, m_rows or n not a multiple of K.  A solver that was never asked launches and allocates what it did. */
 int zf_solver_set_responses(zf_solver* s, int32_t K);
 
 /* ---- the multinomial (softmax) loss on K responses, on the least-squares kinds 2 and 4 (csrc/zf_kernels_softmax.h) ---------------
@@ -709,13 +734,9 @@ int zf_solver_set_responses(zf_solver* s, int32_t K);
  * Row weights stay one double per FLATTENED entry (m K of them, zf_solver_set_row_weights as before) so that neither the ABI nor
  * the snapshot format changes, but a row of this loss has ONE weight: the kernels read w[i K] alone - the caller repeats w_i K
  * times - and w_i == 0 is a row that is not there, whatever y_i holds.
- * zf_solver_set_multinomial: after zf_solver_create(_sparse_responses), before zf_solver_enqueue_init / zf_solver_restore
- * (ZF_ERR_STATE afterwards).  The solver already has its K >= 2 responses: a dense one by zf_solver_set_responses BEFORE this call
- * (the reverse order is ZF_ERR_ARG), a sparse one from zf_solver_create_sparse_responses.  ZF_ERR_ARG also: a kind other than
- * ZF_PROBLEM_LEAST_SQUARES_L1 / ZF_PROBLEM_SPARSE_LS_L1, world > 1, ZF_ACCEPT_REMAINDER / ZF_ACCEPT_RESOLVED, a solver with Huber's or
- * the Poisson loss (and those two setters after this call), a second call.  Composes with zf_solver_set_l2 / _row_weights /
- * _penalty_factors in any order.  A resumed solve calls it again before zf_solver_restore.  A solver that was never asked launches
- * and allocates what it did.  Additive to ABI 7: one enumerator, one entry, no struct change. */
+ * zf_solver_set_multinomial (when, and with what: the options table above, and its ordering rule).  ZF_ERR_ARG of its own: b (the
+ * rows of Y) not 16-byte aligned.  A solver that was never asked launches and allocates what it did.  Additive to ABI 7: one
+ * enumerator, one entry, no struct change. */
 enum { ZF_LOSS_MULTINOMIAL = 4 };   /* the fifth ZF_LOSS_* code */
 int zf_solver_set_multinomial(zf_solver* s);
 

@@ -29,6 +29,7 @@
 #include "zf_kernels_softmax.h"
 #include "zf_loss_dispatch.h"
 #include "zf_kernels_step.h"
+#include "zf_solver_options.h"
 #include "zf_trial_launch.h"
 
 thread_local char zf_errbuf[512] = "";
@@ -249,22 +250,17 @@ struct zf_solver {
     bool initialised = false;
     bool init_enqueued = false;   // zf_solver_enqueue_init(_all) ran: x0 is in the ring (zf_solver_set_comm may no longer reallocate it)
     bool own_packs = true;
-    bool ls_small = false;        // cache-resident A: two fused launches per trial (zf_kernels_ls_small.h)
-    // the matrix kinds: A as the two sweeps see it (zf_matview.h) - mat.A32: the matrix stored in fp32 (zf_solver_set_matrix_f32; borrowed
-    // as desc.A is; nothing reads desc.A then); mat.k: responses (zf_solver_set_responses, zf_solver_create_sparse_responses: mat.m x
-    // mat.n is the matrix, desc holds the flattened lengths); mat.h: the caller's CSR handle (never written through); mat.mfma:
-    // A^T r on v_mfma_f64_16x16x4 (n % 32 == 0; ZF_GEMV_MFMA=0 disables) - and what the sweeps write between their launches: the
-    // slab of ws.slices * n doubles, or this solver's segment sums of the split rows of A / of A^T
-    zf_matview mat = {nullptr, 0, 0, nullptr, false, nullptr, 1, false};
+    // the matrix kinds: the options of the eight zf_solver_set_* entries (zf_solver_options.h: the record, the rules, what follows
+    // from them - zf_loss_of, zf_mat_of, zf_small_open below); small_shape, mfma_shape: what zf_solver_create found of the shape for
+    // them (zf_options_base); sp: the caller's CSR handle (never written through), NULL for dense - and what the sweeps write between
+    // their launches: the slab of ws.slices * n doubles, or this solver's segment sums of the split rows of A / of A^T
+    zf_solver_options o;
+    bool small_shape = false;
+    bool mfma_shape = false;
+    const zf_spmat* sp = nullptr;
     zf_sweep_ws ws = {nullptr, 1, 0, nullptr, nullptr};
-    double huber = 0.0;           // Huber's loss (zf_solver_set_huber): delta > 0 swaps the residual kernels for the rows kernel of zf_kernels_loss.h; 0: the squared loss
-    bool multinomial = false;     // the multinomial loss on K responses (zf_solver_set_multinomial): the rows kernels of zf_kernels_softmax.h
-    bool poisson = false;         // the Poisson loss (zf_solver_set_poisson): the residual kernels swapped for the rows kernel of zf_kernels_loss.h
-    bool loss_part = false;       // the dense least-squares kind holds the 2 x ZF_SPMV_RESID_MAX_CHUNKS chunk sums of the loss kernels (zf_loss_part)
-    const double* roww = nullptr; // per-row sample weights (zf_solver_set_row_weights; borrowed as b is): the loss sites take the weighted rows kernels; NULL: what ran before
-    double l2 = 0.0;              // elastic net (zf_solver_set_l2): g = lam |x|_1 + (l2 / 2) |x|^2; 0: every path is the l1 one
-    const double* pf = nullptr;   // per-column penalty factors (zf_solver_set_penalty_factors; borrowed as b is): g = lam sum p_j |x_j|; NULL: what ran before
-    double* gap_xp = nullptr;     // ... the certificate's scaled iterate p o x_k (n doubles, allocated by the first zf_solver_duality_gap)
+    bool loss_part = false;       // the dense least-squares kind holds the 2 x ZF_SPMV_RESID_MAX_CHUNKS chunk sums of the loss kernels (zf_solver_set_option)
+    double* gap_xp = nullptr;     // penalty factors: the certificate's scaled iterate p o x_k (n doubles, allocated by the first zf_solver_duality_gap)
     zf_op_plan op_plan = {};      // operator problem: which instantiation of the correlation kernels runs it (zf_op_make_plan)
     double* op_buf = nullptr;     // its taps as launched (zero-padded to K x K) and, behind them, the rank-1 factors u, v when the kernel is separable
     const double* op_taps = nullptr, *op_sep = nullptr;
@@ -439,16 +435,25 @@ static bool zf_is_dense_mat(int kind) { return kind == ZF_PROBLEM_LEAST_SQUARES_
 static bool zf_is_sparse_mat(int kind) { return kind == ZF_PROBLEM_SPARSE_LS_L1 || kind == ZF_PROBLEM_SPARSE_LOGISTIC_L1; }
 // f is a loss of A x: the margins of x_k, x_{k-1} are kept in a ring and A y follows by linearity
 static bool zf_has_margins(int kind) { return zf_is_ls(kind) || zf_is_logistic(kind); }
-// the loss of a solver (zf_loss_dispatch.h): the one place that reads the problem kind, zf_solver_set_huber, zf_solver_set_poisson,
-// zf_solver_set_multinomial and zf_solver_set_row_weights for it
-static zf_loss zf_loss_of(const zf_solver* s) {
-    const int kind = zf_is_logistic(s->desc.kind) ? ZF_LOSS_LOGISTIC
-                     : s->huber > 0.0            ? ZF_LOSS_HUBER
-                     : s->poisson                ? ZF_LOSS_POISSON
-                     : s->multinomial            ? ZF_LOSS_MULTINOMIAL
-                                                 : ZF_LOSS_SQUARE;
-    return zf_loss{kind, s->huber, s->roww, s->mat.k};
+// ---- what a solver's options record implies (zf_solver_options.h) ----
+static_assert(ZF_OPT_MAX_K == ZF_MR_MAX_K && ZF_OPT_MAX_K == ZF_SPMM_MAX_K, "one bound of the response count");
+static zf_options_base zf_base_of(const zf_solver* s) {
+    const zf_problem_desc& d = s->desc;
+    return zf_options_base{(int)d.kind, (int)d.world, s->accept_mode, s->init_enqueued || s->initialised, d.m_rows, d.n, d.b, s->small_shape, s->mfma_shape};
 }
+// the loss (zf_loss_dispatch.h)
+static zf_loss zf_loss_of(const zf_solver* s) { return zf_loss{zf_options_loss(s->desc.kind, s->o), s->o.huber, s->o.roww, s->o.K}; }
+// A as the two sweeps see it (zf_matview.h): desc.A, or the matrix stored in fp32 (nothing reads desc.A then), or the handle's
+// (o: the solver's record, or the record a setter is about to store)
+static zf_matview zf_mat_of(const zf_solver* s, const zf_solver_options& o) {
+    const zf_options_view v = zf_options_view_of(zf_base_of(s), o);
+    return zf_matview{v.f32 ? nullptr : s->desc.A, v.m, v.n, s->sp, s->sp != nullptr, o.A32, v.K, v.mfma};
+}
+static zf_matview zf_mat_of(const zf_solver* s) { return zf_mat_of(s, s->o); }
+// cache-resident A: two fused launches per trial (zf_kernels_ls_small.h)
+static bool zf_small_open(const zf_solver* s) { return zf_options_small_open(zf_base_of(s), s->o); }
+// the factor of the g sum in the finalisation of a trial and of the initial point: the l1 kernels leave sum |x| (or sum p |x|) there
+static double zf_g_scale(const zf_solver* s) { return zf_options_g_is_whole(s->o) ? 1.0 : s->desc.lam; }
 static zf_op_args zf_op_of(const zf_problem_desc& d, const zf_control* ctl, const zf_op_plan& pl, const double* taps, const double* sep) {
     zf_op_args P;
     P.ctl = ctl;
@@ -501,7 +506,7 @@ static void zf_launch_apply_A(zf_solver* s, const zf_control* ctl, zf_ring3 xr, 
         zf_launch_op_apply(s->op_plan, s->stream, zf_op_of(s, ctl), xr.p[0], xr.p[1], xr.p[2], sout.p[0], sout.p[1], sout.p[2], slot,
                            zf_op_no_fuse());
     else
-        zf_launch_apply(s->mat, s->stream, ctl, xr, sout, slot, s->ws);
+        zf_launch_apply(zf_mat_of(s), s->stream, ctl, xr, sout, slot, s->ws);
 }
 
 // What two passes in flight need: the second stream (non-blocking, at the highest priority: what runs there - a waiting
@@ -587,9 +592,11 @@ static int zf_solver_create_impl(zf_solver** out, const zf_problem_desc* desc, c
     s->desc = *desc;
     s->opt = *opt;
     s->env = zf_env_read();
-    if (zf_is_sparse_mat(desc->kind)) s->mat = zf_matview{nullptr, sp->m, sp->n, sp, true, nullptr, K, false};
-    if (zf_is_dense_mat(desc->kind))
-        s->mat = zf_matview{desc->A, desc->m_rows, desc->n, nullptr, false, nullptr, 1, desc->n % 32 == 0 && s->env.gemv_mfma};
+    if (zf_is_sparse_mat(desc->kind)) {
+        s->sp = sp;
+        s->o.K = K;
+    }
+    s->mfma_shape = zf_is_dense_mat(desc->kind) && desc->n % 32 == 0 && s->env.gemv_mfma;
     s->pass_seq = s->env.pass_seq_start;
     s->stream = reinterpret_cast<hipStream_t>(stream);
     s->box = !(desc->box_lo == -INFINITY && desc->box_hi == INFINITY);
@@ -734,7 +741,7 @@ static int zf_solver_create_impl(zf_solver** out, const zf_problem_desc* desc, c
     }
     if (zf_is_dense_mat(desc->kind)) {
         const int64_t m = desc->m_rows;
-        zf_view_slices(s->mat, &s->ws.slices, &s->ws.rows_per_slice);
+        zf_view_slices(zf_mat_of(s), &s->ws.slices, &s->ws.rows_per_slice);
         ZF_TRY(hipMalloc(&s->ws.slab, sizeof(double) * s->ws.slices * n));
         if (desc->world > 1) {   // exchanged vector: A_p x_p (m) for column blocks, A_p^T r_p (n) for row blocks
             const int64_t len = desc->row_sharded ? n : m;
@@ -743,9 +750,10 @@ static int zf_solver_create_impl(zf_solver** out, const zf_problem_desc* desc, c
         }
         // launch-bound sizes (BASELINE cfg1): two fused launches per trial; ZF_LS_SMALL=0 keeps the general path
         // (the squared loss is written into those two kernels: the logistic kind always takes the general path)
-        s->ls_small = desc->kind == ZF_PROBLEM_LEAST_SQUARES_L1 && desc->world == 1 && n % LS_SMALL_COLS == 0 && m <= LS_SMALL_MAX_M &&
-                      m * n <= LS_SMALL_MAX_ELEMS && zf_aligned16(desc->A) && s->env.ls_small;
-        if (s->ls_small) {
+        // (an option set later leaves the path: zf_options_small_open)
+        s->small_shape = desc->kind == ZF_PROBLEM_LEAST_SQUARES_L1 && desc->world == 1 && n % LS_SMALL_COLS == 0 && m <= LS_SMALL_MAX_M &&
+                         m * n <= LS_SMALL_MAX_ELEMS && zf_aligned16(desc->A) && s->env.ls_small;
+        if (s->small_shape) {
             // (twice the workgroups of the rows kernel: their sums of (s+ - b)^2 and - ZF_ACCEPT_REMAINDER - of (s+ - s_y)^2)
             ZF_TRY(hipMalloc(&s->row_part, sizeof(double) * 2 * ((m + ZF_WAVES - 1) / ZF_WAVES)));
             ZF_TRY(hipMalloc(&s->ls_cnt, 64));
@@ -808,10 +816,10 @@ static void zf_launch_trial_kernels(zf_solver* s, const zf_step_args& a, bool gr
     const int grid = s->grid;
     hipStream_t st = s->stream;
     if (!grad_inline) {   // least squares: one trial per pass
-        if (s->l2 > 0.0) zf_launch_enet(v, s->hist != nullptr, grid, st, a, s->l2);
-        else if (s->pf) {   // (the factors travel in the stream the vector path leaves unused)
+        if (s->o.l2 > 0.0) zf_launch_enet(v, s->hist != nullptr, grid, st, a, s->o.l2);
+        else if (s->o.pf) {   // (the factors travel in the stream the vector path leaves unused)
             zf_step_args f = a;
-            f.p1 = s->pf;
+            f.p1 = s->o.pf;
             zf_launch_pf(v, s->hist != nullptr, grid, st, f);
         } else if (s->hist) zf_launch_hist(v, false, 1, 0, grid, st, a);
         else zf_launch_vec(v, grid, st, a);
@@ -863,8 +871,7 @@ static void zf_launch_finalize(zf_solver* s, bool decide) {
     F.slice_part = s->slice_part;
     F.cnt = s->fin_cnt;
     for (int k = 0; k < ZF_NPART; ++k) F.scale[k] = 1.0;
-    F.scale[3] = d.lam;               // g = lam * sum|x|
-    if (s->l2 > 0.0) F.scale[3] = 1.0;   // (elastic net: the fourth sum is g(x+) itself, zf_elem_vec_enet)
+    F.scale[3] = zf_g_scale(s);       // g = lam * sum|x| (elastic net: the fourth sum is g(x+) itself, zf_elem_vec_enet)
     F.f_y_ext = nullptr;
     F.f_x_ext = nullptr;
     F.r_ext = nullptr;
@@ -1449,7 +1456,7 @@ static int zf_trial_matrix(zf_solver* s, zf_step_args& a, bool decide_in_launch,
     const zf_problem_desc& d = s->desc;
     const int64_t m = d.m_rows;
     // (the sparse kind times the whole trial - the event pair brackets every launch of it; the dense kind the prox step alone)
-    const bool time_whole = s->mat.csr;
+    const bool time_whole = (s->sp != nullptr);
     // every loss but the unweighted squared one: psi(y), f(y) and f(x+) from its rows kernels, grad = gfac A^T psi by the same sweeps
     const zf_loss loss = zf_loss_of(s);
     const double gfac = zf_gfac(loss, d.scale);
@@ -1458,7 +1465,7 @@ static int zf_trial_matrix(zf_solver* s, zf_step_args& a, bool decide_in_launch,
     // (sparse matrices have 1e5 .. 1e7 rows: beyond what one workgroup should walk, the residuals take many - zf_kernels_spmv.h)
     // (K responses: m is m K rows of the interleaved margins - the same threshold on the same count, so the order of f is a
     //  function of the row count alone)
-    const bool wide_resid = (d.kind == ZF_PROBLEM_SPARSE_LS_L1 || (s->mat.k > 1 && d.kind == ZF_PROBLEM_LEAST_SQUARES_L1)) &&
+    const bool wide_resid = (d.kind == ZF_PROBLEM_SPARSE_LS_L1 || (s->o.K > 1 && d.kind == ZF_PROBLEM_LEAST_SQUARES_L1)) &&
                             m > ZF_SPMV_WIDE_RESID_MIN_ROWS;
     if (!zf_launch_loss_y(s->stream, s->ctl, s->sring.p[0], s->sring.p[1], s->sring.p[2], d.b, loss, s->resid, d.scale, m,
                           (int)s->opt.nesterov, s->row_part, s->ls_scal + 0)) {
@@ -1472,7 +1479,7 @@ static int zf_trial_matrix(zf_solver* s, zf_step_args& a, bool decide_in_launch,
     // (row blocks: this rank's part 2 scale A_p^T r_p goes to s_part, its combine unguarded; the caller gathers the parts
     //  and zf_solver_enqueue_trial_finish() adds them and runs the rest of the trial)
     const bool rows = d.world > 1 && d.row_sharded;
-    zf_launch_adjoint(s->mat, s->stream, s->ctl, s->resid, rows ? s->s_part : s->grad, gfac, s->ws, !rows);
+    zf_launch_adjoint(zf_mat_of(s), s->stream, s->ctl, s->resid, rows ? s->s_part : s->grad, gfac, s->ws, !rows);
     if (rows) {
         // (the prox step of a row-sharded trial runs in zf_solver_enqueue_trial_finish, after the exchange: the
         //  event pair and the log slot taken by zf_launch_trial belong to a launch that does not happen here - give them
@@ -1495,11 +1502,11 @@ static int zf_trial_matrix(zf_solver* s, zf_step_args& a, bool decide_in_launch,
     zf_ring3 xr = {{s->xb[0], s->xb[1], s->xb[2]}};
     zf_ring3 sout = s->sring;
     if (d.world > 1) sout = {{s->s_part, s->s_part, s->s_part}};   // (column blocks; row blocks returned above)
-    zf_launch_apply(s->mat, s->stream, s->ctl, xr, sout, 1, s->ws);
+    zf_launch_apply(zf_mat_of(s), s->stream, s->ctl, xr, sout, 1, s->ws);
     if (d.world == 1) {
         if (!zf_launch_loss_x(s->stream, s->ctl, s->sring.p[0], s->sring.p[1], s->sring.p[2], 1, d.b, loss, d.scale, m,
                               s->row_part + ZF_SPMV_RESID_MAX_CHUNKS, s->ls_scal + 1)) {
-            if (wide_resid && s->rem && s->mat.csr)   // (ZF_ACCEPT_REMAINDER beyond the threshold: the sparse kind only)
+            if (wide_resid && s->rem && (s->sp != nullptr))   // (ZF_ACCEPT_REMAINDER beyond the threshold: the sparse kind only)
                 zf_launch_spmv_resid_x_rem(s->stream, s->ctl, s->sring.p[0], s->sring.p[1], s->sring.p[2], 1, d.b, d.scale, m,
                                            (int)s->opt.nesterov, 0.0, s->row_part + ZF_SPMV_RESID_MAX_CHUNKS,
                                            s->row_part + 2 * ZF_SPMV_RESID_MAX_CHUNKS, s->ls_scal + 1, s->ls_scal + 2);
@@ -1541,7 +1548,7 @@ static int zf_launch_trial(zf_solver* s, bool decide_in_launch, bool dry = false
         s->ev_used++;
     }
     if (d.kind == ZF_PROBLEM_DIAG_QUAD_L1) return zf_trial_diag(s, a, decide_in_launch, dry, done_ahead, e0, e1);
-    if (s->ls_small && !dry && decide_in_launch) return zf_trial_ls_small(s, a, e0, e1);
+    if (zf_small_open(s) && !dry && decide_in_launch) return zf_trial_ls_small(s, a, e0, e1);
     if (d.kind == ZF_PROBLEM_BLUR_HAAR_L1) return zf_trial_op(s, a, decide_in_launch, e0, e1);
     return zf_trial_matrix(s, a, decide_in_launch, e0, e1);
 }
@@ -1567,7 +1574,7 @@ extern "C" int zf_solver_enqueue_trial_finish(zf_solver* s) {
         a.p1 = nullptr;
         zf_launch_trial_kernels(s, a, false);
         zf_ring3 xr = {{s->xb[0], s->xb[1], s->xb[2]}};
-        zf_launch_apply(s->mat, s->stream, s->ctl, xr, s->sring, 1, s->ws);
+        zf_launch_apply(zf_mat_of(s), s->stream, s->ctl, xr, s->sring, 1, s->ws);
         zf_launch_resid_x(s);
         zf_launch_finalize(s, false);
         ZF_HIP(hipGetLastError());
@@ -1599,18 +1606,18 @@ static int zf_init_ls_tail(zf_solver* s) {
                            m, s->ls_scal + 1);
     }
     const int g = zf_grid_for(n);
-    if (s->l2 > 0.0) {   // (x0 != 0 on every warm start of a path)
+    if (s->o.l2 > 0.0) {   // (x0 != 0 on every warm start of a path)
         if (s->box)
-            hipLaunchKernelGGL(zf_eval_enet_kernel<true>, dim3(g), dim3(ZF_BLOCK), 0, s->stream, s->xb[0], d.lam, 0.5 * s->l2, d.box_lo,
+            hipLaunchKernelGGL(zf_eval_enet_kernel<true>, dim3(g), dim3(ZF_BLOCK), 0, s->stream, s->xb[0], d.lam, 0.5 * s->o.l2, d.box_lo,
                                d.box_hi, n, s->partials);
         else
-            hipLaunchKernelGGL(zf_eval_enet_kernel<false>, dim3(g), dim3(ZF_BLOCK), 0, s->stream, s->xb[0], d.lam, 0.5 * s->l2, d.box_lo,
+            hipLaunchKernelGGL(zf_eval_enet_kernel<false>, dim3(g), dim3(ZF_BLOCK), 0, s->stream, s->xb[0], d.lam, 0.5 * s->o.l2, d.box_lo,
                                d.box_hi, n, s->partials);
-    } else if (s->pf) {
+    } else if (s->o.pf) {
         if (s->box)
-            hipLaunchKernelGGL(zf_eval_pf_kernel<true>, dim3(g), dim3(ZF_BLOCK), 0, s->stream, s->xb[0], s->pf, d.box_lo, d.box_hi, n, s->partials);
+            hipLaunchKernelGGL(zf_eval_pf_kernel<true>, dim3(g), dim3(ZF_BLOCK), 0, s->stream, s->xb[0], s->o.pf, d.box_lo, d.box_hi, n, s->partials);
         else
-            hipLaunchKernelGGL(zf_eval_pf_kernel<false>, dim3(g), dim3(ZF_BLOCK), 0, s->stream, s->xb[0], s->pf, d.box_lo, d.box_hi, n, s->partials);
+            hipLaunchKernelGGL(zf_eval_pf_kernel<false>, dim3(g), dim3(ZF_BLOCK), 0, s->stream, s->xb[0], s->o.pf, d.box_lo, d.box_hi, n, s->partials);
     } else if (s->box)
         hipLaunchKernelGGL((zf_eval_kernel<false, true>), dim3(g), dim3(ZF_BLOCK), 0, s->stream, s->xb[0], nullptr,
                            nullptr, d.box_lo, d.box_hi, n, s->partials);
@@ -1621,7 +1628,7 @@ static int zf_init_ls_tail(zf_solver* s) {
     I.partials = s->partials;
     I.nblocks = g;
     I.f_scale = 0.0;
-    I.lam = s->l2 > 0.0 ? 1.0 : d.lam;
+    I.lam = zf_g_scale(s);
     I.f_ext = s->ls_scal + 1;
     I.pack = s->pack_local;
     I.contribute_g = (d.world == 1 || !d.row_sharded || d.rank == 0) ? 1 : 0;
@@ -1728,19 +1735,19 @@ extern "C" int zf_solver_enqueue_init(zf_solver* s, const double* x0_dev) {
 // host re-uploads the factors from accepted count `nit` on (zf_solver_set_beta), which also
 // resolves beta_next.  Least squares: A x_k and A x_{k-1} are recomputed by the same kernel that
 // produced them (unsharded only), so that the resumed solve continues bit for bit.  On the general paths that is
-// zf_launch_apply_A for every iterate.  On the fused small-matrix path (s->ls_small) the kernel depends on the iterate's
+// zf_launch_apply_A for every iterate.  On the fused small-matrix path (zf_small_open) the kernel depends on the iterate's
 // accepted count: x_0 got its margins from zf_solver_enqueue_init (zf_gemv_rows_kernel), every later iterate is the x+ of
 // an accepted trial of zf_ls_small_rows_kernel - another summation order, other last bits.  Index rule, from saved->nit:
 //     A x_k      in the small-matrix order (zf_ls_small_apply_kernel) iff nit >= 1
 //     A x_{k-1}  in the small-matrix order                            iff nit >= 2     (nit <= 1: x_{k-1} is x_0)
-// s->ls_small alone only says that the shape is eligible: the fused kernels run when a pass decides in its launch
+// zf_small_open alone only says that the shape is eligible: the fused kernels run when a pass decides in its launch
 // (zf_solver_enqueue_steps without a communicator).  Behind a communicator (one rank too: zf_solver_set_comm comes before the
 // restore) and in the host-driven sequence trial / gather / decide every margin vector comes from the general row sweep, and
 // is rebuilt by it: zf_fused_small_runs.
-// Whether the passes of this solver run the fused small-matrix kernels (zf_launch_trial: ls_small and the decision in the
+// Whether the passes of this solver run the fused small-matrix kernels (zf_launch_trial: zf_small_open and the decision in the
 // launch).  Not behind a communicator, whose steps decide in a launch of their own; not with caller-owned pack buffers
 // (zf_solver_set_pack_buffers), the mark of the host-driven sequence zf_solver_enqueue_trial / _trial_finish / _decide.
-static bool zf_fused_small_runs(const zf_solver* s) { return s->ls_small && !s->comm && s->own_packs; }
+static bool zf_fused_small_runs(const zf_solver* s) { return zf_small_open(s) && !s->comm && s->own_packs; }
 
 extern "C" int zf_solver_restore(zf_solver* s, const double* xk_dev, const double* xprev_dev,
                                  const zf_control* saved, int64_t saved_bytes) {
@@ -1893,204 +1900,76 @@ extern "C" int zf_solver_set_history(zf_solver* s, double* hist_dev, int64_t cap
     return ZF_OK;
 }
 
-// Elastic net (include/zfista_hip.h): between create and init.  l2 = 0 leaves the solver as it was created.
-extern "C" int zf_solver_set_l2(zf_solver* s, double l2) {
-    ZF_REQUIRE(s, "zf_solver_set_l2: null argument");
-    if (s->init_enqueued || s->initialised)
-        return zf_fail(ZF_ERR_STATE, "zf_solver_set_l2: call after zf_solver_create and before zf_solver_enqueue_init / zf_solver_restore%s%s");
-    const zf_problem_desc& d = s->desc;
-    ZF_REQUIRE(zf_is_dense_mat(d.kind) || zf_is_sparse_mat(d.kind),
-               "zf_solver_set_l2: only for ZF_PROBLEM_LEAST_SQUARES_L1, ZF_PROBLEM_SPARSE_LS_L1, ZF_PROBLEM_LOGISTIC_L1 and "
-               "ZF_PROBLEM_SPARSE_LOGISTIC_L1");
-    ZF_REQUIRE(d.world == 1, "zf_solver_set_l2: not for a sharded solve (world > 1)");
-    ZF_REQUIRE(l2 >= 0.0 && l2 <= DBL_MAX, "zf_solver_set_l2: l2 must be finite and >= 0");
-    ZF_REQUIRE(!(l2 > 0.0 && s->pf), "zf_solver_set_l2: not with penalty factors (zf_solver_set_penalty_factors: the ridge term would need them too)");
-    s->l2 = l2;
-    if (l2 > 0.0) s->ls_small = false;   // (the fused small-matrix kernels hold the l1 step: the general path, as the logistic kind)
-    return ZF_OK;
-}
-
-// Per-column penalty factors (include/zfista_hip.h): between create and init, on the four margins kinds.
-extern "C" int zf_solver_set_penalty_factors(zf_solver* s, const double* p_dev) {
-    ZF_REQUIRE(s && p_dev, "zf_solver_set_penalty_factors: null argument");
-    if (s->init_enqueued || s->initialised)
-        return zf_fail(ZF_ERR_STATE, "zf_solver_set_penalty_factors: call after zf_solver_create and before zf_solver_enqueue_init / zf_solver_restore%s%s");
-    const zf_problem_desc& d = s->desc;
-    ZF_REQUIRE(zf_is_dense_mat(d.kind) || zf_is_sparse_mat(d.kind),
-               "zf_solver_set_penalty_factors: only for ZF_PROBLEM_LEAST_SQUARES_L1, ZF_PROBLEM_SPARSE_LS_L1, ZF_PROBLEM_LOGISTIC_L1 and "
-               "ZF_PROBLEM_SPARSE_LOGISTIC_L1");
-    ZF_REQUIRE(d.world == 1, "zf_solver_set_penalty_factors: not for a sharded solve (world > 1)");
-    ZF_REQUIRE(!(s->l2 > 0.0), "zf_solver_set_penalty_factors: not with l2 > 0 (zf_solver_set_l2: the ridge term would need the factors too)");
-    ZF_REQUIRE(zf_aligned16(p_dev), "zf_solver_set_penalty_factors: the factors must be 16-byte aligned");
-    s->pf = p_dev;
-    s->ls_small = false;   // (the fused small-matrix kernels hold the unfactored l1 step: the general path, as the logistic kind)
-    return ZF_OK;
-}
-
-// chunk sums of the loss at y and at x+ for the dense least-squares kind, as the dense logistic kind holds them (the fused
-// small-matrix path's are shorter): allocated once, by the first of zf_solver_set_huber / zf_solver_set_poisson /
-// zf_solver_set_row_weights
-static int zf_loss_part(zf_solver* s) {
-    if (s->desc.kind != ZF_PROBLEM_LEAST_SQUARES_L1 || s->loss_part) return ZF_OK;
-    double* part = nullptr;
-    ZF_HIP(hipMalloc(&part, sizeof(double) * 2 * ZF_SPMV_RESID_MAX_CHUNKS));
-    if (s->row_part) (void)hipFree(s->row_part);
-    s->row_part = part;
-    s->loss_part = true;
-    return ZF_OK;
-}
-
-// Huber's loss (include/zfista_hip.h): between create and init, on the two least-squares kinds.
-extern "C" int zf_solver_set_huber(zf_solver* s, double delta) {
-    ZF_REQUIRE(s, "zf_solver_set_huber: null argument");
-    if (s->init_enqueued || s->initialised)
-        return zf_fail(ZF_ERR_STATE, "zf_solver_set_huber: call after zf_solver_create and before zf_solver_enqueue_init / zf_solver_restore%s%s");
-    const zf_problem_desc& d = s->desc;
-    ZF_REQUIRE(d.kind == ZF_PROBLEM_LEAST_SQUARES_L1 || d.kind == ZF_PROBLEM_SPARSE_LS_L1,
-               "zf_solver_set_huber: only for ZF_PROBLEM_LEAST_SQUARES_L1 and ZF_PROBLEM_SPARSE_LS_L1");
-    ZF_REQUIRE(d.world == 1, "zf_solver_set_huber: not for a sharded solve (world > 1)");
-    ZF_REQUIRE(delta > 0.0 && delta <= DBL_MAX, "zf_solver_set_huber: delta must be finite and > 0");
-    ZF_REQUIRE(!s->rem, "zf_solver_set_huber: not with ZF_ACCEPT_REMAINDER (scale |A (x+ - y)|^2 is not the Taylor remainder of this loss)");
-    ZF_REQUIRE(!s->poisson, "zf_solver_set_huber: the solver already has the Poisson loss (zf_solver_set_poisson)");
-    ZF_REQUIRE(!s->multinomial, "zf_solver_set_huber: the solver already has the multinomial loss (zf_solver_set_multinomial)");
-    ZF_REQUIRE(s->mat.k == 1, "zf_solver_set_huber: not with several responses (zf_solver_set_responses)");
-    const int rc = zf_loss_part(s);
-    if (rc) return rc;
-    s->huber = delta;
-    s->ls_small = false;   // (the fused small-matrix kernels hold the squared loss: the general path, as the logistic kind)
-    return ZF_OK;
-}
-
-// The Poisson loss (include/zfista_hip.h): between create and init, on the two least-squares kinds.
-extern "C" int zf_solver_set_poisson(zf_solver* s) {
-    ZF_REQUIRE(s, "zf_solver_set_poisson: null argument");
-    if (s->init_enqueued || s->initialised)
-        return zf_fail(ZF_ERR_STATE, "zf_solver_set_poisson: call after zf_solver_create and before zf_solver_enqueue_init / zf_solver_restore%s%s");
-    const zf_problem_desc& d = s->desc;
-    ZF_REQUIRE(d.kind == ZF_PROBLEM_LEAST_SQUARES_L1 || d.kind == ZF_PROBLEM_SPARSE_LS_L1,
-               "zf_solver_set_poisson: only for ZF_PROBLEM_LEAST_SQUARES_L1 and ZF_PROBLEM_SPARSE_LS_L1");
-    ZF_REQUIRE(d.world == 1, "zf_solver_set_poisson: not for a sharded solve (world > 1)");
-    ZF_REQUIRE(!s->rem, "zf_solver_set_poisson: not with ZF_ACCEPT_REMAINDER (scale |A (x+ - y)|^2 is not the Taylor remainder of this loss)");
-    ZF_REQUIRE(!s->res, "zf_solver_set_poisson: not with ZF_ACCEPT_RESOLVED");
-    ZF_REQUIRE(!(s->huber > 0.0), "zf_solver_set_poisson: the solver already has Huber's loss (zf_solver_set_huber)");
-    ZF_REQUIRE(!s->multinomial, "zf_solver_set_poisson: the solver already has the multinomial loss (zf_solver_set_multinomial)");
-    ZF_REQUIRE(s->mat.k == 1, "zf_solver_set_poisson: not with several responses (zf_solver_set_responses)");
-    const int rc = zf_loss_part(s);
-    if (rc) return rc;
-    s->poisson = true;
-    s->ls_small = false;   // (the fused small-matrix kernels hold the squared loss: the general path, as the logistic kind)
-    return ZF_OK;
-}
-
-// The multinomial loss (include/zfista_hip.h): between create and init, on the two least-squares kinds with K >= 2 responses.
-extern "C" int zf_solver_set_multinomial(zf_solver* s) {
-    ZF_REQUIRE(s, "zf_solver_set_multinomial: null argument");
-    if (s->init_enqueued || s->initialised)
-        return zf_fail(ZF_ERR_STATE, "zf_solver_set_multinomial: call after zf_solver_create and before zf_solver_enqueue_init / zf_solver_restore%s%s");
-    const zf_problem_desc& d = s->desc;
-    ZF_REQUIRE(d.kind == ZF_PROBLEM_LEAST_SQUARES_L1 || d.kind == ZF_PROBLEM_SPARSE_LS_L1,
-               "zf_solver_set_multinomial: only for ZF_PROBLEM_LEAST_SQUARES_L1 and ZF_PROBLEM_SPARSE_LS_L1");
-    ZF_REQUIRE(d.world == 1, "zf_solver_set_multinomial: not for a sharded solve (world > 1)");
-    ZF_REQUIRE(!s->rem, "zf_solver_set_multinomial: not with ZF_ACCEPT_REMAINDER (scale |A (x+ - y)|^2 is not the Taylor remainder of this loss)");
-    ZF_REQUIRE(!s->res, "zf_solver_set_multinomial: not with ZF_ACCEPT_RESOLVED");
-    ZF_REQUIRE(!(s->huber > 0.0), "zf_solver_set_multinomial: the solver already has Huber's loss (zf_solver_set_huber)");
-    ZF_REQUIRE(!s->poisson, "zf_solver_set_multinomial: the solver already has the Poisson loss (zf_solver_set_poisson)");
-    ZF_REQUIRE(!s->multinomial, "zf_solver_set_multinomial: the solver already has the multinomial loss");
-    ZF_REQUIRE(s->mat.k >= 2,
-               "zf_solver_set_multinomial: the solver has no responses yet - a dense solver calls zf_solver_set_responses (K >= 2) BEFORE this "
-               "setter, a sparse one comes from zf_solver_create_sparse_responses");
-    ZF_REQUIRE(zf_aligned16(d.b), "zf_solver_set_multinomial: b (the rows of Y) must be 16-byte aligned");
-    const int rc = zf_loss_part(s);
-    if (rc) return rc;
-    s->multinomial = true;
-    s->ls_small = false;   // (the fused small-matrix kernels hold the squared loss: the general path, as the logistic kind)
-    return ZF_OK;
-}
-
-// Per-row sample weights (include/zfista_hip.h): between create and init, on the four margins kinds.
-extern "C" int zf_solver_set_row_weights(zf_solver* s, const double* w_dev) {
-    ZF_REQUIRE(s && w_dev, "zf_solver_set_row_weights: null argument");
-    if (s->init_enqueued || s->initialised)
-        return zf_fail(ZF_ERR_STATE, "zf_solver_set_row_weights: call after zf_solver_create and before zf_solver_enqueue_init / zf_solver_restore%s%s");
-    const zf_problem_desc& d = s->desc;
-    ZF_REQUIRE(zf_is_dense_mat(d.kind) || zf_is_sparse_mat(d.kind),
-               "zf_solver_set_row_weights: only for ZF_PROBLEM_LEAST_SQUARES_L1, ZF_PROBLEM_SPARSE_LS_L1, ZF_PROBLEM_LOGISTIC_L1 and "
-               "ZF_PROBLEM_SPARSE_LOGISTIC_L1");
-    ZF_REQUIRE(d.world == 1, "zf_solver_set_row_weights: not for a sharded solve (world > 1)");
-    ZF_REQUIRE(!s->rem, "zf_solver_set_row_weights: not with ZF_ACCEPT_REMAINDER (the residual kernels that form scale |A (x+ - y)|^2 carry no weights)");
-    ZF_REQUIRE(!s->res, "zf_solver_set_row_weights: not with ZF_ACCEPT_RESOLVED");
-    const int rc = zf_loss_part(s);
-    if (rc) return rc;
-    s->roww = w_dev;
-    s->ls_small = false;   // (the fused small-matrix kernels hold the unweighted squared loss: the general path, as the logistic kind)
-    return ZF_OK;
-}
-
-// What the two setters that change the storage form of a dense A share: the slices of the column sweep over the new view, a slab
-// that holds them - regrown only when the new rule takes more slices than the present one, the new one allocated before the old
-// one is freed - and then the view itself.  A failed allocation leaves the solver as it was.
-static int zf_solver_adopt_view(zf_solver* s, const zf_matview& V) {
-    int slices = 1;
-    int64_t rows_per_slice = V.m;
-    zf_view_slices(V, &slices, &rows_per_slice);
-    if (slices > s->ws.slices) {
-        double* slab = nullptr;
-        ZF_HIP(hipMalloc(&slab, sizeof(double) * slices * s->desc.n));
+// ---- the eight options of a margins solver (include/zfista_hip.h: the compatibility table; zf_solver_options.h: the rules) ----
+// One option into the record: the rule table's verdict, then what the record with the option needs allocated - the dense
+// least-squares kind's chunk sums of the loss kernels (2 x ZF_SPMV_RESID_MAX_CHUNKS, as the dense logistic kind holds them; the fused
+// small-matrix path's are shorter), a slab for the slices of the column sweep over the new view (regrown only when the new rule
+// takes more slices than the present one) - then the assignments.  A refusal or a failed allocation leaves the solver as it was.
+static int zf_solver_set_option(zf_solver* s, int opt, const zf_option_arg& a) {
+    char why[400];
+    const zf_options_base B = zf_base_of(s);
+    const int rc = zf_option_check(B, s->o, opt, a, why, sizeof(why));
+    if (rc) return zf_fail(rc, "%s%s", why);
+    zf_solver_options next = s->o;
+    zf_option_store(&next, opt, a);
+    double *part = nullptr, *slab = nullptr;
+    if (zf_options_need_loss_part(B, next) && !s->loss_part) ZF_HIP(hipMalloc(&part, sizeof(double) * 2 * ZF_SPMV_RESID_MAX_CHUNKS));
+    int slices = s->ws.slices;
+    int64_t rows_per_slice = s->ws.rows_per_slice;
+    if (zf_is_dense_mat(B.kind)) zf_view_slices(zf_mat_of(s, next), &slices, &rows_per_slice);
+    const hipError_t e = slices > s->ws.slices ? hipMalloc(&slab, sizeof(double) * slices * B.n) : hipSuccess;
+    if (e != hipSuccess) {
+        if (part) (void)hipFree(part);
+        return zf_fail(ZF_ERR_HIP, "%s: the slab of the column sweep: %s", ZF_OPTION_RULES[opt].entry, hipGetErrorString(e));
+    }
+    if (part) {
+        if (s->row_part) (void)hipFree(s->row_part);
+        s->row_part = part;
+        s->loss_part = true;
+    }
+    if (slab) {
         if (s->ws.slab) (void)hipFree(s->ws.slab);
         s->ws.slab = slab;
     }
     s->ws.slices = slices;
     s->ws.rows_per_slice = rows_per_slice;
-    s->mat = V;
+    s->o = next;
+    s->small_shape = zf_options_small_open(B, next);   // (a solver that has left the path stays off it: l2 > 0 and then l2 = 0 runs the l1 kernels of the general path)
     return ZF_OK;
 }
 
-// The matrix stored in fp32 (include/zfista_hip.h): between create and init, on the two dense kinds.
+// (what each option is and computes: include/zfista_hip.h, section by section; all between create and init)
+extern "C" int zf_solver_set_l2(zf_solver* s, double l2) {
+    ZF_REQUIRE(s, "zf_solver_set_l2: null argument");
+    return zf_solver_set_option(s, ZF_OPT_L2, zf_option_arg{l2, nullptr, 0});
+}
+extern "C" int zf_solver_set_penalty_factors(zf_solver* s, const double* p_dev) {
+    ZF_REQUIRE(s, "zf_solver_set_penalty_factors: null argument");
+    return zf_solver_set_option(s, ZF_OPT_PF, zf_option_arg{0.0, p_dev, 0});
+}
+extern "C" int zf_solver_set_huber(zf_solver* s, double delta) {
+    ZF_REQUIRE(s, "zf_solver_set_huber: null argument");
+    return zf_solver_set_option(s, ZF_OPT_HUBER, zf_option_arg{delta, nullptr, 0});
+}
+extern "C" int zf_solver_set_poisson(zf_solver* s) {
+    ZF_REQUIRE(s, "zf_solver_set_poisson: null argument");
+    return zf_solver_set_option(s, ZF_OPT_POISSON, zf_option_arg{0.0, nullptr, 0});
+}
+extern "C" int zf_solver_set_multinomial(zf_solver* s) {
+    ZF_REQUIRE(s, "zf_solver_set_multinomial: null argument");
+    return zf_solver_set_option(s, ZF_OPT_MULTINOMIAL, zf_option_arg{0.0, nullptr, 0});
+}
+extern "C" int zf_solver_set_row_weights(zf_solver* s, const double* w_dev) {
+    ZF_REQUIRE(s, "zf_solver_set_row_weights: null argument");
+    return zf_solver_set_option(s, ZF_OPT_ROWW, zf_option_arg{0.0, w_dev, 0});
+}
 extern "C" int zf_solver_set_matrix_f32(zf_solver* s, const float* A32_dev) {
-    ZF_REQUIRE(s && A32_dev, "zf_solver_set_matrix_f32: null argument");
-    ZF_REQUIRE(!(s->init_enqueued || s->initialised),
-               "zf_solver_set_matrix_f32: call after zf_solver_create and before zf_solver_enqueue_init / zf_solver_restore");
-    const zf_problem_desc& d = s->desc;
-    ZF_REQUIRE(zf_is_dense_mat(d.kind),"zf_solver_set_matrix_f32: only for ZF_PROBLEM_LEAST_SQUARES_L1 and ZF_PROBLEM_LOGISTIC_L1");
-    ZF_REQUIRE(d.world == 1, "zf_solver_set_matrix_f32: not for a sharded solve (world > 1)");
-    ZF_REQUIRE(zf_aligned16(A32_dev), "zf_solver_set_matrix_f32: the matrix must be 16-byte aligned");
-    ZF_REQUIRE(s->mat.k == 1, "zf_solver_set_matrix_f32: not with several responses (zf_solver_set_responses)");
-    zf_matview V = s->mat;
-    V.A = nullptr;
-    V.A32 = A32_dev;
-    V.mfma = false;   // (the MFMA column sweep reads fp64 A: ZF_GEMV_MFMA has no effect here)
-    const int rc = zf_solver_adopt_view(s, V);   // (wider panels, so fewer of them: the fp32 rule may take more slices than the slab of zf_solver_create holds)
-    if (rc) return rc;
-    s->ls_small = false;   // (the fused small-matrix kernels read fp64 A: the general path, as the logistic kind)
-    return ZF_OK;
+    ZF_REQUIRE(s, "zf_solver_set_matrix_f32: null argument");
+    return zf_solver_set_option(s, ZF_OPT_A32, zf_option_arg{0.0, A32_dev, 0});
 }
-
-// K responses on one matrix (include/zfista_hip.h): between create and init, on the two dense kinds.
 extern "C" int zf_solver_set_responses(zf_solver* s, int32_t K) {
     ZF_REQUIRE(s, "zf_solver_set_responses: null argument");
-    if (s->init_enqueued || s->initialised)
-        return zf_fail(ZF_ERR_STATE, "zf_solver_set_responses: call after zf_solver_create and before zf_solver_enqueue_init / zf_solver_restore%s%s");
-    const zf_problem_desc& d = s->desc;
-    ZF_REQUIRE(zf_is_dense_mat(d.kind), "zf_solver_set_responses: only for ZF_PROBLEM_LEAST_SQUARES_L1 and ZF_PROBLEM_LOGISTIC_L1");
-    ZF_REQUIRE(d.world == 1, "zf_solver_set_responses: not for a sharded solve (world > 1)");
-    ZF_REQUIRE(K >= 2 && K <= ZF_MR_MAX_K, "zf_solver_set_responses: K must be 2 .. 16");
-    ZF_REQUIRE(s->mat.k == 1, "zf_solver_set_responses: the solver already has its responses");
-    ZF_REQUIRE(d.m_rows % K == 0 && d.n % K == 0, "zf_solver_set_responses: m_rows and n of the solver must be multiples of K (they are m K and n K)");
-    ZF_REQUIRE(!s->rem && !s->res, "zf_solver_set_responses: not with ZF_ACCEPT_REMAINDER or ZF_ACCEPT_RESOLVED");
-    ZF_REQUIRE(!(s->huber > 0.0) && !s->poisson, "zf_solver_set_responses: not with Huber's or the Poisson loss (zf_solver_set_huber, zf_solver_set_poisson)");
-    ZF_REQUIRE(!s->multinomial, "zf_solver_set_responses: zf_solver_set_multinomial comes after this setter, not before");
-    ZF_REQUIRE(!s->mat.A32, "zf_solver_set_responses: not with a matrix stored in fp32 (zf_solver_set_matrix_f32)");
-    int rc = zf_loss_part(s);   // (the wide residual kernels beyond ZF_SPMV_WIDE_RESID_MIN_ROWS rows write chunk sums)
-    if (rc) return rc;
-    zf_matview V = s->mat;
-    V.m = d.m_rows / K;
-    V.n = d.n / K;
-    V.k = K;
-    V.mfma = false;   // (no MFMA form of the K-response sweeps)
-    rc = zf_solver_adopt_view(s, V);   // (the rule runs on A's own shape: it may take more slices than the slab of zf_solver_create holds)
-    if (rc) return rc;
-    s->ls_small = false;   // (the fused small-matrix kernels hold one response: the general path, as the logistic kind)
-    return ZF_OK;
+    return zf_solver_set_option(s, ZF_OPT_K, zf_option_arg{0.0, nullptr, (int)K});
 }
 
 extern "C" int zf_solver_launch_counts(zf_solver* s, int64_t* out, int64_t count) {
@@ -2131,20 +2010,20 @@ extern "C" int zf_solver_ls_plan(zf_solver* s, int64_t* out, int64_t count) {
     }
     if (zf_is_sparse_mat(s->desc.kind)) {
         out[0] = 5;
-        out[1] = s->mat.h->A.lanes;
-        out[2] = s->mat.h->At.lanes;
-        out[3] = s->mat.h->A.nsplit + s->mat.h->At.nsplit;
+        out[1] = s->sp->A.lanes;
+        out[2] = s->sp->At.lanes;
+        out[3] = s->sp->A.nsplit + s->sp->At.nsplit;
         if (count >= 6) {   // responses (zf_solver_create_sparse_responses; 1 otherwise)
-            out[4] = s->mat.k;
+            out[4] = s->o.K;
             out[5] = 0;
         }
         return ZF_OK;
     }
     if (!zf_is_dense_mat(s->desc.kind)) return ZF_OK;
-    const zf_matview& V = s->mat;
+    const zf_matview V = zf_mat_of(s);
     const bool odd = V.n % 2 != 0;   // (K responses: the parity of the matrix's own column count)
-    out[0] = s->ls_small ? 1 : V.mfma ? 2 : odd ? 4 : 3;
-    out[1] = s->ls_small ? 1 : odd ? 3 : 2;
+    out[0] = zf_small_open(s) ? 1 : V.mfma ? 2 : odd ? 4 : 3;
+    out[1] = zf_small_open(s) ? 1 : odd ? 3 : 2;
     if (V.A32) {   // zf_kernels_gemv_f32.h: 16-byte, 8-byte or scalar loads of floats
         const int w = zf_f32_width(V.n);
         out[0] = w == 4 ? 6 : w == 2 ? 7 : 8;
@@ -2697,7 +2576,8 @@ static void zf_sweep_ws_free(zf_sweep_ws* W) {
 }
 
 // The checks the three evaluation entries share (`who`: the entry's name; `io_ok`: its own host pointers), all before anything
-// touches a device or reads through the handle: the descriptor and its size, the matrix, the pointers, the loss, the responses.
+// touches a device or reads through the handle: the descriptor and its size, the matrix, the pointers, the loss, the responses
+// (which loss, response count and storage form exist together: the predicates of zf_solver_options.h, which a solver's setters ask too).
 // Leaves the loss in *L.
 static int zf_desc_args(const char* who, const zf_eval_desc* d, int64_t desc_bytes, bool io_ok, zf_loss* L) {
     if (!d || desc_bytes != (int64_t)sizeof(zf_eval_desc))
@@ -2709,9 +2589,9 @@ static int zf_desc_args(const char* who, const zf_eval_desc* d, int64_t desc_byt
     if (!csr && !(d->m_rows >= 1 && d->n >= 1)) return zf_fail(ZF_ERR_ARG, "%s: bad argument (m_rows and n must be >= 1)%s", who);
     if (!csr && !zf_aligned16(d->A32 ? (const void*)d->A32 : (const void*)d->A)) return zf_fail(ZF_ERR_ARG, "%s: A must be 16-byte aligned%s", who);
     if (!(d->K >= 1 && d->K <= ZF_MR_MAX_K)) return zf_fail(ZF_ERR_ARG, "%s: K must be 1 .. 16%s", who);
-    if (d->K > 1 && d->loss != ZF_LOSS_SQUARE && d->loss != ZF_LOSS_LOGISTIC && d->loss != ZF_LOSS_MULTINOMIAL)
+    if (d->K > 1 && !zf_loss_takes_responses(d->loss))
         return zf_fail(ZF_ERR_ARG, "%s: with K > 1 the loss must be ZF_LOSS_SQUARE or ZF_LOSS_LOGISTIC (or ZF_LOSS_MULTINOMIAL, whose rows couple the K responses)%s", who);
-    if (d->loss == ZF_LOSS_MULTINOMIAL && (d->K < 2 || d->A32))
+    if (d->loss == ZF_LOSS_MULTINOMIAL && !zf_multinomial_fits(d->K, d->A32 != nullptr))
         return zf_fail(ZF_ERR_ARG, "%s: ZF_LOSS_MULTINOMIAL needs K = 2 .. 16 responses on A or spmat, not a matrix stored in fp32 (the other codes: ZF_LOSS_SQUARE, "
                        "ZF_LOSS_LOGISTIC, ZF_LOSS_HUBER, ZF_LOSS_POISSON)%s", who);
     if (d->loss != ZF_LOSS_SQUARE && d->loss != ZF_LOSS_LOGISTIC && d->loss != ZF_LOSS_HUBER && d->loss != ZF_LOSS_POISSON &&
@@ -2719,7 +2599,7 @@ static int zf_desc_args(const char* who, const zf_eval_desc* d, int64_t desc_byt
         return zf_fail(ZF_ERR_ARG, "%s: loss must be ZF_LOSS_SQUARE, ZF_LOSS_LOGISTIC, ZF_LOSS_HUBER, ZF_LOSS_POISSON or ZF_LOSS_MULTINOMIAL%s", who);
     if (d->loss == ZF_LOSS_MULTINOMIAL && !zf_aligned16(d->b)) return zf_fail(ZF_ERR_ARG, "%s: with ZF_LOSS_MULTINOMIAL b must be 16-byte aligned%s", who);
     if (d->loss == ZF_LOSS_HUBER && !(d->delta > 0.0 && d->delta <= DBL_MAX)) return zf_fail(ZF_ERR_ARG, "%s: delta must be finite and > 0%s", who);
-    if (d->K > 1 && d->A32) return zf_fail(ZF_ERR_ARG, "%s: not with K > 1 and a matrix stored in fp32 (the K-response sweeps read an fp64 A)%s", who);
+    if (!zf_responses_fit_storage(d->K, d->A32 != nullptr)) return zf_fail(ZF_ERR_ARG, "%s: not with K > 1 and a matrix stored in fp32 (the K-response sweeps read an fp64 A)%s", who);
     *L = zf_loss{d->loss, d->loss == ZF_LOSS_HUBER ? d->delta : 0.0, d->w, d->K};
     return ZF_OK;
 }
@@ -2987,7 +2867,7 @@ extern "C" int zf_solver_duality_gap(zf_solver* s, double* out, int64_t count) {
             return rc;
         }
     }
-    if (s->pf && !s->gap_xp) ZF_HIP(hipMalloc(&s->gap_xp, sizeof(double) * n));
+    if (s->o.pf && !s->gap_xp) ZF_HIP(hipMalloc(&s->gap_xp, sizeof(double) * n));
     zf_control c;
     ZF_HIP(hipMemcpyAsync(&c, s->ctl, sizeof(c), hipMemcpyDeviceToHost, s->stream));
     ZF_HIP(hipStreamSynchronize(s->stream));
@@ -2996,12 +2876,12 @@ extern "C" int zf_solver_duality_gap(zf_solver* s, double* out, int64_t count) {
     const double* z = s->sring.p[c.cur];   // A x_k: every path of these kinds keeps it there (the fused small-matrix path too)
     const zf_gap_ws& ws = s->gap;
     zf_launch_loss_gap_rows(s->stream, loss, z, d.b, m, d.scale, ws);
-    zf_launch_adjoint(s->mat, s->stream, nullptr, ws.rvec, ws.g, zf_gfac(loss, d.scale), s->ws);
-    if (s->pf) {   // (penalty factors: the tails run on g / p and p o x_k)
-        zf_launch_gap_pf_scale(s->stream, ws.g, x, s->pf, s->gap_xp, n);
+    zf_launch_adjoint(zf_mat_of(s), s->stream, nullptr, ws.rvec, ws.g, zf_gfac(loss, d.scale), s->ws);
+    if (s->o.pf) {   // (penalty factors: the tails run on g / p and p o x_k)
+        zf_launch_gap_pf_scale(s->stream, ws.g, x, s->o.pf, s->gap_xp, n);
         x = s->gap_xp;
     }
-    const zf_gap_out res = zf_launch_loss_gap_tail(s->stream, loss, z, d.b, x, m, n, d.scale, d.lam, s->l2, ws, count);
+    const zf_gap_out res = zf_launch_loss_gap_tail(s->stream, loss, z, d.b, x, m, n, d.scale, d.lam, s->o.l2, ws, count);
     ZF_HIP(hipGetLastError());
     ZF_HIP(hipMemcpyAsync(out, ws.scal + res.slot, sizeof(double) * res.count, hipMemcpyDeviceToHost, s->stream));
     ZF_HIP(hipStreamSynchronize(s->stream));

@@ -52,6 +52,39 @@ def gather_packs(pack_all, pack_local, group):
     dist.all_gather_into_tensor(pack_all, pack_local, group=group)
 
 
+def _positive(v):
+    v = float(v or 0.0)
+    return (v,) if v > 0 else None
+
+
+def _flag(v):
+    return () if v else None
+
+
+def _pointer(v):
+    return (C.c_void_p(v),) if v else None
+
+
+def _count(v):   # (K = 1 is the plain problem: the setter is not called)
+    v = int(v or 1)
+    return (v,) if v > 1 else None
+
+
+# The options of a margins solver are no descriptor fields: (key of the descriptor dict, the library's entry, how the value becomes
+# the entry's arguments behind the handle - None: not asked for), in call order (the multinomial loss after the responses: the
+# setter refuses a solver without them; include/zfista_hip.h has the compatibility table).  Pointers are device pointers as ints.
+OPTION_SETTERS = (
+    ("l2", "zf_solver_set_l2", _positive),                               # elastic net
+    ("huber_delta", "zf_solver_set_huber", _positive),                   # Huber's loss on a least-squares kind
+    ("poisson", "zf_solver_set_poisson", _flag),                         # the Poisson loss on a least-squares kind
+    ("row_weights", "zf_solver_set_row_weights", _pointer),              # per-row sample weights
+    ("penalty_factors", "zf_solver_set_penalty_factors", _pointer),      # per-column penalty factors
+    ("matrix_f32", "zf_solver_set_matrix_f32", _pointer),                # the dense matrix stored in fp32
+    ("responses", "zf_solver_set_responses", _count),                    # K responses on one dense matrix (with spmat: zf_solver_create_sparse_responses)
+    ("multinomial", "zf_solver_set_multinomial", _flag),                 # the multinomial loss on K responses
+)
+
+
 class DeviceSolver:
     """One ``zf_solver``: a problem descriptor bound to device buffers + options.
 
@@ -78,18 +111,13 @@ class DeviceSolver:
             stream = torch.cuda.current_stream().cuda_stream
         self.stream = stream
         d = _lib.ProblemDesc()
-        spmat = desc_fields.get("spmat")   # a zf_spmat handle: the matrix of a sparse problem is no descriptor field
-        l2 = float(desc_fields.get("l2", 0.0) or 0.0)   # elastic net: no descriptor field either (zf_solver_set_l2)
-        huber = float(desc_fields.get("huber_delta", 0.0) or 0.0)   # Huber's loss on a least-squares kind: likewise (zf_solver_set_huber)
-        poisson = bool(desc_fields.get("poisson", False))   # the Poisson loss on a least-squares kind: likewise (zf_solver_set_poisson)
-        multinomial = bool(desc_fields.get("multinomial", False))   # the multinomial loss on K responses: likewise (zf_solver_set_multinomial, after the responses)
-        roww = desc_fields.get("row_weights")   # per-row sample weights (a device pointer): likewise (zf_solver_set_row_weights)
-        pf = desc_fields.get("penalty_factors")   # per-column penalty factors (a device pointer): likewise (zf_solver_set_penalty_factors)
-        a32 = desc_fields.get("matrix_f32")   # the matrix stored in fp32 (a device pointer): likewise (zf_solver_set_matrix_f32)
-        responses = int(desc_fields.get("responses", 1) or 1)   # K responses on one matrix: likewise (dense: zf_solver_set_responses; with spmat: zf_solver_create_sparse_responses)
+        # no descriptor fields: the zf_spmat handle of a sparse problem, and the options (OPTION_SETTERS)
+        desc_fields = dict(desc_fields)
+        spmat = desc_fields.pop("spmat", None)
+        asked = {entry: as_args(desc_fields.pop(key, None)) for key, entry, as_args in OPTION_SETTERS}   # None: not asked for
+        responses = (asked["zf_solver_set_responses"] or (1,))[0]
         for k, v in desc_fields.items():
-            if k not in ("spmat", "l2", "huber_delta", "poisson", "multinomial", "row_weights", "penalty_factors", "matrix_f32", "responses"):
-                setattr(d, k, v)
+            setattr(d, k, v)
         o = _lib.Options()
         for k, v in options.items():
             setattr(o, k, v)
@@ -105,23 +133,12 @@ class DeviceSolver:
             _lib.check(self.lib.zf_solver_create(C.byref(h), C.byref(d), C.byref(o), C.c_void_p(stream)),
                        "zf_solver_create")
         self.handle = h
-        self.l2 = l2
-        if l2 > 0:
-            _lib.check(self.lib.zf_solver_set_l2(h, l2), "zf_solver_set_l2")
-        if huber > 0:
-            _lib.check(self.lib.zf_solver_set_huber(h, huber), "zf_solver_set_huber")
-        if poisson:
-            _lib.check(self.lib.zf_solver_set_poisson(h), "zf_solver_set_poisson")
-        if roww:
-            _lib.check(self.lib.zf_solver_set_row_weights(h, C.c_void_p(roww)), "zf_solver_set_row_weights")
-        if pf:
-            _lib.check(self.lib.zf_solver_set_penalty_factors(h, C.c_void_p(pf)), "zf_solver_set_penalty_factors")
-        if a32:
-            _lib.check(self.lib.zf_solver_set_matrix_f32(h, C.c_void_p(a32)), "zf_solver_set_matrix_f32")
-        if responses > 1 and spmat is None:   # (K = 1 is the plain problem: the setter is not called)
-            _lib.check(self.lib.zf_solver_set_responses(h, responses), "zf_solver_set_responses")
-        if multinomial:   # (call order: the responses first - the setter refuses a solver without them)
-            _lib.check(self.lib.zf_solver_set_multinomial(h), "zf_solver_set_multinomial")
+        self.l2 = (asked["zf_solver_set_l2"] or (0.0,))[0]
+        if spmat is not None:
+            asked["zf_solver_set_responses"] = None   # (K of a sparse solver: the creator took it)
+        for entry, args in asked.items():   # (in the table's order)
+            if args is not None:
+                _lib.check(getattr(self.lib, entry)(h, *args), entry)
         sub = C.c_int32(1)
         _lib.check(self.lib.zf_solver_sub_iters(h, C.byref(sub)), "zf_solver_sub_iters")
         self.sub_iters = int(sub.value)   # iterations one pass may accept (temporal blocking)
